@@ -17,13 +17,16 @@ per-texel radiance of each tile is gathered to rank 0 (RCCL over xGMI) which run
 Total work is fixed by the config, so scaling is "strong".
 
 Rank 0 prints ONE JSON line.  `value` = rays traced by all ranks / wall time of the K timed frames
-(inputs resident in HBM).  `roofline` prices the traversal kernel THE TIMED REGION LAUNCHES (with frames in
+(inputs resident in HBM).  A plain run sets up, warms up, takes the timed call of K steps once, writes its outputs
+(--dump-outputs DIR) and prints the line.  Everything else below is measured with --full only (the timed call then
+taken 5 times, the line from the median call).  `roofline` prices the traversal kernel THE TIMED REGION LAUNCHES (with frames in
 flight: the hand-over kernel rt_traverse<false,false,true>): HIP events around every traversal launch on every
 lane's stream in a repeat of the timed call, algorithmic bytes (R*44 + V*64 + T*36, from per-round
 counters) over that time, and first the physical figures of the committed PMC passes (profiles/traffic_r04.json:
 HBM-side traffic, VALU issue and lane utilisation); the single-launch kernel of a frame running alone is priced
 beside it.  `cpu_baseline` times the CPU oracle's traversal (oracle/, scalar C + OpenMP, every hardware thread)
-on a bounded sample of the same rays.
+on a bounded sample of the same rays.  On several ranks --full also proves sharded == unsharded before it times
+(sharded_self_check) and reports what every rank did.
 """
 import argparse
 import importlib
@@ -78,8 +81,15 @@ def parse():
                     help="tuning study: traversal kernel schedule (psm_rt_set_traverse_mode); results never depend on it")
     ap.add_argument("--trav-caps", default="96", help="phased: wave-step caps, comma separated")
     ap.add_argument("--trav-adaptive", default="", help="adaptive: min_live,min_steps,final_rays,max_launches,min_rays")
-    ap.add_argument("--repeats", type=int, default=5, help="how many times the timed call of K steps is taken; the line reports the "
-                                                            "median call, and all of them under \"timing\"")
+    ap.add_argument("--repeats", type=int, default=None, help="how many times the timed call of K steps is taken (default 1, with --full 5); "
+                                                               "the line reports the median call, and all of them under \"timing\"")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the counting and kernel passes behind stage_ms_per_frame and roofline, "
+                         "the copy bandwidth, the CPU baseline, and on several ranks the sharded self-check and the per-rank figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed call hands its caller as DIR/<name>.npy (rank 0): the "
+                         "accumulated HDR image (a seeded sample of its texels where it passes 48 MB) and, on one rank, the rounds "
+                         "and rays of every frame of the last timed call")
     ap.add_argument("--solo", type=int, default=-1, help="tuning study: rays a traversal wave takes into the solo gear at most "
                                                           "(psm_rt_set_traverse_solo, 0..4; -1 = the library's default)")
     return ap.parse_args()
@@ -612,6 +622,30 @@ def dry_run(world):
     return 0 if total == world and [int(r[0]) for r in rows] == list(range(world)) else 1
 
 
+IMAGE_DUMP_BYTES = 48 << 20   # --dump-outputs: the whole image up to this size (1080p: 33 MB), a seeded sample of its texels beyond
+
+
+def dump_outputs(path, img, frames):
+    """--dump-outputs: what the timed call hands its caller -- the accumulated HDR image (snapHdr) and, where known, every
+    frame's (rounds, rays) of the last timed call -- as float32 / float64 .npy files, 64 MB at most in all. Same arguments,
+    same inputs: two builds of the project can be compared file for file."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    if img.nbytes <= IMAGE_DUMP_BYTES:
+        out["image"] = img
+    else:
+        texels = img.reshape(-1, img.shape[-1])
+        n = IMAGE_DUMP_BYTES // (texels[0].nbytes + 8)   # each texel and its float64 index
+        pick = np.sort(np.random.RandomState(0).choice(texels.shape[0], n, replace=False))
+        out["image_sample"] = texels[pick]
+        out["image_sample_texel"] = pick.astype(np.float64)   # row-major texel index into the image
+    if frames is not None:
+        out["frame_rounds"] = np.asarray([r for r, _ in frames], np.float64)
+        out["frame_rays"] = np.asarray([n for _, n in frames], np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -665,13 +699,17 @@ def main():
         sys.exit(3)
     ctx = R.ctx
     check = None
-    if dist.active and dist.world > 1 and R.native is not None:
+    if args.full and dist.active and dist.world > 1 and R.native is not None:
         check = sharded_self_check(psm, scenes, dist, R)   # exits non-zero (every rank) unless sharded == unsharded
+    repeats = max(args.repeats if args.repeats is not None else (5 if args.full else 1), 1)
+
+    last = {"frames": None}   # per-frame (rounds, rays) of the latest call, for --dump-outputs (a sharded call returns only its total)
 
     def run_steps(k):
         if dist.active:
             return R.frames_in_flight_sharded(k)
-        return sum(r for _, r in R.frames_in_flight(k))
+        last["frames"] = R.frames_in_flight(k)
+        return sum(r for _, r in last["frames"])
 
     def reseed():
         R.batch.setSeed(1000)
@@ -708,68 +746,70 @@ def main():
         lane_cal = {"what": "untimed stretches of %d steps before the timed region, ms per step, maximum over the ranks" % kc,
                     "lanes_%d" % R.lanes: full, "lanes_%d" % alt: fewer, "chosen": R.active_lanes}
 
-    # counting pass: the frames of the timed region (same rand() streams), one after another on lane 0,
-    # counters on: V, T, R are deterministic per seed; logged per bounce round
-    reseed()
-    ctx.stats_enable(False, True)
-    ctx.stats_reset()
-    ray_sets = [] if (dist.rank == 0 and not args.no_cpu_baseline) else None
-    round_log = []
-    for i in range(args.steps):
-        R.frame(record=ray_sets if i == 0 else None, round_log=round_log)
-    cnt = ctx.stats()
-    V, T, Rr = cnt.node_visits, cnt.tri_tests, cnt.rays_traced
-    assert sum(r[1] for r in round_log) == V and sum(r[2] for r in round_log) == T and sum(r[0] for r in round_log) == Rr
+    ray_sets, Rr = None, None
+    if args.full:
+        # counting pass: the frames of the timed region (same rand() streams), one after another on lane 0,
+        # counters on: V, T, R are deterministic per seed; logged per bounce round
+        reseed()
+        ctx.stats_enable(False, True)
+        ctx.stats_reset()
+        ray_sets = [] if (dist.rank == 0 and not args.no_cpu_baseline) else None
+        round_log = []
+        for i in range(args.steps):
+            R.frame(record=ray_sets if i == 0 else None, round_log=round_log)
+        cnt = ctx.stats()
+        V, T, Rr = cnt.node_visits, cnt.tri_tests, cnt.rays_traced
+        assert sum(r[1] for r in round_log) == V and sum(r[2] for r in round_log) == T and sum(r[0] for r in round_log) == Rr
 
-    # kernel pass, serial: the same frames again, one after another on lane 0, HIP events on every launch (on the launching
-    # stream): per-stage times, and the single-launch traversal kernel running alone
-    reseed()
-    R.batch.sync()
-    ctx.stats_enable(True, False)
-    ctx.stats_reset()
-    for i in range(args.steps):
-        R.frame()
-    ctx.sync()
-    kst = ctx.stats()
-    assert kst.rays_traced == Rr, (kst.rays_traced, Rr)
-    ctx.stats_enable(False, False)
+        # kernel pass, serial: the same frames again, one after another on lane 0, HIP events on every launch (on the launching
+        # stream): per-stage times, and the single-launch traversal kernel running alone
+        reseed()
+        R.batch.sync()
+        ctx.stats_enable(True, False)
+        ctx.stats_reset()
+        for i in range(args.steps):
+            R.frame()
+        ctx.sync()
+        kst = ctx.stats()
+        assert kst.rays_traced == Rr, (kst.rays_traced, Rr)
+        ctx.stats_enable(False, False)
 
-    # kernel pass, as timed: the call of the timed region with HIP events around every traversal launch on every lane's own
-    # stream (psm_stats_enable(2, 0): traversal launches only, so the rebuild keeps its captured graph and the schedule is
-    # the timed one). Prices the kernel the timed region actually launches.
-    reseed()
-    tctx = list(R.batch.contexts())        # every context that traces in the timed region (all parts of all frames in flight)
-    for c_ in tctx:
-        c_.stats_enable(2, False)
-        c_.stats_reset()
-        c_.stats_reference(tctx[0])        # one time axis for all their launches
-    dist.barrier()
-    R.batch.sync()
-    e0 = time.perf_counter()
-    traced_ev = run_steps(args.steps)
-    R.batch.sync()
-    ev_elapsed = time.perf_counter() - e0
-    assert traced_ev == Rr, (traced_ev, Rr)
-    lane_stats = [c_.stats() for c_ in tctx]
-    spans = sorted(iv for c_ in tctx for iv in c_.traverse_intervals())
-    busy_ms, edge = 0.0, -1e30        # union of the traversal launches' intervals: time with at least one of them on the chip
-    for a, b in spans:
-        if b > edge:
-            busy_ms += b - max(a, edge)
-            edge = b
-    for c_ in tctx:
-        c_.stats_enable(False, False)
-    ho_launches = sum(s_.handover_launches for s_ in lane_stats)
-    ho_ms = sum(s_.handover_ms for s_ in lane_stats)
-    wh_launches = sum(s_.traverse_launches for s_ in lane_stats) - ho_launches
-    wh_ms = sum(s_.traverse_ms for s_ in lane_stats) - ho_ms
+        # kernel pass, as timed: the call of the timed region with HIP events around every traversal launch on every lane's own
+        # stream (psm_stats_enable(2, 0): traversal launches only, so the rebuild keeps its captured graph and the schedule is
+        # the timed one). Prices the kernel the timed region actually launches.
+        reseed()
+        tctx = list(R.batch.contexts())        # every context that traces in the timed region (all parts of all frames in flight)
+        for c_ in tctx:
+            c_.stats_enable(2, False)
+            c_.stats_reset()
+            c_.stats_reference(tctx[0])        # one time axis for all their launches
+        dist.barrier()
+        R.batch.sync()
+        e0 = time.perf_counter()
+        traced_ev = run_steps(args.steps)
+        R.batch.sync()
+        ev_elapsed = time.perf_counter() - e0
+        assert traced_ev == Rr, (traced_ev, Rr)
+        lane_stats = [c_.stats() for c_ in tctx]
+        spans = sorted(iv for c_ in tctx for iv in c_.traverse_intervals())
+        busy_ms, edge = 0.0, -1e30        # union of the traversal launches' intervals: time with at least one of them on the chip
+        for a, b in spans:
+            if b > edge:
+                busy_ms += b - max(a, edge)
+                edge = b
+        for c_ in tctx:
+            c_.stats_enable(False, False)
+        ho_launches = sum(s_.handover_launches for s_ in lane_stats)
+        ho_ms = sum(s_.handover_ms for s_ in lane_stats)
+        wh_launches = sum(s_.traverse_launches for s_ in lane_stats) - ho_launches
+        wh_ms = sum(s_.traverse_ms for s_ in lane_stats) - ho_ms
 
     # timed region: exactly K steps between barrier + synchronize on both sides, the maximum over the ranks -- taken
     # `repeats` times over (the same frames: reseeded), `value` and `ms_per_step` from the MEDIAN call, every call's figure
     # in the line's "timing" object (median and minimum over repeats; one wall-clock sample of a 45 ms call
     # moves by 1-2 % with whatever else the box does)
     samples = []
-    for rep in range(max(args.repeats, 1)):
+    for rep in range(repeats):
         reseed()
         ctx.stats_reset()
         dist.barrier()
@@ -779,10 +819,13 @@ def main():
         R.batch.sync()
         dist.barrier()
         samples.append(dist.max_float(time.perf_counter() - t0))
+        Rr = traced if Rr is None else Rr   # a plain run counts the rays its first timed call traced
         assert traced == Rr, (traced, Rr)
     elapsed = sorted(samples)[(len(samples) - 1) // 2]   # the median call (the lower one of an even count)
-    st = kst
     total_rays = dist.sum_int(int(Rr))
+    img = R.batch.snapHdr() if dist.rank == 0 else None   # the image the timed call accumulated (its frames reseeded: all of it)
+    if args.dump_outputs and dist.rank == 0:
+        dump_outputs(args.dump_outputs, img, last["frames"])
 
     if args.diag_clock and not dist.active:
         reseed()
@@ -806,7 +849,7 @@ def main():
         reseed()
 
     per_rank = None
-    if dist.active:
+    if args.full and dist.active:
         # what every rank did, to rank 0's line: a rank that idles or a tile that costs twice the others' shows here
         gather_ms = -1.0
         if R.native is not None:   # one frame's gather, timed on its own: 5 x (pack, gather, unpack on rank 0), drained by a barrier on the communicator
@@ -820,68 +863,69 @@ def main():
         per_rank = dist.gather_floats([float(Rr), kst.build_ms / args.steps, kst.traverse_ms / args.steps, kst.shade_ms / args.steps, gather_ms])
 
     if dist.rank == 0:
-        img = R.batch.snapHdr()
-        copy_gbs = ctx.copy_bandwidth(1 << 30, 5)  # the box's achievable ceiling next to the vendor peak
-        # which rounds of the timed region ran the hand-over kernel: plan_traverse's rule (csrc/trace.hip) -- frames in flight
-        # (or a forced hand-over schedule) and at least phase_min_rays rays in the round
-        min_rays = 1 << 19
-        if args.trav_adaptive and len(args.trav_adaptive.split(",")) >= 5:
-            min_rays = int(args.trav_adaptive.split(",")[4])
-        hand = args.traverse in ("phased", "adaptive") or (args.traverse == "auto" and R.lanes > 1)
-        ho_rounds = [r for r in round_log if hand and r[0] >= min_rays]
-        wh_rounds = [r for r in round_log if not (hand and r[0] >= min_rays)]
-        assert (ho_launches > 0) == (len(ho_rounds) > 0), (ho_launches, len(ho_rounds))
-        ms_step = elapsed / args.steps * 1e3
-        how = ("the call of the timed region repeated with HIP events around every traversal launch on every lane's stream "
-               "(%d frame(s) in flight: a launch shares the chip with the other frames' kernels); that pass ran at %.3f ms per "
-               "step against %.3f timed" % (R.lanes, ev_elapsed / args.steps * 1e3, ms_step))
-        sums = lambda rs: (sum(r[0] for r in rs), sum(r[1] for r in rs), sum(r[2] for r in rs))
-        whole_frame = not dist.active and not args.emulate_tile
-        if ho_rounds:
-            timed_k = price("rt_traverse<false, false, true>", ho_launches, ho_ms, *sums(ho_rounds), len(ho_rounds), args.steps,
-                            args.scene, args.width, args.height, how, whole_frame)
-            if wh_launches:
-                timed_k["rounds_below_min_rays_run_single_launch"] = price(
-                    "rt_traverse<false, false, false>", wh_launches, wh_ms, *sums(wh_rounds), len(wh_rounds), args.steps,
-                    args.scene, args.width, args.height, how, whole_frame)
-        else:
-            timed_k = price("rt_traverse<false, false, false>", wh_launches, wh_ms, *sums(wh_rounds), len(wh_rounds), args.steps,
-                            args.scene, args.width, args.height, how, whole_frame)
-        whole_k = price("rt_traverse<false, false, false>", st.traverse_launches, st.traverse_ms, Rr, V, T, len(round_log), args.steps,
-                        args.scene, args.width, args.height,
-                        "serial kernel pass: the same frames one after another on one stream, every launch alone on the chip", whole_frame)
-        # launches of different frames overlap: their summed durations exceed the wall time; the union of their intervals is
-        # the time during which traversal is on the chip at all, and the ratio is how many run side by side on average
-        timed_k["traversal_busy_ms_per_step"] = busy_ms / args.steps
-        timed_k["launches_side_by_side"] = (ho_ms + wh_ms) / busy_ms if busy_ms > 0 else None
-        timed_k["achieved_over_busy_time"] = (Rr * 44 + V * 64 + T * 36) / (busy_ms * 1e-3) / 1e9 if busy_ms > 0 else None
-        if timed_k.get("traffic") and busy_ms > 0:
-            # chip level: the HBM-side bytes of all traversal launches of a step over the time traversal is on the chip
-            tot = timed_k["traffic"] * timed_k["launches"]
-            small = timed_k.get("rounds_below_min_rays_run_single_launch")
-            if small and small.get("traffic"):
-                tot += small["traffic"] * small["launches"] * (small["algorithmic_bytes_per_launch"] / max(whole_k["algorithmic_bytes_per_launch"], 1.0))
-            timed_k["hbm_gbs"] = tot / (busy_ms * 1e-3) / 1e9
-            timed_k["hbm_frac"] = timed_k["hbm_gbs"] / HBM_PEAK_GBS
-            timed_k["hbm_frac_note"] = ("HBM-side bytes (PMC: 2 x FETCH_SIZE + WRITE_SIZE per launch, committed passes) of all traversal "
-                                        "launches of a step over traversal_busy_ms_per_step, the time at least one of them is on the chip")
-        if whole_frame and timed_k.get("valu_insts_per_launch"):
-            # How much of the chip's VALU issue capacity the timed step uses: wave-instructions of the traversal and shading
-            # launches of a step (PMC: SQ_INSTS_VALU per launch of the committed passes; the small rounds' single launches scaled by
-            # their rays) x 4 cycles per wave64 instruction per SIMD (the step's mix issues at 3.9-4.3, tools/ubench/valu_rate)
-            # over 1024 SIMDs x 2.4 GHz x ms_per_step. This -- not HBM -- is the roof the path runs under.
-            insts = timed_k["valu_insts_per_launch"] * timed_k["launches"]
-            small = timed_k.get("rounds_below_min_rays_run_single_launch")
-            if small and whole_k.get("valu_insts_per_launch") and whole_k["R"]:
-                insts += whole_k["valu_insts_per_launch"] * whole_k["launches"] * (small["R"] / whole_k["R"])
-            e_sh, _ = pmc_entry(args.scene, args.width, args.height, "rt_shade<false, false, false>")   # TEX, MULTI, BOTH: the texture-less, single-hierarchy, one-lobe instantiation the bench scenes run
-            sh = (e_sh or {}).get("sq_per_launch", {}).get("SQ_INSTS_VALU")
-            if sh:
-                insts += sh * len(round_log)
-            timed_k["valu_wave_insts_per_step"] = insts / args.steps
-            timed_k["valu_issue_frac_of_step"] = insts / args.steps * VALU_QUAD_CYCLES / (SIMDS * 2.4e9 * ms_step * 1e-3)
-            timed_k["valu_issue_frac_of_step_covers"] = "traversal + shading launches" if sh else "traversal launches"
-        roof = roofline(timed_k, whole_k, (Rr * 44 + V * 64 + T * 36) / args.steps, ms_step, copy_gbs)  # rank 0's launches
+        if args.full:
+            st = kst
+            copy_gbs = ctx.copy_bandwidth(1 << 30, 5)  # the box's achievable ceiling next to the vendor peak
+            # which rounds of the timed region ran the hand-over kernel: plan_traverse's rule (csrc/trace.hip) -- frames in flight
+            # (or a forced hand-over schedule) and at least phase_min_rays rays in the round
+            min_rays = 1 << 19
+            if args.trav_adaptive and len(args.trav_adaptive.split(",")) >= 5:
+                min_rays = int(args.trav_adaptive.split(",")[4])
+            hand = args.traverse in ("phased", "adaptive") or (args.traverse == "auto" and R.lanes > 1)
+            ho_rounds = [r for r in round_log if hand and r[0] >= min_rays]
+            wh_rounds = [r for r in round_log if not (hand and r[0] >= min_rays)]
+            assert (ho_launches > 0) == (len(ho_rounds) > 0), (ho_launches, len(ho_rounds))
+            ms_step = elapsed / args.steps * 1e3
+            how = ("the call of the timed region repeated with HIP events around every traversal launch on every lane's stream "
+                   "(%d frame(s) in flight: a launch shares the chip with the other frames' kernels); that pass ran at %.3f ms per "
+                   "step against %.3f timed" % (R.lanes, ev_elapsed / args.steps * 1e3, ms_step))
+            sums = lambda rs: (sum(r[0] for r in rs), sum(r[1] for r in rs), sum(r[2] for r in rs))
+            whole_frame = not dist.active and not args.emulate_tile
+            if ho_rounds:
+                timed_k = price("rt_traverse<false, false, true>", ho_launches, ho_ms, *sums(ho_rounds), len(ho_rounds), args.steps,
+                                args.scene, args.width, args.height, how, whole_frame)
+                if wh_launches:
+                    timed_k["rounds_below_min_rays_run_single_launch"] = price(
+                        "rt_traverse<false, false, false>", wh_launches, wh_ms, *sums(wh_rounds), len(wh_rounds), args.steps,
+                        args.scene, args.width, args.height, how, whole_frame)
+            else:
+                timed_k = price("rt_traverse<false, false, false>", wh_launches, wh_ms, *sums(wh_rounds), len(wh_rounds), args.steps,
+                                args.scene, args.width, args.height, how, whole_frame)
+            whole_k = price("rt_traverse<false, false, false>", st.traverse_launches, st.traverse_ms, Rr, V, T, len(round_log), args.steps,
+                            args.scene, args.width, args.height,
+                            "serial kernel pass: the same frames one after another on one stream, every launch alone on the chip", whole_frame)
+            # launches of different frames overlap: their summed durations exceed the wall time; the union of their intervals is
+            # the time during which traversal is on the chip at all, and the ratio is how many run side by side on average
+            timed_k["traversal_busy_ms_per_step"] = busy_ms / args.steps
+            timed_k["launches_side_by_side"] = (ho_ms + wh_ms) / busy_ms if busy_ms > 0 else None
+            timed_k["achieved_over_busy_time"] = (Rr * 44 + V * 64 + T * 36) / (busy_ms * 1e-3) / 1e9 if busy_ms > 0 else None
+            if timed_k.get("traffic") and busy_ms > 0:
+                # chip level: the HBM-side bytes of all traversal launches of a step over the time traversal is on the chip
+                tot = timed_k["traffic"] * timed_k["launches"]
+                small = timed_k.get("rounds_below_min_rays_run_single_launch")
+                if small and small.get("traffic"):
+                    tot += small["traffic"] * small["launches"] * (small["algorithmic_bytes_per_launch"] / max(whole_k["algorithmic_bytes_per_launch"], 1.0))
+                timed_k["hbm_gbs"] = tot / (busy_ms * 1e-3) / 1e9
+                timed_k["hbm_frac"] = timed_k["hbm_gbs"] / HBM_PEAK_GBS
+                timed_k["hbm_frac_note"] = ("HBM-side bytes (PMC: 2 x FETCH_SIZE + WRITE_SIZE per launch, committed passes) of all traversal "
+                                            "launches of a step over traversal_busy_ms_per_step, the time at least one of them is on the chip")
+            if whole_frame and timed_k.get("valu_insts_per_launch"):
+                # How much of the chip's VALU issue capacity the timed step uses: wave-instructions of the traversal and shading
+                # launches of a step (PMC: SQ_INSTS_VALU per launch of the committed passes; the small rounds' single launches scaled by
+                # their rays) x 4 cycles per wave64 instruction per SIMD (the step's mix issues at 3.9-4.3, tools/ubench/valu_rate)
+                # over 1024 SIMDs x 2.4 GHz x ms_per_step. This -- not HBM -- is the roof the path runs under.
+                insts = timed_k["valu_insts_per_launch"] * timed_k["launches"]
+                small = timed_k.get("rounds_below_min_rays_run_single_launch")
+                if small and whole_k.get("valu_insts_per_launch") and whole_k["R"]:
+                    insts += whole_k["valu_insts_per_launch"] * whole_k["launches"] * (small["R"] / whole_k["R"])
+                e_sh, _ = pmc_entry(args.scene, args.width, args.height, "rt_shade<false, false, false>")   # TEX, MULTI, BOTH: the texture-less, single-hierarchy, one-lobe instantiation the bench scenes run
+                sh = (e_sh or {}).get("sq_per_launch", {}).get("SQ_INSTS_VALU")
+                if sh:
+                    insts += sh * len(round_log)
+                timed_k["valu_wave_insts_per_step"] = insts / args.steps
+                timed_k["valu_issue_frac_of_step"] = insts / args.steps * VALU_QUAD_CYCLES / (SIMDS * 2.4e9 * ms_step * 1e-3)
+                timed_k["valu_issue_frac_of_step_covers"] = "traversal + shading launches" if sh else "traversal launches"
+            roof = roofline(timed_k, whole_k, (Rr * 44 + V * 64 + T * 36) / args.steps, ms_step, copy_gbs)  # rank 0's launches
         out = {
             "metric": "Mrays/sec + ms/frame, Sponza 1920x1080 4spp",
             "value": total_rays / elapsed / 1e6,
@@ -903,32 +947,38 @@ def main():
                                        "psm_dist_* (transport %s%s)" % (R.native.transport, ": a REHEARSAL, the ranks share a GPU and exchange through host memory -- not a scaling measurement" if R.hoststaged else " from libpsm_hip.so")
                                        if R.native is not None else "torch.distributed " + dist.backend)},
             "rays_per_frame": total_rays / args.steps,
-            "traverse_mrays_s": (Rr / (st.traverse_ms * 1e-3) / 1e6) if st.traverse_ms > 0 else None,
-            "stage_ms_per_frame_measured": ("serial kernel pass: the same frames one after another on one stream (with frames in "
-                                            "flight the stages of different frames overlap, so these do not add up to ms_per_step)"),
-            "stage_ms_per_frame": {"build": st.build_ms / args.steps, "bounds": st.bounds_ms / args.steps,
-                                   "morton": st.morton_ms / args.steps, "sort": st.sort_ms / args.steps,
-                                   "emit_refit": st.emit_ms / args.steps,
-                                   "camera": st.camera_ms / args.steps, "traverse": st.traverse_ms / args.steps,
-                                   "shade": st.shade_ms / args.steps, "sample": st.sample_ms / args.steps},
-            "timing": {"repeats": len(samples), "what": "the timed call of `steps` steps taken this many times over the same frames; value and ms_per_step are the median call's",
-                       "ms_per_step_median": elapsed / args.steps * 1e3, "ms_per_step_min": min(samples) / args.steps * 1e3,
-                       "ms_per_step_max": max(samples) / args.steps * 1e3, "ms_per_step_all": [t_ / args.steps * 1e3 for t_ in samples]},
-            "roofline": roof,
-            "image_mean": float(img[..., :3].mean()),
         }
+        if args.full:
+            out.update({
+                "traverse_mrays_s": (Rr / (st.traverse_ms * 1e-3) / 1e6) if st.traverse_ms > 0 else None,
+                "stage_ms_per_frame_measured": ("serial kernel pass: the same frames one after another on one stream (with frames in "
+                                                "flight the stages of different frames overlap, so these do not add up to ms_per_step)"),
+                "stage_ms_per_frame": {"build": st.build_ms / args.steps, "bounds": st.bounds_ms / args.steps,
+                                       "morton": st.morton_ms / args.steps, "sort": st.sort_ms / args.steps,
+                                       "emit_refit": st.emit_ms / args.steps,
+                                       "camera": st.camera_ms / args.steps, "traverse": st.traverse_ms / args.steps,
+                                       "shade": st.shade_ms / args.steps, "sample": st.sample_ms / args.steps}})
+        out["timing"] = {"repeats": len(samples), "what": "the timed call of `steps` steps taken this many times over the same frames; value and ms_per_step are the median call's",
+                         "ms_per_step_median": elapsed / args.steps * 1e3, "ms_per_step_min": min(samples) / args.steps * 1e3,
+                         "ms_per_step_max": max(samples) / args.steps * 1e3, "ms_per_step_all": [t_ / args.steps * 1e3 for t_ in samples]}
+        if args.full:
+            out["roofline"] = roof
+        out["image_mean"] = float(img[..., :3].mean())
         if dist.active:
-            mm = lambda col: {"min": min(r[col] for r in per_rank), "max": max(r[col] for r in per_rank)}
             out["ranks"] = {
                 "world": world, "transport": R.native.transport if R.native is not None else "torch.distributed " + dist.backend,
                 "comm_ranks": R.native.comm_ranks if R.native is not None else None,
-                "frames_in_flight_per_rank": R.active_lanes, "lane_calibration": lane_cal, "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
-                "rays_traced_per_rank": [int(r[0]) for r in per_rank],
-                "per_frame_ms_over_ranks": {"what": "serial kernel pass of every rank (its tile's frames one after another); gather: pack + gather + rank 0's unpack, 5 in a row",
-                                            "build": mm(1), "traverse": mm(2), "shade": mm(3), "gather": mm(4) if R.native is not None else None}}
+                "frames_in_flight_per_rank": R.active_lanes, "lane_calibration": lane_cal, "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")}
+            if per_rank is not None:
+                mm = lambda col: {"min": min(r[col] for r in per_rank), "max": max(r[col] for r in per_rank)}
+                out["ranks"].update({
+                    "rays_traced_per_rank": [int(r[0]) for r in per_rank],
+                    "per_frame_ms_over_ranks": {"what": "serial kernel pass of every rank (its tile's frames one after another); gather: pack + gather + rank 0's unpack, 5 in a row",
+                                                "build": mm(1), "traverse": mm(2), "shade": mm(3), "gather": mm(4) if R.native is not None else None}})
             # the communicator's own count (ncclCommCount) next to n_gpus: what proves that N ranks took part
             out["rccl_ranks"] = R.native.comm_ranks if (R.native is not None and R.native.transport == "rccl") else None
-            out["sharded_check"] = check["result"] if check else ("not run: one rank" if world == 1 else "not run: no native communicator")
+            out["sharded_check"] = check["result"] if check else ("not run: one rank" if world == 1 else "not run: needs --full" if not args.full
+                                                                  else "not run: no native communicator")
             out["sharded_check_detail"] = check
         if dist.active and R.hoststaged:
             # ranks that share one GPU and exchange through host memory: a rehearsal of the scheduler, never a scaling

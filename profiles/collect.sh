@@ -21,7 +21,7 @@ OUT=$REPO/gpurun_out
 ( cd $REPO && sha256sum prismarine-core_amd/csrc/trace.hip prismarine-core_amd/csrc/shade.hip prismarine-core_amd/csrc/psm_common.h prismarine-core_amd/csrc/psm_math.h prismarine-core_amd/csrc/psm_internal.h ) > $OUT/${TAG}_sources.sha256
 cd /tmp && export TMPDIR=/tmp
 export GPU_MAX_HW_QUEUES=8   # the profiler initialises the runtime before bench.py can set it
-B="python3 $REPO/bench.py --no-cpu-baseline --no-obj-roundtrip --repeats 1"
+B="python3 $REPO/bench.py --full --no-cpu-baseline --no-obj-roundtrip --repeats 1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_kt -- $B --steps $STEPS --warmup 2 $EXTRA > $OUT/${TAG}_kt_bench.json 2> $OUT/${TAG}_kt.err
 echo "kt done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_kt1 -- $B --steps $STEPS --warmup 2 --lanes 1 $EXTRA > $OUT/${TAG}_kt1_bench.json 2> $OUT/${TAG}_kt1.err

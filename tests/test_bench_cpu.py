@@ -113,3 +113,30 @@ def test_committed_traffic_file_matches_its_profiles():
         rows = [l.split() for l in open(os.path.join(ROOT, "profiles", "r05_%s_kt_stats.txt" % c)) if "false, false, tru" in l]
         avg_us = float(rows[0][-2])
         assert abs(avg_us - ents[(scene, "psm::rt_traverse<false, false, true>")]["in_flight_avg_us"]) < 0.01 * avg_us
+
+
+def test_dump_outputs_writes_the_image_whole_or_a_seeded_sample(tmp_path):
+    """--dump-outputs: the accumulated image whole where it fits, a seeded texel sample where it does not (C5's 2160p image:
+    133 MB), every frame's rounds and rays; float32 / float64 only, 64 MB at most in all, the same files for the same inputs."""
+    bench = importlib.import_module("bench")
+    import numpy as np
+    rng = np.random.RandomState(3)
+    small = rng.rand(184, 320, 4).astype(np.float32)
+    frames = [(7, 123456), (9, 123001)]
+    bench.dump_outputs(str(tmp_path / "a"), small, frames)
+    assert sorted(os.listdir(tmp_path / "a")) == ["frame_rays.npy", "frame_rounds.npy", "image.npy"]
+    img = np.load(tmp_path / "a" / "image.npy")
+    assert img.dtype == np.float32 and np.array_equal(img, small)
+    assert np.load(tmp_path / "a" / "frame_rounds.npy").tolist() == [7.0, 9.0]
+    assert np.load(tmp_path / "a" / "frame_rays.npy").dtype == np.float64
+    big = rng.rand(2160, 3840, 4).astype(np.float32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, None)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["image_sample.npy", "image_sample_texel.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= 64 << 20
+    sample, texel = np.load(tmp_path / "b" / "image_sample.npy"), np.load(tmp_path / "b" / "image_sample_texel.npy")
+    assert sample.dtype == np.float32 and texel.dtype == np.float64 and sample.shape == (texel.shape[0], 4)
+    assert np.array_equal(sample, big.reshape(-1, 4)[texel.astype(np.int64)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))

@@ -222,13 +222,13 @@ def test_missing_peer_times_out_instead_of_hanging(psm, ctx):
 
 
 def _bench_ranks(tmp_path, world, extra_env=None, timeout=420):
-    """bench.py --gpus N the way a user starts it (it spawns its ranks itself), the ranks sharing GPU 0 over the host-staged
-    transport: a rehearsal line (value null) -- here for its self-check and its multi-rank fields."""
+    """bench.py --gpus N --full the way a user starts it (it spawns its ranks itself), the ranks sharing GPU 0 over the host-staged
+    transport: a rehearsal line (value null) -- here for its self-check and its multi-rank fields (both --full only)."""
     env = dict(os.environ, PSM_DIST_TRANSPORT="hoststaged", PSM_DIST_BACKEND="gloo", **(extra_env or {}))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--scene", "cornell", "--width", "320", "--height", "184",
-                           "--steps", "4", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--no-obj-roundtrip"],
+                           "--steps", "4", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--no-obj-roundtrip", "--full"],
                           env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
 
 

@@ -18,6 +18,7 @@ case $what in
     tail -3 gpurun_out/gputests.log ;;
   bench)
     tag=$1; shift
+    set -- --full "$@"   # the summary reads the roofline object: --full only
     timeout -k 10 900 python bench.py "$@" > gpurun_out/$tag.json 2> gpurun_out/$tag.err || { tail -20 gpurun_out/$tag.err; exit 1; }
     python - <<PY
 import json
@@ -49,6 +50,7 @@ PY
     bash profiles/collect.sh "$@" ;;
   rehearsal)
     tag=$1; shift
+    set -- --full "$@"   # the summary reads sharded_check and the per-rank rays: --full only
     for n in 2 4; do
       PSM_DIST_TRANSPORT=hoststaged PSM_DIST_BACKEND=gloo timeout -k 10 400 python bench.py --gpus $n --steps 16 --warmup 4 --no-cpu-baseline --repeats 2 "$@" > gpurun_out/${tag}_gpus${n}_hoststaged.json 2> gpurun_out/${tag}_gpus${n}.err || { tail -20 gpurun_out/${tag}_gpus${n}.err; exit 1; }
       python - <<PY
