@@ -39,7 +39,11 @@ constexpr int TRAV_BLOCK = PSM_TRAV_BLOCK;
 constexpr uint32_t XCD_RUN = PSM_XCD_GROUP;
 
 // (leaf tests run once half of a wave's lanes with work wait for one: a third is equal, two thirds and more lose 2-18 %,
-// profiles/r03_park_trigger.txt)
+// profiles/r03_park_trigger.txt; re-swept with the one-pass leaf block: two fifths and a third equal within the noise, two
+// thirds 2 % slower, profiles/r06_leaf_block.txt). PSM_PARK_X2: the wave keeps stepping while nl > np * PSM_PARK_X2 / 2.
+#ifndef PSM_PARK_X2
+#define PSM_PARK_X2 4
+#endif
 
 struct Slab {
     float hit, near;
@@ -118,6 +122,34 @@ PSM_D float tri_test(const float4* __restrict__ tri48, int tri, v3 orig, v3 dir,
     U = u;
     V = v;
     return t;
+}
+
+// tri_test with the ray taken from lane sa / 4 of the wave (ds_bpermute): the leaf block's helper lanes run another lane's test
+// (`run`: this lane has a test). Every operation of tri_test on the same operands, so the same d, u, v bit for bit; its four
+// early exits become one flag, as the permutes need every lane of the wave active. The ray arrives in two halves, origin first,
+// each where it is used: the block has no register to hold a second copy of the whole ray (64 VGPRs, 8 waves per SIMD).
+PSM_D float pull_f(float x, int sa) { return u2f((uint32_t)__builtin_amdgcn_ds_bpermute(sa, (int)f2u(x))); }
+PSM_D float tri_test_pulled(const float4* __restrict__ tri48, int tri, bool run, int sa, v3 orig_, v3 dir_, float& U, float& V) {
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a, c = a;
+    if (run) { a = tri48[(size_t)3 * tri + 0]; b = tri48[(size_t)3 * tri + 1]; c = tri48[(size_t)3 * tri + 2]; }
+    const v3 v0 = mk3(a.x, a.y, a.z), e1 = mk3(b.x, b.y, b.z), e2 = mk3(c.x, c.y, c.z);
+    const v3 orig = mk3(pull_f(orig_.x, sa), pull_f(orig_.y, sa), pull_f(orig_.z, sa));
+    const v3 tvec = orig - v0;
+    const v3 qvec = cross3(tvec, e1);
+    __builtin_amdgcn_sched_barrier(0);   // (else the scheduler issues all six permutes together: two copies of the ray at once)
+    const v3 dir = mk3(pull_f(dir_.x, sa), pull_f(dir_.y, sa), pull_f(dir_.z, sa));
+    const v3 pvec = cross3(dir, e2);
+    const float vd = dot3(dir, qvec);
+    const float det = dot3(e1, pvec);
+    const float invDev = 1.f / (pmax(pabs(det), 0.000001f) * psign(det));
+    const float u = dot3(tvec, pvec) * invDev;
+    const float v = vd * invDev;
+    const float t = dot3(e2, qvec) * invDev;
+    // tri_test's four exits as one flag: the same values, the same decision
+    const bool hit = run && !(pabs(det) <= 0.0f) && !(u < -0.00001f || u > 1.00001f) && !(v < -0.00001f || (u + v) > 1.00001f) && greaterEqualF(t, 0.0f);
+    U = hit ? u : U;
+    V = hit ? v : V;
+    return hit ? t : INF;
 }
 
 struct Baked {
@@ -541,29 +573,69 @@ __global__ __launch_bounds__(TRAV_BLOCK, 8) void rt_traverse(TravArgs ka) {
             wsteps++;
             const int thr1 = wsteps >= minSteps ? minLive1 : -1;   // nl > thr1  <=>  nl >= min_live once min_steps have run
             handover = (thr1 - nl) & (wsteps - capI);              // < 0: enough lanes live and below the cap
-            if (((max(np << 1, soloMax) - nl) & handover) < 0) continue;
-        } else if (nl > max(np << 1, soloMax)) continue;
+            if (((max((np * PSM_PARK_X2) >> 1, soloMax) - nl) & handover) < 0) continue;
+        } else if (nl > max((np * PSM_PARK_X2) >> 1, soloMax)) continue;
         const bool capHit = PHASED && handover >= 0;
         // nobody left -- or at most solo_max rays and nobody to hand them to: the wave walks those one at a time, all lanes on
         // one ray (below the loop). One more difference in the AND above and this compare are all the node step pays for it.
         if (nl <= soloMax) break;
-        if ((pl | pr) < 0) {  // testIntersectionPacked, :261-309
-            // both leaves: the nearer one first (:441-448); otherwise the one that is a leaf (pl, pr are 0 when not)
+        if (np != 0) {  // testIntersectionPacked, :261-309 -- the whole wave takes part (np is wave-uniform, every lane is active here)
+            // both leaves: the nearer one first (:441-448); otherwise the one that is a leaf (pl, pr are 0 when not; a lane that is
+            // not parked has tx = ty = -1 and no test)
             const bool lo = (pl < 0) && (pLeftNear != 0 || pr >= 0);
             const int tx = ~(lo ? pl : pr), ty = ~(lo ? pr : pl);  // triangle ids, -1 = none (~0)
             const bool validx = (tx >= 0) && (tx != lastTri);
             const bool validy = (ty >= 0) && (ty != lastTri) && (tx != ty);
-            int tri = validx ? tx : ty;       // first test: x, or y straight away when x is skipped
-            bool valid = validx || validy;
-            bool again = validx && validy;    // second test: y after x
-#pragma unroll 1
-            for (int pass = 0; pass < 2; pass++) {
-                if (valid) {
-                    float u = 0.f, v = 0.f;
-                    float d = tri_test(tri48, tri, origin, direct, u, v);
+            const int tri = validx ? tx : ty;     // first test: x, or y straight away when x is skipped
+            const bool valid = validx || validy;
+            const bool again = validx && validy;  // second test: y after x
+            // One pass for both tests of a pair. tri_test reads neither predist nor lastTri, so a pair's two tests are independent
+            // and only their acceptance is ordered. Every lane with a test runs its first one in its own lane; the second one
+            // (`again`) runs at the same time in a HELPER lane, one without a test of its own (stepping, done or outside the batch):
+            // the r-th `again` owner pairs with the r-th free lane (ranks by mbcnt over two ballots). The pairing goes through 64
+            // words of the solo gear's exchange area (free while this loop runs): owner r writes its lane to tbl[r], helper k reads
+            // tbl[k] and writes its own lane back. The helper pulls the ray and the triangle by ds_bpermute, the owner pulls d, u, v
+            // back and accepts x, then y, exactly as two serial passes would.
+            // (the lane number behind an opaque zero, computed here: otherwise it is hoisted out of the loop and held in a register
+            // across the node steps)
+            uint32_t zero;
+            asm volatile("s_mov_b32 %0, 0" : "=s"(zero));
+            const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
+            const unsigned long long vm = lane_mask(valid), am = lane_mask(again);
+            const uint32_t nFree = 64u - (uint32_t)__popcll(vm), nAgain = (uint32_t)__popcll(am);
+            const uint32_t rFree = __builtin_amdgcn_mbcnt_hi((uint32_t)(~vm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)~vm, 0u));
+            const uint32_t rAgain = __builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
+            const bool handed = again && rAgain < nFree;     // this lane's second test runs in a helper lane
+            const bool helper = !valid && rFree < nAgain;    // this lane runs another lane's second test
+            uint32_t* tbl = &xch[tid >> 6][0][0];            // 64 of the 128 words (TRAV_BLOCK 64: one wave, SOLO_MAX x XCH_WORDS)
+            int src = lane, hsrc = lane;
+            if (nAgain != 0u) {
+                if (handed) tbl[rAgain] = (uint32_t)lane;
+                // (one wave: its LDS operations execute in program order; the fences keep the compiler from moving the reads up)
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                if (helper) src = (int)tbl[rFree];
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                if (helper) tbl[rFree] = (uint32_t)lane;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                if (handed) hsrc = (int)tbl[rAgain];
+            }
+            // every lane active: a helper takes its owner's second triangle and ray, every other lane its own
+            const int sa = src << 2;
+            const int yt = __builtin_amdgcn_ds_bpermute(sa, ty);
+            float u = 0.f, v = 0.f;
+            float d = tri_test_pulled(tri48, helper ? yt : tri, valid || helper, sa, origin, direct, u, v);
+            // acceptance in the reference's order: the first test, then the second one. The second one's result is pulled into the
+            // registers of the first one once that has been accepted (one set of d, u, v live in the block, not two)
+            const auto accept = [&](bool run, float d, float u, float v, int tri) {
+                if (run) {
                     if (COUNT) nT++;
-                    bool near = lessF(d, INF) && lessEqualF(d, predist) && greaterEqualF(d, 0.0f);
-                    if (near) {
+                    if (lessF(d, INF) && lessEqualF(d, predist) && greaterEqualF(d, 0.0f)) {
                         if (!equalF(d, predist)) bakedCount = 0;
                         predist = d;
                         lastTri = tri;
@@ -573,16 +645,24 @@ __global__ __launch_bounds__(TRAV_BLOCK, 8) void rt_traverse(TravArgs ka) {
                         else if (COUNT) nBakedDrop++;
                     }
                 }
-                tri = ty;
-                valid = again;
-                again = false;
-            }
-            pl = 0; pr = 0;
+            };
+            accept(valid, d, u, v, tri);
+            const int ha = hsrc << 2;
+            d = pull_f(d, ha);
+            u = pull_f(u, ha);
+            v = pull_f(v, ha);
+            accept(handed, d, u, v, ty);
+            // More than 64 tests (more than 32 lanes parked): a second test left without a helper stays parked, as the pair's only
+            // leaf, and runs in the next block -- before the lane's next node step, as in the reference (ty != lastTri still holds:
+            // lastTri is now either what it was or tx).
+            pl = (again && !handed) ? ~ty : 0;
+            pr = 0;
         }
         if (capHit) {
             // every parked test has just run. Rays with work left and a chain of at most one hit hand their state
             // to the next launch (a longer chain lives in registers / scratch: such a ray, < 0.1 %, finishes here)
-            const bool susp = sp >= 0 && bakedCount <= 1;
+            // (a lane still parked -- a second test the block had no helper for -- is not handed over: it finishes here)
+            const bool susp = sp >= 0 && bakedCount <= 1 && (pl | pr) >= 0;
             const unsigned long long sb = lane_mask(susp);
             if (sb != 0ull) {
                 const TravArgs* K = cold_args();
@@ -604,9 +684,9 @@ __global__ __launch_bounds__(TRAV_BLOCK, 8) void rt_traverse(TravArgs ka) {
                     suspendedFlag = true;
                 }
             }
-            if (lane_mask(sp >= 0) == 0ull) break;
+            if (lane_mask((sp >= 0) || ((pl | pr) < 0)) == 0ull) break;
         }
-        stepping = sp >= 0;   // nobody is parked now
+        stepping = (sp | pl | pr) >= 0;   // (a lane can still be parked: see the end of the leaf block)
     }
     // The solo gear (solo_ray): the rays the loop above has left are walked one at a time, all lanes on one ray. (Behind the
     // loop, not in it: inside, its values would be live across the node steps, which have no register to spare.)
