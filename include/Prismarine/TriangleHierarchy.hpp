@@ -42,6 +42,10 @@ namespace NSM {
         void configureIntersection(bool clearDepth);
         void refit();                     // not in the reference: boxes only, for triangles reloaded in place; the tree is the last build's
         void setBuildGraph(bool enable);  // not in the reference: replay rebuilds as one captured hipGraph (default on)
+        // not in the reference: closest hit / any hit of n rays over device arrays (psm_bvh_intersect_dev / psm_bvh_occluded_dev),
+        // stream-ordered on the context; returns the psm_status
+        int intersect(const psm_query_ray * d_rays, size_t n, psm_hit * d_hits);
+        int occluded(const psm_query_ray * d_rays, size_t n, uint8_t * d_hit);
         psm_bvh * handle() { return bvh; }
     };
 }

@@ -32,6 +32,16 @@ namespace NSM {
     }
 
     inline void TriangleHierarchy::refit() { if (bvh) { check(psm_bvh_refit(bvh), "TriangleHierarchy::refit"); this->resolve(); } }
+    inline int TriangleHierarchy::intersect(const psm_query_ray * d_rays, size_t n, psm_hit * d_hits) {
+        const int rc = psm_bvh_intersect_dev(bvh, d_rays, n, d_hits);
+        check(rc, "TriangleHierarchy::intersect");
+        return rc;
+    }
+    inline int TriangleHierarchy::occluded(const psm_query_ray * d_rays, size_t n, uint8_t * d_hit) {
+        const int rc = psm_bvh_occluded_dev(bvh, d_rays, n, d_hit);
+        check(rc, "TriangleHierarchy::occluded");
+        return rc;
+    }
     inline void TriangleHierarchy::setBuildGraph(bool enable) { if (bvh) check(psm_bvh_set_build_graph(bvh, enable ? 1 : 0), "TriangleHierarchy::setBuildGraph"); }
     inline void TriangleHierarchy::configureIntersection(bool clearDepth) { (void)clearDepth; }  // ignored by the reference's shaders too
 

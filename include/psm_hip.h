@@ -344,6 +344,33 @@ int psm_rt_upload_rays(psm_rt* rt, const psm_ray* src, uint32_t count);
 int psm_rt_download_texels(psm_rt* rt, float* sum_rgba, float* coord_xy, int32_t* flags);
 
 /* ---------------------------------------------------------------------------------------------
+ * ray queries against a built hierarchy (new; no reference counterpart): batched closest-hit and any-hit over device arrays,
+ * beside the Pipeline's wavefront traversal (psm_rt_traverse keeps directTraverse.comp's semantics). Semantics:
+ *   - a ray is {origin, tmin, direct, tmax}; direct is normalised with normalize3 (the pipeline's) and t is the distance along
+ *     that unit direction, as the oracle's brute force measures it
+ *   - the candidates are the hierarchy's leaves (PSM_BVH_LEAF_TRI: the triangles the build kept), by load-order triangle id
+ *   - the triangle test is intersectTriangle's arithmetic (tri_test) without the clamp of |det| at 1e-6: invDev = 1 / det,
+ *     det == 0 is a miss, the 1e-5 tolerances on u, v, u + v stay. Where |det| >= 1e-6 the values are tri_test's bit for bit
+ *   - a hit counts iff tmin <= t <= tmax as floats (no PZERO / INF = 10000 rule). A miss: NaN in any operand, a non-finite
+ *     origin or direction, a zero direction, tmin > tmax
+ *   - closest: the smallest t; on bit-equal t the lowest triangle id -- the result does not depend on the traversal order.
+ *     psm_hit {u, v, t, tri}; a miss is {0, 0, +inf, -1}
+ *   - any: d_hit[i] = 1 iff some candidate is hit inside the window, else 0 (uint8_t, torch.bool-compatible)
+ *   - a hierarchy of 0 leaves misses everything; one of 1 leaf tests that leaf
+ *   - after psm_bvh_refit the refitted boxes are used; as for every refit this is right only for triangles that moved within
+ *     the build's bounds (the fit transform and the fp16 box padding are the build's)
+ * Stream-ordered on the hierarchy's context, no host synchronisation (a query can be captured into a graph, except the first one
+ * of a context, which allocates its stack area). The stack is sized to the builder's height bound (63 Morton bits + log2 of the
+ * largest run of equal codes): no subtree is ever dropped. Any n; d_rays and d_hits 16-byte aligned (PSM_ERR_INVALID otherwise);
+ * n = 0 is a no-op; PSM_ERR_STATE before the first build (as psm_rt_traverse). */
+typedef struct {
+    float origin[3], tmin;
+    float direct[3], tmax;
+} psm_query_ray; /* 32 B: two 16-byte loads */
+int psm_bvh_intersect_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits);
+int psm_bvh_occluded_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, uint8_t* d_hit);
+
+/* ---------------------------------------------------------------------------------------------
  * several frames in flight (new; DESIGN.md "lanes")
  * `frames` x GltfViewer::process() (Viewer.cpp:296-312) with up to `lanes` of them in flight: lane s =
  * (rts[s], bvhs[s]) on its own context / stream. Frame f has its own CRT-rand() stand-in, started from

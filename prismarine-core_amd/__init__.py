@@ -25,7 +25,7 @@ EXPORTS = [
     "psm_sort_u64_u32", "psm_sort_u64_u32_dev", "psm_sort_set_algorithm", "psm_sort_get_algorithm",
     "psm_bvh_create", "psm_bvh_destroy", "psm_bvh_clear", "psm_bvh_load_triangles", "psm_bvh_set_texcoords", "psm_bvh_load_mesh", "psm_bvh_build", "psm_bvh_set_build_graph", "psm_bvh_refit",
     "psm_bvh_get_info", "psm_bvh_stage_bounds", "psm_bvh_stage_morton", "psm_bvh_stage_sort",
-    "psm_bvh_stage_emit", "psm_bvh_download",
+    "psm_bvh_stage_emit", "psm_bvh_download", "psm_bvh_intersect_dev", "psm_bvh_occluded_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -47,6 +47,7 @@ TRAVERSE_MODES = {"auto": TRAVERSE_AUTO, "whole": TRAVERSE_WHOLE, "phased": TRAV
 RAY_DT = np.dtype([("origin", "<f4", 3), ("direct", "<f4", 3), ("color", "<f4", 3),
                    ("bitfield", "<i4"), ("texel", "<i4"), ("pkey", "<u4")])
 HIT_DT = np.dtype([("u", "<f4"), ("v", "<f4"), ("t", "<f4"), ("tri", "<i4")])
+QUERY_RAY_DT = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direct", "<f4", 3), ("tmax", "<f4")])   # psm_query_ray
 LIGHT_DT = np.dtype([("lightVector", "<f4", 4), ("lightColor", "<f4", 4),
                      ("lightOffset", "<f4", 4), ("lightAmbient", "<f4", 4)])
 
@@ -361,6 +362,46 @@ class TriangleHierarchy:
         self.ctx.check(lib().psm_bvh_refit(self._h), "psm_bvh_refit")
         self.resolve()
 
+    def intersect(self, origins, directions, tmin=0.0, tmax=np.inf):
+        """Closest hit of every ray (psm_bvh_intersect_dev; not in the reference): origins, directions [n, 3], tmin / tmax scalars or
+        per-ray [n]. numpy in: numpy out (staged through device buffers; synchronises). torch device tensors in: torch tensors out on
+        the same device, no copy through the host, ordered against torch's current stream without synchronising. Returns QueryHits:
+        t, u, v, tri (tri = -1, t = +inf on a miss) as views of one [n, 4] float32 buffer (u, v, t, tri as int32 bits)."""
+        return self._query(origins, directions, tmin, tmax, False)
+
+    def occluded(self, origins, directions, tmin=0.0, tmax=np.inf):
+        """Any hit inside [tmin, tmax] per ray (psm_bvh_occluded_dev; not in the reference): a bool array / tensor. Arguments and
+        placement as intersect()."""
+        return self._query(origins, directions, tmin, tmax, True)
+
+    def _query(self, origins, directions, tmin, tmax, any_hit):
+        if type(origins).__module__.split(".")[0] == "torch":
+            return _query_torch(self, origins, directions, tmin, tmax, any_hit)
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError("origins and directions: %d against %d rays" % (n, d.shape[0]))
+        rays = np.empty((n, 8), np.float32)
+        rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7] = o, tmin, d, tmax
+        out_bytes = n if any_hit else 16 * n
+        hr, ho = self.ctx.buf_alloc(max(32 * n, 32)), self.ctx.buf_alloc(max(out_bytes, 16))
+        try:
+            if n:
+                self.ctx.buf_upload(hr, rays)
+            fn = lib().psm_bvh_occluded_dev if any_hit else lib().psm_bvh_intersect_dev
+            self.ctx.check(fn(self._h, C.c_void_p(self.ctx.buf_ptr(hr)[0]), C.c_size_t(n), C.c_void_p(self.ctx.buf_ptr(ho)[0])),
+                           "psm_bvh_occluded_dev" if any_hit else "psm_bvh_intersect_dev")
+            if n == 0:
+                self.ctx.sync()
+                return np.zeros(0, np.bool_) if any_hit else QueryHits(np.zeros((0, 4), np.float32))
+            if any_hit:
+                return self.ctx.buf_download(ho, np.uint8, n).view(np.bool_)
+            return QueryHits(self.ctx.buf_download(ho, np.float32, 4 * n).reshape(n, 4))
+        finally:
+            self.ctx.buf_free(hr)
+            self.ctx.buf_free(ho)
+
     def setBuildGraph(self, enable=True):
         """Replay rebuilds as one captured hipGraph from the second build of a triangle count on (default), or keep plain launches."""
         self.ctx.check(lib().psm_bvh_set_build_graph(self._h, C.c_int(1 if enable else 0)), "psm_bvh_set_build_graph")
@@ -389,6 +430,78 @@ class TriangleHierarchy:
         if self._h:
             lib().psm_bvh_destroy(self._h)
             self._h = C.c_void_p()
+
+
+class QueryHits:
+    """Closest hits of TriangleHierarchy.intersect: `buffer` [n, 4] float32 (numpy array or torch tensor) holds psm_hit records
+    (u, v, t, tri); t, u, v and tri (int32) are views of it."""
+
+    def __init__(self, buffer):
+        self.buffer = buffer
+        self.u, self.v, self.t = buffer[:, 0], buffer[:, 1], buffer[:, 2]
+        if isinstance(buffer, np.ndarray):
+            self.tri = buffer.view(np.int32)[:, 3]
+        else:
+            import torch
+            self.tri = buffer.view(torch.int32)[:, 3]
+
+    def __len__(self):
+        return self.buffer.shape[0]
+
+
+_hip_lib = None
+
+
+def _hip():
+    """The HIP runtime libpsm_hip.so runs on (loaded once per process; torch's streams and events are its handles). torch's own
+    cross-stream waits reject a stream it did not create (ExternalStream), so the two waits of _query_torch are made here."""
+    global _hip_lib
+    if _hip_lib is None:
+        lib()
+        _hip_lib = C.CDLL("libamdhip64.so.7", mode=C.RTLD_GLOBAL)
+    return _hip_lib
+
+
+def _hip_check(rc, what):
+    if rc != 0:
+        raise PsmError("%s failed (%d)" % (what, rc))
+
+
+def _query_torch(th, origins, directions, tmin, tmax, any_hit):
+    """TriangleHierarchy.intersect / occluded on torch device tensors: rays packed on torch's current stream, the kernel on the
+    context's stream, the two ordered by events when they differ -- no host synchronisation."""
+    import torch
+    dev = origins.device
+    if dev.type != "cuda" or directions.device != dev:
+        raise ValueError("intersect / occluded: origins and directions must be tensors on the context's device")
+    o = origins.reshape(-1, 3)
+    d = directions.reshape(-1, 3)
+    n = o.shape[0]
+    if d.shape[0] != n:
+        raise ValueError("origins and directions: %d against %d rays" % (n, d.shape[0]))
+    rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    rays[:, 0:3] = o
+    rays[:, 3] = torch.as_tensor(tmin, dtype=torch.float32, device=dev)
+    rays[:, 4:7] = d
+    rays[:, 7] = torch.as_tensor(tmax, dtype=torch.float32, device=dev)
+    out = torch.empty((n,) if any_hit else (n, 4), dtype=torch.uint8 if any_hit else torch.float32, device=dev)
+    cur = torch.cuda.current_stream(dev)
+    mine = th.ctx.stream or 0   # (NULL: the device's null stream, torch's default stream)
+    other = mine != cur.cuda_stream
+    if other:   # the context's stream waits for the packing above (torch's event, HIP's wait: no host synchronisation)
+        ev_in = torch.cuda.Event()
+        ev_in.record(cur)
+        _hip_check(_hip().hipStreamWaitEvent(C.c_void_p(mine), C.c_void_p(ev_in.cuda_event), C.c_uint(0)), "hipStreamWaitEvent")
+    fn = lib().psm_bvh_occluded_dev if any_hit else lib().psm_bvh_intersect_dev
+    th.ctx.check(fn(th._h, C.c_void_p(rays.data_ptr()), C.c_size_t(n), C.c_void_p(out.data_ptr())),
+                 "psm_bvh_occluded_dev" if any_hit else "psm_bvh_intersect_dev")
+    if other:   # ... and torch's stream for the kernel: every later use of `out`, and of the memory of `rays`, comes after it
+        hip, ev = _hip(), C.c_void_p()
+        _hip_check(hip.hipEventCreateWithFlags(C.byref(ev), C.c_uint(2)), "hipEventCreateWithFlags")   # hipEventDisableTiming
+        _hip_check(hip.hipEventRecord(ev, C.c_void_p(mine)), "hipEventRecord")
+        _hip_check(hip.hipStreamWaitEvent(C.c_void_p(cur.cuda_stream), ev, C.c_uint(0)), "hipStreamWaitEvent")
+        _hip_check(hip.hipEventDestroy(ev), "hipEventDestroy")
+    return out.view(torch.bool) if any_hit else QueryHits(out)
 
 
 class TextureSet:

@@ -10,6 +10,8 @@
 
 namespace psm {
 
+void query_release(psm_ctx* c);   // query.hip
+
 constexpr int SM_COUNT = 24;
 constexpr int SM_ROOT = 25;
 constexpr int SM_BFLOAT = 26;
@@ -143,6 +145,7 @@ int psm_ctx_destroy(psm_ctx* c) {
     dev_free(c->sort_hist);
     if (c->sort_overflow) (void)hipHostFree(c->sort_overflow);
     dev_free(c->d_counters);
+    psm::query_release(c);   // query.hip: the ray queries' stack area
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return PSM_OK;

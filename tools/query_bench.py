@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""Ray-query benchmark (psm_bvh_intersect_dev / psm_bvh_occluded_dev): Mrays/s of closest hit and any hit over the Sponza-class
+scene's 1920 x 1080 camera rays, over as many bounce-like rays (origins at the primary hits, random directions in the hemisphere of
+the hit triangle's face normal), and psm_rt_traverse WHOLE over the same primary rays for comparison. Each figure: the median of
+REPS (5) device-synchronised calls after a warm-up call. Prints one JSON line.
+A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py"""
+import ctypes as C
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+psm = importlib.import_module("prismarine-core_amd")
+scenes = importlib.import_module("prismarine-core_amd.scenes")
+
+W, H = 1920, 1080
+REPS = int(os.environ.get("REPS", "5"))
+
+
+def median_ms(ctx, fn):
+    fn()
+    ctx.sync()
+    ts = []
+    for _ in range(REPS):
+        t0 = time.perf_counter()
+        fn()
+        ctx.sync()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
+def main():
+    sc = scenes.sponza_like()
+    ctx = psm.Context(0)
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(sc["tris"].shape[0])
+    th.loadTriangles(sc["tris"], sc["normals"], sc["mats"])
+    th.build()
+    rt = psm.Pipeline(ctx, seed=1000)
+    rt.resizeBuffers(W, H)
+    rt.resize(W, H)
+    cam = scenes.camera_matrices(sc["eye"], sc["view"], W, H)
+    rt.camera_matrices(cam[0], cam[1])
+    prim = rt.download_rays()
+    n = prim.shape[0]
+    o, d = prim["origin"].copy(), prim["direct"].copy()
+
+    lib = psm.lib()
+    h_rays, h_hits, h_occ = ctx.buf_alloc(32 * n), ctx.buf_alloc(16 * n), ctx.buf_alloc(n)
+    p_rays, p_hits, p_occ = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in (h_rays, h_hits, h_occ))
+
+    def upload(o, d, tmin):
+        r = np.zeros((n, 8), np.float32)
+        r[:, 0:3], r[:, 3], r[:, 4:7], r[:, 7] = o, tmin, d, np.inf
+        ctx.buf_upload(h_rays, r)
+
+    def closest():
+        ctx.check(lib.psm_bvh_intersect_dev(th._h, p_rays, C.c_size_t(n), p_hits), "psm_bvh_intersect_dev")
+
+    def anyhit():
+        ctx.check(lib.psm_bvh_occluded_dev(th._h, p_rays, C.c_size_t(n), p_occ), "psm_bvh_occluded_dev")
+
+    out = {"rays": n, "reps": REPS}
+    upload(o, d, 0.0)
+    out["primary_closest_ms"] = median_ms(ctx, closest)
+    out["primary_any_ms"] = median_ms(ctx, anyhit)
+    hits = ctx.buf_download(h_hits, np.float32, 4 * n).reshape(n, 4)
+    tri = hits.view(np.int32)[:, 3]
+    out["primary_hit_fraction"] = float((tri >= 0).mean())
+
+    # bounce-like rays: from the primary hits (rays that missed start at their origin), a cosine-ish direction about the face normal
+    # turned towards the incoming ray
+    rng = np.random.RandomState(7)
+    dn = d / np.linalg.norm(d, axis=1, keepdims=True)
+    hit = tri >= 0
+    bo = np.where(hit[:, None], o + dn * np.where(hit, hits[:, 2], 0)[:, None], o).astype(np.float32)
+    t3 = sc["tris"].reshape(-1, 3, 3)[np.maximum(tri, 0)]
+    nrm = np.cross(t3[:, 1] - t3[:, 0], t3[:, 2] - t3[:, 0])
+    nrm /= np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-30)
+    nrm = np.where((np.sum(nrm * dn, axis=1) > 0)[:, None], -nrm, nrm)
+    nrm = np.where(hit[:, None], nrm, dn)
+    u = rng.normal(size=(n, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    bd = (nrm + u).astype(np.float32)
+    upload(bo, bd, 1e-3)
+    out["bounce_closest_ms"] = median_ms(ctx, closest)
+    out["bounce_any_ms"] = median_ms(ctx, anyhit)
+
+    # the pipeline's traversal of the same primary rays, one launch (WHOLE)
+    rt.setTraverseMode("whole")
+    rt.upload_rays(prim)
+
+    def pipeline():
+        rt.resetHits()
+        rt.intersection(th, force=True)
+
+    out["pipeline_whole_ms"] = median_ms(ctx, pipeline)
+    for k in ("primary_closest", "primary_any", "bounce_closest", "bounce_any", "pipeline_whole"):
+        out[k + "_mrays_s"] = round(n / out[k + "_ms"] / 1e3, 1)
+        out[k + "_ms"] = round(out[k + "_ms"], 4)
+    for h in (h_rays, h_hits, h_occ):
+        ctx.buf_free(h)
+    rt.close()
+    th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
