@@ -46,6 +46,10 @@ namespace NSM {
         // stream-ordered on the context; returns the psm_status
         int intersect(const psm_query_ray * d_rays, size_t n, psm_hit * d_hits);
         int occluded(const psm_query_ray * d_rays, size_t n, uint8_t * d_hit);
+        // not in the reference: closest point within rmax / any triangle within rmax of n points over device arrays
+        // (psm_bvh_closest_point_dev / psm_bvh_within_dev), stream-ordered on the context; returns the psm_status
+        int closestPoint(const psm_point_query * d_points, size_t n, psm_hit * d_hits);
+        int within(const psm_point_query * d_points, size_t n, uint8_t * d_hit);
         psm_bvh * handle() { return bvh; }
     };
 }

@@ -42,6 +42,16 @@ namespace NSM {
         check(rc, "TriangleHierarchy::occluded");
         return rc;
     }
+    inline int TriangleHierarchy::closestPoint(const psm_point_query * d_points, size_t n, psm_hit * d_hits) {
+        const int rc = psm_bvh_closest_point_dev(bvh, d_points, n, d_hits);
+        check(rc, "TriangleHierarchy::closestPoint");
+        return rc;
+    }
+    inline int TriangleHierarchy::within(const psm_point_query * d_points, size_t n, uint8_t * d_hit) {
+        const int rc = psm_bvh_within_dev(bvh, d_points, n, d_hit);
+        check(rc, "TriangleHierarchy::within");
+        return rc;
+    }
     inline void TriangleHierarchy::setBuildGraph(bool enable) { if (bvh) check(psm_bvh_set_build_graph(bvh, enable ? 1 : 0), "TriangleHierarchy::setBuildGraph"); }
     inline void TriangleHierarchy::configureIntersection(bool clearDepth) { (void)clearDepth; }  // ignored by the reference's shaders too
 

@@ -370,6 +370,33 @@ typedef struct {
 int psm_bvh_intersect_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits);
 int psm_bvh_occluded_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, uint8_t* d_hit);
 
+/* point queries against a built hierarchy (new; no reference counterpart): closest point and within-radius over device arrays,
+ * on the same leaves, stack, context and checks as the ray queries above. Semantics:
+ *   - a query is {p, rmax}; the candidates are the hierarchy's leaves (PSM_BVH_LEAF_TRI) by load-order triangle id, a triangle
+ *     read as the build stores it: v0, e1 = v1 - v0, e2 = v2 - v0
+ *   - closest point on a triangle: Ericson's region test (vertex, edge and face regions) in terms of v0, e1, e2, one fixed
+ *     float32 operation order (query.hip closest_on_tri; tests/point_query_model.py restates it). The result is barycentrics u
+ *     (weight of e1) and v (weight of e2); the point is c = (v0 + u e1) + v e2 in every region; d2 = dot3(p - c, p - c),
+ *     dist = sqrtf(d2)
+ *   - degenerate triangles give a finite result for finite input: an edge region is taken only when its denominator is positive
+ *     (a zero-length edge never matches; the other regions decide); the face is taken only when aa bb - ab^2 > 2^-16 aa bb
+ *     (aa = e1.e1, ab = e1.e2, bb = e2.e2), otherwise the triangle is a sliver and c is the clamped projection onto its longest
+ *     edge; the face's u, v are clamped into the triangle (u in [0, 1], v in [0, 1 - u]). The cost of thin triangles, with s the
+ *     sine of the angle at v0 and L the longest edge: a face's dist is off by up to ~8 eps / s^2 L (float32 barycentrics), a
+ *     sliver's by up to s L (its width) -- up to ~2^-7 L near s = 2^-8, 1e-6 of the size for well-shaped and for collinear or
+ *     zero-area triangles. The result is still exact against the same formula over all leaves
+ *   - a candidate counts iff dist <= rmax. closest: the smallest d2, on a bit-equal d2 the lowest triangle id -- the result does
+ *     not depend on the traversal order. psm_hit {u, v, t = dist, tri}; a miss is {0, 0, +inf, -1}. (tri, u, v) reproduce c
+ *   - within: d_hit[i] = 1 iff some candidate counts, else 0 (uint8_t, torch.bool-compatible)
+ *   - a non-finite p, or an rmax that is NaN or negative, misses; rmax = +inf is no limit
+ *   - 0 / 1 leaves, refit, stream order, capture, alignment (d_points and d_hits 16-byte aligned), NULL checks, n = 0 and
+ *     PSM_ERR_STATE before the first build: as for the ray queries */
+typedef struct {
+    float p[3], rmax;
+} psm_point_query; /* 16 B: one 16-byte load */
+int psm_bvh_closest_point_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, psm_hit* d_hits);
+int psm_bvh_within_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, uint8_t* d_hit);
+
 /* ---------------------------------------------------------------------------------------------
  * several frames in flight (new; DESIGN.md "lanes")
  * `frames` x GltfViewer::process() (Viewer.cpp:296-312) with up to `lanes` of them in flight: lane s =

@@ -26,6 +26,7 @@ EXPORTS = [
     "psm_bvh_create", "psm_bvh_destroy", "psm_bvh_clear", "psm_bvh_load_triangles", "psm_bvh_set_texcoords", "psm_bvh_load_mesh", "psm_bvh_build", "psm_bvh_set_build_graph", "psm_bvh_refit",
     "psm_bvh_get_info", "psm_bvh_stage_bounds", "psm_bvh_stage_morton", "psm_bvh_stage_sort",
     "psm_bvh_stage_emit", "psm_bvh_download", "psm_bvh_intersect_dev", "psm_bvh_occluded_dev",
+    "psm_bvh_closest_point_dev", "psm_bvh_within_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -48,6 +49,7 @@ RAY_DT = np.dtype([("origin", "<f4", 3), ("direct", "<f4", 3), ("color", "<f4", 
                    ("bitfield", "<i4"), ("texel", "<i4"), ("pkey", "<u4")])
 HIT_DT = np.dtype([("u", "<f4"), ("v", "<f4"), ("t", "<f4"), ("tri", "<i4")])
 QUERY_RAY_DT = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direct", "<f4", 3), ("tmax", "<f4")])   # psm_query_ray
+POINT_QUERY_DT = np.dtype([("p", "<f4", 3), ("rmax", "<f4")])   # psm_point_query
 LIGHT_DT = np.dtype([("lightVector", "<f4", 4), ("lightColor", "<f4", 4),
                      ("lightOffset", "<f4", 4), ("lightAmbient", "<f4", 4)])
 
@@ -384,18 +386,51 @@ class TriangleHierarchy:
             raise ValueError("origins and directions: %d against %d rays" % (n, d.shape[0]))
         rays = np.empty((n, 8), np.float32)
         rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7] = o, tmin, d, tmax
-        out_bytes = n if any_hit else 16 * n
-        hr, ho = self.ctx.buf_alloc(max(32 * n, 32)), self.ctx.buf_alloc(max(out_bytes, 16))
+        return self._launch_np(rays, any_hit, "psm_bvh_occluded_dev" if any_hit else "psm_bvh_intersect_dev")
+
+    def closestPoint(self, points, rmax=np.inf):
+        """Closest point on the hierarchy's triangles of every point within rmax (psm_bvh_closest_point_dev; not in the reference):
+        points [n, 3], rmax a scalar or per-point [n]. numpy in: numpy out; torch device tensors in: torch tensors out on the same
+        device, ordered against torch's current stream (as intersect()). Returns QueryHits: t = the distance, tri, and u, v with
+        the point = (v0 + u e1) + v e2 of triangle tri (tri = -1, t = +inf when no triangle is within rmax)."""
+        return self._point_query(points, rmax, False)
+
+    def within(self, points, radius):
+        """Whether some triangle is within `radius` (a scalar or per-point [n]) of each point (psm_bvh_within_dev; not in the
+        reference): a bool array / tensor. Arguments and placement as closestPoint()."""
+        return self._point_query(points, radius, True)
+
+    def _point_query(self, points, rmax, flag):
+        name = "psm_bvh_within_dev" if flag else "psm_bvh_closest_point_dev"
+        if type(points).__module__.split(".")[0] == "torch":
+            import torch
+            dev = points.device
+            if dev.type != "cuda":
+                raise ValueError("closestPoint / within: points must be a tensor on the context's device")
+            p = points.reshape(-1, 3)
+            q = torch.empty((p.shape[0], 4), dtype=torch.float32, device=dev)
+            q[:, 0:3] = p
+            q[:, 3] = torch.as_tensor(rmax, dtype=torch.float32, device=dev)
+            return _launch_torch(self, q, flag, name)
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        q = np.empty((p.shape[0], 4), np.float32)
+        q[:, 0:3], q[:, 3] = p, rmax
+        return self._launch_np(q, flag, name)
+
+    def _launch_np(self, packed, flag, name):
+        """one query launch over host records `packed` [n, k] float32: staged through device buffers, synchronises"""
+        n = packed.shape[0]
+        out_bytes = n if flag else 16 * n
+        hr, ho = self.ctx.buf_alloc(max(packed.nbytes, 32)), self.ctx.buf_alloc(max(out_bytes, 16))
         try:
             if n:
-                self.ctx.buf_upload(hr, rays)
-            fn = lib().psm_bvh_occluded_dev if any_hit else lib().psm_bvh_intersect_dev
-            self.ctx.check(fn(self._h, C.c_void_p(self.ctx.buf_ptr(hr)[0]), C.c_size_t(n), C.c_void_p(self.ctx.buf_ptr(ho)[0])),
-                           "psm_bvh_occluded_dev" if any_hit else "psm_bvh_intersect_dev")
+                self.ctx.buf_upload(hr, packed)
+            self.ctx.check(getattr(lib(), name)(self._h, C.c_void_p(self.ctx.buf_ptr(hr)[0]), C.c_size_t(n),
+                                                C.c_void_p(self.ctx.buf_ptr(ho)[0])), name)
             if n == 0:
                 self.ctx.sync()
-                return np.zeros(0, np.bool_) if any_hit else QueryHits(np.zeros((0, 4), np.float32))
-            if any_hit:
+                return np.zeros(0, np.bool_) if flag else QueryHits(np.zeros((0, 4), np.float32))
+            if flag:
                 return self.ctx.buf_download(ho, np.uint8, n).view(np.bool_)
             return QueryHits(self.ctx.buf_download(ho, np.float32, 4 * n).reshape(n, 4))
         finally:
@@ -433,7 +468,7 @@ class TriangleHierarchy:
 
 
 class QueryHits:
-    """Closest hits of TriangleHierarchy.intersect: `buffer` [n, 4] float32 (numpy array or torch tensor) holds psm_hit records
+    """Closest hits of TriangleHierarchy.intersect (closest points of .closestPoint: t is the distance): `buffer` [n, 4] float32 (numpy array or torch tensor) holds psm_hit records
     (u, v, t, tri); t, u, v and tri (int32) are views of it."""
 
     def __init__(self, buffer):
@@ -484,24 +519,31 @@ def _query_torch(th, origins, directions, tmin, tmax, any_hit):
     rays[:, 3] = torch.as_tensor(tmin, dtype=torch.float32, device=dev)
     rays[:, 4:7] = d
     rays[:, 7] = torch.as_tensor(tmax, dtype=torch.float32, device=dev)
-    out = torch.empty((n,) if any_hit else (n, 4), dtype=torch.uint8 if any_hit else torch.float32, device=dev)
+    return _launch_torch(th, rays, any_hit, "psm_bvh_occluded_dev" if any_hit else "psm_bvh_intersect_dev")
+
+
+def _launch_torch(th, packed, flag, name):
+    """One query launch over device records `packed` (made on torch's current stream) on the context's stream: the two streams
+    ordered by events when they differ -- no host synchronisation. flag: a bool per query, else QueryHits."""
+    import torch
+    dev = packed.device
+    n = packed.shape[0]
+    out = torch.empty((n,) if flag else (n, 4), dtype=torch.uint8 if flag else torch.float32, device=dev)
     cur = torch.cuda.current_stream(dev)
     mine = th.ctx.stream or 0   # (NULL: the device's null stream, torch's default stream)
     other = mine != cur.cuda_stream
-    if other:   # the context's stream waits for the packing above (torch's event, HIP's wait: no host synchronisation)
+    if other:   # the context's stream waits for the packing (torch's event, HIP's wait: no host synchronisation)
         ev_in = torch.cuda.Event()
         ev_in.record(cur)
         _hip_check(_hip().hipStreamWaitEvent(C.c_void_p(mine), C.c_void_p(ev_in.cuda_event), C.c_uint(0)), "hipStreamWaitEvent")
-    fn = lib().psm_bvh_occluded_dev if any_hit else lib().psm_bvh_intersect_dev
-    th.ctx.check(fn(th._h, C.c_void_p(rays.data_ptr()), C.c_size_t(n), C.c_void_p(out.data_ptr())),
-                 "psm_bvh_occluded_dev" if any_hit else "psm_bvh_intersect_dev")
-    if other:   # ... and torch's stream for the kernel: every later use of `out`, and of the memory of `rays`, comes after it
+    th.ctx.check(getattr(lib(), name)(th._h, C.c_void_p(packed.data_ptr()), C.c_size_t(n), C.c_void_p(out.data_ptr())), name)
+    if other:   # ... and torch's stream for the kernel: every later use of `out`, and of the memory of `packed`, comes after it
         hip, ev = _hip(), C.c_void_p()
         _hip_check(hip.hipEventCreateWithFlags(C.byref(ev), C.c_uint(2)), "hipEventCreateWithFlags")   # hipEventDisableTiming
         _hip_check(hip.hipEventRecord(ev, C.c_void_p(mine)), "hipEventRecord")
         _hip_check(hip.hipStreamWaitEvent(C.c_void_p(cur.cuda_stream), ev, C.c_uint(0)), "hipStreamWaitEvent")
         _hip_check(hip.hipEventDestroy(ev), "hipEventDestroy")
-    return out.view(torch.bool) if any_hit else QueryHits(out)
+    return out.view(torch.bool) if flag else QueryHits(out)
 
 
 class TextureSet:

@@ -1,4 +1,5 @@
-// query.hip -- batched ray queries against a built hierarchy: closest hit and any hit (new; no reference counterpart).
+// query.hip -- batched queries against a built hierarchy (new; no reference counterpart): closest hit and any hit of rays,
+// closest point and within-radius of points (the point queries are described at point_body below).
 //
 // psm_rt_traverse follows directTraverse.comp bit for bit: a 16-entry stack that drops subtrees (STACK_CAP), a PZERO-tolerant
 // "closest", intersectTriangle's clamp of |det| at 1e-6. These kernels answer "what does this ray hit?" exactly instead
@@ -8,7 +9,9 @@
 //     not depend on the traversal order;
 //   * the stack never drops an entry: 16 levels in LDS, the rest in a per-lane global area sized to the builder's height bound.
 // Structure as rt_traverse (trace.hip): one ray per lane, one wave64 per workgroup, the stack in LDS laid out [depth][lane],
-// child boxes by fmaf on the fp16 record coordinates (v_fma_mix_f32), nearer child first. The kernels are grid-stride.
+// child boxes by fmaf on the fp16 record coordinates (v_fma_mix_f32), nearer child first. The kernels are grid-stride. The walk
+// (query_walk: grid-stride loop, stack, leaf scheduling) is shared by the ray and the point kernels; a body says what a query is.
+#include <cstdio>
 #include <mutex>
 #include <unordered_map>
 
@@ -36,15 +39,15 @@ constexpr int QSTACK_MAX = 96;
 constexpr uint32_t QUERY_GRID_CAP = PSM_QUERY_GRID_CAP;
 
 struct QueryArgs {
-    const float4* rays;      // psm_query_ray: origin.xyz tmin | direct.xyz tmax
+    const float4* rays;      // psm_query_ray: origin.xyz tmin | direct.xyz tmax (ray kernels) / psm_point_query: p.xyz rmax (point kernels)
     size_t n;
     const uint4* node32;     // the build's traversal records (bvh_emit)
     const float4* tri48;     // v0, e1, e2 per triangle (bvh_prepare_tris / bvh_load_mesh)
     const uint32_t* sm;      // transform, leaf count, root
     const int32_t* sorted_tri;  // [0]: the lone leaf's triangle when the leaf count is 1 (bvh_segtree<true> writes it)
     int* spill;              // [QSTACK_MAX - QSTACK_LDS][gridDim.x * 64]
-    float4* hits;            // closest: psm_hit per ray
-    uint8_t* occluded;       // any: 0 / 1 per ray
+    float4* hits;            // closest hit / closest point: psm_hit per query
+    uint8_t* occluded;       // any hit / within: 0 / 1 per query
 };
 
 // tri_test (trace.hip) operation for operation, with invDev = 1 / det instead of 1 / (max(|det|, 1e-6) * sign(det)) and without
@@ -69,9 +72,25 @@ PSM_D bool tri_query(const float4* __restrict__ tri48, int tri, v3 orig, v3 dir,
     return true;
 }
 
+
 namespace {
 
 PSM_D bool finite3(v3 a) { return __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z); }
+
+// Row k of the build's affine map applied to a point x: P = (M (x, 1)).k in the order mat_vec evaluates it (the w row is never
+// read), and the per-axis margin h = 2^-16 (2 + S), S = |m0 x| + |m1 y| + |m2 z| + |m3| (a bound on |P| and on the rounding of its
+// sum). Shared by the rays' slabs and the points' gaps.
+struct Row {
+    float P, h;
+};
+PSM_D Row affine_row(const float* M, int k, v3 x) {
+    const float m0 = M[4 * k + 0], m1 = M[4 * k + 1], m2 = M[4 * k + 2], m3 = M[4 * k + 3];
+    Row r;
+    r.P = ((m0 * x.x + m1 * x.y) + m2 * x.z) + m3;
+    const float S = ((pabs(m0 * x.x) + pabs(m1 * x.y)) + pabs(m2 * x.z)) + pabs(m3);
+    r.h = (2.0f + S) * 0x1p-16f;
+    return r;
+}
 
 // One axis of the ray in the build's normalised space, set up so that a box plane b gives its (inflated) distance in ONE fmaf:
 //   P = (M (o, 1)).k, D = (M (d, 0)).k      -- the affine map aabbmaker applied to the vertices (mat_vec with w = 1; the w row is
@@ -91,16 +110,14 @@ struct Axis {
     float inv, nlo, nhi;
 };
 PSM_D Axis ray_axis(const float* M, int k, v3 o, v3 d) {
-    const float m0 = M[4 * k + 0], m1 = M[4 * k + 1], m2 = M[4 * k + 2], m3 = M[4 * k + 3];
-    const float P = ((m0 * o.x + m1 * o.y) + m2 * o.z) + m3;
+    const float m0 = M[4 * k + 0], m1 = M[4 * k + 1], m2 = M[4 * k + 2];
+    const Row r = affine_row(M, k, o);
     float D = (m0 * d.x + m1 * d.y) + m2 * d.z;
-    const float S = ((pabs(m0 * o.x) + pabs(m1 * o.y)) + pabs(m2 * o.z)) + pabs(m3);
-    const float h = (2.0f + S) * 0x1p-16f;
     if (!(pabs(D) >= 1e-20f)) D = __builtin_copysignf(1e-20f, D);
     Axis a;
     a.inv = 1.0f / D;
-    a.nlo = -(P + h) * a.inv;
-    a.nhi = (h - P) * a.inv;
+    a.nlo = -(r.P + r.h) * a.inv;
+    a.nhi = (r.h - r.P) * a.inv;
     return a;
 }
 
@@ -114,69 +131,51 @@ PSM_D void slab(const Axis& X, const Axis& Y, const Axis& Z, float mnx, float mn
     tFar = sminf(sminf(smaxf(ax, bx), smaxf(ay, by)), smaxf(az, bz));
 }
 
-template <bool ANY>
-PSM_D void query_body(const QueryArgs& a) {
+// The walk every query kernel runs: one query per lane, grid-stride over the batch; per query the lone leaf of a one-leaf
+// hierarchy, then the tree from the root. A node's two child boxes are judged by the body (kept or not, and an order key: nearer
+// first), the accepted leaves are tested one after the other (one copy of the leaf code in the loop), and a kept internal child
+// that is not visited next goes on the stack: QSTACK_LDS entries per lane in LDS ([depth][lane]), the rest in the context's spill
+// area (spill_for). The body:
+//   bool begin(i, alive)  load query i (alive: i < n) and set up; false: the query misses without a walk
+//   void children(n0, n1, okL, okR, kL, kR), void leaf(tri), bool done() (the lane retires), void finish(i)
+// The stack holds links only: a popped subtree is visited and its children judged against the best as it is then
+// (keeping each entry's bound to drop it at the pop measured 8 % slower on the point queries).
+template <class Body>
+PSM_D void query_walk(const QueryArgs& a, Body& q) {
     __shared__ int stack[QSTACK_LDS][QUERY_BLOCK];
     const int lane = (int)threadIdx.x;
     __builtin_assume(lane >= 0 && lane < QUERY_BLOCK);
     const size_t spill_stride = (size_t)gridDim.x * QUERY_BLOCK;
     int* __restrict__ spill = a.spill + (size_t)blockIdx.x * QUERY_BLOCK + lane;
     const uint4* __restrict__ node32 = a.node32;
-    const float4* __restrict__ tri48 = a.tri48;
     const int root = (int)a.sm[SM_ROOT];
     const uint32_t count = a.sm[SM_COUNT];
     const int lone = (count == 1u) ? a.sorted_tri[0] : -1;   // one leaf: no tree, the leaf's triangle is the only candidate
     for (size_t i = (size_t)blockIdx.x * QUERY_BLOCK + (size_t)lane; i - (size_t)lane < a.n; i += spill_stride) {
         const bool alive = i < a.n;
-        float4 r0 = make_float4(0.f, 0.f, 0.f, 1.f), r1 = make_float4(1.f, 0.f, 0.f, -1.f);
-        if (alive) { r0 = a.rays[2 * i]; r1 = a.rays[2 * i + 1]; }
-        const v3 o = mk3(r0.x, r0.y, r0.z);
-        const v3 d = normalize3(mk3(r1.x, r1.y, r1.z));   // t is the distance along the unit direction (as the oracle's brute force)
-        const float tmin = r0.w, tmax = r1.w;
-        // NaN anywhere, a zero direction (normalize3 gives NaN) or an empty window: a miss
-        const bool valid = alive && finite3(o) && finite3(d) && tmin <= tmax;
-        float best = tmax, bu = 0.f, bv = 0.f;
-        int btri = -1;
-        bool found = false;
-        float M[16];
-#pragma unroll
-        for (int k = 0; k < 16; k++) M[k] = u2f(a.sm[SM_M + k]);
-        const Axis X = ray_axis(M, 0, o, d), Y = ray_axis(M, 1, o, d), Z = ray_axis(M, 2, o, d);
-        // a candidate triangle: inside the window, and (closest) before the best so far or as far and of a lower id
-        // ((uint32_t) btri: -1 is the largest, so the first hit inside the window always counts)
-        auto test = [&](int tri) {
-            float t, u, v;
-            if (tri_query(tri48, tri, o, d, t, u, v) && t >= tmin && (t < best || (t == best && (uint32_t)tri < (uint32_t)btri))) {
-                found = true;
-                if (!ANY) { best = t; bu = u; bv = v; btri = tri; }
-            }
-        };
-        if (valid && lone >= 0) test(lone);
+        const bool valid = q.begin(i, alive);
+        if (valid && lone >= 0) q.leaf(lone);
         int cur = root, sp = 0;
         bool walking = valid && root >= 0;
         while (walking) {
             const uint4* np = (const uint4*)((const char*)node32 + ((uint32_t)cur << 5));
             const uint4 n0 = np[0], n1 = np[1];
             const int lkx = (int)n1.z, lky = (int)n1.w;
-            float nL, fL, nR, fR;
-            slab(X, Y, Z, half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z), nL, fL);
-            slab(X, Y, Z, half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y), nR, fR);
-            // closest: pruned against the best hit so far (a hit at exactly `best` with a lower id still counts: <=)
-            const float lim = ANY ? tmax : best;
-            const bool okL = (nL <= fL) & (nL <= lim) & (fL >= tmin);
-            const bool okR = (nR <= fR) & (nR <= lim) & (fR >= tmin);
+            bool okL, okR;
+            float kL, kR;
+            q.children(n0, n1, okL, okR, kL, kR);
             const bool leafL = okL && lkx < 0, leafR = okR && lky < 0;
             // the accepted leaves, one test after the other (one copy of the triangle code in the loop)
             int t0 = leafL ? ~lkx : (leafR ? ~lky : -1);
             int t1 = (leafL && leafR) ? ~lky : -1;
             while (t0 >= 0) {
-                test(t0);
+                q.leaf(t0);
                 t0 = t1;
                 t1 = -1;
             }
-            if (ANY && found) break;   // any hit: the lane retires at its first hit
+            if (q.done()) break;
             const bool intL = okL && !leafL, intR = okR && !leafR;
-            const bool leftFirst = intL && (!intR || nL <= nR);   // nearer child first
+            const bool leftFirst = intL && (!intR || kL <= kR);   // nearer child first
             const int first = leftFirst ? lkx : lky, second = leftFirst ? lky : lkx;
             if (intL && intR) {
                 // (sp < QSTACK_MAX always: see QSTACK_MAX; the host refuses hierarchies whose bound exceeds it)
@@ -191,32 +190,282 @@ PSM_D void query_body(const QueryArgs& a) {
                 cur = sp < QSTACK_LDS ? stack[sp][lane] : spill[(size_t)(sp - QSTACK_LDS) * spill_stride];
             }
         }
-        if (alive) {
-            if (ANY) a.occluded[i] = found ? 1 : 0;
-            else a.hits[i] = found ? make_float4(bu, bv, best, __int_as_float(btri)) : make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1));
+        if (alive) q.finish(i);
+    }
+}
+
+// the ray queries: closest hit (ANY = false) and any hit (ANY = true); psm_query_ray, DESIGN.md 4.5
+template <bool ANY>
+struct RayBody {
+    const QueryArgs& a;
+    v3 o, d;
+    float tmin, tmax, best, bu, bv;
+    int btri;
+    bool found;
+    Axis X, Y, Z;
+
+    PSM_D bool begin(size_t i, bool alive) {
+        float4 r0 = make_float4(0.f, 0.f, 0.f, 1.f), r1 = make_float4(1.f, 0.f, 0.f, -1.f);
+        if (alive) { r0 = a.rays[2 * i]; r1 = a.rays[2 * i + 1]; }
+        o = mk3(r0.x, r0.y, r0.z);
+        d = normalize3(mk3(r1.x, r1.y, r1.z));   // t is the distance along the unit direction (as the oracle's brute force)
+        tmin = r0.w;
+        tmax = r1.w;
+        // NaN anywhere, a zero direction (normalize3 gives NaN) or an empty window: a miss
+        const bool valid = alive && finite3(o) && finite3(d) && tmin <= tmax;
+        best = tmax;
+        bu = 0.f;
+        bv = 0.f;
+        btri = -1;
+        found = false;
+        float M[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) M[k] = u2f(a.sm[SM_M + k]);
+        X = ray_axis(M, 0, o, d);
+        Y = ray_axis(M, 1, o, d);
+        Z = ray_axis(M, 2, o, d);
+        return valid;
+    }
+    PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& nL, float& nR) const {
+        float fL, fR;
+        slab(X, Y, Z, half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z), nL, fL);
+        slab(X, Y, Z, half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y), nR, fR);
+        // closest: pruned against the best hit so far (a hit at exactly `best` with a lower id still counts: <=)
+        const float lim = ANY ? tmax : best;
+        okL = (nL <= fL) & (nL <= lim) & (fL >= tmin);
+        okR = (nR <= fR) & (nR <= lim) & (fR >= tmin);
+    }
+    // a candidate triangle: inside the window, and (closest) before the best so far or as far and of a lower id
+    // ((uint32_t) btri: -1 is the largest, so the first hit inside the window always counts)
+    PSM_D void leaf(int tri) {
+        float t, u, v;
+        if (tri_query(a.tri48, tri, o, d, t, u, v) && t >= tmin && (t < best || (t == best && (uint32_t)tri < (uint32_t)btri))) {
+            found = true;
+            if (!ANY) { best = t; bu = u; bv = v; btri = tri; }
         }
     }
+    PSM_D bool done() const { return ANY && found; }   // any hit: the lane retires at its first hit
+    PSM_D void finish(size_t i) const {
+        if (ANY) a.occluded[i] = found ? 1 : 0;
+        else a.hits[i] = found ? make_float4(bu, bv, best, __int_as_float(btri)) : make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1));
+    }
+};
+
+// ---- point queries: closest point and within radius (psm_point_query; include/psm_hip.h) ---------------------
+
+PSM_D float clamp01(float x) {   // (x > 0 ? x : 0) then (x < 1 ? x : 1): NaN and -0 give +0 (tests/point_query_model.py _clamp01)
+    x = x > 0.f ? x : 0.f;
+    return x < 1.f ? x : 1.f;
+}
+
+// The closest point of triangle (v0, e1 = v1 - v0, e2 = v2 - v0) to p: Ericson's region test (Real-Time Collision Detection 5.1.5)
+// with the dot products of the edges hoisted (d3 = d1 - aa, ... are Ericson's d3..d6 for bp = ap - e1, cp = ap - e2, and vc / vb
+// his vc / vb multiplied out). Returns d2 = |p - c|^2 for c = (v0 + u e1) + v e2, the point in every region.
+// Guards (a degenerate triangle gives a finite answer for finite input):
+//   * an edge region is taken only when its denominator is positive; a zero-length edge never matches and its vertices' and the
+//     other edges' regions decide (for a triangle with two equal vertices every region of the zero edge holds with equality)
+//   * the face: det = aa bb - ab^2 (= |e1 x e2|^2, Ericson's va + vb + vc) must exceed 2^-16 aa bb (sin^2 of the angle at v0). The
+//     rounding of det is ~14 eps aa bb, so a thinner triangle's face barycentrics are noise; it is taken as its longest edge, the
+//     clamped projection onto it (a collinear triangle's longest edge spans it; a thin one lies within its width, <= s L with
+//     s <= 2^-8 the sine at v0, of it). A face just above the threshold keeps ~8 eps / s^2 L of barycentric noise: near
+//     s = 2^-8 a distance can be off by ~2^-7 L either way.
+//     The face's u, v are clamped into the triangle (u in [0, 1], v in [0, 1 - u]): c never leaves the triangle by more than
+//     rounding, which the pruning bound relies on.
+PSM_D float closest_on_tri(v3 v0, v3 e1, v3 e2, v3 p, float& U, float& V) {
+    const v3 ap = p - v0;
+    const float aa = dot3(e1, e1), ab = dot3(e1, e2), bb = dot3(e2, e2);
+    const float d1 = dot3(e1, ap), d2 = dot3(e2, ap);
+    const float d3 = d1 - aa, d4 = d2 - ab, d5 = d1 - ab, d6 = d2 - bb;
+    const float vc = aa * d2 - ab * d1;
+    const float vb = bb * d1 - ab * d2;
+    const float va = d3 * d6 - d5 * d4;
+    const float e43 = d4 - d3, e56 = d5 - d6;
+    const float det = aa * bb - ab * ab;
+    const v3 e21 = e2 - e1;
+    const float cc = dot3(e21, e21);
+    // The region, first match wins: taken from the last to the first, each match overriding, so one small integer and the
+    // operands of the one division it needs stay live (branch-free; a wave meets every region anyway). reg: 0 vertex v0, 1 vertex
+    // v1, 2 edge v0 v1, 3 vertex v2, 4 edge v0 v2, 5 edge v1 v2, 6 face, 7 / 8 / 9 a sliver's longest edge e1 / e2 / e2 - e1.
+    const bool sa = aa >= bb && aa >= cc, sb = bb >= cc;
+    int reg = sa ? 7 : (sb ? 8 : 9);
+    float n1 = sa ? d1 : (sb ? d2 : e43), q1d = sa ? aa : (sb ? bb : cc);
+    if (det > (aa * bb) * 0x1p-16f) { reg = 6; n1 = vb; q1d = det; }
+    if (va <= 0.f && e43 >= 0.f && e56 >= 0.f && e43 + e56 > 0.f) { reg = 5; n1 = e43; q1d = e43 + e56; }
+    if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f && d2 - d6 > 0.f) { reg = 4; n1 = d2; q1d = d2 - d6; }
+    if (d6 >= 0.f && d5 <= d6) { reg = 3; n1 = 0.f; q1d = 1.f; }
+    if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f && d1 - d3 > 0.f) { reg = 2; n1 = d1; q1d = d1 - d3; }
+    if (d3 >= 0.f && d4 <= d3) { reg = 1; n1 = 0.f; q1d = 1.f; }
+    if (d1 <= 0.f && d2 <= 0.f) { reg = 0; n1 = 0.f; q1d = 1.f; }
+    const float q1 = n1 / q1d;
+    const float q2 = (reg == 6 ? vc : 0.f) / (reg == 6 ? det : 1.f);
+    const float c1 = clamp01(q1);
+    float u = 0.f, v = 0.f;
+    if (reg == 1) u = 1.f;
+    if (reg == 2) u = q1;
+    if (reg == 3) v = 1.f;
+    if (reg == 4) v = q1;
+    if (reg == 5) { u = 1.f - q1; v = q1; }
+    if (reg == 6) {
+        u = c1;
+        const float f = q2 > 0.f ? q2 : 0.f, lim = 1.f - c1;
+        v = f < lim ? f : lim;
+    }
+    if (reg == 7) u = c1;
+    if (reg == 8) v = c1;
+    if (reg == 9) { u = 1.f - c1; v = c1; }
+    const v3 c = mk3((v0.x + u * e1.x) + v * e2.x, (v0.y + u * e1.y) + v * e2.y, (v0.z + u * e1.z) + v * e2.z);
+    const v3 dp = p - c;
+    U = u;
+    V = v;
+    return dot3(dp, dp);
+}
+
+// The pruning bound of a point (per launch; every workgroup evaluates it once before its loop, from the build's transform).
+// A box of the tree holds, for every point x of every triangle under it, the exact normalised image y = M3 x + m: the leaf box is
+// the triangle's padded by PZERO before the fp16 rounding, far above the rounding of aabbmaker's float M v. For the query point
+// p let P = M3 p + m (computed: within ~3 eps S of exact per axis, S as affine_row) and g_k >= 0 the gap on axis k from P to the
+// box grown by h = 2^-16 (2 + S): h >> the rounding of P and of the two subtractions, so g_k <= G_k, the exact gap of the exact
+// image of p to the ungrown box, and |(M3 (x - p)).k| >= G_k >= g_k for every x in it. World distance from normalised gaps:
+//   * rows r_k of M3 with norms lambda_k = |r_k| and cosines c_ij = r_i . r_j / (lambda_i lambda_j); with M3 = D R, D = diag
+//     (lambda), |x - p| = |R^-1 D^-1 M3 (x - p)| >= |D^-1 M3 (x - p)| / sigma_max(R), and sigma_max(R)^2 = the largest eigenvalue
+//     of R R^T (unit diagonal, off-diagonal c_ij) <= 1 + 2 c_max (Gershgorin). So LB^2 = sum_k (g_k / lambda_k)^2 / (1 + 2 c_max)
+//     holds for every invertible M3, and is exact for orthogonal rows (the fit transform: diagonal; a rotate-and-scale
+//     optimisation matrix: D R).
+//   * |(M3 (x - p)).k| <= lambda_k |x - p| (Cauchy-Schwarz), so LB = max_k g_k / lambda_k holds too, whatever the rows.
+// Tolerance: the orthogonal form is used iff c_max <= 2^-11, where its factor 1 / (1 + 2 c_max) costs at most 2^-10 of the bound
+// (a float rotation's rows have c ~ 1e-7); a shear leaves c_max far above it and takes the max form, which the sum form scaled
+// by 1 / (1 + 2 c_max) would not always beat. c_max is taken 2^-20 above its computed value (the rounding of the cosines).
+// Rounding: lambda, 1 / lambda, the squares and the sum are < 20 eps in all, and the distance a triangle is judged by,
+// d2 = dot3(p - c, p - c), is >= (1 - 6 eps) |p - c|^2 for its c in the box: every LB^2 is scaled by 1 - 2^-18 (64 eps). A box is
+// dropped only when LB^2 > the bound: every point of it is farther than the best so far (or than rmax, below), so a triangle
+// with a smaller d2, or an equal d2 and a lower id, is never dropped.
+// rmax: a candidate counts iff sqrtf(d2) <= rmax; sqrtf is correctly rounded, so such a d2 is <= rmax^2 (1 + 2^-22), and the
+// bound starts at fl(rmax^2) (1 + 2^-20) + 2^-126 (above it for every rmax; +inf for rmax = +inf). Non-finite or overflowing
+// arithmetic only makes h infinite or a gap NaN, which fmaxf takes as 0: the box is kept.
+struct PointBound {
+    float il0, il1, il2;   // (1 / lambda_k), 0 for a zero row
+    float wf;              // (1 - 2^-18), divided by (1 + 2 c_max) for the orthogonal form
+    bool orth;
+};
+PSM_D PointBound point_bound(const float* M) {
+    PointBound b;
+    float il[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float lam = sqrtf(dot3(mk3(M[4 * k], M[4 * k + 1], M[4 * k + 2]), mk3(M[4 * k], M[4 * k + 1], M[4 * k + 2])));
+        il[k] = lam > 0.f ? 1.0f / lam : 0.f;
+    }
+    const v3 r0 = mk3(M[0], M[1], M[2]), r1 = mk3(M[4], M[5], M[6]), r2 = mk3(M[8], M[9], M[10]);
+    const float c01 = pabs(dot3(r0, r1)) * il[0] * il[1], c02 = pabs(dot3(r0, r2)) * il[0] * il[2];
+    const float c12 = pabs(dot3(r1, r2)) * il[1] * il[2];
+    const float cmax = smaxf(smaxf(c01, c02), c12) + 0x1p-20f;
+    b.il0 = il[0];
+    b.il1 = il[1];
+    b.il2 = il[2];
+    b.orth = cmax <= 0x1p-11f && il[0] > 0.f && il[1] > 0.f && il[2] > 0.f;
+    b.wf = b.orth ? (1.0f - 0x1p-18f) / (1.0f + 2.0f * cmax) : (1.0f - 0x1p-18f);
+    return b;
+}
+
+// the point queries: closest point (WITHIN = false) and within radius (WITHIN = true)
+template <bool WITHIN>
+struct PointBody {
+    const QueryArgs& a;
+    const PointBound B;
+    v3 p;
+    float rmax, best, bu, bv;   // best: the pruning bound -- the best d2 so far, the rmax bound until one is found
+    int btri;
+    bool found;
+    float Px, Py, Pz, h;   // p in normalised space; the margin: the largest of the three axes' h
+
+    PSM_D bool begin(size_t i, bool alive) {
+        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
+        if (alive) q = a.rays[i];
+        p = mk3(q.x, q.y, q.z);
+        rmax = q.w;
+        const bool valid = alive && finite3(p) && rmax >= 0.f;   // NaN or negative rmax: a miss; +inf: no limit
+        best = (rmax * rmax) * 1.00000095367431640625f + 0x1p-126f;   // fl(rmax^2) (1 + 2^-20) + 2^-126
+        bu = 0.f;
+        bv = 0.f;
+        btri = -1;
+        found = false;
+        float M[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) M[k] = u2f(a.sm[SM_M + k]);
+        const Row X = affine_row(M, 0, p), Y = affine_row(M, 1, p), Z = affine_row(M, 2, p);
+        Px = X.P;
+        Py = Y.P;
+        Pz = Z.P;
+        h = smaxf(smaxf(X.h, Y.h), Z.h);
+        return valid;
+    }
+    // LB^2 of one child box (mn / mx: its fp16 corners)
+    PSM_D float lb2(float mnx, float mny, float mnz, float mxx, float mxy, float mxz) const {
+        const float tx = smaxf(smaxf(mnx - Px, Px - mxx) - h, 0.f) * B.il0;
+        const float ty = smaxf(smaxf(mny - Py, Py - mxy) - h, 0.f) * B.il1;
+        const float tz = smaxf(smaxf(mnz - Pz, Pz - mxz) - h, 0.f) * B.il2;
+        const float m = smaxf(smaxf(tx, ty), tz);
+        return (B.orth ? ((tx * tx + ty * ty) + tz * tz) : m * m) * B.wf;
+    }
+    PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& kL, float& kR) const {
+        kL = lb2(half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z));
+        kR = lb2(half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y));
+        okL = kL <= best;   // <=: a triangle as near as the best and of a lower id still counts
+        okR = kR <= best;
+    }
+    // a candidate: within rmax, and (closest) nearer than the best so far or as near and of a lower id
+    // ((uint32_t) btri: -1 is the largest; before the first, best is the rmax bound, >= every d2 that counts)
+    PSM_D void leaf(int tri) {
+        const float4 A = a.tri48[(size_t)3 * tri + 0], Bv = a.tri48[(size_t)3 * tri + 1], C = a.tri48[(size_t)3 * tri + 2];
+        float u, v;
+        const float d2 = closest_on_tri(mk3(A.x, A.y, A.z), mk3(Bv.x, Bv.y, Bv.z), mk3(C.x, C.y, C.z), p, u, v);
+        if (sqrtf(d2) <= rmax && (d2 < best || (d2 == best && (uint32_t)tri < (uint32_t)btri))) {
+            found = true;
+            if (!WITHIN) { best = d2; bu = u; bv = v; btri = tri; }
+        }
+    }
+    PSM_D bool done() const { return WITHIN && found; }   // within: the lane retires at its first counting candidate
+    PSM_D void finish(size_t i) const {
+        if (WITHIN) a.occluded[i] = found ? 1 : 0;
+        else a.hits[i] = found ? make_float4(bu, bv, sqrtf(best), __int_as_float(btri)) : make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1));
+    }
+};
+
+template <bool ANY>
+PSM_D void query_body(const QueryArgs& a) {
+    RayBody<ANY> q{a};
+    query_walk(a, q);
+}
+
+template <bool WITHIN>
+PSM_D void point_body(const QueryArgs& a) {
+    float M[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) M[k] = u2f(a.sm[SM_M + k]);
+    PointBody<WITHIN> q{a, point_bound(M)};
+    query_walk(a, q);
 }
 
 }  // namespace
 
-// the two kernels, under names of their own (profiles and the codegen test find them by these)
+// the kernels, under names of their own (profiles and the codegen tests find them by these)
 __global__ __launch_bounds__(QUERY_BLOCK, 8) void bvh_query_closest(QueryArgs a) { query_body<false>(a); }
 __global__ __launch_bounds__(QUERY_BLOCK, 8) void bvh_query_any(QueryArgs a) { query_body<true>(a); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void bvh_query_point(QueryArgs a) { point_body<false>(a); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void bvh_query_within(QueryArgs a) { point_body<true>(a); }
 
 namespace {
 
-// the stack entries beyond the LDS part, per context: one column per lane of a launch (allocated on the context's first query)
+// the stack entries beyond the LDS part, per context, shared by every query kind (all run on the context's stream, never at
+// once): one column per lane of a launch (allocated on the context's first query)
+constexpr size_t SPILL_BYTES = (size_t)(QSTACK_MAX - QSTACK_LDS) * QUERY_GRID_CAP * QUERY_BLOCK * sizeof(int);
 std::mutex spill_mu;
 std::unordered_map<const psm_ctx*, void*> spill_area;
 
 int spill_for(psm_ctx* c, void** out) {
     std::lock_guard<std::mutex> lk(spill_mu);
     void*& p = spill_area[c];
-    if (!p) {
-        const size_t bytes = (size_t)(QSTACK_MAX - QSTACK_LDS) * QUERY_GRID_CAP * QUERY_BLOCK * sizeof(int);
-        PSM_HIP(c, hipMalloc(&p, bytes));
-    }
+    if (!p) PSM_HIP(c, hipMalloc(&p, SPILL_BYTES));
     *out = p;
     return PSM_OK;
 }
@@ -228,31 +477,46 @@ int ceil_log2(size_t n) {
     return k;
 }
 
-template <bool ANY>
-int query(psm_bvh* b, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits, uint8_t* d_hit) {
+enum QueryKind { Q_CLOSEST, Q_ANY, Q_POINT, Q_WITHIN };
+const char* const QUERY_NAME[] = {"psm_bvh_intersect_dev", "psm_bvh_occluded_dev", "psm_bvh_closest_point_dev", "psm_bvh_within_dev"};
+
+// the checks and the launch every query shares: in / out must be non-NULL, in (and a psm_hit out) 16-byte aligned
+int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, psm_hit* d_hits, uint8_t* d_hit) {
     if (!b) return PSM_ERR_INVALID;
     if (n == 0) return PSM_OK;
     psm_ctx* c = b->ctx;
-    if (!d_rays || (ANY ? (const void*)d_hit : (const void*)d_hits) == nullptr)
-        return set_err(c, PSM_ERR_INVALID, ANY ? "psm_bvh_occluded_dev: NULL pointer" : "psm_bvh_intersect_dev: NULL pointer");
-    if (((uintptr_t)d_rays & 15u) != 0 || (!ANY && ((uintptr_t)d_hits & 15u) != 0))
-        return set_err(c, PSM_ERR_INVALID, ANY ? "psm_bvh_occluded_dev: rays not 16-byte aligned"
-                                               : "psm_bvh_intersect_dev: rays or hits not 16-byte aligned");
+    const bool flags = kind == Q_ANY || kind == Q_WITHIN;
+    char msg[96];
+    if (!d_in || (flags ? (const void*)d_hit : (const void*)d_hits) == nullptr) {
+        snprintf(msg, sizeof msg, "%s: NULL pointer", QUERY_NAME[kind]);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (((uintptr_t)d_in & 15u) != 0 || (!flags && ((uintptr_t)d_hits & 15u) != 0)) {
+        const char* what = kind < Q_POINT ? (flags ? "rays" : "rays or hits") : (flags ? "points" : "points or hits");
+        snprintf(msg, sizeof msg, "%s: %s not 16-byte aligned", QUERY_NAME[kind], what);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
     (void)hipSetDevice(c->device);
-    if (!b->built) return set_err(c, PSM_ERR_STATE, "ray query before build");
-    if (63 + ceil_log2(b->cap) > QSTACK_MAX) return set_err(c, PSM_ERR_CAPACITY, "ray query: hierarchy deeper than the query stack");
+    if (!b->built) return set_err(c, PSM_ERR_STATE, kind < Q_POINT ? "ray query before build" : "point query before build");
+    if (63 + ceil_log2(b->cap) > QSTACK_MAX)
+        return set_err(c, PSM_ERR_CAPACITY, kind < Q_POINT ? "ray query: hierarchy deeper than the query stack"
+                                                           : "point query: hierarchy deeper than the query stack");
     void* spill = nullptr;
     const int rc = spill_for(c, &spill);   // (a context's first query allocates: a later one can be captured into a graph)
     if (rc != PSM_OK) return rc;
     const size_t waves = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;
     const uint32_t grid = (uint32_t)(waves < QUERY_GRID_CAP ? waves : QUERY_GRID_CAP);
     QueryArgs qa = {};
-    qa.rays = (const float4*)d_rays; qa.n = n;
+    qa.rays = (const float4*)d_in; qa.n = n;
     qa.node32 = b->d_node32; qa.tri48 = b->d_tri48; qa.sm = b->d_small; qa.sorted_tri = b->d_sorted_tri;
     qa.spill = (int*)spill;
     qa.hits = (float4*)d_hits; qa.occluded = d_hit;
-    if (ANY) bvh_query_any<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa);
-    else bvh_query_closest<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa);
+    switch (kind) {
+        case Q_CLOSEST: bvh_query_closest<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
+        case Q_ANY: bvh_query_any<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
+        case Q_POINT: bvh_query_point<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
+        case Q_WITHIN: bvh_query_within<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
+    }
     PSM_HIP(c, hipGetLastError());
     return PSM_OK;
 }
@@ -271,9 +535,17 @@ void query_release(psm_ctx* c) {
 }  // namespace psm
 
 int psm_bvh_intersect_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits) {
-    return psm::query<false>(bvh, d_rays, n, d_hits, nullptr);
+    return psm::query(bvh, psm::Q_CLOSEST, d_rays, n, d_hits, nullptr);
 }
 
 int psm_bvh_occluded_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, uint8_t* d_hit) {
-    return psm::query<true>(bvh, d_rays, n, nullptr, d_hit);
+    return psm::query(bvh, psm::Q_ANY, d_rays, n, nullptr, d_hit);
+}
+
+int psm_bvh_closest_point_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, psm_hit* d_hits) {
+    return psm::query(bvh, psm::Q_POINT, d_points, n, d_hits, nullptr);
+}
+
+int psm_bvh_within_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, uint8_t* d_hit) {
+    return psm::query(bvh, psm::Q_WITHIN, d_points, n, nullptr, d_hit);
 }

@@ -3,7 +3,10 @@
 scene's 1920 x 1080 camera rays, over as many bounce-like rays (origins at the primary hits, random directions in the hemisphere of
 the hit triangle's face normal), and psm_rt_traverse WHOLE over the same primary rays for comparison. Each figure: the median of
 REPS (5) device-synchronised calls after a warm-up call. Prints one JSON line.
-A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py"""
+`query_bench.py points`: the point queries (psm_bvh_closest_point_dev / psm_bvh_within_dev) on the same scene instead, NPTS (2^21)
+points per set: (a) surface samples plus Gaussian noise of 1 % of the scene diagonal, closest point with rmax = inf; (b) uniform in
+the scene's bounds, rmax = inf; (c) set (b) through within with a radius of 0.5 % of the diagonal.
+A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points]"""
 import ctypes as C
 import importlib
 import json
@@ -19,6 +22,7 @@ scenes = importlib.import_module("prismarine-core_amd.scenes")
 
 W, H = 1920, 1080
 REPS = int(os.environ.get("REPS", "5"))
+NPTS = int(os.environ.get("NPTS", str(1 << 21)))
 
 
 def median_ms(ctx, fn):
@@ -31,6 +35,57 @@ def median_ms(ctx, fn):
         ctx.sync()
         ts.append((time.perf_counter() - t0) * 1e3)
     return float(np.median(ts))
+
+
+def points():
+    sc = scenes.sponza_like()
+    ctx = psm.Context(0)
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(sc["tris"].shape[0])
+    th.loadTriangles(sc["tris"], sc["normals"], sc["mats"])
+    th.build()
+    tris = sc["tris"].reshape(-1, 3, 3)
+    lo, hi = tris.reshape(-1, 3).min(0), tris.reshape(-1, 3).max(0)
+    diag = float(np.linalg.norm(hi - lo))
+    rng = np.random.RandomState(7)
+    n = NPTS
+    w = rng.dirichlet([1, 1, 1], n).astype(np.float32)
+    surf = np.einsum("ij,ijk->ik", w, tris[rng.randint(0, tris.shape[0], n)])
+    sets = {"surface_noise": (surf + rng.normal(0, 0.01 * diag, (n, 3))).astype(np.float32),
+            "uniform": rng.uniform(lo, hi, (n, 3)).astype(np.float32)}
+    lib = psm.lib()
+    h_pts, h_hits, h_in = ctx.buf_alloc(16 * n), ctx.buf_alloc(16 * n), ctx.buf_alloc(n)
+    p_pts, p_hits, p_in = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in (h_pts, h_hits, h_in))
+
+    def upload(p, r):
+        q = np.empty((n, 4), np.float32)
+        q[:, 0:3], q[:, 3] = p, r
+        ctx.buf_upload(h_pts, q)
+
+    def closest():
+        ctx.check(lib.psm_bvh_closest_point_dev(th._h, p_pts, C.c_size_t(n), p_hits), "psm_bvh_closest_point_dev")
+
+    def within():
+        ctx.check(lib.psm_bvh_within_dev(th._h, p_pts, C.c_size_t(n), p_in), "psm_bvh_within_dev")
+
+    radius = 0.005 * diag
+    out = {"points": n, "reps": REPS, "tris": int(tris.shape[0]), "diag": round(diag, 3), "within_radius": round(radius, 4)}
+    upload(sets["surface_noise"], np.inf)
+    out["a_surface_noise_closest_ms"] = median_ms(ctx, closest)
+    upload(sets["uniform"], np.inf)
+    out["b_uniform_closest_ms"] = median_ms(ctx, closest)
+    upload(sets["uniform"], radius)
+    out["c_uniform_within_ms"] = median_ms(ctx, within)
+    out["c_within_fraction"] = float(ctx.buf_download(h_in, np.uint8, n).mean())
+    for k in ("a_surface_noise_closest", "b_uniform_closest", "c_uniform_within"):
+        out[k + "_mpts_s"] = round(n / out[k + "_ms"] / 1e3, 1)
+        out[k + "_ms"] = round(out[k + "_ms"], 4)
+    out["lib"] = os.path.basename(psm.LIB_PATH)
+    for h in (h_pts, h_hits, h_in):
+        ctx.buf_free(h)
+    th.close()
+    ctx.close()
+    print(json.dumps(out))
 
 
 def main():
@@ -111,4 +166,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    points() if sys.argv[1:] == ["points"] else main()
