@@ -50,6 +50,12 @@ namespace NSM {
         // (psm_bvh_closest_point_dev / psm_bvh_within_dev), stream-ordered on the context; returns the psm_status
         int closestPoint(const psm_point_query * d_points, size_t n, psm_hit * d_hits);
         int within(const psm_point_query * d_points, size_t n, uint8_t * d_hit);
+        // not in the reference: crossings of n rays inside their windows / inside-outside of n points by the parity vote of
+        // `samples` (1, 3 or 5) rays / closest point with the sign bit of t set inside (psm_bvh_count_hits_dev / psm_bvh_inside_dev
+        // / psm_bvh_signed_distance_dev), stream-ordered on the context; returns the psm_status
+        int countHits(const psm_query_ray * d_rays, size_t n, uint32_t * d_count);
+        int inside(const psm_point_query * d_points, size_t n, uint8_t * d_inside, uint32_t samples = 3);
+        int signedDistance(const psm_point_query * d_points, size_t n, psm_hit * d_hits, uint32_t samples = 3);
         psm_bvh * handle() { return bvh; }
     };
 }

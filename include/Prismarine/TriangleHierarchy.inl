@@ -52,6 +52,21 @@ namespace NSM {
         check(rc, "TriangleHierarchy::within");
         return rc;
     }
+    inline int TriangleHierarchy::countHits(const psm_query_ray * d_rays, size_t n, uint32_t * d_count) {
+        const int rc = psm_bvh_count_hits_dev(bvh, d_rays, n, d_count);
+        check(rc, "TriangleHierarchy::countHits");
+        return rc;
+    }
+    inline int TriangleHierarchy::inside(const psm_point_query * d_points, size_t n, uint8_t * d_inside, uint32_t samples) {
+        const int rc = psm_bvh_inside_dev(bvh, d_points, n, samples, d_inside);
+        check(rc, "TriangleHierarchy::inside");
+        return rc;
+    }
+    inline int TriangleHierarchy::signedDistance(const psm_point_query * d_points, size_t n, psm_hit * d_hits, uint32_t samples) {
+        const int rc = psm_bvh_signed_distance_dev(bvh, d_points, n, samples, d_hits);
+        check(rc, "TriangleHierarchy::signedDistance");
+        return rc;
+    }
     inline void TriangleHierarchy::setBuildGraph(bool enable) { if (bvh) check(psm_bvh_set_build_graph(bvh, enable ? 1 : 0), "TriangleHierarchy::setBuildGraph"); }
     inline void TriangleHierarchy::configureIntersection(bool clearDepth) { (void)clearDepth; }  // ignored by the reference's shaders too
 

@@ -26,7 +26,7 @@ EXPORTS = [
     "psm_bvh_create", "psm_bvh_destroy", "psm_bvh_clear", "psm_bvh_load_triangles", "psm_bvh_set_texcoords", "psm_bvh_load_mesh", "psm_bvh_build", "psm_bvh_set_build_graph", "psm_bvh_refit",
     "psm_bvh_get_info", "psm_bvh_stage_bounds", "psm_bvh_stage_morton", "psm_bvh_stage_sort",
     "psm_bvh_stage_emit", "psm_bvh_download", "psm_bvh_intersect_dev", "psm_bvh_occluded_dev",
-    "psm_bvh_closest_point_dev", "psm_bvh_within_dev",
+    "psm_bvh_closest_point_dev", "psm_bvh_within_dev", "psm_bvh_count_hits_dev", "psm_bvh_inside_dev", "psm_bvh_signed_distance_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -50,6 +50,10 @@ RAY_DT = np.dtype([("origin", "<f4", 3), ("direct", "<f4", 3), ("color", "<f4", 
 HIT_DT = np.dtype([("u", "<f4"), ("v", "<f4"), ("t", "<f4"), ("tri", "<i4")])
 QUERY_RAY_DT = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direct", "<f4", 3), ("tmax", "<f4")])   # psm_query_ray
 POINT_QUERY_DT = np.dtype([("p", "<f4", 3), ("rmax", "<f4")])   # psm_point_query
+# PSM_INSIDE_DIRECTIONS (include/psm_hip.h): ray k of TriangleHierarchy.inside / .signedDistance goes along row k
+INSIDE_DIRECTIONS = np.array([[0.4082483, 0.57735026, 0.70710677], [-0.7905694, 0.35355338, 0.5],
+                              [0.52223295, -0.797724, 0.30151135], [-0.35355338, -0.4330127, -0.8291562],
+                              [0.7337994, 0.2773501, -0.6201737]], np.float32)
 LIGHT_DT = np.dtype([("lightVector", "<f4", 4), ("lightColor", "<f4", 4),
                      ("lightOffset", "<f4", 4), ("lightAmbient", "<f4", 4)])
 
@@ -369,16 +373,16 @@ class TriangleHierarchy:
         per-ray [n]. numpy in: numpy out (staged through device buffers; synchronises). torch device tensors in: torch tensors out on
         the same device, no copy through the host, ordered against torch's current stream without synchronising. Returns QueryHits:
         t, u, v, tri (tri = -1, t = +inf on a miss) as views of one [n, 4] float32 buffer (u, v, t, tri as int32 bits)."""
-        return self._query(origins, directions, tmin, tmax, False)
+        return self._query(origins, directions, tmin, tmax, "hits")
 
     def occluded(self, origins, directions, tmin=0.0, tmax=np.inf):
         """Any hit inside [tmin, tmax] per ray (psm_bvh_occluded_dev; not in the reference): a bool array / tensor. Arguments and
         placement as intersect()."""
-        return self._query(origins, directions, tmin, tmax, True)
+        return self._query(origins, directions, tmin, tmax, "bool")
 
-    def _query(self, origins, directions, tmin, tmax, any_hit):
+    def _query(self, origins, directions, tmin, tmax, out):
         if type(origins).__module__.split(".")[0] == "torch":
-            return _query_torch(self, origins, directions, tmin, tmax, any_hit)
+            return _query_torch(self, origins, directions, tmin, tmax, out)
         o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
         n = o.shape[0]
@@ -386,52 +390,82 @@ class TriangleHierarchy:
             raise ValueError("origins and directions: %d against %d rays" % (n, d.shape[0]))
         rays = np.empty((n, 8), np.float32)
         rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7] = o, tmin, d, tmax
-        return self._launch_np(rays, any_hit, "psm_bvh_occluded_dev" if any_hit else "psm_bvh_intersect_dev")
+        return self._launch_np(rays, out, _RAY_QUERIES[out])
+
+    def countHits(self, origins, directions, tmin=0.0, tmax=np.inf):
+        """The number of triangles each ray hits inside [tmin, tmax] (psm_bvh_count_hits_dev; not in the reference): what occluded()
+        asks "is there one?" about, counted. A uint32 array, or for torch tensors an int32 tensor on the same device (torch has
+        no general uint32). Arguments and placement as intersect()."""
+        return self._query(origins, directions, tmin, tmax, "count")
+
+    def inside(self, points, samples=3):
+        """Whether each point is inside the surface (psm_bvh_inside_dev; not in the reference): `samples` (1, 3 or 5) rays from
+        the point along INSIDE_DIRECTIONS, each voting "inside" iff it crosses an odd number of triangles; the majority decides. A
+        bool array / tensor. Right for a closed surface (a vote, because a ray within 1e-5 of a shared edge is counted by both of
+        its triangles); for an open one merely deterministic. points and placement as closestPoint(); a packed [n, 4] array or
+        tensor of (p, rmax) records is taken as it is (rmax is ignored)."""
+        return self._point_query(points, np.inf, "bool", "psm_bvh_inside_dev", samples)
+
+    def signedDistance(self, points, rmax=np.inf, samples=3):
+        """closestPoint() with the sign of inside() (psm_bvh_signed_distance_dev; not in the reference): QueryHits whose t is the
+        distance, negative inside (-0.0 for a point on the surface that the vote takes as inside). A point with no triangle within
+        rmax stays a miss (tri = -1, t = +inf) and casts no rays: with a finite rmax, a narrow-band distance field."""
+        return self._point_query(points, rmax, "hits", "psm_bvh_signed_distance_dev", samples)
 
     def closestPoint(self, points, rmax=np.inf):
         """Closest point on the hierarchy's triangles of every point within rmax (psm_bvh_closest_point_dev; not in the reference):
         points [n, 3], rmax a scalar or per-point [n]. numpy in: numpy out; torch device tensors in: torch tensors out on the same
         device, ordered against torch's current stream (as intersect()). Returns QueryHits: t = the distance, tri, and u, v with
         the point = (v0 + u e1) + v e2 of triangle tri (tri = -1, t = +inf when no triangle is within rmax)."""
-        return self._point_query(points, rmax, False)
+        return self._point_query(points, rmax, "hits", "psm_bvh_closest_point_dev")
 
     def within(self, points, radius):
         """Whether some triangle is within `radius` (a scalar or per-point [n]) of each point (psm_bvh_within_dev; not in the
         reference): a bool array / tensor. Arguments and placement as closestPoint()."""
-        return self._point_query(points, radius, True)
+        return self._point_query(points, radius, "bool", "psm_bvh_within_dev")
 
-    def _point_query(self, points, rmax, flag):
-        name = "psm_bvh_within_dev" if flag else "psm_bvh_closest_point_dev"
+    def _point_query(self, points, rmax, out, name, samples=None):
+        """points [n, 3] with rmax, or (the inside queries only) [n, 4] records already packed; samples: the inside queries' extra
+        argument"""
+        extra = () if samples is None else (C.c_uint32(_samples(samples, name)),)
+        packed = samples is not None and getattr(points, "ndim", 0) == 2 and points.shape[1] == 4
         if type(points).__module__.split(".")[0] == "torch":
             import torch
             dev = points.device
             if dev.type != "cuda":
-                raise ValueError("closestPoint / within: points must be a tensor on the context's device")
-            p = points.reshape(-1, 3)
+                raise ValueError("point queries: points must be a tensor on the context's device")
+            if packed and points.dtype == torch.float32 and points.is_contiguous():
+                return _launch_torch(self, points, out, name, *extra)
+            p = points[:, 0:3] if packed else points.reshape(-1, 3)
             q = torch.empty((p.shape[0], 4), dtype=torch.float32, device=dev)
             q[:, 0:3] = p
-            q[:, 3] = torch.as_tensor(rmax, dtype=torch.float32, device=dev)
-            return _launch_torch(self, q, flag, name)
+            q[:, 3] = points[:, 3] if packed else torch.as_tensor(rmax, dtype=torch.float32, device=dev)
+            return _launch_torch(self, q, out, name, *extra)
+        if packed:
+            return self._launch_np(np.ascontiguousarray(points, np.float32), out, name, *extra)
         p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
         q = np.empty((p.shape[0], 4), np.float32)
         q[:, 0:3], q[:, 3] = p, rmax
-        return self._launch_np(q, flag, name)
+        return self._launch_np(q, out, name, *extra)
 
-    def _launch_np(self, packed, flag, name):
-        """one query launch over host records `packed` [n, k] float32: staged through device buffers, synchronises"""
+    def _launch_np(self, packed, out, name, *extra):
+        """one query launch over host records `packed` [n, k] float32: staged through device buffers, synchronises. out: the
+        result's kind (_QUERY_OUT); extra: arguments between n and the output pointer"""
         n = packed.shape[0]
-        out_bytes = n if flag else 16 * n
-        hr, ho = self.ctx.buf_alloc(max(packed.nbytes, 32)), self.ctx.buf_alloc(max(out_bytes, 16))
+        per, dtype = _QUERY_OUT[out]
+        hr, ho = self.ctx.buf_alloc(max(packed.nbytes, 32)), self.ctx.buf_alloc(max(per * n, 16))
         try:
             if n:
                 self.ctx.buf_upload(hr, packed)
-            self.ctx.check(getattr(lib(), name)(self._h, C.c_void_p(self.ctx.buf_ptr(hr)[0]), C.c_size_t(n),
+            self.ctx.check(getattr(lib(), name)(self._h, C.c_void_p(self.ctx.buf_ptr(hr)[0]), C.c_size_t(n), *extra,
                                                 C.c_void_p(self.ctx.buf_ptr(ho)[0])), name)
             if n == 0:
                 self.ctx.sync()
-                return np.zeros(0, np.bool_) if flag else QueryHits(np.zeros((0, 4), np.float32))
-            if flag:
+                return QueryHits(np.zeros((0, 4), np.float32)) if out == "hits" else np.zeros(0, dtype)
+            if out == "bool":
                 return self.ctx.buf_download(ho, np.uint8, n).view(np.bool_)
+            if out == "count":
+                return self.ctx.buf_download(ho, np.uint32, n)
             return QueryHits(self.ctx.buf_download(ho, np.float32, 4 * n).reshape(n, 4))
         finally:
             self.ctx.buf_free(hr)
@@ -467,8 +501,21 @@ class TriangleHierarchy:
             self._h = C.c_void_p()
 
 
+# a query's result by kind: bytes per query and the numpy type of the array returned ("hits": QueryHits over float32 [n, 4])
+_QUERY_OUT = {"hits": (16, np.float32), "bool": (1, np.bool_), "count": (4, np.uint32)}
+_RAY_QUERIES = {"hits": "psm_bvh_intersect_dev", "bool": "psm_bvh_occluded_dev", "count": "psm_bvh_count_hits_dev"}
+
+
+def _samples(samples, name):
+    """the inside queries' sample count as the C ABI takes it (a uint32; which values are allowed is the library's to say)"""
+    s = int(samples)
+    if s != samples or not 0 <= s < 1 << 32:
+        raise ValueError("%s: samples must be 1, 3 or 5" % name)
+    return s
+
+
 class QueryHits:
-    """Closest hits of TriangleHierarchy.intersect (closest points of .closestPoint: t is the distance): `buffer` [n, 4] float32 (numpy array or torch tensor) holds psm_hit records
+    """Closest hits of TriangleHierarchy.intersect (closest points of .closestPoint and .signedDistance: t is the distance): `buffer` [n, 4] float32 (numpy array or torch tensor) holds psm_hit records
     (u, v, t, tri); t, u, v and tri (int32) are views of it."""
 
     def __init__(self, buffer):
@@ -502,7 +549,7 @@ def _hip_check(rc, what):
         raise PsmError("%s failed (%d)" % (what, rc))
 
 
-def _query_torch(th, origins, directions, tmin, tmax, any_hit):
+def _query_torch(th, origins, directions, tmin, tmax, out):
     """TriangleHierarchy.intersect / occluded on torch device tensors: rays packed on torch's current stream, the kernel on the
     context's stream, the two ordered by events when they differ -- no host synchronisation."""
     import torch
@@ -519,16 +566,18 @@ def _query_torch(th, origins, directions, tmin, tmax, any_hit):
     rays[:, 3] = torch.as_tensor(tmin, dtype=torch.float32, device=dev)
     rays[:, 4:7] = d
     rays[:, 7] = torch.as_tensor(tmax, dtype=torch.float32, device=dev)
-    return _launch_torch(th, rays, any_hit, "psm_bvh_occluded_dev" if any_hit else "psm_bvh_intersect_dev")
+    return _launch_torch(th, rays, out, _RAY_QUERIES[out])
 
 
-def _launch_torch(th, packed, flag, name):
+def _launch_torch(th, packed, kind, name, *extra):
     """One query launch over device records `packed` (made on torch's current stream) on the context's stream: the two streams
-    ordered by events when they differ -- no host synchronisation. flag: a bool per query, else QueryHits."""
+    ordered by events when they differ -- no host synchronisation. kind: the result's (_QUERY_OUT): QueryHits, a bool or an int32
+    count per query; extra: arguments between n and the output pointer."""
     import torch
     dev = packed.device
     n = packed.shape[0]
-    out = torch.empty((n,) if flag else (n, 4), dtype=torch.uint8 if flag else torch.float32, device=dev)
+    shape, dtype = {"hits": ((n, 4), torch.float32), "bool": ((n,), torch.uint8), "count": ((n,), torch.int32)}[kind]
+    out = torch.empty(shape, dtype=dtype, device=dev)
     cur = torch.cuda.current_stream(dev)
     mine = th.ctx.stream or 0   # (NULL: the device's null stream, torch's default stream)
     other = mine != cur.cuda_stream
@@ -536,14 +585,14 @@ def _launch_torch(th, packed, flag, name):
         ev_in = torch.cuda.Event()
         ev_in.record(cur)
         _hip_check(_hip().hipStreamWaitEvent(C.c_void_p(mine), C.c_void_p(ev_in.cuda_event), C.c_uint(0)), "hipStreamWaitEvent")
-    th.ctx.check(getattr(lib(), name)(th._h, C.c_void_p(packed.data_ptr()), C.c_size_t(n), C.c_void_p(out.data_ptr())), name)
+    th.ctx.check(getattr(lib(), name)(th._h, C.c_void_p(packed.data_ptr()), C.c_size_t(n), *extra, C.c_void_p(out.data_ptr())), name)
     if other:   # ... and torch's stream for the kernel: every later use of `out`, and of the memory of `packed`, comes after it
         hip, ev = _hip(), C.c_void_p()
         _hip_check(hip.hipEventCreateWithFlags(C.byref(ev), C.c_uint(2)), "hipEventCreateWithFlags")   # hipEventDisableTiming
         _hip_check(hip.hipEventRecord(ev, C.c_void_p(mine)), "hipEventRecord")
         _hip_check(hip.hipStreamWaitEvent(C.c_void_p(cur.cuda_stream), ev, C.c_uint(0)), "hipStreamWaitEvent")
         _hip_check(hip.hipEventDestroy(ev), "hipEventDestroy")
-    return out.view(torch.bool) if flag else QueryHits(out)
+    return QueryHits(out) if kind == "hits" else (out.view(torch.bool) if kind == "bool" else out)
 
 
 class TextureSet:

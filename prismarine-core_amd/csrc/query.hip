@@ -1,5 +1,6 @@
 // query.hip -- batched queries against a built hierarchy (new; no reference counterpart): closest hit and any hit of rays,
-// closest point and within-radius of points (the point queries are described at point_body below).
+// closest point and within-radius of points (the point queries are described at point_body below), and the hit
+// count of rays with the inside / outside and signed-distance queries of points built on it (CountRay below).
 //
 // psm_rt_traverse follows directTraverse.comp bit for bit: a 16-entry stack that drops subtrees (STACK_CAP), a PZERO-tolerant
 // "closest", intersectTriangle's clamp of |det| at 1e-6. These kernels answer "what does this ray hit?" exactly instead
@@ -46,8 +47,10 @@ struct QueryArgs {
     const uint32_t* sm;      // transform, leaf count, root
     const int32_t* sorted_tri;  // [0]: the lone leaf's triangle when the leaf count is 1 (bvh_segtree<true> writes it)
     int* spill;              // [QSTACK_MAX - QSTACK_LDS][gridDim.x * 64]
-    float4* hits;            // closest hit / closest point: psm_hit per query
-    uint8_t* occluded;       // any hit / within: 0 / 1 per query
+    float4* hits;            // closest hit / closest point: psm_hit per query (signed distance: read, and t rewritten)
+    uint8_t* occluded;       // any hit / within / inside: 0 / 1 per query
+    uint32_t* count;         // hit count: crossings per ray
+    uint32_t samples;        // inside / signed distance: rays per point (1, 3 or 5)
 };
 
 // tri_test (trace.hip) operation for operation, with invDev = 1 / det instead of 1 / (max(|det|, 1e-6) * sign(det)) and without
@@ -138,6 +141,7 @@ PSM_D void slab(const Axis& X, const Axis& Y, const Axis& Z, float mnx, float mn
 // area (spill_for). The body:
 //   bool begin(i, alive)  load query i (alive: i < n) and set up; false: the query misses without a walk
 //   void children(n0, n1, okL, okR, kL, kR), void leaf(tri), bool done() (the lane retires), void finish(i)
+//   bool again()          after a walk: true sets up another walk of the same query (the inside queries' next ray)
 // The stack holds links only: a popped subtree is visited and its children judged against the best as it is then
 // (keeping each entry's bound to drop it at the pop measured 8 % slower on the point queries).
 template <class Body>
@@ -154,42 +158,44 @@ PSM_D void query_walk(const QueryArgs& a, Body& q) {
     for (size_t i = (size_t)blockIdx.x * QUERY_BLOCK + (size_t)lane; i - (size_t)lane < a.n; i += spill_stride) {
         const bool alive = i < a.n;
         const bool valid = q.begin(i, alive);
-        if (valid && lone >= 0) q.leaf(lone);
-        int cur = root, sp = 0;
-        bool walking = valid && root >= 0;
-        while (walking) {
-            const uint4* np = (const uint4*)((const char*)node32 + ((uint32_t)cur << 5));
-            const uint4 n0 = np[0], n1 = np[1];
-            const int lkx = (int)n1.z, lky = (int)n1.w;
-            bool okL, okR;
-            float kL, kR;
-            q.children(n0, n1, okL, okR, kL, kR);
-            const bool leafL = okL && lkx < 0, leafR = okR && lky < 0;
-            // the accepted leaves, one test after the other (one copy of the triangle code in the loop)
-            int t0 = leafL ? ~lkx : (leafR ? ~lky : -1);
-            int t1 = (leafL && leafR) ? ~lky : -1;
-            while (t0 >= 0) {
-                q.leaf(t0);
-                t0 = t1;
-                t1 = -1;
+        do {
+            if (valid && lone >= 0) q.leaf(lone);
+            int cur = root, sp = 0;
+            bool walking = valid && root >= 0;
+            while (walking) {
+                const uint4* np = (const uint4*)((const char*)node32 + ((uint32_t)cur << 5));
+                const uint4 n0 = np[0], n1 = np[1];
+                const int lkx = (int)n1.z, lky = (int)n1.w;
+                bool okL, okR;
+                float kL, kR;
+                q.children(n0, n1, okL, okR, kL, kR);
+                const bool leafL = okL && lkx < 0, leafR = okR && lky < 0;
+                // the accepted leaves, one test after the other (one copy of the triangle code in the loop)
+                int t0 = leafL ? ~lkx : (leafR ? ~lky : -1);
+                int t1 = (leafL && leafR) ? ~lky : -1;
+                while (t0 >= 0) {
+                    q.leaf(t0);
+                    t0 = t1;
+                    t1 = -1;
+                }
+                if (q.done()) break;
+                const bool intL = okL && !leafL, intR = okR && !leafR;
+                const bool leftFirst = intL && (!intR || kL <= kR);   // nearer child first
+                const int first = leftFirst ? lkx : lky, second = leftFirst ? lky : lkx;
+                if (intL && intR) {
+                    // (sp < QSTACK_MAX always: see QSTACK_MAX; the host refuses hierarchies whose bound exceeds it)
+                    if (sp < QSTACK_LDS) stack[sp][lane] = second;
+                    else if (sp < QSTACK_MAX) spill[(size_t)(sp - QSTACK_LDS) * spill_stride] = second;
+                    sp++;
+                }
+                cur = first;
+                if (!(intL || intR)) {
+                    if (sp == 0) break;
+                    sp--;
+                    cur = sp < QSTACK_LDS ? stack[sp][lane] : spill[(size_t)(sp - QSTACK_LDS) * spill_stride];
+                }
             }
-            if (q.done()) break;
-            const bool intL = okL && !leafL, intR = okR && !leafR;
-            const bool leftFirst = intL && (!intR || kL <= kR);   // nearer child first
-            const int first = leftFirst ? lkx : lky, second = leftFirst ? lky : lkx;
-            if (intL && intR) {
-                // (sp < QSTACK_MAX always: see QSTACK_MAX; the host refuses hierarchies whose bound exceeds it)
-                if (sp < QSTACK_LDS) stack[sp][lane] = second;
-                else if (sp < QSTACK_MAX) spill[(size_t)(sp - QSTACK_LDS) * spill_stride] = second;
-                sp++;
-            }
-            cur = first;
-            if (!(intL || intR)) {
-                if (sp == 0) break;
-                sp--;
-                cur = sp < QSTACK_LDS ? stack[sp][lane] : spill[(size_t)(sp - QSTACK_LDS) * spill_stride];
-            }
-        }
+        } while (q.again());
         if (alive) q.finish(i);
     }
 }
@@ -245,6 +251,7 @@ struct RayBody {
         }
     }
     PSM_D bool done() const { return ANY && found; }   // any hit: the lane retires at its first hit
+    PSM_D bool again() const { return false; }
     PSM_D void finish(size_t i) const {
         if (ANY) a.occluded[i] = found ? 1 : 0;
         else a.hits[i] = found ? make_float4(bu, bv, best, __int_as_float(btri)) : make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1));
@@ -425,6 +432,7 @@ struct PointBody {
         }
     }
     PSM_D bool done() const { return WITHIN && found; }   // within: the lane retires at its first counting candidate
+    PSM_D bool again() const { return false; }
     PSM_D void finish(size_t i) const {
         if (WITHIN) a.occluded[i] = found ? 1 : 0;
         else a.hits[i] = found ? make_float4(bu, bv, sqrtf(best), __int_as_float(btri)) : make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1));
@@ -446,6 +454,121 @@ PSM_D void point_body(const QueryArgs& a) {
     query_walk(a, q);
 }
 
+// ---- hit count, inside / outside, signed distance (include/psm_hip.h) ------------------------------------------
+
+// The ray every one of these walks: all candidates with tri_query's acceptance and tmin <= t <= tmax are counted -- the any-hit
+// predicate, asked "how many?". Against the any-hit body: a child box is kept against [tmin, tmax] only (there is no best t to
+// prune by) and the lane never retires early. The count is a sum of integers: it does not depend on the traversal order, so the
+// children's order key (the near distance, as the other ray bodies) is only a matter of memory locality.
+struct CountRay {
+    const QueryArgs& a;
+    v3 o, d;
+    float tmin, tmax;
+    uint32_t count;
+    Axis X, Y, Z;
+
+    // aim the ray (dir: as given, normalised here as every query ray's) and clear the count; false: the ray is invalid (RayBody)
+    PSM_D bool aim(v3 orig, v3 dir, float lo, float hi) {
+        o = orig;
+        d = normalize3(dir);
+        tmin = lo;
+        tmax = hi;
+        count = 0u;
+        float M[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) M[k] = u2f(a.sm[SM_M + k]);
+        X = ray_axis(M, 0, o, d);
+        Y = ray_axis(M, 1, o, d);
+        Z = ray_axis(M, 2, o, d);
+        return finite3(o) && finite3(d) && tmin <= tmax;
+    }
+    PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& nL, float& nR) const {
+        float fL, fR;
+        slab(X, Y, Z, half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z), nL, fL);
+        slab(X, Y, Z, half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y), nR, fR);
+        okL = (nL <= fL) & (nL <= tmax) & (fL >= tmin);
+        okR = (nR <= fR) & (nR <= tmax) & (fR >= tmin);
+    }
+    PSM_D void leaf(int tri) {
+        float t, u, v;
+        if (tri_query(a.tri48, tri, o, d, t, u, v) && t >= tmin && t <= tmax) count++;
+    }
+    PSM_D bool done() const { return false; }   // every crossing counts: the walk ends when the stack is empty
+};
+
+// hit count of a ray (psm_bvh_count_hits_dev)
+struct CountBody : CountRay {
+    PSM_D bool begin(size_t i, bool alive) {
+        float4 r0 = make_float4(0.f, 0.f, 0.f, 1.f), r1 = make_float4(1.f, 0.f, 0.f, -1.f);
+        if (alive) { r0 = a.rays[2 * i]; r1 = a.rays[2 * i + 1]; }
+        return aim(mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), r0.w, r1.w) && alive;
+    }
+    PSM_D bool again() const { return false; }
+    PSM_D void finish(size_t i) const { a.count[i] = count; }
+};
+
+// The rays of the inside test (psm_hip.h PSM_INSIDE_DIRECTIONS: written there once): ray k of a point p is {p, 0, row k, +inf}.
+__device__ const float INSIDE_DIR[PSM_INSIDE_MAX_SAMPLES][3] = PSM_INSIDE_DIRECTIONS;
+
+// inside / outside of a point (SIGN = false: psm_bvh_inside_dev) and the sign of a closest-point result (SIGN = true: the second
+// kernel of psm_bvh_signed_distance_dev, after bvh_query_point has written hits[i]). One point per lane; its `samples` rays are
+// walked one after the other (again()), so at any moment every lane of the wave follows the same direction from nearby origins.
+// A ray votes "inside" iff its count is odd; the point is inside iff more than half of the rays vote so.
+// SIGN: a point whose closest-point result is a miss (no triangle within rmax, an invalid query) walks nothing and keeps its
+// record; the others get the sign bit of t set when inside (a distance of 0 becomes -0).
+template <bool SIGN>
+struct InsideBody : CountRay {
+    v3 p;
+    uint32_t k, votes;
+    float dist;
+    bool valid;
+
+    PSM_D bool shoot() {
+        const int r = __builtin_amdgcn_readfirstlane((int)k);   // (the same k in every lane that walks: the row by scalar loads)
+        return aim(p, mk3(INSIDE_DIR[r][0], INSIDE_DIR[r][1], INSIDE_DIR[r][2]), 0.f, __builtin_inff());
+    }
+    PSM_D bool begin(size_t i, bool alive) {
+        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
+        if (alive) q = a.rays[i];
+        p = mk3(q.x, q.y, q.z);
+        k = 0u;
+        votes = 0u;
+        dist = 0.f;
+        valid = alive;
+        if (SIGN) {
+            float4 h = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+            if (alive) h = a.hits[i];
+            dist = h.z;
+            valid = __float_as_int(h.w) >= 0;
+        }
+        valid = shoot() && valid;   // (a non-finite p: outside)
+        return valid;
+    }
+    PSM_D bool again() {
+        votes += count & 1u;
+        k++;
+        if (!valid || k >= a.samples) return false;
+        shoot();
+        return true;
+    }
+    PSM_D void finish(size_t i) const {
+        const bool in = 2u * votes > a.samples;
+        if (!SIGN) a.occluded[i] = in ? 1 : 0;
+        else if (in) ((float*)(a.hits + i))[2] = __uint_as_float(__float_as_uint(dist) | 0x80000000u);
+    }
+};
+
+PSM_D void count_body(const QueryArgs& a) {
+    CountBody q{{a}};
+    query_walk(a, q);
+}
+
+template <bool SIGN>
+PSM_D void inside_body(const QueryArgs& a) {
+    InsideBody<SIGN> q{{a}};
+    query_walk(a, q);
+}
+
 }  // namespace
 
 // the kernels, under names of their own (profiles and the codegen tests find them by these)
@@ -453,6 +576,9 @@ __global__ __launch_bounds__(QUERY_BLOCK, 8) void bvh_query_closest(QueryArgs a)
 __global__ __launch_bounds__(QUERY_BLOCK, 8) void bvh_query_any(QueryArgs a) { query_body<true>(a); }
 __global__ __launch_bounds__(QUERY_BLOCK, 8) void bvh_query_point(QueryArgs a) { point_body<false>(a); }
 __global__ __launch_bounds__(QUERY_BLOCK, 8) void bvh_query_within(QueryArgs a) { point_body<true>(a); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void bvh_query_count(QueryArgs a) { count_body(a); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void bvh_query_inside(QueryArgs a) { inside_body<false>(a); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void bvh_query_sign(QueryArgs a) { inside_body<true>(a); }
 
 namespace {
 
@@ -477,30 +603,52 @@ int ceil_log2(size_t n) {
     return k;
 }
 
-enum QueryKind { Q_CLOSEST, Q_ANY, Q_POINT, Q_WITHIN };
-const char* const QUERY_NAME[] = {"psm_bvh_intersect_dev", "psm_bvh_occluded_dev", "psm_bvh_closest_point_dev", "psm_bvh_within_dev"};
+enum QueryKind { Q_CLOSEST, Q_ANY, Q_POINT, Q_WITHIN, Q_COUNT, Q_INSIDE, Q_SIGNED };
+// per kind: the entry point, what the input and the output are called in its messages (out: NULL when its alignment is not
+// checked: a byte per query), the output's alignment, the family in the state / capacity texts
+struct QueryDesc {
+    const char* name;
+    const char* in;
+    const char* out;
+    unsigned out_align;
+    bool points;
+};
+const QueryDesc QUERY_DESC[] = {{"psm_bvh_intersect_dev", "rays", "hits", 16, false},
+                                {"psm_bvh_occluded_dev", "rays", nullptr, 1, false},
+                                {"psm_bvh_closest_point_dev", "points", "hits", 16, true},
+                                {"psm_bvh_within_dev", "points", nullptr, 1, true},
+                                {"psm_bvh_count_hits_dev", "rays", "counts", 4, false},
+                                {"psm_bvh_inside_dev", "points", nullptr, 1, true},
+                                {"psm_bvh_signed_distance_dev", "points", "hits", 16, true}};
 
-// the checks and the launch every query shares: in / out must be non-NULL, in (and a psm_hit out) 16-byte aligned
-int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, psm_hit* d_hits, uint8_t* d_hit) {
+// the checks and the launch every query shares: in / out must be non-NULL, in 16-byte aligned, out as its kind asks (a psm_hit
+// 16 bytes, a count 4); samples (the inside kinds only): 1, 3 or 5
+int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, void* d_out, uint32_t samples = 0) {
     if (!b) return PSM_ERR_INVALID;
     if (n == 0) return PSM_OK;
     psm_ctx* c = b->ctx;
-    const bool flags = kind == Q_ANY || kind == Q_WITHIN;
+    const QueryDesc& k = QUERY_DESC[kind];
     char msg[96];
-    if (!d_in || (flags ? (const void*)d_hit : (const void*)d_hits) == nullptr) {
-        snprintf(msg, sizeof msg, "%s: NULL pointer", QUERY_NAME[kind]);
+    if (!d_in || !d_out) {
+        snprintf(msg, sizeof msg, "%s: NULL pointer", k.name);
         return set_err(c, PSM_ERR_INVALID, msg);
     }
-    if (((uintptr_t)d_in & 15u) != 0 || (!flags && ((uintptr_t)d_hits & 15u) != 0)) {
-        const char* what = kind < Q_POINT ? (flags ? "rays" : "rays or hits") : (flags ? "points" : "points or hits");
-        snprintf(msg, sizeof msg, "%s: %s not 16-byte aligned", QUERY_NAME[kind], what);
+    const bool in_bad = ((uintptr_t)d_in & 15u) != 0, out_bad = ((uintptr_t)d_out & (uintptr_t)(k.out_align - 1)) != 0;
+    if (in_bad || out_bad) {
+        if (k.out_align == 16) snprintf(msg, sizeof msg, "%s: %s or %s not 16-byte aligned", k.name, k.in, k.out);
+        else if (in_bad) snprintf(msg, sizeof msg, "%s: %s not 16-byte aligned", k.name, k.in);
+        else snprintf(msg, sizeof msg, "%s: %s not %u-byte aligned", k.name, k.out, k.out_align);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if ((kind == Q_INSIDE || kind == Q_SIGNED) && samples != 1 && samples != 3 && samples != 5) {
+        snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", k.name);
         return set_err(c, PSM_ERR_INVALID, msg);
     }
     (void)hipSetDevice(c->device);
-    if (!b->built) return set_err(c, PSM_ERR_STATE, kind < Q_POINT ? "ray query before build" : "point query before build");
+    if (!b->built) return set_err(c, PSM_ERR_STATE, k.points ? "point query before build" : "ray query before build");
     if (63 + ceil_log2(b->cap) > QSTACK_MAX)
-        return set_err(c, PSM_ERR_CAPACITY, kind < Q_POINT ? "ray query: hierarchy deeper than the query stack"
-                                                           : "point query: hierarchy deeper than the query stack");
+        return set_err(c, PSM_ERR_CAPACITY, k.points ? "point query: hierarchy deeper than the query stack"
+                                                     : "ray query: hierarchy deeper than the query stack");
     void* spill = nullptr;
     const int rc = spill_for(c, &spill);   // (a context's first query allocates: a later one can be captured into a graph)
     if (rc != PSM_OK) return rc;
@@ -510,12 +658,20 @@ int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, psm_hit* d_hit
     qa.rays = (const float4*)d_in; qa.n = n;
     qa.node32 = b->d_node32; qa.tri48 = b->d_tri48; qa.sm = b->d_small; qa.sorted_tri = b->d_sorted_tri;
     qa.spill = (int*)spill;
-    qa.hits = (float4*)d_hits; qa.occluded = d_hit;
+    qa.hits = (float4*)d_out; qa.occluded = (uint8_t*)d_out; qa.count = (uint32_t*)d_out;   // (a kernel reads its own)
+    qa.samples = samples;
     switch (kind) {
         case Q_CLOSEST: bvh_query_closest<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
         case Q_ANY: bvh_query_any<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
         case Q_POINT: bvh_query_point<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
         case Q_WITHIN: bvh_query_within<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
+        case Q_COUNT: bvh_query_count<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
+        case Q_INSIDE: bvh_query_inside<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
+        case Q_SIGNED:   // the unchanged closest-point kernel, then the sign of what it found (the same stream: in order)
+            bvh_query_point<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa);
+            PSM_HIP(c, hipGetLastError());
+            bvh_query_sign<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa);
+            break;
     }
     PSM_HIP(c, hipGetLastError());
     return PSM_OK;
@@ -535,17 +691,29 @@ void query_release(psm_ctx* c) {
 }  // namespace psm
 
 int psm_bvh_intersect_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits) {
-    return psm::query(bvh, psm::Q_CLOSEST, d_rays, n, d_hits, nullptr);
+    return psm::query(bvh, psm::Q_CLOSEST, d_rays, n, d_hits);
 }
 
 int psm_bvh_occluded_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, uint8_t* d_hit) {
-    return psm::query(bvh, psm::Q_ANY, d_rays, n, nullptr, d_hit);
+    return psm::query(bvh, psm::Q_ANY, d_rays, n, d_hit);
 }
 
 int psm_bvh_closest_point_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, psm_hit* d_hits) {
-    return psm::query(bvh, psm::Q_POINT, d_points, n, d_hits, nullptr);
+    return psm::query(bvh, psm::Q_POINT, d_points, n, d_hits);
 }
 
 int psm_bvh_within_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, uint8_t* d_hit) {
-    return psm::query(bvh, psm::Q_WITHIN, d_points, n, nullptr, d_hit);
+    return psm::query(bvh, psm::Q_WITHIN, d_points, n, d_hit);
+}
+
+int psm_bvh_count_hits_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, uint32_t* d_count) {
+    return psm::query(bvh, psm::Q_COUNT, d_rays, n, d_count);
+}
+
+int psm_bvh_inside_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, uint32_t samples, uint8_t* d_inside) {
+    return psm::query(bvh, psm::Q_INSIDE, d_points, n, d_inside, samples);
+}
+
+int psm_bvh_signed_distance_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, uint32_t samples, psm_hit* d_hits) {
+    return psm::query(bvh, psm::Q_SIGNED, d_points, n, d_hits, samples);
 }

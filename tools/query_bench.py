@@ -6,7 +6,11 @@ REPS (5) device-synchronised calls after a warm-up call. Prints one JSON line.
 `query_bench.py points`: the point queries (psm_bvh_closest_point_dev / psm_bvh_within_dev) on the same scene instead, NPTS (2^21)
 points per set: (a) surface samples plus Gaussian noise of 1 % of the scene diagonal, closest point with rmax = inf; (b) uniform in
 the scene's bounds, rmax = inf; (c) set (b) through within with a radius of 0.5 % of the diagonal.
-A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points]"""
+`query_bench.py signed`: the hit count and the queries built on it (psm_bvh_count_hits_dev / psm_bvh_inside_dev /
+psm_bvh_signed_distance_dev): (a) count beside closest and any on the ray mode's primary and bounce-like rays; (b) on a closed mesh
+(a torus of TORUS_NU x TORUS_NV quads, 2 M triangles) and a regular grid of NPTS points over its bounds: inside with 1 / 3 / 5
+rays, closest point, and signed distance with rmax = inf and with a band of 2 % of the diagonal.
+A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed]"""
 import ctypes as C
 import importlib
 import json
@@ -23,6 +27,7 @@ scenes = importlib.import_module("prismarine-core_amd.scenes")
 W, H = 1920, 1080
 REPS = int(os.environ.get("REPS", "5"))
 NPTS = int(os.environ.get("NPTS", str(1 << 21)))
+TORUS_NU, TORUS_NV = int(os.environ.get("TORUS_NU", "1448")), int(os.environ.get("TORUS_NV", "724"))
 
 
 def median_ms(ctx, fn):
@@ -88,6 +93,145 @@ def points():
     print(json.dumps(out))
 
 
+def bounce_rays(sc, o, d, hits):
+    """bounce-like rays: from the primary hits (rays that missed start at their origin), a cosine-ish direction about the face
+    normal turned towards the incoming ray"""
+    n = o.shape[0]
+    tri = hits.view(np.int32)[:, 3]
+    rng = np.random.RandomState(7)
+    dn = d / np.linalg.norm(d, axis=1, keepdims=True)
+    hit = tri >= 0
+    bo = np.where(hit[:, None], o + dn * np.where(hit, hits[:, 2], 0)[:, None], o).astype(np.float32)
+    t3 = sc["tris"].reshape(-1, 3, 3)[np.maximum(tri, 0)]
+    nrm = np.cross(t3[:, 1] - t3[:, 0], t3[:, 2] - t3[:, 0])
+    nrm /= np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-30)
+    nrm = np.where((np.sum(nrm * dn, axis=1) > 0)[:, None], -nrm, nrm)
+    nrm = np.where(hit[:, None], nrm, dn)
+    u = rng.normal(size=(n, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    return bo, (nrm + u).astype(np.float32)
+
+
+def torus(nu, nv, R=1.0, r=0.4):
+    """a closed mesh: a torus around the z axis, nu x nv quads split in two, vertices on the surface"""
+    u, w = np.arange(nu) * (2 * np.pi / nu), np.arange(nv) * (2 * np.pi / nv)
+    U, Wv = np.meshgrid(u, w, indexing="ij")
+    vs = np.stack([(R + r * np.cos(Wv)) * np.cos(U), (R + r * np.cos(Wv)) * np.sin(U), r * np.sin(Wv)], -1).astype(np.float32)
+    i, j = np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij")
+    i1, j1 = (i + 1) % nu, (j + 1) % nv
+    a, b, c, d = vs[i, j], vs[i1, j], vs[i1, j1], vs[i, j1]
+    return np.concatenate([np.stack([a, b, c], -2).reshape(-1, 9), np.stack([a, c, d], -2).reshape(-1, 9)]).astype(np.float32)
+
+
+def signed():
+    lib = psm.lib()
+    out = {"reps": REPS}
+    # (a) count beside closest and any: the ray mode's rays
+    sc = scenes.sponza_like()
+    ctx = psm.Context(0)
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(sc["tris"].shape[0])
+    th.loadTriangles(sc["tris"], sc["normals"], sc["mats"])
+    th.build()
+    rt = psm.Pipeline(ctx, seed=1000)
+    rt.resizeBuffers(W, H)
+    rt.resize(W, H)
+    cam = scenes.camera_matrices(sc["eye"], sc["view"], W, H)
+    rt.camera_matrices(cam[0], cam[1])
+    prim = rt.download_rays()
+    rt.close()
+    n = prim.shape[0]
+    o, d = prim["origin"].copy(), prim["direct"].copy()
+    h_rays, h_hits, h_occ, h_cnt = ctx.buf_alloc(32 * n), ctx.buf_alloc(16 * n), ctx.buf_alloc(n), ctx.buf_alloc(4 * n)
+    p_rays, p_hits, p_occ, p_cnt = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in (h_rays, h_hits, h_occ, h_cnt))
+
+    def upload(o, d, tmin):
+        r = np.zeros((n, 8), np.float32)
+        r[:, 0:3], r[:, 3], r[:, 4:7], r[:, 7] = o, tmin, d, np.inf
+        ctx.buf_upload(h_rays, r)
+
+    def closest():
+        ctx.check(lib.psm_bvh_intersect_dev(th._h, p_rays, C.c_size_t(n), p_hits), "psm_bvh_intersect_dev")
+
+    def anyhit():
+        ctx.check(lib.psm_bvh_occluded_dev(th._h, p_rays, C.c_size_t(n), p_occ), "psm_bvh_occluded_dev")
+
+    def count():
+        ctx.check(lib.psm_bvh_count_hits_dev(th._h, p_rays, C.c_size_t(n), p_cnt), "psm_bvh_count_hits_dev")
+
+    out["rays"] = n
+    upload(o, d, 0.0)
+    for k, fn in (("closest", closest), ("any", anyhit), ("count", count)):
+        out["primary_%s_ms" % k] = median_ms(ctx, fn)
+    out["primary_mean_count"] = float(ctx.buf_download(h_cnt, np.uint32, n).mean())
+    hits = ctx.buf_download(h_hits, np.float32, 4 * n).reshape(n, 4)
+    upload(*bounce_rays(sc, o, d, hits), 1e-3)
+    for k, fn in (("closest", closest), ("any", anyhit), ("count", count)):
+        out["bounce_%s_ms" % k] = median_ms(ctx, fn)
+    out["bounce_mean_count"] = float(ctx.buf_download(h_cnt, np.uint32, n).mean())
+    for s in ("primary", "bounce"):
+        out[s + "_count_over_closest"] = round(out[s + "_count_ms"] / out[s + "_closest_ms"], 3)
+        out[s + "_count_over_any"] = round(out[s + "_count_ms"] / out[s + "_any_ms"], 3)
+        for k in ("closest", "any", "count"):
+            out["%s_%s_mrays_s" % (s, k)] = round(n / out["%s_%s_ms" % (s, k)] / 1e3, 1)
+            out["%s_%s_ms" % (s, k)] = round(out["%s_%s_ms" % (s, k)], 4)
+    for h in (h_rays, h_hits, h_occ, h_cnt):
+        ctx.buf_free(h)
+    th.close()
+
+    # (b) a closed mesh and a regular grid over its bounds
+    tris = torus(TORUS_NU, TORUS_NV)
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(tris.shape[0])
+    th.loadTriangles(tris)
+    th.build()
+    lo, hi = tris.reshape(-1, 3).min(0), tris.reshape(-1, 3).max(0)
+    diag = float(np.linalg.norm(hi - lo))
+    g = int(round(NPTS ** (1.0 / 3.0)))
+    m = g * g * g
+    ax = [np.linspace(lo[k], hi[k], g, dtype=np.float32) for k in range(3)]
+    grid = np.stack(np.meshgrid(*ax, indexing="ij"), -1).reshape(-1, 3)
+    h_pts, h_hits, h_in = ctx.buf_alloc(16 * m), ctx.buf_alloc(16 * m), ctx.buf_alloc(m)
+    p_pts, p_hits, p_in = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in (h_pts, h_hits, h_in))
+
+    def upload_points(r):
+        q = np.empty((m, 4), np.float32)
+        q[:, 0:3], q[:, 3] = grid, r
+        ctx.buf_upload(h_pts, q)
+
+    def inside(s):
+        return lambda: ctx.check(lib.psm_bvh_inside_dev(th._h, p_pts, C.c_size_t(m), C.c_uint32(s), p_in), "psm_bvh_inside_dev")
+
+    def closest_point():
+        ctx.check(lib.psm_bvh_closest_point_dev(th._h, p_pts, C.c_size_t(m), p_hits), "psm_bvh_closest_point_dev")
+
+    def signed_distance():
+        ctx.check(lib.psm_bvh_signed_distance_dev(th._h, p_pts, C.c_size_t(m), C.c_uint32(3), p_hits), "psm_bvh_signed_distance_dev")
+
+    band = 0.02 * diag
+    out.update({"points": m, "grid": g, "mesh_tris": int(tris.shape[0]), "diag": round(diag, 3), "band": round(band, 4)})
+    upload_points(np.inf)
+    times = {}
+    for s in (1, 3, 5):
+        times["inside_%d" % s] = median_ms(ctx, inside(s))
+        out["inside_%d_fraction" % s] = float(ctx.buf_download(h_in, np.uint8, m).mean())
+    times["closest_point"] = median_ms(ctx, closest_point)
+    times["signed_distance_3"] = median_ms(ctx, signed_distance)
+    upload_points(band)
+    times["closest_point_band"] = median_ms(ctx, closest_point)
+    times["signed_distance_3_band"] = median_ms(ctx, signed_distance)
+    out["band_fraction"] = float((ctx.buf_download(h_hits, np.float32, 4 * m).view(np.int32)[3::4] >= 0).mean())
+    for k, v in times.items():
+        out[k + "_ms"] = round(v, 4)
+        out[k + "_mpts_s"] = round(m / v / 1e3, 1)
+    out["lib"] = os.path.basename(psm.LIB_PATH)
+    for h in (h_pts, h_hits, h_in):
+        ctx.buf_free(h)
+    th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def main():
     sc = scenes.sponza_like()
     ctx = psm.Context(0)
@@ -127,20 +271,7 @@ def main():
     tri = hits.view(np.int32)[:, 3]
     out["primary_hit_fraction"] = float((tri >= 0).mean())
 
-    # bounce-like rays: from the primary hits (rays that missed start at their origin), a cosine-ish direction about the face normal
-    # turned towards the incoming ray
-    rng = np.random.RandomState(7)
-    dn = d / np.linalg.norm(d, axis=1, keepdims=True)
-    hit = tri >= 0
-    bo = np.where(hit[:, None], o + dn * np.where(hit, hits[:, 2], 0)[:, None], o).astype(np.float32)
-    t3 = sc["tris"].reshape(-1, 3, 3)[np.maximum(tri, 0)]
-    nrm = np.cross(t3[:, 1] - t3[:, 0], t3[:, 2] - t3[:, 0])
-    nrm /= np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-30)
-    nrm = np.where((np.sum(nrm * dn, axis=1) > 0)[:, None], -nrm, nrm)
-    nrm = np.where(hit[:, None], nrm, dn)
-    u = rng.normal(size=(n, 3))
-    u /= np.linalg.norm(u, axis=1, keepdims=True)
-    bd = (nrm + u).astype(np.float32)
+    bo, bd = bounce_rays(sc, o, d, hits)
     upload(bo, bd, 1e-3)
     out["bounce_closest_ms"] = median_ms(ctx, closest)
     out["bounce_any_ms"] = median_ms(ctx, anyhit)
@@ -166,4 +297,4 @@ def main():
 
 
 if __name__ == "__main__":
-    points() if sys.argv[1:] == ["points"] else main()
+    {"points": points, "signed": signed}.get(" ".join(sys.argv[1:]), main)()
