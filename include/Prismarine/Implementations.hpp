@@ -1,4 +1,5 @@
 #pragma once
 // Prismarine/Implementations.hpp -- inline implementations (reference Implementations.hpp:5-9)
 #include "TriangleHierarchy.inl"
+#include "QueryScene.inl"
 #include "Pipeline.inl"

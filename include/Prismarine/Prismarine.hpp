@@ -7,5 +7,6 @@
 #include "TextureSet.hpp"
 #include "MaterialSet.hpp"
 #include "TriangleHierarchy.hpp"
+#include "QueryScene.hpp"          // addition: the queries over several hierarchies at once (psm_scene_*_dev)
 #include "Pipeline.hpp"
 #include "FrameBatch.hpp"   // addition: several frames in flight (psm_lanes_render)

@@ -435,6 +435,47 @@ int psm_bvh_count_hits_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, 
 int psm_bvh_inside_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, uint32_t samples, uint8_t* d_inside);
 int psm_bvh_signed_distance_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, uint32_t samples, psm_hit* d_hits);
 
+/* scene queries: the seven queries above over several hierarchies at once (new; no reference counterpart).
+ * A scene is an ordered list of G built hierarchies of ONE context, 1 <= G <= PSM_SCENE_MAX_GEOMETRIES, passed per call (there
+ * is no scene handle). The limit is 32 because the per-geometry table then travels with the launch (32 x four pointers = 1 KB
+ * of kernel arguments): it needs no device allocation and cannot go stale when a geometry is rebuilt. Semantics:
+ *   - the candidates are the leaves of all geometries, each identified by (geom, tri): geom is the index in the list, tri that
+ *     hierarchy's load-order triangle id. Every per-candidate rule is the single-hierarchy query's, unchanged: the triangle
+ *     test, closest_on_tri, the windows and radii, which queries are invalid, the 1e-5 tolerances. Only the combination across
+ *     the geometries is new, and a scene answers exactly as the psm_bvh_* queries of its geometries combined by these rules:
+ *   - intersect, closest_point: the smallest t (d2) over the whole scene; on a bit-equal value the lexicographically lowest
+ *     (geom, tri). d_hits[i] is the psm_hit the winning hierarchy alone would have written, d_geom[i] its index, -1 on a miss
+ *     (d_hits[i] then {0, 0, +inf, -1}). d_geom must be non-NULL and 4-byte aligned. tmax / rmax apply over the whole scene
+ *   - occluded, within: the OR over the geometries
+ *   - count_hits: the sum over the geometries
+ *   - inside: ray k votes "inside" iff its crossings SUMMED OVER ALL GEOMETRIES are odd; then the majority vote of
+ *     psm_bvh_inside_dev. A closed surface split over several hierarchies therefore behaves like the unsplit one -- which no
+ *     combination of per-hierarchy inside answers can give. Nested or overlapping bodies behave as they do inside one hierarchy:
+ *     parity of all crossings (a point in a cavity between two nested shells is outside, whichever geometries hold the shells)
+ *   - signed_distance: the scene's closest-point record (and d_geom) with the scene's inside sign; a miss casts no rays
+ *   - the same hierarchy may appear more than once: the lower index wins every tie (its count and parity count once per entry)
+ *   - a refitted geometry behaves as a refitted hierarchy does; a geometry of 0 leaves contributes nothing
+ *   - there are no per-instance transforms, there is no top-level hierarchy over the geometries (every geometry is entered by
+ *     every query, pruned from its root on) and no more than 32 geometries
+ * Checks: geoms == NULL, count == 0 or count > PSM_SCENE_MAX_GEOMETRIES: PSM_ERR_INVALID. Then every entry, the whole call being
+ * refused with a message that names the first failing index: a NULL entry or one of another context than the others
+ * (PSM_ERR_INVALID), one that is not built (PSM_ERR_STATE), one too deep for the query stack (PSM_ERR_CAPACITY). The list is
+ * checked for n == 0 too; after that n == 0 is a no-op. The data pointers, their alignment and samples as for the psm_bvh_* forms.
+ * Stream-ordered on the geometries' context, no host synchronisation, one launch per query (signed distance: two); capturable
+ * into a graph after the context's first query of any kind; the context's one stack area serves these queries too. */
+#define PSM_SCENE_MAX_GEOMETRIES 32
+int psm_scene_intersect_dev(psm_bvh* const* geoms, uint32_t count, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits,
+                            int32_t* d_geom);
+int psm_scene_occluded_dev(psm_bvh* const* geoms, uint32_t count, const psm_query_ray* d_rays, size_t n, uint8_t* d_hit);
+int psm_scene_count_hits_dev(psm_bvh* const* geoms, uint32_t count, const psm_query_ray* d_rays, size_t n, uint32_t* d_count);
+int psm_scene_closest_point_dev(psm_bvh* const* geoms, uint32_t count, const psm_point_query* d_points, size_t n, psm_hit* d_hits,
+                                int32_t* d_geom);
+int psm_scene_within_dev(psm_bvh* const* geoms, uint32_t count, const psm_point_query* d_points, size_t n, uint8_t* d_hit);
+int psm_scene_inside_dev(psm_bvh* const* geoms, uint32_t count, const psm_point_query* d_points, size_t n, uint32_t samples,
+                         uint8_t* d_inside);
+int psm_scene_signed_distance_dev(psm_bvh* const* geoms, uint32_t count, const psm_point_query* d_points, size_t n,
+                                  uint32_t samples, psm_hit* d_hits, int32_t* d_geom);
+
 /* ---------------------------------------------------------------------------------------------
  * several frames in flight (new; DESIGN.md "lanes")
  * `frames` x GltfViewer::process() (Viewer.cpp:296-312) with up to `lanes` of them in flight: lane s =

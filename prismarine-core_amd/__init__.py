@@ -27,6 +27,8 @@ EXPORTS = [
     "psm_bvh_get_info", "psm_bvh_stage_bounds", "psm_bvh_stage_morton", "psm_bvh_stage_sort",
     "psm_bvh_stage_emit", "psm_bvh_download", "psm_bvh_intersect_dev", "psm_bvh_occluded_dev",
     "psm_bvh_closest_point_dev", "psm_bvh_within_dev", "psm_bvh_count_hits_dev", "psm_bvh_inside_dev", "psm_bvh_signed_distance_dev",
+    "psm_scene_intersect_dev", "psm_scene_occluded_dev", "psm_scene_count_hits_dev", "psm_scene_closest_point_dev", "psm_scene_within_dev",
+    "psm_scene_inside_dev", "psm_scene_signed_distance_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -50,6 +52,7 @@ RAY_DT = np.dtype([("origin", "<f4", 3), ("direct", "<f4", 3), ("color", "<f4", 
 HIT_DT = np.dtype([("u", "<f4"), ("v", "<f4"), ("t", "<f4"), ("tri", "<i4")])
 QUERY_RAY_DT = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direct", "<f4", 3), ("tmax", "<f4")])   # psm_query_ray
 POINT_QUERY_DT = np.dtype([("p", "<f4", 3), ("rmax", "<f4")])   # psm_point_query
+SCENE_MAX_GEOMETRIES = 32   # psm_hip.h PSM_SCENE_MAX_GEOMETRIES
 # PSM_INSIDE_DIRECTIONS (include/psm_hip.h): ray k of TriangleHierarchy.inside / .signedDistance goes along row k
 INSIDE_DIRECTIONS = np.array([[0.4082483, 0.57735026, 0.70710677], [-0.7905694, 0.35355338, 0.5],
                               [0.52223295, -0.797724, 0.30151135], [-0.35355338, -0.4330127, -0.8291562],
@@ -449,27 +452,13 @@ class TriangleHierarchy:
         return self._launch_np(q, out, name, *extra)
 
     def _launch_np(self, packed, out, name, *extra):
-        """one query launch over host records `packed` [n, k] float32: staged through device buffers, synchronises. out: the
-        result's kind (_QUERY_OUT); extra: arguments between n and the output pointer"""
-        n = packed.shape[0]
-        per, dtype = _QUERY_OUT[out]
-        hr, ho = self.ctx.buf_alloc(max(packed.nbytes, 32)), self.ctx.buf_alloc(max(per * n, 16))
-        try:
-            if n:
-                self.ctx.buf_upload(hr, packed)
-            self.ctx.check(getattr(lib(), name)(self._h, C.c_void_p(self.ctx.buf_ptr(hr)[0]), C.c_size_t(n), *extra,
-                                                C.c_void_p(self.ctx.buf_ptr(ho)[0])), name)
-            if n == 0:
-                self.ctx.sync()
-                return QueryHits(np.zeros((0, 4), np.float32)) if out == "hits" else np.zeros(0, dtype)
-            if out == "bool":
-                return self.ctx.buf_download(ho, np.uint8, n).view(np.bool_)
-            if out == "count":
-                return self.ctx.buf_download(ho, np.uint32, n)
-            return QueryHits(self.ctx.buf_download(ho, np.float32, 4 * n).reshape(n, 4))
-        finally:
-            self.ctx.buf_free(hr)
-            self.ctx.buf_free(ho)
+        return _launch_np(self, packed, out, name, *extra)
+
+    def _call(self, name, d_in, n, extra, d_out, d_geom):
+        """the native call of one query launch (d_geom: unused -- a single hierarchy reports no geometry)"""
+        self.ctx.check(getattr(lib(), name)(self._h, C.c_void_p(d_in), C.c_size_t(n), *extra, C.c_void_p(d_out)), name)
+
+    _scene = False   # (QueryScene: True -- a "hits" result then carries QueryHits.geom)
 
     def setBuildGraph(self, enable=True):
         """Replay rebuilds as one captured hipGraph from the second build of a triangle count on (default), or keep plain launches."""
@@ -516,10 +505,12 @@ def _samples(samples, name):
 
 class QueryHits:
     """Closest hits of TriangleHierarchy.intersect (closest points of .closestPoint and .signedDistance: t is the distance): `buffer` [n, 4] float32 (numpy array or torch tensor) holds psm_hit records
-    (u, v, t, tri); t, u, v and tri (int32) are views of it."""
+    (u, v, t, tri); t, u, v and tri (int32) are views of it. geom: for a QueryScene's results the int32 array / tensor of the
+    winning geometry's index in the scene (-1 on a miss, tri is that geometry's id); None for a single hierarchy's."""
 
-    def __init__(self, buffer):
+    def __init__(self, buffer, geom=None):
         self.buffer = buffer
+        self.geom = geom
         self.u, self.v, self.t = buffer[:, 0], buffer[:, 1], buffer[:, 2]
         if isinstance(buffer, np.ndarray):
             self.tri = buffer.view(np.int32)[:, 3]
@@ -529,6 +520,36 @@ class QueryHits:
 
     def __len__(self):
         return self.buffer.shape[0]
+
+
+def _launch_np(th, packed, out, name, *extra):
+    """one query launch of `th` (a TriangleHierarchy or a QueryScene) over host records `packed` [n, k] float32: staged through
+    device buffers, synchronises. out: the result's kind (_QUERY_OUT); extra: arguments between n and the output pointer"""
+    ctx = th.ctx
+    n = packed.shape[0]
+    per, dtype = _QUERY_OUT[out]
+    geom = th._scene and out == "hits"
+    hr, ho = ctx.buf_alloc(max(packed.nbytes, 32)), ctx.buf_alloc(max(per * n, 16))
+    hg = ctx.buf_alloc(max(4 * n, 16)) if geom else None
+    try:
+        if n:
+            ctx.buf_upload(hr, packed)
+        th._call(name, ctx.buf_ptr(hr)[0], n, extra, ctx.buf_ptr(ho)[0], ctx.buf_ptr(hg)[0] if geom else None)
+        if n == 0:
+            ctx.sync()
+            if out == "hits":
+                return QueryHits(np.zeros((0, 4), np.float32), np.zeros(0, np.int32) if geom else None)
+            return np.zeros(0, dtype)
+        if out == "bool":
+            return ctx.buf_download(ho, np.uint8, n).view(np.bool_)
+        if out == "count":
+            return ctx.buf_download(ho, np.uint32, n)
+        return QueryHits(ctx.buf_download(ho, np.float32, 4 * n).reshape(n, 4), ctx.buf_download(hg, np.int32, n) if geom else None)
+    finally:
+        ctx.buf_free(hr)
+        ctx.buf_free(ho)
+        if geom:
+            ctx.buf_free(hg)
 
 
 _hip_lib = None
@@ -578,6 +599,7 @@ def _launch_torch(th, packed, kind, name, *extra):
     n = packed.shape[0]
     shape, dtype = {"hits": ((n, 4), torch.float32), "bool": ((n,), torch.uint8), "count": ((n,), torch.int32)}[kind]
     out = torch.empty(shape, dtype=dtype, device=dev)
+    geom = torch.empty((n,), dtype=torch.int32, device=dev) if th._scene and kind == "hits" else None
     cur = torch.cuda.current_stream(dev)
     mine = th.ctx.stream or 0   # (NULL: the device's null stream, torch's default stream)
     other = mine != cur.cuda_stream
@@ -585,14 +607,73 @@ def _launch_torch(th, packed, kind, name, *extra):
         ev_in = torch.cuda.Event()
         ev_in.record(cur)
         _hip_check(_hip().hipStreamWaitEvent(C.c_void_p(mine), C.c_void_p(ev_in.cuda_event), C.c_uint(0)), "hipStreamWaitEvent")
-    th.ctx.check(getattr(lib(), name)(th._h, C.c_void_p(packed.data_ptr()), C.c_size_t(n), *extra, C.c_void_p(out.data_ptr())), name)
+    th._call(name, packed.data_ptr(), n, extra, out.data_ptr(), None if geom is None else geom.data_ptr())
     if other:   # ... and torch's stream for the kernel: every later use of `out`, and of the memory of `packed`, comes after it
         hip, ev = _hip(), C.c_void_p()
         _hip_check(hip.hipEventCreateWithFlags(C.byref(ev), C.c_uint(2)), "hipEventCreateWithFlags")   # hipEventDisableTiming
         _hip_check(hip.hipEventRecord(ev, C.c_void_p(mine)), "hipEventRecord")
         _hip_check(hip.hipStreamWaitEvent(C.c_void_p(cur.cuda_stream), ev, C.c_uint(0)), "hipStreamWaitEvent")
         _hip_check(hip.hipEventDestroy(ev), "hipEventDestroy")
-    return QueryHits(out) if kind == "hits" else (out.view(torch.bool) if kind == "bool" else out)
+    return QueryHits(out, geom) if kind == "hits" else (out.view(torch.bool) if kind == "bool" else out)
+
+
+class QueryScene:
+    """The queries of TriangleHierarchy over several hierarchies at once (psm_scene_*_dev; not in the reference): an ordered list
+    of 1 .. SCENE_MAX_GEOMETRIES built hierarchies of one context, e.g. a static set and the objects that move -- each rebuilt or
+    refitted on its own, none merged. A candidate is (geom, tri): geom the index in the list, tri that hierarchy's triangle id.
+    Closest hit / closest point: the smallest value over the scene, on a tie the lowest (geom, tri), and QueryHits.geom says
+    which geometry; occluded / within: the OR; countHits: the sum; inside: parity over the crossings of ALL geometries (a closed
+    surface split over several hierarchies is one surface). Arguments, numpy / torch placement and stream ordering of every
+    method are those of the TriangleHierarchy method of the same name. The scene keeps references to its hierarchies and reads
+    their handles at every call: a hierarchy that was rebuilt, refitted or reallocated is used as it then is."""
+    _scene = True
+
+    def __init__(self, ctx, hierarchies):
+        self.ctx = ctx
+        self.hierarchies = list(hierarchies)
+        if not 1 <= len(self.hierarchies) <= SCENE_MAX_GEOMETRIES:
+            raise ValueError("QueryScene: %d hierarchies (1 .. %d)" % (len(self.hierarchies), SCENE_MAX_GEOMETRIES))
+
+    def _call(self, name, d_in, n, extra, d_out, d_geom):
+        name = name.replace("psm_bvh_", "psm_scene_")
+        g = len(self.hierarchies)
+        handles = (C.c_void_p * g)(*[th._h for th in self.hierarchies])
+        tail = () if d_geom is None else (C.c_void_p(d_geom),)
+        self.ctx.check(getattr(lib(), name)(handles, C.c_uint32(g), C.c_void_p(d_in), C.c_size_t(n), *extra, C.c_void_p(d_out), *tail), name)
+
+    def _launch_np(self, packed, out, name, *extra):
+        return _launch_np(self, packed, out, name, *extra)
+
+    _query = TriangleHierarchy._query
+    _point_query = TriangleHierarchy._point_query
+
+    def intersect(self, origins, directions, tmin=0.0, tmax=np.inf):
+        """Closest hit of every ray over the scene (psm_scene_intersect_dev): QueryHits with geom."""
+        return self._query(origins, directions, tmin, tmax, "hits")
+
+    def occluded(self, origins, directions, tmin=0.0, tmax=np.inf):
+        """Any hit inside [tmin, tmax] in any geometry (psm_scene_occluded_dev): bool."""
+        return self._query(origins, directions, tmin, tmax, "bool")
+
+    def countHits(self, origins, directions, tmin=0.0, tmax=np.inf):
+        """Hits inside [tmin, tmax] summed over the geometries (psm_scene_count_hits_dev)."""
+        return self._query(origins, directions, tmin, tmax, "count")
+
+    def closestPoint(self, points, rmax=np.inf):
+        """Closest point over the scene within rmax (psm_scene_closest_point_dev): QueryHits with geom."""
+        return self._point_query(points, rmax, "hits", "psm_bvh_closest_point_dev")
+
+    def within(self, points, radius):
+        """Whether some triangle of some geometry is within radius (psm_scene_within_dev): bool."""
+        return self._point_query(points, radius, "bool", "psm_bvh_within_dev")
+
+    def inside(self, points, samples=3):
+        """Inside / outside by the parity of each ray's crossings over ALL geometries, then the vote (psm_scene_inside_dev)."""
+        return self._point_query(points, np.inf, "bool", "psm_bvh_inside_dev", samples)
+
+    def signedDistance(self, points, rmax=np.inf, samples=3):
+        """closestPoint() over the scene with the sign of inside() over the scene (psm_scene_signed_distance_dev)."""
+        return self._point_query(points, rmax, "hits", "psm_bvh_signed_distance_dev", samples)
 
 
 class TextureSet:

@@ -580,6 +580,372 @@ __global__ __launch_bounds__(QUERY_BLOCK, 8) void bvh_query_count(QueryArgs a) {
 __global__ __launch_bounds__(QUERY_BLOCK, 8) void bvh_query_inside(QueryArgs a) { inside_body<false>(a); }
 __global__ __launch_bounds__(QUERY_BLOCK, 8) void bvh_query_sign(QueryArgs a) { inside_body<true>(a); }
 
+// ---- scene queries: the seven queries over several hierarchies at once (include/psm_hip.h "scene queries") ------
+
+// One geometry of a scene as a kernel reads it: QueryArgs' four hierarchy pointers. The table of a launch travels in the
+// kernel-argument segment (PSM_SCENE_MAX_GEOMETRIES x 32 B = 1 KB): no device allocation, nothing that could go stale.
+struct SceneGeom {
+    const uint4* node32;
+    const float4* tri48;
+    const uint32_t* sm;
+    const int32_t* sorted_tri;
+};
+struct SceneArgs {
+    const float4* rays;      // as QueryArgs
+    size_t n;
+    int* spill;
+    float4* hits;
+    uint8_t* occluded;
+    uint32_t* count;
+    int32_t* geom;           // closest hit / closest point / signed distance: the winning geometry per query, -1 on a miss
+    uint32_t samples;
+    uint32_t geoms;          // G: 1 .. PSM_SCENE_MAX_GEOMETRIES
+    SceneGeom g[PSM_SCENE_MAX_GEOMETRIES];
+};
+
+namespace {
+
+// query_walk over a scene, as a walk of its own (the seven single-hierarchy kernels keep theirs, and with it their code): per
+// query the geometries one after the other, geometry 0 first, each walked as query_walk walks its hierarchy. The geometry index
+// is the same in every lane of the wave, so the four pointers, the root and the leaf count of a geometry are scalar loads from
+// the kernel-argument table. The body carries its running state (best, count, parity, found) from one geometry to the next:
+//   bool begin(i, alive)     load query i and clear the running state; false: the query misses without a walk
+//   void enter(gm, g)        the per-geometry set-up (the ray's axes / the point's bound from that geometry's fit transform)
+//   children, leaf, done, again, finish: as query_walk's; a lane that is done() skips the remaining geometries
+//   again(): every geometry is walked again (the inside queries' next ray: its parity is summed over the whole scene)
+template <class Body>
+PSM_D void scene_walk(const SceneArgs& s, Body& q) {
+    __shared__ int stack[QSTACK_LDS][QUERY_BLOCK];
+    const int lane = (int)threadIdx.x;
+    __builtin_assume(lane >= 0 && lane < QUERY_BLOCK);
+    const size_t spill_stride = (size_t)gridDim.x * QUERY_BLOCK;
+    int* __restrict__ spill = s.spill + (size_t)blockIdx.x * QUERY_BLOCK + lane;
+    for (size_t i = (size_t)blockIdx.x * QUERY_BLOCK + (size_t)lane; i - (size_t)lane < s.n; i += spill_stride) {
+        const bool alive = i < s.n;
+        const bool valid = q.begin(i, alive);
+        do {
+            for (uint32_t g = 0; g < s.geoms; g++) {
+                const SceneGeom gm = s.g[g];
+                const uint4* __restrict__ node32 = gm.node32;
+                const int root = (int)gm.sm[SM_ROOT];
+                const uint32_t count = gm.sm[SM_COUNT];
+                const int lone = (count == 1u) ? gm.sorted_tri[0] : -1;
+                q.enter(gm, (int)g);
+                const bool go = valid && !q.done();
+                if (go && lone >= 0) q.leaf(lone);
+                int cur = root, sp = 0;
+                bool walking = go && root >= 0;
+                while (walking) {
+                    const uint4* np = (const uint4*)((const char*)node32 + ((uint32_t)cur << 5));
+                    const uint4 n0 = np[0], n1 = np[1];
+                    const int lkx = (int)n1.z, lky = (int)n1.w;
+                    bool okL, okR;
+                    float kL, kR;
+                    q.children(n0, n1, okL, okR, kL, kR);
+                    const bool leafL = okL && lkx < 0, leafR = okR && lky < 0;
+                    int t0 = leafL ? ~lkx : (leafR ? ~lky : -1);
+                    int t1 = (leafL && leafR) ? ~lky : -1;
+                    while (t0 >= 0) {
+                        q.leaf(t0);
+                        t0 = t1;
+                        t1 = -1;
+                    }
+                    if (q.done()) break;
+                    const bool intL = okL && !leafL, intR = okR && !leafR;
+                    const bool leftFirst = intL && (!intR || kL <= kR);
+                    const int first = leftFirst ? lkx : lky, second = leftFirst ? lky : lkx;
+                    if (intL && intR) {
+                        if (sp < QSTACK_LDS) stack[sp][lane] = second;
+                        else if (sp < QSTACK_MAX) spill[(size_t)(sp - QSTACK_LDS) * spill_stride] = second;
+                        sp++;
+                    }
+                    cur = first;
+                    if (!(intL || intR)) {
+                        if (sp == 0) break;
+                        sp--;
+                        cur = sp < QSTACK_LDS ? stack[sp][lane] : spill[(size_t)(sp - QSTACK_LDS) * spill_stride];
+                    }
+                }
+            }
+        } while (q.again());
+        if (alive) q.finish(i);
+    }
+}
+
+// The tie rule across geometries (closest hit and closest point; `best` is t or d2). The winner is the smallest value, on a
+// bit-equal value the lexicographically lowest (geom, tri). The geometries are walked in ascending order, so at a candidate
+// (g, tri) with value x every earlier record is of a geometry <= g:
+//   x <  best                                   wins, whatever the ids
+//   x == best, the record is of geometry g      wins iff tri < btri: `<` on the id, as inside one hierarchy
+//   x == best, the record is of a geometry < g  loses: (geom, tri) of the record is lower whatever tri is
+//   x == best, no record yet                    wins (best is the window's / the radius' own bound): any id is below "none"
+// One unsigned key `tie` holds all of it as "tri < tie": 0xffffffff while there is no record, 0 from enter() on when the record
+// is of an earlier geometry (no id is below 0), the record's tri once it is of this geometry. The same hierarchy twice
+// therefore answers with the lower index. Boxes are kept with `<=` against best in every case: inside geometry g a candidate at
+// exactly best with a lower id must still be reached, and best may have become this geometry's at any leaf. For a best that is
+// still an earlier geometry's, `<` would be enough (an equal value loses); keeping `<=` there visits, and rejects at the leaf,
+// only candidates at exactly the earlier best -- never a wrong answer, and no second compare in the node loop.
+struct SceneBest {
+    float best, bu, bv;
+    int btri, bgeom, cur;
+    uint32_t tie;
+    PSM_D void clear(float bound) {
+        best = bound;
+        bu = 0.f;
+        bv = 0.f;
+        btri = -1;
+        bgeom = -1;
+        tie = 0xffffffffu;
+    }
+    PSM_D void enter_geom(int g) {
+        cur = g;
+        if (bgeom >= 0) tie = 0u;
+    }
+    PSM_D bool wins(float x, int tri) const { return x < best || (x == best && (uint32_t)tri < tie); }
+    PSM_D void take(float x, float u, float v, int tri) {
+        best = x;
+        bu = u;
+        bv = v;
+        btri = tri;
+        bgeom = cur;
+        tie = (uint32_t)tri;
+    }
+};
+
+// a ray in a scene: RayBody's / CountRay's ray, with the axes redone per geometry (each has a fit transform of its own)
+struct SceneRay {
+    SceneGeom gm;
+    v3 o, d;
+    float tmin, tmax;
+    Axis X, Y, Z;
+
+    PSM_D bool aim(v3 orig, v3 dir, float lo, float hi) {
+        o = orig;
+        d = normalize3(dir);
+        tmin = lo;
+        tmax = hi;
+        return finite3(o) && finite3(d) && tmin <= tmax;
+    }
+    PSM_D bool load(const SceneArgs& s, size_t i, bool alive) {
+        float4 r0 = make_float4(0.f, 0.f, 0.f, 1.f), r1 = make_float4(1.f, 0.f, 0.f, -1.f);
+        if (alive) { r0 = s.rays[2 * i]; r1 = s.rays[2 * i + 1]; }
+        return aim(mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), r0.w, r1.w) && alive;
+    }
+    PSM_D void axes(const SceneGeom& g) {
+        gm = g;
+        float M[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) M[k] = u2f(g.sm[SM_M + k]);
+        X = ray_axis(M, 0, o, d);
+        Y = ray_axis(M, 1, o, d);
+        Z = ray_axis(M, 2, o, d);
+    }
+    PSM_D void boxes(uint4 n0, uint4 n1, float lim, bool& okL, bool& okR, float& nL, float& nR) const {
+        float fL, fR;
+        slab(X, Y, Z, half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z), nL, fL);
+        slab(X, Y, Z, half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y), nR, fR);
+        okL = (nL <= fL) & (nL <= lim) & (fL >= tmin);
+        okR = (nR <= fR) & (nR <= lim) & (fR >= tmin);
+    }
+};
+
+// closest hit (ANY = false) and any hit (ANY = true) of a scene: RayBody with the best carried across the geometries
+template <bool ANY>
+struct SceneRayBody : SceneRay {
+    const SceneArgs& s;
+    SceneBest b;
+    bool found;
+
+    PSM_D SceneRayBody(const SceneArgs& a) : s(a) {}
+    PSM_D bool begin(size_t i, bool alive) {
+        const bool valid = load(s, i, alive);
+        b.clear(tmax);
+        found = false;
+        return valid;
+    }
+    PSM_D void enter(const SceneGeom& g, int gi) {
+        axes(g);
+        b.enter_geom(gi);
+    }
+    PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& nL, float& nR) const {
+        boxes(n0, n1, ANY ? tmax : b.best, okL, okR, nL, nR);   // (<=: see SceneBest)
+    }
+    PSM_D void leaf(int tri) {
+        float t, u, v;
+        if (tri_query(gm.tri48, tri, o, d, t, u, v) && t >= tmin && b.wins(t, tri)) {
+            found = true;
+            if (!ANY) b.take(t, u, v, tri);
+        }
+    }
+    PSM_D bool done() const { return ANY && found; }
+    PSM_D bool again() const { return false; }
+    PSM_D void finish(size_t i) const {
+        if (ANY) {
+            s.occluded[i] = found ? 1 : 0;
+        } else {
+            s.hits[i] = found ? make_float4(b.bu, b.bv, b.best, __int_as_float(b.btri)) : make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1));
+            s.geom[i] = b.bgeom;
+        }
+    }
+};
+
+// closest point (WITHIN = false) and within radius (WITHIN = true) of a scene: PointBody with the best d2 carried across the
+// geometries; the point's normalised image and the bound's factors are redone per geometry (point_bound: per fit transform)
+template <bool WITHIN>
+struct ScenePointBody {
+    const SceneArgs& s;
+    SceneGeom gm;
+    PointBound B;
+    v3 p;
+    float rmax;
+    SceneBest b;
+    bool found;
+    float Px, Py, Pz, h;
+
+    PSM_D ScenePointBody(const SceneArgs& a) : s(a) {}
+    PSM_D bool begin(size_t i, bool alive) {
+        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
+        if (alive) q = s.rays[i];
+        p = mk3(q.x, q.y, q.z);
+        rmax = q.w;
+        b.clear((rmax * rmax) * 1.00000095367431640625f + 0x1p-126f);   // (PointBody::begin)
+        found = false;
+        return alive && finite3(p) && rmax >= 0.f;
+    }
+    PSM_D void enter(const SceneGeom& g, int gi) {
+        gm = g;
+        float M[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) M[k] = u2f(g.sm[SM_M + k]);
+        B = point_bound(M);
+        const Row X = affine_row(M, 0, p), Y = affine_row(M, 1, p), Z = affine_row(M, 2, p);
+        Px = X.P;
+        Py = Y.P;
+        Pz = Z.P;
+        h = smaxf(smaxf(X.h, Y.h), Z.h);
+        b.enter_geom(gi);
+    }
+    PSM_D float lb2(float mnx, float mny, float mnz, float mxx, float mxy, float mxz) const {
+        const float tx = smaxf(smaxf(mnx - Px, Px - mxx) - h, 0.f) * B.il0;
+        const float ty = smaxf(smaxf(mny - Py, Py - mxy) - h, 0.f) * B.il1;
+        const float tz = smaxf(smaxf(mnz - Pz, Pz - mxz) - h, 0.f) * B.il2;
+        const float m = smaxf(smaxf(tx, ty), tz);
+        return (B.orth ? ((tx * tx + ty * ty) + tz * tz) : m * m) * B.wf;
+    }
+    PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& kL, float& kR) const {
+        kL = lb2(half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z));
+        kR = lb2(half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y));
+        okL = kL <= b.best;   // (<=: see SceneBest; LB^2 is a world distance, comparable across the geometries' transforms)
+        okR = kR <= b.best;
+    }
+    PSM_D void leaf(int tri) {
+        const float4 A = gm.tri48[(size_t)3 * tri + 0], Bv = gm.tri48[(size_t)3 * tri + 1], Cv = gm.tri48[(size_t)3 * tri + 2];
+        float u, v;
+        const float d2 = closest_on_tri(mk3(A.x, A.y, A.z), mk3(Bv.x, Bv.y, Bv.z), mk3(Cv.x, Cv.y, Cv.z), p, u, v);
+        if (sqrtf(d2) <= rmax && b.wins(d2, tri)) {
+            found = true;
+            if (!WITHIN) b.take(d2, u, v, tri);
+        }
+    }
+    PSM_D bool done() const { return WITHIN && found; }
+    PSM_D bool again() const { return false; }
+    PSM_D void finish(size_t i) const {
+        if (WITHIN) {
+            s.occluded[i] = found ? 1 : 0;
+        } else {
+            s.hits[i] = found ? make_float4(b.bu, b.bv, sqrtf(b.best), __int_as_float(b.btri)) : make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1));
+            s.geom[i] = b.bgeom;
+        }
+    }
+};
+
+// the counting ray of a scene (CountRay): the count runs on across the geometries
+struct SceneCountRay : SceneRay {
+    uint32_t count;
+    PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& nL, float& nR) const { boxes(n0, n1, tmax, okL, okR, nL, nR); }
+    PSM_D void leaf(int tri) {
+        float t, u, v;
+        if (tri_query(gm.tri48, tri, o, d, t, u, v) && t >= tmin && t <= tmax) count++;
+    }
+    PSM_D bool done() const { return false; }
+};
+
+struct SceneCountBody : SceneCountRay {
+    const SceneArgs& s;
+    PSM_D SceneCountBody(const SceneArgs& a) : s(a) {}
+    PSM_D bool begin(size_t i, bool alive) {
+        count = 0u;
+        return load(s, i, alive);
+    }
+    PSM_D void enter(const SceneGeom& g, int) { axes(g); }
+    PSM_D bool again() const { return false; }
+    PSM_D void finish(size_t i) const { s.count[i] = count; }
+};
+
+// inside / outside of a point against a scene (SIGN = false) and the sign of a scene closest-point result (SIGN = true):
+// InsideBody, with ray k's crossings summed over all geometries before it votes (again() comes after the last geometry)
+template <bool SIGN>
+struct SceneInsideBody : SceneCountRay {
+    const SceneArgs& s;
+    v3 p;
+    uint32_t k, votes;
+    float dist;
+    bool valid;
+
+    PSM_D SceneInsideBody(const SceneArgs& a) : s(a) {}
+    PSM_D bool shoot() {
+        const int r = __builtin_amdgcn_readfirstlane((int)k);
+        count = 0u;
+        return aim(p, mk3(INSIDE_DIR[r][0], INSIDE_DIR[r][1], INSIDE_DIR[r][2]), 0.f, __builtin_inff());
+    }
+    PSM_D bool begin(size_t i, bool alive) {
+        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
+        if (alive) q = s.rays[i];
+        p = mk3(q.x, q.y, q.z);
+        k = 0u;
+        votes = 0u;
+        dist = 0.f;
+        valid = alive;
+        if (SIGN) {
+            float4 h = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+            if (alive) h = s.hits[i];
+            dist = h.z;
+            valid = __float_as_int(h.w) >= 0;
+        }
+        valid = shoot() && valid;
+        return valid;
+    }
+    PSM_D void enter(const SceneGeom& g, int) { axes(g); }
+    PSM_D bool again() {
+        votes += count & 1u;
+        k++;
+        if (!valid || k >= s.samples) return false;
+        shoot();
+        return true;
+    }
+    PSM_D void finish(size_t i) const {
+        const bool in = 2u * votes > s.samples;
+        if (!SIGN) s.occluded[i] = in ? 1 : 0;
+        else if (in) ((float*)(s.hits + i))[2] = __uint_as_float(__float_as_uint(dist) | 0x80000000u);
+    }
+};
+
+template <class Body>
+PSM_D void scene_body(const SceneArgs& s) {
+    Body q(s);
+    scene_walk(s, q);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_closest(SceneArgs s) { scene_body<SceneRayBody<false>>(s); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_any(SceneArgs s) { scene_body<SceneRayBody<true>>(s); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_point(SceneArgs s) { scene_body<ScenePointBody<false>>(s); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_within(SceneArgs s) { scene_body<ScenePointBody<true>>(s); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_count(SceneArgs s) { scene_body<SceneCountBody>(s); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_inside(SceneArgs s) { scene_body<SceneInsideBody<false>>(s); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_sign(SceneArgs s) { scene_body<SceneInsideBody<true>>(s); }
+
 namespace {
 
 // the stack entries beyond the LDS part, per context, shared by every query kind (all run on the context's stream, never at
@@ -677,6 +1043,101 @@ int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, void* d_out, u
     return PSM_OK;
 }
 
+
+// ---- the scene entry points' checks and launch ---------------------------------------------------------------------------
+const char* const SCENE_NAME[] = {"psm_scene_intersect_dev", "psm_scene_occluded_dev", "psm_scene_closest_point_dev",
+                                  "psm_scene_within_dev", "psm_scene_count_hits_dev", "psm_scene_inside_dev",
+                                  "psm_scene_signed_distance_dev"};
+
+// query() for a scene. The list is checked first and whole, also for n == 0: its length, then every entry (NULL, another
+// context than entry 0's, not built, too deep for the stack), the message naming the first failing index. The message goes to
+// the context of the first non-NULL entry (a list of NULLs only has no context to tell: the return code alone). d_geom: the
+// kinds with a psm_hit output only.
+int scene_query(psm_bvh* const* geoms, uint32_t count, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_geom,
+                uint32_t samples = 0) {
+    if (!geoms || count == 0 || count > PSM_SCENE_MAX_GEOMETRIES) return PSM_ERR_INVALID;
+    const QueryDesc& k = QUERY_DESC[kind];
+    const char* name = SCENE_NAME[kind];
+    psm_ctx* c = nullptr;
+    for (uint32_t g = 0; g < count && !c; g++)
+        if (geoms[g]) c = geoms[g]->ctx;
+    if (!c) return PSM_ERR_INVALID;
+    char msg[128];
+    for (uint32_t g = 0; g < count; g++) {
+        if (!geoms[g]) {
+            snprintf(msg, sizeof msg, "%s: geometry %u is NULL", name, g);
+            return set_err(c, PSM_ERR_INVALID, msg);
+        }
+        if (geoms[g]->ctx != c) {
+            snprintf(msg, sizeof msg, "%s: geometry %u belongs to another context", name, g);
+            return set_err(c, PSM_ERR_INVALID, msg);
+        }
+    }
+    for (uint32_t g = 0; g < count; g++) {
+        if (!geoms[g]->built) {
+            snprintf(msg, sizeof msg, "%s: geometry %u is not built", name, g);
+            return set_err(c, PSM_ERR_STATE, msg);
+        }
+        if (63 + ceil_log2(geoms[g]->cap) > QSTACK_MAX) {
+            snprintf(msg, sizeof msg, "%s: geometry %u is deeper than the query stack", name, g);
+            return set_err(c, PSM_ERR_CAPACITY, msg);
+        }
+    }
+    if (n == 0) return PSM_OK;
+    const bool with_geom = k.out_align == 16;
+    if (!d_in || !d_out || (with_geom && !d_geom)) {
+        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    const bool in_bad = ((uintptr_t)d_in & 15u) != 0, out_bad = ((uintptr_t)d_out & (uintptr_t)(k.out_align - 1)) != 0;
+    if (in_bad || out_bad) {
+        if (k.out_align == 16) snprintf(msg, sizeof msg, "%s: %s or %s not 16-byte aligned", name, k.in, k.out);
+        else if (in_bad) snprintf(msg, sizeof msg, "%s: %s not 16-byte aligned", name, k.in);
+        else snprintf(msg, sizeof msg, "%s: %s not %u-byte aligned", name, k.out, k.out_align);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (with_geom && ((uintptr_t)d_geom & 3u) != 0) {
+        snprintf(msg, sizeof msg, "%s: geom not 4-byte aligned", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if ((kind == Q_INSIDE || kind == Q_SIGNED) && samples != 1 && samples != 3 && samples != 5) {
+        snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    (void)hipSetDevice(c->device);
+    void* spill = nullptr;
+    const int rc = spill_for(c, &spill);
+    if (rc != PSM_OK) return rc;
+    const size_t waves = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;
+    const uint32_t grid = (uint32_t)(waves < QUERY_GRID_CAP ? waves : QUERY_GRID_CAP);
+    SceneArgs sa = {};
+    sa.rays = (const float4*)d_in; sa.n = n;
+    sa.spill = (int*)spill;
+    sa.hits = (float4*)d_out; sa.occluded = (uint8_t*)d_out; sa.count = (uint32_t*)d_out;
+    sa.geom = d_geom;
+    sa.samples = samples;
+    sa.geoms = count;
+    for (uint32_t g = 0; g < count; g++) {
+        const psm_bvh* b = geoms[g];
+        sa.g[g] = SceneGeom{b->d_node32, b->d_tri48, b->d_small, b->d_sorted_tri};
+    }
+    switch (kind) {
+        case Q_CLOSEST: scene_query_closest<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa); break;
+        case Q_ANY: scene_query_any<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa); break;
+        case Q_POINT: scene_query_point<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa); break;
+        case Q_WITHIN: scene_query_within<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa); break;
+        case Q_COUNT: scene_query_count<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa); break;
+        case Q_INSIDE: scene_query_inside<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa); break;
+        case Q_SIGNED:   // the scene's closest point, then the scene's sign of what it found (the same stream: in order)
+            scene_query_point<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa);
+            PSM_HIP(c, hipGetLastError());
+            scene_query_sign<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa);
+            break;
+    }
+    PSM_HIP(c, hipGetLastError());
+    return PSM_OK;
+}
+
 }  // namespace
 
 // psm_ctx_destroy (api.hip): the context's spill area goes with it (the stream has been synchronised)
@@ -716,4 +1177,35 @@ int psm_bvh_inside_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, 
 
 int psm_bvh_signed_distance_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, uint32_t samples, psm_hit* d_hits) {
     return psm::query(bvh, psm::Q_SIGNED, d_points, n, d_hits, samples);
+}
+
+int psm_scene_intersect_dev(psm_bvh* const* geoms, uint32_t count, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits, int32_t* d_geom) {
+    return psm::scene_query(geoms, count, psm::Q_CLOSEST, d_rays, n, d_hits, d_geom);
+}
+
+int psm_scene_occluded_dev(psm_bvh* const* geoms, uint32_t count, const psm_query_ray* d_rays, size_t n, uint8_t* d_hit) {
+    return psm::scene_query(geoms, count, psm::Q_ANY, d_rays, n, d_hit, nullptr);
+}
+
+int psm_scene_closest_point_dev(psm_bvh* const* geoms, uint32_t count, const psm_point_query* d_points, size_t n, psm_hit* d_hits,
+                                int32_t* d_geom) {
+    return psm::scene_query(geoms, count, psm::Q_POINT, d_points, n, d_hits, d_geom);
+}
+
+int psm_scene_within_dev(psm_bvh* const* geoms, uint32_t count, const psm_point_query* d_points, size_t n, uint8_t* d_hit) {
+    return psm::scene_query(geoms, count, psm::Q_WITHIN, d_points, n, d_hit, nullptr);
+}
+
+int psm_scene_count_hits_dev(psm_bvh* const* geoms, uint32_t count, const psm_query_ray* d_rays, size_t n, uint32_t* d_count) {
+    return psm::scene_query(geoms, count, psm::Q_COUNT, d_rays, n, d_count, nullptr);
+}
+
+int psm_scene_inside_dev(psm_bvh* const* geoms, uint32_t count, const psm_point_query* d_points, size_t n, uint32_t samples,
+                         uint8_t* d_inside) {
+    return psm::scene_query(geoms, count, psm::Q_INSIDE, d_points, n, d_inside, nullptr, samples);
+}
+
+int psm_scene_signed_distance_dev(psm_bvh* const* geoms, uint32_t count, const psm_point_query* d_points, size_t n, uint32_t samples,
+                                  psm_hit* d_hits, int32_t* d_geom) {
+    return psm::scene_query(geoms, count, psm::Q_SIGNED, d_points, n, d_hits, d_geom, samples);
 }

@@ -10,7 +10,12 @@ the scene's bounds, rmax = inf; (c) set (b) through within with a radius of 0.5 
 psm_bvh_signed_distance_dev): (a) count beside closest and any on the ray mode's primary and bounce-like rays; (b) on a closed mesh
 (a torus of TORUS_NU x TORUS_NV quads, 2 M triangles) and a regular grid of NPTS points over its bounds: inside with 1 / 3 / 5
 rays, closest point, and signed distance with rmax = inf and with a band of 2 % of the diagonal.
-A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed]"""
+`query_bench.py scene`: the scene queries (psm_scene_*_dev) on the ray mode's primary and bounce-like rays and the point mode's
+uniform points: (a) a scene of ONE geometry against the plain query (the cost of the machinery); (b) the scene cut into 2, 8 and 32
+spatially separate parts (slabs of equal triangle count along x): one scene launch against the merged hierarchy and against the sum
+of G plain launches; (c) the static scene plus a small mesh that moves (MOVING_NU x MOVING_NV torus): rebuild of the small mesh +
+a scene query against rebuild of the merged hierarchy + a plain query.
+A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene]"""
 import ctypes as C
 import importlib
 import json
@@ -232,6 +237,126 @@ def signed():
     print(json.dumps(out))
 
 
+def scene():
+    lib = psm.lib()
+    sc = scenes.sponza_like()
+    tris = np.ascontiguousarray(sc["tris"], np.float32).reshape(-1, 9)
+    ctx = psm.Context(0)
+
+    def hier(t):
+        th = psm.TriangleHierarchy(ctx)
+        th.allocate(t.shape[0])
+        th.loadTriangles(t)
+        th.build()
+        return th
+
+    merged = hier(tris)
+    rt = psm.Pipeline(ctx, seed=1000)
+    rt.resizeBuffers(W, H)
+    rt.resize(W, H)
+    cam = scenes.camera_matrices(sc["eye"], sc["view"], W, H)
+    rt.camera_matrices(cam[0], cam[1])
+    prim = rt.download_rays()
+    rt.close()
+    n = prim.shape[0]
+    o, d = prim["origin"].copy(), prim["direct"].copy()
+    m = NPTS
+    t3 = tris.reshape(-1, 3, 3)
+    lo, hi = t3.reshape(-1, 3).min(0), t3.reshape(-1, 3).max(0)
+    pts = np.empty((m, 4), np.float32)
+    pts[:, 0:3], pts[:, 3] = np.random.RandomState(7).uniform(lo, hi, (m, 3)), np.inf
+    k = max(n, m)
+    h_rays, h_pts, h_hits, h_geom, h_occ = (ctx.buf_alloc(x) for x in (32 * n, 16 * m, 16 * k, 4 * k, k))
+    p_rays, p_pts, p_hits, p_geom, p_occ = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in (h_rays, h_pts, h_hits, h_geom, h_occ))
+    ctx.buf_upload(h_pts, pts)
+    cn, cm = C.c_size_t(n), C.c_size_t(m)
+
+    def upload(o, d, tmin):
+        r = np.zeros((n, 8), np.float32)
+        r[:, 0:3], r[:, 3], r[:, 4:7], r[:, 7] = o, tmin, d, np.inf
+        ctx.buf_upload(h_rays, r)
+
+    def handles(ths):
+        return (C.c_void_p * len(ths))(*[t._h for t in ths]), C.c_uint32(len(ths))
+
+    # the four workloads, plain (one hierarchy) and scene (a list)
+    def plain(kind, th):
+        if kind == "closest":
+            return lambda: ctx.check(lib.psm_bvh_intersect_dev(th._h, p_rays, cn, p_hits), "psm_bvh_intersect_dev")
+        if kind == "any":
+            return lambda: ctx.check(lib.psm_bvh_occluded_dev(th._h, p_rays, cn, p_occ), "psm_bvh_occluded_dev")
+        if kind == "point":
+            return lambda: ctx.check(lib.psm_bvh_closest_point_dev(th._h, p_pts, cm, p_hits), "psm_bvh_closest_point_dev")
+        return lambda: ctx.check(lib.psm_bvh_inside_dev(th._h, p_pts, cm, C.c_uint32(3), p_occ), "psm_bvh_inside_dev")
+
+    def scene_of(kind, ths):
+        g, c = handles(ths)
+        if kind == "closest":
+            return lambda: ctx.check(lib.psm_scene_intersect_dev(g, c, p_rays, cn, p_hits, p_geom), "psm_scene_intersect_dev")
+        if kind == "any":
+            return lambda: ctx.check(lib.psm_scene_occluded_dev(g, c, p_rays, cn, p_occ), "psm_scene_occluded_dev")
+        if kind == "point":
+            return lambda: ctx.check(lib.psm_scene_closest_point_dev(g, c, p_pts, cm, p_hits, p_geom), "psm_scene_closest_point_dev")
+        return lambda: ctx.check(lib.psm_scene_inside_dev(g, c, p_pts, cm, C.c_uint32(3), p_occ), "psm_scene_inside_dev")
+
+    def each(kind, ths):
+        fns = [plain(kind, t) for t in ths]
+        return lambda: [f() for f in fns]
+
+    out = {"rays": n, "points": m, "reps": REPS, "tris": int(tris.shape[0])}
+    upload(o, d, 0.0)
+    plain("closest", merged)()
+    hits = ctx.buf_download(h_hits, np.float32, 4 * n).reshape(n, 4)
+    bounce = bounce_rays(sc, o, d, hits)
+    # slabs of equal triangle count along x
+    order = np.argsort(t3[:, :, 0].mean(axis=1), kind="stable")
+    parts = {g: [hier(tris[np.sort(idx)]) for idx in np.array_split(order, g)] for g in (2, 8, 32)}
+    workloads = (("primary_closest", "closest", (o, d, 0.0)), ("bounce_closest", "closest", (*bounce, 1e-3)),
+                 ("bounce_any", "any", None), ("points_closest", "point", None), ("points_inside3", "inside", None))
+    for name, kind, rays in workloads:
+        if rays is not None:
+            upload(*rays)
+        # (a): plain, scene of one, plain again (the plain query's own spread beside the difference)
+        out[name + "_plain_ms"] = [round(median_ms(ctx, plain(kind, merged)), 4)]
+        out[name + "_g1_ms"] = round(median_ms(ctx, scene_of(kind, [merged])), 4)
+        out[name + "_plain_ms"].append(round(median_ms(ctx, plain(kind, merged)), 4))
+        # (b)
+        for g, ths in parts.items():
+            out["%s_g%d_scene_ms" % (name, g)] = round(median_ms(ctx, scene_of(kind, ths)), 4)
+            out["%s_g%d_launches_ms" % (name, g)] = round(median_ms(ctx, each(kind, ths)), 4)
+    # (c) the static scene and a small mesh that moves: a rebuild of what moved + a query
+    small = (torus(int(os.environ.get("MOVING_NU", "100")), int(os.environ.get("MOVING_NV", "50"))) * np.float32(1.5)
+             + np.tile(np.float32([0.0, 3.0, 0.0]), 3)).astype(np.float32)
+    mover = hier(small)
+    both = hier(np.concatenate([tris, small]))
+    out["moving_tris"] = int(small.shape[0])
+    upload(*bounce, 1e-3)
+    for name, kind in (("bounce_closest", "closest"), ("points_closest", "point")):
+        q_scene, q_plain = scene_of(kind, [merged, mover]), plain(kind, both)
+
+        def frame_scene():
+            mover.markDirty()
+            mover.build()
+            q_scene()
+
+        def frame_merged():
+            both.markDirty()
+            both.build()
+            q_plain()
+
+        out["moving_%s_rebuild_small_plus_scene_ms" % name] = round(median_ms(ctx, frame_scene), 4)
+        out["moving_%s_rebuild_merged_plus_plain_ms" % name] = round(median_ms(ctx, frame_merged), 4)
+        out["moving_%s_scene_query_ms" % name] = round(median_ms(ctx, q_scene), 4)
+        out["moving_%s_plain_query_ms" % name] = round(median_ms(ctx, q_plain), 4)
+    out["lib"] = os.path.basename(psm.LIB_PATH)
+    for h in (h_rays, h_pts, h_hits, h_geom, h_occ):
+        ctx.buf_free(h)
+    for th in [merged, mover, both] + [t for ths in parts.values() for t in ths]:
+        th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def main():
     sc = scenes.sponza_like()
     ctx = psm.Context(0)
@@ -297,4 +422,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene}.get(" ".join(sys.argv[1:]), main)()
