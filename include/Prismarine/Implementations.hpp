@@ -2,4 +2,5 @@
 // Prismarine/Implementations.hpp -- inline implementations (reference Implementations.hpp:5-9)
 #include "TriangleHierarchy.inl"
 #include "QueryScene.inl"
+#include "InstancedScene.inl"
 #include "Pipeline.inl"

@@ -8,5 +8,6 @@
 #include "MaterialSet.hpp"
 #include "TriangleHierarchy.hpp"
 #include "QueryScene.hpp"          // addition: the queries over several hierarchies at once (psm_scene_*_dev)
+#include "InstancedScene.hpp"      // addition: the same over instances, a hierarchy and a rigid pose each (psm_instances_*_dev)
 #include "Pipeline.hpp"
 #include "FrameBatch.hpp"   // addition: several frames in flight (psm_lanes_render)

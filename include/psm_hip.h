@@ -455,8 +455,9 @@ int psm_bvh_signed_distance_dev(psm_bvh* bvh, const psm_point_query* d_points, s
  *   - signed_distance: the scene's closest-point record (and d_geom) with the scene's inside sign; a miss casts no rays
  *   - the same hierarchy may appear more than once: the lower index wins every tie (its count and parity count once per entry)
  *   - a refitted geometry behaves as a refitted hierarchy does; a geometry of 0 leaves contributes nothing
- *   - there are no per-instance transforms, there is no top-level hierarchy over the geometries (every geometry is entered by
- *     every query, pruned from its root on) and no more than 32 geometries
+ *   - a geometry is where its triangles are; a rigid transform per entry is what the instanced scene queries below add
+ *     (psm_instances_*_dev). There is no top-level hierarchy over the geometries (every geometry is entered by every query,
+ *     pruned from its root on) and no more than 32 geometries
  * Checks: geoms == NULL, count == 0 or count > PSM_SCENE_MAX_GEOMETRIES: PSM_ERR_INVALID. Then every entry, the whole call being
  * refused with a message that names the first failing index: a NULL entry or one of another context than the others
  * (PSM_ERR_INVALID), one that is not built (PSM_ERR_STATE), one too deep for the query stack (PSM_ERR_CAPACITY). The list is
@@ -475,6 +476,55 @@ int psm_scene_inside_dev(psm_bvh* const* geoms, uint32_t count, const psm_point_
                          uint8_t* d_inside);
 int psm_scene_signed_distance_dev(psm_bvh* const* geoms, uint32_t count, const psm_point_query* d_points, size_t n,
                                   uint32_t samples, psm_hit* d_hits, int32_t* d_geom);
+
+/* instanced scene queries: the seven scene queries over an ordered list of INSTANCES, an instance being a built hierarchy and a
+ * rigid transform (new; no reference counterpart). A body that moves costs nothing to move: the next call reads
+ * the new matrix, and one built hierarchy can stand at up to PSM_SCENE_MAX_GEOMETRIES poses. The list lives in host memory and
+ * is read at the call; count is 1 .. PSM_SCENE_MAX_GEOMETRIES; the same bvh may appear many times with different transforms.
+ * Semantics:
+ *   - instance k answers exactly what psm_bvh_*_dev on its hierarchy answers for the query MOVED INTO ITS OBJECT SPACE, and the
+ *     scene combines the instances' answers by the rules of the scene queries above, unchanged: closest hit and closest point
+ *     take the smallest value, on a bit-equal value the lowest (inst, tri); occluded and within the OR; count_hits the sum;
+ *     inside sums the parity over all instances before the vote; signed_distance is the closest point with the scene's sign,
+ *     and a miss casts no rays. tmax and rmax apply over the whole scene
+ *   - the canonical move, one fixed float32 operation order (nothing is contracted): with world_from_object = [R | T] and
+ *     d = x - T per component, x'_j = (R[0][j] d.x + R[1][j] d.y) + R[2][j] d.z. A direction goes through the same rotation
+ *     without the subtraction: a ray's direction is rotated as given, and the single-hierarchy rule then normalises it as it
+ *     does today. tmin, tmax and rmax pass through unchanged
+ *   - validity is judged per instance on the moved query. A query that is invalid in world space is invalid in every instance
+ *     (NaN and infinity propagate through the move)
+ *   - inside: the rays {p, 0, PSM_INSIDE_DIRECTIONS[k], +inf} are WORLD rays from p, each moved per instance
+ *   - what comes back: psm_hit {u, v, t, tri} holds the OBJECT-SPACE values of the winning instance, d_inst[i] its index in the
+ *     list (-1 on a miss, the hit then {0, 0, +inf, -1}). (tri, u, v) reproduce the object-space point (v0 + u e1) + v e2; the
+ *     caller maps it to world space with that instance's matrix, world = R * object + T
+ *   - reflections (det R = -1) are accepted: distance and parity do not depend on winding. Scale and shear are out of scope and
+ *     refused (below). The bound of that check also means that t and dist are world distances only to within 1e-5 relative
+ *   - a refitted or rebuilt hierarchy is used as it then is, at every pose it stands at
+ * Checks, all on the host and before any device is touched; the call is refused with a message that names the first failing
+ * index: insts == NULL, count == 0 or count > PSM_SCENE_MAX_GEOMETRIES: PSM_ERR_INVALID. Then every entry: a NULL bvh or one of
+ * another context than the others (PSM_ERR_INVALID); then every matrix, in double: a non-finite entry, or an R whose R^T R
+ * differs from the identity by more than 1e-5 in any entry (PSM_ERR_INVALID); then every hierarchy: not built (PSM_ERR_STATE),
+ * too deep for the query stack (PSM_ERR_CAPACITY). The list is checked for n == 0 too; after that n == 0 is a no-op. The data
+ * pointers, their alignment (d_inst: non-NULL, 4 bytes) and samples as for the psm_scene_* forms.
+ * Stream-ordered on the hierarchies' context, no host synchronisation, no device allocation, one launch per query (signed
+ * distance: two); capturable into a graph after the context's first query of any kind. The transforms travel in the kernel
+ * arguments (32 x (four pointers + 12 floats) = 2560 B): a replayed graph answers with the poses it was CAPTURED with, whatever
+ * the host's list holds by then; a plain call always reads the list as it is. */
+typedef struct {
+    psm_bvh* bvh;
+    float world_from_object[12];   /* row-major 3x4 [R | T]: world = R * object + T */
+} psm_instance;                    /* host memory, read at the call */
+int psm_instances_intersect_dev(const psm_instance* insts, uint32_t count, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits,
+                                int32_t* d_inst);
+int psm_instances_occluded_dev(const psm_instance* insts, uint32_t count, const psm_query_ray* d_rays, size_t n, uint8_t* d_hit);
+int psm_instances_count_hits_dev(const psm_instance* insts, uint32_t count, const psm_query_ray* d_rays, size_t n, uint32_t* d_count);
+int psm_instances_closest_point_dev(const psm_instance* insts, uint32_t count, const psm_point_query* d_points, size_t n,
+                                    psm_hit* d_hits, int32_t* d_inst);
+int psm_instances_within_dev(const psm_instance* insts, uint32_t count, const psm_point_query* d_points, size_t n, uint8_t* d_hit);
+int psm_instances_inside_dev(const psm_instance* insts, uint32_t count, const psm_point_query* d_points, size_t n, uint32_t samples,
+                             uint8_t* d_inside);
+int psm_instances_signed_distance_dev(const psm_instance* insts, uint32_t count, const psm_point_query* d_points, size_t n,
+                                      uint32_t samples, psm_hit* d_hits, int32_t* d_inst);
 
 /* ---------------------------------------------------------------------------------------------
  * several frames in flight (new; DESIGN.md "lanes")

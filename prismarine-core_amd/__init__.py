@@ -29,6 +29,8 @@ EXPORTS = [
     "psm_bvh_closest_point_dev", "psm_bvh_within_dev", "psm_bvh_count_hits_dev", "psm_bvh_inside_dev", "psm_bvh_signed_distance_dev",
     "psm_scene_intersect_dev", "psm_scene_occluded_dev", "psm_scene_count_hits_dev", "psm_scene_closest_point_dev", "psm_scene_within_dev",
     "psm_scene_inside_dev", "psm_scene_signed_distance_dev",
+    "psm_instances_intersect_dev", "psm_instances_occluded_dev", "psm_instances_count_hits_dev", "psm_instances_closest_point_dev",
+    "psm_instances_within_dev", "psm_instances_inside_dev", "psm_instances_signed_distance_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -68,6 +70,11 @@ class PsmError(RuntimeError):
 class BvhInfo(C.Structure):
     _fields_ = [("triangle_count", C.c_uint32), ("leaf_count", C.c_uint32), ("root", C.c_int32),
                 ("transform", C.c_float * 16), ("bounds_min", C.c_float * 4), ("bounds_max", C.c_float * 4)]
+
+
+class Instance(C.Structure):
+    """psm_instance: a built hierarchy and its pose, world_from_object a row-major 3 x 4 [R | T]"""
+    _fields_ = [("bvh", C.c_void_p), ("world_from_object", C.c_float * 12)]
 
 
 class Accessor(C.Structure):
@@ -674,6 +681,59 @@ class QueryScene:
     def signedDistance(self, points, rmax=np.inf, samples=3):
         """closestPoint() over the scene with the sign of inside() over the scene (psm_scene_signed_distance_dev)."""
         return self._point_query(points, rmax, "hits", "psm_bvh_signed_distance_dev", samples)
+
+
+INSTANCE_ORTHONORMAL_TOL = 1e-5   # psm_hip.h: the largest entry of R^T R - 1 a pose may have
+
+
+def _pose(matrix, what):
+    """a pose as psm_instance takes it: float32 [3, 4] from a 3 x 4 or a 4 x 4 (last row 0 0 0 1) world-from-object matrix,
+    checked as the library checks it (finite; R^T R within INSTANCE_ORTHONORMAL_TOL of the identity, in double)"""
+    m = np.asarray(matrix)
+    if m.shape not in ((3, 4), (4, 4)):
+        raise ValueError("%s: a transform must be 3 x 4 or 4 x 4, not %s" % (what, "x".join(str(k) for k in m.shape) or "a scalar"))
+    m = m.astype(np.float32)
+    if not np.isfinite(m).all():
+        raise ValueError("%s: a transform has a non-finite entry" % what)
+    if m.shape == (4, 4) and not np.array_equal(m[3], [0, 0, 0, 1]):
+        raise ValueError("%s: the last row of a 4 x 4 transform must be 0 0 0 1" % what)
+    r = m[:3, :3].astype(np.float64)
+    if np.abs(r.T @ r - np.eye(3)).max() > INSTANCE_ORTHONORMAL_TOL:
+        raise ValueError("%s: a transform must be rigid (a rotation or reflection and a translation: no scale, no shear)" % what)
+    return np.ascontiguousarray(m[:3])
+
+
+class InstancedScene(QueryScene):
+    """QueryScene with a pose per entry (psm_instances_*_dev; not in the reference): an ordered list of 1 .. SCENE_MAX_GEOMETRIES
+    instances (TriangleHierarchy, matrix), the matrix a rigid world-from-object transform, 3 x 4 [R | T] or 4 x 4 with the last
+    row 0 0 0 1. The same hierarchy may stand at many poses. A query is moved into each instance's object space and answered
+    there; the answers combine as QueryScene's. Moving a body is setTransform(): nothing is rebuilt, the next call reads the new
+    matrix. QueryHits.geom is the index of the winning INSTANCE; u, v, t, tri are that instance's object-space values (the point
+    of triangle tri at (u, v), mapped through transforms()[geom], is the world point). Methods, arguments and numpy / torch
+    placement: QueryScene's."""
+
+    def __init__(self, ctx, instances):
+        pairs = list(instances)
+        super().__init__(ctx, [th for th, _ in pairs])
+        self._poses = np.stack([_pose(m, "InstancedScene") for _, m in pairs])
+
+    def setTransform(self, i, matrix):
+        """Place instance i anew: the next query reads it (no rebuild, no upload)."""
+        self._poses[range(len(self.hierarchies))[i]] = _pose(matrix, "InstancedScene.setTransform")
+
+    def transforms(self):
+        """The poses, float32 [instances, 3, 4] (a copy)."""
+        return self._poses.copy()
+
+    def _call(self, name, d_in, n, extra, d_out, d_geom):
+        name = name.replace("psm_bvh_", "psm_instances_")
+        g = len(self.hierarchies)
+        insts = (Instance * g)()
+        for k, th in enumerate(self.hierarchies):
+            insts[k].bvh = th._h.value if isinstance(th._h, C.c_void_p) else th._h
+            insts[k].world_from_object[:] = self._poses[k].reshape(12).tolist()
+        tail = () if d_geom is None else (C.c_void_p(d_geom),)
+        self.ctx.check(getattr(lib(), name)(insts, C.c_uint32(g), C.c_void_p(d_in), C.c_size_t(n), *extra, C.c_void_p(d_out), *tail), name)
 
 
 class TextureSet:

@@ -12,8 +12,10 @@
 // Structure as rt_traverse (trace.hip): one ray per lane, one wave64 per workgroup, the stack in LDS laid out [depth][lane],
 // child boxes by fmaf on the fp16 record coordinates (v_fma_mix_f32), nearer child first. The kernels are grid-stride. The walk
 // (query_walk: grid-stride loop, stack, leaf scheduling) is shared by the ray and the point kernels; a body says what a query is.
+#include <cmath>
 #include <cstdio>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 #include "psm_common.h"
@@ -613,8 +615,11 @@ namespace {
 //   void enter(gm, g)        the per-geometry set-up (the ray's axes / the point's bound from that geometry's fit transform)
 //   children, leaf, done, again, finish: as query_walk's; a lane that is done() skips the remaining geometries
 //   again(): every geometry is walked again (the inside queries' next ray: its parity is summed over the whole scene)
-template <class Body>
-PSM_D void scene_walk(const SceneArgs& s, Body& q) {
+// Args: SceneArgs, or the instanced queries' InstArgs (below): the same walk over a table whose entries also carry a pose. A
+// body whose enter() returns bool says whether the query is valid in that entry (the instanced queries: validity is judged
+// per instance, on the moved query); one that returns void is valid everywhere (the scene bodies, whose code this leaves as it was).
+template <class Args, class Body>
+PSM_D void scene_walk(const Args& s, Body& q) {
     __shared__ int stack[QSTACK_LDS][QUERY_BLOCK];
     const int lane = (int)threadIdx.x;
     __builtin_assume(lane >= 0 && lane < QUERY_BLOCK);
@@ -625,13 +630,15 @@ PSM_D void scene_walk(const SceneArgs& s, Body& q) {
         const bool valid = q.begin(i, alive);
         do {
             for (uint32_t g = 0; g < s.geoms; g++) {
-                const SceneGeom gm = s.g[g];
+                const auto gm = s.g[g];
                 const uint4* __restrict__ node32 = gm.node32;
                 const int root = (int)gm.sm[SM_ROOT];
                 const uint32_t count = gm.sm[SM_COUNT];
                 const int lone = (count == 1u) ? gm.sorted_tri[0] : -1;
-                q.enter(gm, (int)g);
-                const bool go = valid && !q.done();
+                bool here = true;
+                if constexpr (std::is_void_v<decltype(q.enter(gm, (int)g))>) q.enter(gm, (int)g);
+                else here = q.enter(gm, (int)g);
+                const bool go = valid && here && !q.done();
                 if (go && lone >= 0) q.leaf(lone);
                 int cur = root, sp = 0;
                 bool walking = go && root >= 0;
@@ -726,7 +733,8 @@ struct SceneRay {
         tmax = hi;
         return finite3(o) && finite3(d) && tmin <= tmax;
     }
-    PSM_D bool load(const SceneArgs& s, size_t i, bool alive) {
+    template <class Args>
+    PSM_D bool load(const Args& s, size_t i, bool alive) {
         float4 r0 = make_float4(0.f, 0.f, 0.f, 1.f), r1 = make_float4(1.f, 0.f, 0.f, -1.f);
         if (alive) { r0 = s.rays[2 * i]; r1 = s.rays[2 * i + 1]; }
         return aim(mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), r0.w, r1.w) && alive;
@@ -750,13 +758,14 @@ struct SceneRay {
 };
 
 // closest hit (ANY = false) and any hit (ANY = true) of a scene: RayBody with the best carried across the geometries
-template <bool ANY>
+// (Args: SceneArgs; the instanced bodies below derive from these over InstArgs and replace begin() and enter())
+template <bool ANY, class Args = SceneArgs>
 struct SceneRayBody : SceneRay {
-    const SceneArgs& s;
+    const Args& s;
     SceneBest b;
     bool found;
 
-    PSM_D SceneRayBody(const SceneArgs& a) : s(a) {}
+    PSM_D SceneRayBody(const Args& a) : s(a) {}
     PSM_D bool begin(size_t i, bool alive) {
         const bool valid = load(s, i, alive);
         b.clear(tmax);
@@ -791,9 +800,9 @@ struct SceneRayBody : SceneRay {
 
 // closest point (WITHIN = false) and within radius (WITHIN = true) of a scene: PointBody with the best d2 carried across the
 // geometries; the point's normalised image and the bound's factors are redone per geometry (point_bound: per fit transform)
-template <bool WITHIN>
+template <bool WITHIN, class Args = SceneArgs>
 struct ScenePointBody {
-    const SceneArgs& s;
+    const Args& s;
     SceneGeom gm;
     PointBound B;
     v3 p;
@@ -802,7 +811,7 @@ struct ScenePointBody {
     bool found;
     float Px, Py, Pz, h;
 
-    PSM_D ScenePointBody(const SceneArgs& a) : s(a) {}
+    PSM_D ScenePointBody(const Args& a) : s(a) {}
     PSM_D bool begin(size_t i, bool alive) {
         float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
         if (alive) q = s.rays[i];
@@ -870,9 +879,10 @@ struct SceneCountRay : SceneRay {
     PSM_D bool done() const { return false; }
 };
 
+template <class Args = SceneArgs>
 struct SceneCountBody : SceneCountRay {
-    const SceneArgs& s;
-    PSM_D SceneCountBody(const SceneArgs& a) : s(a) {}
+    const Args& s;
+    PSM_D SceneCountBody(const Args& a) : s(a) {}
     PSM_D bool begin(size_t i, bool alive) {
         count = 0u;
         return load(s, i, alive);
@@ -884,15 +894,15 @@ struct SceneCountBody : SceneCountRay {
 
 // inside / outside of a point against a scene (SIGN = false) and the sign of a scene closest-point result (SIGN = true):
 // InsideBody, with ray k's crossings summed over all geometries before it votes (again() comes after the last geometry)
-template <bool SIGN>
+template <bool SIGN, class Args = SceneArgs>
 struct SceneInsideBody : SceneCountRay {
-    const SceneArgs& s;
+    const Args& s;
     v3 p;
     uint32_t k, votes;
     float dist;
     bool valid;
 
-    PSM_D SceneInsideBody(const SceneArgs& a) : s(a) {}
+    PSM_D SceneInsideBody(const Args& a) : s(a) {}
     PSM_D bool shoot() {
         const int r = __builtin_amdgcn_readfirstlane((int)k);
         count = 0u;
@@ -930,8 +940,8 @@ struct SceneInsideBody : SceneCountRay {
     }
 };
 
-template <class Body>
-PSM_D void scene_body(const SceneArgs& s) {
+template <class Body, class Args>
+PSM_D void scene_body(const Args& s) {
     Body q(s);
     scene_walk(s, q);
 }
@@ -942,9 +952,182 @@ __global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_closest(SceneArgs 
 __global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_any(SceneArgs s) { scene_body<SceneRayBody<true>>(s); }
 __global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_point(SceneArgs s) { scene_body<ScenePointBody<false>>(s); }
 __global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_within(SceneArgs s) { scene_body<ScenePointBody<true>>(s); }
-__global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_count(SceneArgs s) { scene_body<SceneCountBody>(s); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_count(SceneArgs s) { scene_body<SceneCountBody<>>(s); }
 __global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_inside(SceneArgs s) { scene_body<SceneInsideBody<false>>(s); }
 __global__ __launch_bounds__(QUERY_BLOCK, 8) void scene_query_sign(SceneArgs s) { scene_body<SceneInsideBody<true>>(s); }
+
+// ---- instanced scene queries: a rigid transform per entry (include/psm_hip.h "instanced scene queries") ---------
+
+// One instance as a kernel reads it: a geometry of a scene and its pose, the 12 floats of psm_instance.world_from_object
+// (row-major 3 x 4 [R | T]). The table travels in the kernel-argument segment as SceneArgs' does (32 x 80 B = 2560 B): a pose
+// changed on the host is the next launch's, and nothing on the device can go stale. The instance index is the same in every
+// lane of a wave, so the matrix is read by scalar loads and never leaves the scalar registers.
+struct InstGeom : SceneGeom {
+    float m[12];
+};
+struct InstArgs {
+    const float4* rays;      // as SceneArgs
+    size_t n;
+    int* spill;
+    float4* hits;
+    uint8_t* occluded;
+    uint32_t* count;
+    int32_t* geom;           // the winning INSTANCE per query, -1 on a miss
+    uint32_t samples;
+    uint32_t geoms;          // instances: 1 .. PSM_SCENE_MAX_GEOMETRIES
+    InstGeom g[PSM_SCENE_MAX_GEOMETRIES];
+};
+static_assert(sizeof(InstGeom) == 80 && sizeof(InstArgs) <= 4096, "the instance table must fit the kernel-argument segment");
+
+namespace {
+
+// The canonical move into an instance's object space (psm_hip.h; tests/instance_query_model.py states it in numpy): a direction
+// goes through R^T, x'_j = (R[0][j] d.x + R[1][j] d.y) + R[2][j] d.z, a point through the same after d = x - T per component.
+// One float32 operation order (the build contracts nothing: -ffp-contract=off).
+PSM_D v3 inst_rotate(const float* m, v3 d) {
+    return mk3((m[0] * d.x + m[4] * d.y) + m[8] * d.z, (m[1] * d.x + m[5] * d.y) + m[9] * d.z, (m[2] * d.x + m[6] * d.y) + m[10] * d.z);
+}
+PSM_D v3 inst_point(const float* m, v3 x) { return inst_rotate(m, mk3(x.x - m[3], x.y - m[7], x.z - m[11])); }
+
+// The instanced bodies are the scene bodies over InstArgs with begin() and enter() replaced. begin() keeps what passes through
+// unchanged (the window, rmax) and the query's index; enter() reads the query again from memory (16 or 32 B, resident in L2),
+// moves it into the instance's object space, then does the scene body's per-geometry set-up. The world query is therefore never
+// live across the walk, which would cost the registers the scene kernels do not have to spare. enter() returns whether the moved
+// query is valid in this instance (NaN and infinity propagate through the move; a finite query can overflow in it).
+
+// enter() of the ray bodies: the ray aimed as SceneRay::aim aims it (the direction rotated as given, then normalised)
+PSM_D bool inst_ray(SceneRay& r, const float4* __restrict__ rays, const InstGeom& g, size_t i, bool alive) {
+    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(1.f, 0.f, 0.f, 0.f);
+    if (alive) { r0 = rays[2 * i]; r1 = rays[2 * i + 1]; }
+    r.o = inst_point(g.m, mk3(r0.x, r0.y, r0.z));
+    r.d = normalize3(inst_rotate(g.m, mk3(r1.x, r1.y, r1.z)));
+    r.axes(g);
+    return finite3(r.o) && finite3(r.d);
+}
+// begin() of the ray bodies: the window alone
+PSM_D bool inst_window(SceneRay& r, const float4* __restrict__ rays, size_t i, bool alive) {
+    r.tmin = 0.f;
+    r.tmax = -1.f;
+    if (alive) { r.tmin = rays[2 * i].w; r.tmax = rays[2 * i + 1].w; }
+    return alive && r.tmin <= r.tmax;
+}
+
+// closest hit / any hit over instances. t is the distance along the moved unit direction: an object-space value, comparable
+// across instances because the move is rigid (to 1e-5 relative: psm_hip.h)
+template <bool ANY>
+struct InstRayBody : SceneRayBody<ANY, InstArgs> {
+    size_t idx;
+    bool alive;
+    PSM_D InstRayBody(const InstArgs& a) : SceneRayBody<ANY, InstArgs>(a) {}
+    PSM_D bool begin(size_t i, bool al) {
+        idx = i;
+        alive = al;
+        const bool valid = inst_window(*this, this->s.rays, i, al);
+        this->b.clear(this->tmax);
+        this->found = false;
+        return valid;
+    }
+    PSM_D bool enter(const InstGeom& g, int gi) {
+        const bool here = inst_ray(*this, this->s.rays, g, idx, alive);   // the move, then the axes; then the tie key
+        this->b.enter_geom(gi);
+        return here;
+    }
+};
+
+struct InstCountBody : SceneCountBody<InstArgs> {
+    size_t idx;
+    bool alive;
+    PSM_D InstCountBody(const InstArgs& a) : SceneCountBody<InstArgs>(a) {}
+    PSM_D bool begin(size_t i, bool al) {
+        idx = i;
+        alive = al;
+        count = 0u;
+        return inst_window(*this, s.rays, i, al);
+    }
+    PSM_D bool enter(const InstGeom& g, int) { return inst_ray(*this, s.rays, g, idx, alive); }
+};
+
+// closest point / within over instances: p is the point in the instance's object space; rmax passes through, d2 is an
+// object-space value (see InstRayBody)
+template <bool WITHIN>
+struct InstPointBody : ScenePointBody<WITHIN, InstArgs> {
+    size_t idx;
+    bool alive;
+    PSM_D InstPointBody(const InstArgs& a) : ScenePointBody<WITHIN, InstArgs>(a) {}
+    PSM_D bool begin(size_t i, bool al) {
+        idx = i;
+        alive = al;
+        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
+        if (al) q = this->s.rays[i];
+        this->rmax = q.w;
+        this->b.clear((q.w * q.w) * 1.00000095367431640625f + 0x1p-126f);   // (PointBody::begin)
+        this->found = false;
+        return al && finite3(mk3(q.x, q.y, q.z)) && q.w >= 0.f;   // (a non-finite world point is non-finite in every instance)
+    }
+    PSM_D bool enter(const InstGeom& g, int gi) {
+        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
+        if (alive) q = this->s.rays[idx];
+        this->p = inst_point(g.m, mk3(q.x, q.y, q.z));
+        ScenePointBody<WITHIN, InstArgs>::enter(g, gi);
+        return finite3(this->p);
+    }
+};
+
+// inside / the sign of a closest-point result over instances: ray k is the WORLD ray {p, 0, PSM_INSIDE_DIRECTIONS[k], +inf},
+// moved per instance; its crossings are summed over all instances before it votes
+template <bool SIGN>
+struct InstInsideBody : SceneInsideBody<SIGN, InstArgs> {
+    size_t idx;
+    bool alive;
+    PSM_D InstInsideBody(const InstArgs& a) : SceneInsideBody<SIGN, InstArgs>(a) {}
+    PSM_D bool begin(size_t i, bool al) {
+        idx = i;
+        alive = al;
+        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
+        if (al) q = this->s.rays[i];
+        this->k = 0u;
+        this->votes = 0u;
+        this->count = 0u;
+        this->dist = 0.f;
+        this->tmin = 0.f;
+        this->tmax = __builtin_inff();
+        this->valid = al;
+        if (SIGN) {
+            float4 h = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+            if (al) h = this->s.hits[i];
+            this->dist = h.z;
+            this->valid = __float_as_int(h.w) >= 0;
+        }
+        this->valid = finite3(mk3(q.x, q.y, q.z)) && this->valid;   // (a non-finite p: outside)
+        return this->valid;
+    }
+    PSM_D bool enter(const InstGeom& g, int) {
+        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
+        if (alive) q = this->s.rays[idx];
+        const int r = __builtin_amdgcn_readfirstlane((int)this->k);
+        this->o = inst_point(g.m, mk3(q.x, q.y, q.z));
+        this->d = normalize3(inst_rotate(g.m, mk3(INSIDE_DIR[r][0], INSIDE_DIR[r][1], INSIDE_DIR[r][2])));
+        this->axes(g);
+        return finite3(this->o) && finite3(this->d);
+    }
+    PSM_D bool again() {
+        this->votes += this->count & 1u;
+        this->k++;
+        if (!this->valid || this->k >= this->s.samples) return false;
+        this->count = 0u;
+        return true;
+    }
+};
+
+}  // namespace
+
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void inst_query_closest(InstArgs s) { scene_body<InstRayBody<false>>(s); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void inst_query_any(InstArgs s) { scene_body<InstRayBody<true>>(s); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void inst_query_point(InstArgs s) { scene_body<InstPointBody<false>>(s); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void inst_query_within(InstArgs s) { scene_body<InstPointBody<true>>(s); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void inst_query_count(InstArgs s) { scene_body<InstCountBody>(s); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void inst_query_inside(InstArgs s) { scene_body<InstInsideBody<false>>(s); }
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void inst_query_sign(InstArgs s) { scene_body<InstInsideBody<true>>(s); }
 
 namespace {
 
@@ -1049,6 +1232,48 @@ const char* const SCENE_NAME[] = {"psm_scene_intersect_dev", "psm_scene_occluded
                                   "psm_scene_within_dev", "psm_scene_count_hits_dev", "psm_scene_inside_dev",
                                   "psm_scene_signed_distance_dev"};
 
+// What scene_query and inst_query do once their list has passed and n > 0: the data pointers (d_geom, called `index` in the
+// messages: the kinds with a psm_hit output only), their alignment and samples; then the context's stack area and the grid, and
+// the scalars of the argument struct (SceneArgs or InstArgs)
+template <class Args>
+int scene_data(psm_ctx* c, const char* name, const char* index, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_geom,
+               uint32_t samples, Args& sa, uint32_t& grid) {
+    const QueryDesc& k = QUERY_DESC[kind];
+    char msg[128];
+    const bool with_geom = k.out_align == 16;
+    if (!d_in || !d_out || (with_geom && !d_geom)) {
+        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    const bool in_bad = ((uintptr_t)d_in & 15u) != 0, out_bad = ((uintptr_t)d_out & (uintptr_t)(k.out_align - 1)) != 0;
+    if (in_bad || out_bad) {
+        if (k.out_align == 16) snprintf(msg, sizeof msg, "%s: %s or %s not 16-byte aligned", name, k.in, k.out);
+        else if (in_bad) snprintf(msg, sizeof msg, "%s: %s not 16-byte aligned", name, k.in);
+        else snprintf(msg, sizeof msg, "%s: %s not %u-byte aligned", name, k.out, k.out_align);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (with_geom && ((uintptr_t)d_geom & 3u) != 0) {
+        snprintf(msg, sizeof msg, "%s: %s not 4-byte aligned", name, index);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if ((kind == Q_INSIDE || kind == Q_SIGNED) && samples != 1 && samples != 3 && samples != 5) {
+        snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    (void)hipSetDevice(c->device);
+    void* spill = nullptr;
+    const int rc = spill_for(c, &spill);
+    if (rc != PSM_OK) return rc;
+    const size_t waves = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;
+    grid = (uint32_t)(waves < QUERY_GRID_CAP ? waves : QUERY_GRID_CAP);
+    sa.rays = (const float4*)d_in; sa.n = n;
+    sa.spill = (int*)spill;
+    sa.hits = (float4*)d_out; sa.occluded = (uint8_t*)d_out; sa.count = (uint32_t*)d_out;
+    sa.geom = d_geom;
+    sa.samples = samples;
+    return PSM_OK;
+}
+
 // query() for a scene. The list is checked first and whole, also for n == 0: its length, then every entry (NULL, another
 // context than entry 0's, not built, too deep for the stack), the message naming the first failing index. The message goes to
 // the context of the first non-NULL entry (a list of NULLs only has no context to tell: the return code alone). d_geom: the
@@ -1056,7 +1281,6 @@ const char* const SCENE_NAME[] = {"psm_scene_intersect_dev", "psm_scene_occluded
 int scene_query(psm_bvh* const* geoms, uint32_t count, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_geom,
                 uint32_t samples = 0) {
     if (!geoms || count == 0 || count > PSM_SCENE_MAX_GEOMETRIES) return PSM_ERR_INVALID;
-    const QueryDesc& k = QUERY_DESC[kind];
     const char* name = SCENE_NAME[kind];
     psm_ctx* c = nullptr;
     for (uint32_t g = 0; g < count && !c; g++)
@@ -1084,38 +1308,10 @@ int scene_query(psm_bvh* const* geoms, uint32_t count, QueryKind kind, const voi
         }
     }
     if (n == 0) return PSM_OK;
-    const bool with_geom = k.out_align == 16;
-    if (!d_in || !d_out || (with_geom && !d_geom)) {
-        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    const bool in_bad = ((uintptr_t)d_in & 15u) != 0, out_bad = ((uintptr_t)d_out & (uintptr_t)(k.out_align - 1)) != 0;
-    if (in_bad || out_bad) {
-        if (k.out_align == 16) snprintf(msg, sizeof msg, "%s: %s or %s not 16-byte aligned", name, k.in, k.out);
-        else if (in_bad) snprintf(msg, sizeof msg, "%s: %s not 16-byte aligned", name, k.in);
-        else snprintf(msg, sizeof msg, "%s: %s not %u-byte aligned", name, k.out, k.out_align);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (with_geom && ((uintptr_t)d_geom & 3u) != 0) {
-        snprintf(msg, sizeof msg, "%s: geom not 4-byte aligned", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if ((kind == Q_INSIDE || kind == Q_SIGNED) && samples != 1 && samples != 3 && samples != 5) {
-        snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    (void)hipSetDevice(c->device);
-    void* spill = nullptr;
-    const int rc = spill_for(c, &spill);
-    if (rc != PSM_OK) return rc;
-    const size_t waves = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;
-    const uint32_t grid = (uint32_t)(waves < QUERY_GRID_CAP ? waves : QUERY_GRID_CAP);
     SceneArgs sa = {};
-    sa.rays = (const float4*)d_in; sa.n = n;
-    sa.spill = (int*)spill;
-    sa.hits = (float4*)d_out; sa.occluded = (uint8_t*)d_out; sa.count = (uint32_t*)d_out;
-    sa.geom = d_geom;
-    sa.samples = samples;
+    uint32_t grid = 0;
+    const int rc = scene_data(c, name, "geom", kind, d_in, n, d_out, d_geom, samples, sa, grid);
+    if (rc != PSM_OK) return rc;
     sa.geoms = count;
     for (uint32_t g = 0; g < count; g++) {
         const psm_bvh* b = geoms[g];
@@ -1132,6 +1328,89 @@ int scene_query(psm_bvh* const* geoms, uint32_t count, QueryKind kind, const voi
             scene_query_point<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa);
             PSM_HIP(c, hipGetLastError());
             scene_query_sign<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa);
+            break;
+    }
+    PSM_HIP(c, hipGetLastError());
+    return PSM_OK;
+}
+
+// ---- the instanced entry points' checks and launch -------------------------------------------------------------------------
+const char* const INST_NAME[] = {"psm_instances_intersect_dev", "psm_instances_occluded_dev", "psm_instances_closest_point_dev",
+                                 "psm_instances_within_dev", "psm_instances_count_hits_dev", "psm_instances_inside_dev",
+                                 "psm_instances_signed_distance_dev"};
+
+// Why a pose is refused, or NULL (psm_hip.h): in double, on the host. A rigid motion or a reflection has R^T R = 1; the bound
+// leaves room for a matrix that was composed in float32 and refuses every scale or shear a user could mean.
+const char* pose_fault(const float* m) {
+    for (int k = 0; k < 12; k++)
+        if (!std::isfinite(m[k])) return "has a non-finite transform";
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) {
+            double dot = 0.0;
+            for (int i = 0; i < 3; i++) dot += (double)m[4 * i + a] * (double)m[4 * i + b];
+            if (std::fabs(dot - (a == b ? 1.0 : 0.0)) > 1e-5) return "has a transform that is not rigid (R^T R differs from 1 by more than 1e-5)";
+        }
+    return nullptr;
+}
+
+// scene_query() for instances: the same order of checks, with the poses judged between the entries' handles and their state --
+// all of it on the host, before any device is touched
+int inst_query(const psm_instance* insts, uint32_t count, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_inst,
+               uint32_t samples = 0) {
+    if (!insts || count == 0 || count > PSM_SCENE_MAX_GEOMETRIES) return PSM_ERR_INVALID;
+    const char* name = INST_NAME[kind];
+    psm_ctx* c = nullptr;
+    for (uint32_t g = 0; g < count && !c; g++)
+        if (insts[g].bvh) c = insts[g].bvh->ctx;
+    if (!c) return PSM_ERR_INVALID;
+    char msg[160];
+    for (uint32_t g = 0; g < count; g++) {
+        if (!insts[g].bvh) {
+            snprintf(msg, sizeof msg, "%s: instance %u is NULL", name, g);
+            return set_err(c, PSM_ERR_INVALID, msg);
+        }
+        if (insts[g].bvh->ctx != c) {
+            snprintf(msg, sizeof msg, "%s: instance %u belongs to another context", name, g);
+            return set_err(c, PSM_ERR_INVALID, msg);
+        }
+    }
+    for (uint32_t g = 0; g < count; g++)
+        if (const char* why = pose_fault(insts[g].world_from_object)) {
+            snprintf(msg, sizeof msg, "%s: instance %u %s", name, g, why);
+            return set_err(c, PSM_ERR_INVALID, msg);
+        }
+    for (uint32_t g = 0; g < count; g++) {
+        if (!insts[g].bvh->built) {
+            snprintf(msg, sizeof msg, "%s: instance %u is not built", name, g);
+            return set_err(c, PSM_ERR_STATE, msg);
+        }
+        if (63 + ceil_log2(insts[g].bvh->cap) > QSTACK_MAX) {
+            snprintf(msg, sizeof msg, "%s: instance %u is deeper than the query stack", name, g);
+            return set_err(c, PSM_ERR_CAPACITY, msg);
+        }
+    }
+    if (n == 0) return PSM_OK;
+    InstArgs ia = {};
+    uint32_t grid = 0;
+    const int rc = scene_data(c, name, "inst", kind, d_in, n, d_out, d_inst, samples, ia, grid);
+    if (rc != PSM_OK) return rc;
+    ia.geoms = count;
+    for (uint32_t g = 0; g < count; g++) {
+        const psm_bvh* b = insts[g].bvh;
+        ia.g[g].node32 = b->d_node32; ia.g[g].tri48 = b->d_tri48; ia.g[g].sm = b->d_small; ia.g[g].sorted_tri = b->d_sorted_tri;
+        for (int k = 0; k < 12; k++) ia.g[g].m[k] = insts[g].world_from_object[k];
+    }
+    switch (kind) {
+        case Q_CLOSEST: inst_query_closest<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia); break;
+        case Q_ANY: inst_query_any<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia); break;
+        case Q_POINT: inst_query_point<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia); break;
+        case Q_WITHIN: inst_query_within<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia); break;
+        case Q_COUNT: inst_query_count<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia); break;
+        case Q_INSIDE: inst_query_inside<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia); break;
+        case Q_SIGNED:   // the closest point over the instances, then the sign of what it found (the same stream: in order)
+            inst_query_point<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia);
+            PSM_HIP(c, hipGetLastError());
+            inst_query_sign<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia);
             break;
     }
     PSM_HIP(c, hipGetLastError());
@@ -1208,4 +1487,36 @@ int psm_scene_inside_dev(psm_bvh* const* geoms, uint32_t count, const psm_point_
 int psm_scene_signed_distance_dev(psm_bvh* const* geoms, uint32_t count, const psm_point_query* d_points, size_t n, uint32_t samples,
                                   psm_hit* d_hits, int32_t* d_geom) {
     return psm::scene_query(geoms, count, psm::Q_SIGNED, d_points, n, d_hits, d_geom, samples);
+}
+
+int psm_instances_intersect_dev(const psm_instance* insts, uint32_t count, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits,
+                                int32_t* d_inst) {
+    return psm::inst_query(insts, count, psm::Q_CLOSEST, d_rays, n, d_hits, d_inst);
+}
+
+int psm_instances_occluded_dev(const psm_instance* insts, uint32_t count, const psm_query_ray* d_rays, size_t n, uint8_t* d_hit) {
+    return psm::inst_query(insts, count, psm::Q_ANY, d_rays, n, d_hit, nullptr);
+}
+
+int psm_instances_closest_point_dev(const psm_instance* insts, uint32_t count, const psm_point_query* d_points, size_t n, psm_hit* d_hits,
+                                    int32_t* d_inst) {
+    return psm::inst_query(insts, count, psm::Q_POINT, d_points, n, d_hits, d_inst);
+}
+
+int psm_instances_within_dev(const psm_instance* insts, uint32_t count, const psm_point_query* d_points, size_t n, uint8_t* d_hit) {
+    return psm::inst_query(insts, count, psm::Q_WITHIN, d_points, n, d_hit, nullptr);
+}
+
+int psm_instances_count_hits_dev(const psm_instance* insts, uint32_t count, const psm_query_ray* d_rays, size_t n, uint32_t* d_count) {
+    return psm::inst_query(insts, count, psm::Q_COUNT, d_rays, n, d_count, nullptr);
+}
+
+int psm_instances_inside_dev(const psm_instance* insts, uint32_t count, const psm_point_query* d_points, size_t n, uint32_t samples,
+                             uint8_t* d_inside) {
+    return psm::inst_query(insts, count, psm::Q_INSIDE, d_points, n, d_inside, nullptr, samples);
+}
+
+int psm_instances_signed_distance_dev(const psm_instance* insts, uint32_t count, const psm_point_query* d_points, size_t n,
+                                      uint32_t samples, psm_hit* d_hits, int32_t* d_inst) {
+    return psm::inst_query(insts, count, psm::Q_SIGNED, d_points, n, d_hits, d_inst, samples);
 }

@@ -15,7 +15,11 @@ uniform points: (a) a scene of ONE geometry against the plain query (the cost of
 spatially separate parts (slabs of equal triangle count along x): one scene launch against the merged hierarchy and against the sum
 of G plain launches; (c) the static scene plus a small mesh that moves (MOVING_NU x MOVING_NV torus): rebuild of the small mesh +
 a scene query against rebuild of the merged hierarchy + a plain query.
-A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene]"""
+`query_bench.py instances`: the instanced scene queries (psm_instances_*_dev) on the scene mode's bounce-like rays and uniform
+points: (a) identity instances against `scene` on the same hierarchies (the merged one; 8 slabs): the cost of the move; (b) ONE torus
+hierarchy (MOVING_NU x MOVING_NV) at 2, 8 and 32 poses on a lattice inside the scene's bounds; (c) the static scene plus a moving
+10 000-triangle torus: a pose update + an instanced query against a re-upload and rebuild of the small mesh + a scene query.
+A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
 import json
@@ -357,6 +361,131 @@ def scene():
     print(json.dumps(out))
 
 
+def instances():
+    lib = psm.lib()
+    sc = scenes.sponza_like()
+    tris = np.ascontiguousarray(sc["tris"], np.float32).reshape(-1, 9)
+    ctx = psm.Context(0)
+
+    def hier(t):
+        th = psm.TriangleHierarchy(ctx)
+        th.allocate(t.shape[0])
+        th.loadTriangles(t)
+        th.build()
+        return th
+
+    merged = hier(tris)
+    rt = psm.Pipeline(ctx, seed=1000)
+    rt.resizeBuffers(W, H)
+    rt.resize(W, H)
+    cam = scenes.camera_matrices(sc["eye"], sc["view"], W, H)
+    rt.camera_matrices(cam[0], cam[1])
+    prim = rt.download_rays()
+    rt.close()
+    n = prim.shape[0]
+    o, d = prim["origin"].copy(), prim["direct"].copy()
+    m = NPTS
+    t3 = tris.reshape(-1, 3, 3)
+    lo, hi = t3.reshape(-1, 3).min(0), t3.reshape(-1, 3).max(0)
+    pts = np.empty((m, 4), np.float32)
+    pts[:, 0:3], pts[:, 3] = np.random.RandomState(7).uniform(lo, hi, (m, 3)), np.inf
+    k = max(n, m)
+    h_rays, h_pts, h_hits, h_geom, h_occ = (ctx.buf_alloc(x) for x in (32 * n, 16 * m, 16 * k, 4 * k, k))
+    p_rays, p_pts, p_hits, p_geom, p_occ = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in (h_rays, h_pts, h_hits, h_geom, h_occ))
+    ctx.buf_upload(h_pts, pts)
+    cn, cm = C.c_size_t(n), C.c_size_t(m)
+    r = np.zeros((n, 8), np.float32)
+    r[:, 0:3], r[:, 4:7], r[:, 7] = o, d, np.inf
+    ctx.buf_upload(h_rays, r)
+    ctx.check(lib.psm_bvh_intersect_dev(merged._h, p_rays, cn, p_hits), "psm_bvh_intersect_dev")
+    bo, bd = bounce_rays(sc, o, d, ctx.buf_download(h_hits, np.float32, 4 * n).reshape(n, 4))
+    r[:, 0:3], r[:, 3], r[:, 4:7] = bo, 1e-3, bd
+    ctx.buf_upload(h_rays, r)
+    eye = np.concatenate([np.eye(3), np.zeros((3, 1))], axis=1).astype(np.float32)
+
+    def turn(angle, at):      # a rotation about y and a translation
+        c, s_ = np.cos(angle), np.sin(angle)
+        return np.array([[c, 0, s_, at[0]], [0, 1, 0, at[1]], [-s_, 0, c, at[2]]], np.float32)
+
+    def scene_of(kind, ths):
+        g, c = (C.c_void_p * len(ths))(*[t._h for t in ths]), C.c_uint32(len(ths))
+        if kind == "closest":
+            return lambda: ctx.check(lib.psm_scene_intersect_dev(g, c, p_rays, cn, p_hits, p_geom), "psm_scene_intersect_dev")
+        if kind == "point":
+            return lambda: ctx.check(lib.psm_scene_closest_point_dev(g, c, p_pts, cm, p_hits, p_geom), "psm_scene_closest_point_dev")
+        return lambda: ctx.check(lib.psm_scene_inside_dev(g, c, p_pts, cm, C.c_uint32(3), p_occ), "psm_scene_inside_dev")
+
+    def inst_list(ths, poses):
+        v = (psm.Instance * len(ths))()
+        for i, (th, pose) in enumerate(zip(ths, poses)):
+            v[i].bvh = th._h.value
+            v[i].world_from_object[:] = np.asarray(pose, np.float32).reshape(12).tolist()
+        return v
+
+    def inst_of(kind, v):
+        c = C.c_uint32(len(v))
+        if kind == "closest":
+            return lambda: ctx.check(lib.psm_instances_intersect_dev(v, c, p_rays, cn, p_hits, p_geom), "psm_instances_intersect_dev")
+        if kind == "point":
+            return lambda: ctx.check(lib.psm_instances_closest_point_dev(v, c, p_pts, cm, p_hits, p_geom), "psm_instances_closest_point_dev")
+        return lambda: ctx.check(lib.psm_instances_inside_dev(v, c, p_pts, cm, C.c_uint32(3), p_occ), "psm_instances_inside_dev")
+
+    kinds = (("bounce_closest", "closest"), ("points_closest", "point"), ("points_inside3", "inside"))
+    out = {"rays": n, "points": m, "reps": REPS, "tris": int(tris.shape[0])}
+    # (a) identity instances against the scene queries on the same hierarchies: scene, instances, scene again
+    order = np.argsort(t3[:, :, 0].mean(axis=1), kind="stable")
+    slabs = [hier(tris[np.sort(idx)]) for idx in np.array_split(order, 8)]
+    for g, ths in ((1, [merged]), (8, slabs)):
+        for name, kind in kinds:
+            a0 = median_ms(ctx, scene_of(kind, ths))
+            b = median_ms(ctx, inst_of(kind, inst_list(ths, [eye] * g)))
+            a1 = median_ms(ctx, scene_of(kind, ths))
+            out["identity_%s_g%d_scene_ms" % (name, g)] = [round(a0, 4), round(a1, 4)]
+            out["identity_%s_g%d_instances_ms" % (name, g)] = round(b, 4)
+            out["identity_%s_g%d_ratio" % (name, g)] = round(b / (0.5 * (a0 + a1)), 4)
+    # (b) one torus at 2 / 8 / 32 poses, on a lattice across the scene's bounds
+    small = torus(int(os.environ.get("MOVING_NU", "100")), int(os.environ.get("MOVING_NV", "50"))).astype(np.float32)
+    mover = hier(small)
+    out["torus_tris"] = int(small.shape[0])
+    rng = np.random.RandomState(3)
+    for g in (2, 8, 32):
+        poses = [turn(rng.uniform(0, 6.28), lo + (hi - lo) * rng.uniform(0.1, 0.9, 3)) for _ in range(g)]
+        for name, kind in kinds:
+            out["torus_%s_p%d_ms" % (name, g)] = round(median_ms(ctx, inst_of(kind, inst_list([mover] * g, poses))), 4)
+    # (c) the static scene and a torus that moves: a new pose + an instanced query, against a rebuild of the torus + a scene query
+    step = [0]
+    for name, kind in kinds[:2]:
+        q_scene = scene_of(kind, [merged, mover])
+
+        v = inst_list([merged, mover], [eye, eye])
+        q_inst = inst_of(kind, v)
+
+        def frame_instances():     # the new pose written into the host's list (12 floats), then the query
+            step[0] += 1
+            v[1].world_from_object[:] = turn(0.01 * step[0], [0.0, 3.0, 0.0]).reshape(12).tolist()
+            q_inst()
+
+        def frame_rebuild():       # what a moved body costs without poses: its triangles uploaded again, rebuilt, then the query
+            mover.clearTribuffer()
+            mover.loadTriangles(small)
+            mover.build()
+            q_scene()
+
+        a0 = median_ms(ctx, frame_rebuild)
+        b = median_ms(ctx, frame_instances)
+        a1 = median_ms(ctx, frame_rebuild)
+        out["moving_%s_rebuild_small_plus_scene_ms" % name] = [round(a0, 4), round(a1, 4)]
+        out["moving_%s_pose_plus_instances_ms" % name] = round(b, 4)
+        out["moving_%s_ratio" % name] = round(b / (0.5 * (a0 + a1)), 4)
+    out["lib"] = os.path.basename(psm.LIB_PATH)
+    for h in (h_rays, h_pts, h_hits, h_geom, h_occ):
+        ctx.buf_free(h)
+    for th in [merged, mover] + slabs:
+        th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def main():
     sc = scenes.sponza_like()
     ctx = psm.Context(0)
@@ -422,4 +551,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances}.get(" ".join(sys.argv[1:]), main)()
