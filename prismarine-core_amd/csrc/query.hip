@@ -12,6 +12,8 @@
 // Structure as rt_traverse (trace.hip): one ray per lane, one wave64 per workgroup, the stack in LDS laid out [depth][lane],
 // child boxes by fmaf on the fp16 record coordinates (v_fma_mix_f32), nearer child first. The kernels are grid-stride. The walk
 // (query_walk: grid-stride loop, stack, leaf scheduling) is shared by the ray and the point kernels; a body says what a query is.
+// The same seven queries over a list of hierarchies (scene_walk) and over posed instances (4.9) follow. The host
+// side is one path for all 21 entry points: check_list / check_data / batch_args / launch over a per-family kernel table (4.10).
 #include <cmath>
 #include <cstdio>
 #include <mutex>
@@ -136,6 +138,20 @@ PSM_D void slab(const Axis& X, const Axis& Y, const Axis& Z, float mnx, float mn
     tFar = sminf(sminf(smaxf(ax, bx), smaxf(ay, by)), smaxf(az, bz));
 }
 
+// Straight-line pieces the three families' bodies share: only those that leave every kernel's instructions as they were
+// (tools/kernel_diff.py). The transform load, the rays' load and two-slab children and the inside vote move kernels when shared
+// and stay written out at each site.
+
+// point i of a batch; a dead lane gets a point with a negative rmax (InstInsideBody keeps its own copy: DESIGN.md 4.10)
+PSM_D float4 load_point(const float4* points, size_t i, bool alive) {
+    float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
+    if (alive) q = points[i];
+    return q;
+}
+
+// the psm_hit of a query that found nothing
+PSM_D float4 miss_hit() { return make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1)); }
+
 // The walk every query kernel runs: one query per lane, grid-stride over the batch; per query the lone leaf of a one-leaf
 // hierarchy, then the tree from the root. A node's two child boxes are judged by the body (kept or not, and an order key: nearer
 // first), the accepted leaves are tested one after the other (one copy of the leaf code in the loop), and a kept internal child
@@ -256,7 +272,7 @@ struct RayBody {
     PSM_D bool again() const { return false; }
     PSM_D void finish(size_t i) const {
         if (ANY) a.occluded[i] = found ? 1 : 0;
-        else a.hits[i] = found ? make_float4(bu, bv, best, __int_as_float(btri)) : make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1));
+        else a.hits[i] = found ? make_float4(bu, bv, best, __int_as_float(btri)) : miss_hit();
     }
 };
 
@@ -376,6 +392,35 @@ PSM_D PointBound point_bound(const float* M) {
     return b;
 }
 
+// a point in a hierarchy's normalised space: its image under the fit transform and the margin, the largest of the three axes' h
+struct PointImage {
+    float Px, Py, Pz, h;
+
+    PSM_D void set(const float* M, v3 p) {
+        const Row X = affine_row(M, 0, p), Y = affine_row(M, 1, p), Z = affine_row(M, 2, p);
+        Px = X.P;
+        Py = Y.P;
+        Pz = Z.P;
+        h = smaxf(smaxf(X.h, Y.h), Z.h);
+    }
+    // LB^2 of one child box (mn / mx: its fp16 corners)
+    PSM_D float lb2(const PointBound& B, float mnx, float mny, float mnz, float mxx, float mxy, float mxz) const {
+        const float tx = smaxf(smaxf(mnx - Px, Px - mxx) - h, 0.f) * B.il0;
+        const float ty = smaxf(smaxf(mny - Py, Py - mxy) - h, 0.f) * B.il1;
+        const float tz = smaxf(smaxf(mnz - Pz, Pz - mxz) - h, 0.f) * B.il2;
+        const float m = smaxf(smaxf(tx, ty), tz);
+        return (B.orth ? ((tx * tx + ty * ty) + tz * tz) : m * m) * B.wf;
+    }
+    // a node's two child boxes: kept iff LB^2 <= best (<=: a triangle as near as the best and of a lower id still counts); the
+    // order key is LB^2
+    PSM_D void children(const PointBound& B, uint4 n0, uint4 n1, float best, bool& okL, bool& okR, float& kL, float& kR) const {
+        kL = lb2(B, half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z));
+        kR = lb2(B, half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y));
+        okL = kL <= best;
+        okR = kR <= best;
+    }
+};
+
 // the point queries: closest point (WITHIN = false) and within radius (WITHIN = true)
 template <bool WITHIN>
 struct PointBody {
@@ -385,11 +430,10 @@ struct PointBody {
     float rmax, best, bu, bv;   // best: the pruning bound -- the best d2 so far, the rmax bound until one is found
     int btri;
     bool found;
-    float Px, Py, Pz, h;   // p in normalised space; the margin: the largest of the three axes' h
+    PointImage P;
 
     PSM_D bool begin(size_t i, bool alive) {
-        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
-        if (alive) q = a.rays[i];
+        const float4 q = load_point(a.rays, i, alive);
         p = mk3(q.x, q.y, q.z);
         rmax = q.w;
         const bool valid = alive && finite3(p) && rmax >= 0.f;   // NaN or negative rmax: a miss; +inf: no limit
@@ -399,28 +443,13 @@ struct PointBody {
         btri = -1;
         found = false;
         float M[16];
-#pragma unroll
+        #pragma unroll
         for (int k = 0; k < 16; k++) M[k] = u2f(a.sm[SM_M + k]);
-        const Row X = affine_row(M, 0, p), Y = affine_row(M, 1, p), Z = affine_row(M, 2, p);
-        Px = X.P;
-        Py = Y.P;
-        Pz = Z.P;
-        h = smaxf(smaxf(X.h, Y.h), Z.h);
+        P.set(M, p);
         return valid;
     }
-    // LB^2 of one child box (mn / mx: its fp16 corners)
-    PSM_D float lb2(float mnx, float mny, float mnz, float mxx, float mxy, float mxz) const {
-        const float tx = smaxf(smaxf(mnx - Px, Px - mxx) - h, 0.f) * B.il0;
-        const float ty = smaxf(smaxf(mny - Py, Py - mxy) - h, 0.f) * B.il1;
-        const float tz = smaxf(smaxf(mnz - Pz, Pz - mxz) - h, 0.f) * B.il2;
-        const float m = smaxf(smaxf(tx, ty), tz);
-        return (B.orth ? ((tx * tx + ty * ty) + tz * tz) : m * m) * B.wf;
-    }
     PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& kL, float& kR) const {
-        kL = lb2(half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z));
-        kR = lb2(half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y));
-        okL = kL <= best;   // <=: a triangle as near as the best and of a lower id still counts
-        okR = kR <= best;
+        P.children(B, n0, n1, best, okL, okR, kL, kR);
     }
     // a candidate: within rmax, and (closest) nearer than the best so far or as near and of a lower id
     // ((uint32_t) btri: -1 is the largest; before the first, best is the rmax bound, >= every d2 that counts)
@@ -437,7 +466,7 @@ struct PointBody {
     PSM_D bool again() const { return false; }
     PSM_D void finish(size_t i) const {
         if (WITHIN) a.occluded[i] = found ? 1 : 0;
-        else a.hits[i] = found ? make_float4(bu, bv, sqrtf(best), __int_as_float(btri)) : make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1));
+        else a.hits[i] = found ? make_float4(bu, bv, sqrtf(best), __int_as_float(btri)) : miss_hit();
     }
 };
 
@@ -530,8 +559,7 @@ struct InsideBody : CountRay {
         return aim(p, mk3(INSIDE_DIR[r][0], INSIDE_DIR[r][1], INSIDE_DIR[r][2]), 0.f, __builtin_inff());
     }
     PSM_D bool begin(size_t i, bool alive) {
-        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
-        if (alive) q = a.rays[i];
+        const float4 q = load_point(a.rays, i, alive);
         p = mk3(q.x, q.y, q.z);
         k = 0u;
         votes = 0u;
@@ -792,7 +820,7 @@ struct SceneRayBody : SceneRay {
         if (ANY) {
             s.occluded[i] = found ? 1 : 0;
         } else {
-            s.hits[i] = found ? make_float4(b.bu, b.bv, b.best, __int_as_float(b.btri)) : make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1));
+            s.hits[i] = found ? make_float4(b.bu, b.bv, b.best, __int_as_float(b.btri)) : miss_hit();
             s.geom[i] = b.bgeom;
         }
     }
@@ -809,12 +837,11 @@ struct ScenePointBody {
     float rmax;
     SceneBest b;
     bool found;
-    float Px, Py, Pz, h;
+    PointImage P;
 
     PSM_D ScenePointBody(const Args& a) : s(a) {}
     PSM_D bool begin(size_t i, bool alive) {
-        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
-        if (alive) q = s.rays[i];
+        const float4 q = load_point(s.rays, i, alive);
         p = mk3(q.x, q.y, q.z);
         rmax = q.w;
         b.clear((rmax * rmax) * 1.00000095367431640625f + 0x1p-126f);   // (PointBody::begin)
@@ -824,28 +851,15 @@ struct ScenePointBody {
     PSM_D void enter(const SceneGeom& g, int gi) {
         gm = g;
         float M[16];
-#pragma unroll
+        #pragma unroll
         for (int k = 0; k < 16; k++) M[k] = u2f(g.sm[SM_M + k]);
         B = point_bound(M);
-        const Row X = affine_row(M, 0, p), Y = affine_row(M, 1, p), Z = affine_row(M, 2, p);
-        Px = X.P;
-        Py = Y.P;
-        Pz = Z.P;
-        h = smaxf(smaxf(X.h, Y.h), Z.h);
+        P.set(M, p);
         b.enter_geom(gi);
     }
-    PSM_D float lb2(float mnx, float mny, float mnz, float mxx, float mxy, float mxz) const {
-        const float tx = smaxf(smaxf(mnx - Px, Px - mxx) - h, 0.f) * B.il0;
-        const float ty = smaxf(smaxf(mny - Py, Py - mxy) - h, 0.f) * B.il1;
-        const float tz = smaxf(smaxf(mnz - Pz, Pz - mxz) - h, 0.f) * B.il2;
-        const float m = smaxf(smaxf(tx, ty), tz);
-        return (B.orth ? ((tx * tx + ty * ty) + tz * tz) : m * m) * B.wf;
-    }
     PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& kL, float& kR) const {
-        kL = lb2(half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z));
-        kR = lb2(half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y));
-        okL = kL <= b.best;   // (<=: see SceneBest; LB^2 is a world distance, comparable across the geometries' transforms)
-        okR = kR <= b.best;
+        // (<=: see SceneBest; LB^2 is a world distance, comparable across the geometries' transforms)
+        P.children(B, n0, n1, b.best, okL, okR, kL, kR);
     }
     PSM_D void leaf(int tri) {
         const float4 A = gm.tri48[(size_t)3 * tri + 0], Bv = gm.tri48[(size_t)3 * tri + 1], Cv = gm.tri48[(size_t)3 * tri + 2];
@@ -862,7 +876,7 @@ struct ScenePointBody {
         if (WITHIN) {
             s.occluded[i] = found ? 1 : 0;
         } else {
-            s.hits[i] = found ? make_float4(b.bu, b.bv, sqrtf(b.best), __int_as_float(b.btri)) : make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1));
+            s.hits[i] = found ? make_float4(b.bu, b.bv, sqrtf(b.best), __int_as_float(b.btri)) : miss_hit();
             s.geom[i] = b.bgeom;
         }
     }
@@ -909,8 +923,7 @@ struct SceneInsideBody : SceneCountRay {
         return aim(p, mk3(INSIDE_DIR[r][0], INSIDE_DIR[r][1], INSIDE_DIR[r][2]), 0.f, __builtin_inff());
     }
     PSM_D bool begin(size_t i, bool alive) {
-        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
-        if (alive) q = s.rays[i];
+        const float4 q = load_point(s.rays, i, alive);
         p = mk3(q.x, q.y, q.z);
         k = 0u;
         votes = 0u;
@@ -1057,16 +1070,14 @@ struct InstPointBody : ScenePointBody<WITHIN, InstArgs> {
     PSM_D bool begin(size_t i, bool al) {
         idx = i;
         alive = al;
-        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
-        if (al) q = this->s.rays[i];
+        const float4 q = load_point(this->s.rays, i, al);
         this->rmax = q.w;
         this->b.clear((q.w * q.w) * 1.00000095367431640625f + 0x1p-126f);   // (PointBody::begin)
         this->found = false;
         return al && finite3(mk3(q.x, q.y, q.z)) && q.w >= 0.f;   // (a non-finite world point is non-finite in every instance)
     }
     PSM_D bool enter(const InstGeom& g, int gi) {
-        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
-        if (alive) q = this->s.rays[idx];
+        const float4 q = load_point(this->s.rays, idx, alive);
         this->p = inst_point(g.m, mk3(q.x, q.y, q.z));
         ScenePointBody<WITHIN, InstArgs>::enter(g, gi);
         return finite3(this->p);
@@ -1153,8 +1164,8 @@ int ceil_log2(size_t n) {
 }
 
 enum QueryKind { Q_CLOSEST, Q_ANY, Q_POINT, Q_WITHIN, Q_COUNT, Q_INSIDE, Q_SIGNED };
-// per kind: the entry point, what the input and the output are called in its messages (out: NULL when its alignment is not
-// checked: a byte per query), the output's alignment, the family in the state / capacity texts
+// per kind: the single-hierarchy entry point, what the input and the output are called in its messages (out: NULL when its
+// alignment is not checked: a byte per query), the output's alignment, the family in the state / capacity texts
 struct QueryDesc {
     const char* name;
     const char* in;
@@ -1169,78 +1180,47 @@ const QueryDesc QUERY_DESC[] = {{"psm_bvh_intersect_dev", "rays", "hits", 16, fa
                                 {"psm_bvh_count_hits_dev", "rays", "counts", 4, false},
                                 {"psm_bvh_inside_dev", "points", nullptr, 1, true},
                                 {"psm_bvh_signed_distance_dev", "points", "hits", 16, true}};
+const char* const SCENE_NAME[] = {"psm_scene_intersect_dev", "psm_scene_occluded_dev", "psm_scene_closest_point_dev",
+                                  "psm_scene_within_dev", "psm_scene_count_hits_dev", "psm_scene_inside_dev",
+                                  "psm_scene_signed_distance_dev"};
+const char* const INST_NAME[] = {"psm_instances_intersect_dev", "psm_instances_occluded_dev", "psm_instances_closest_point_dev",
+                                 "psm_instances_within_dev", "psm_instances_count_hits_dev", "psm_instances_inside_dev",
+                                 "psm_instances_signed_distance_dev"};
 
-// the checks and the launch every query shares: in / out must be non-NULL, in 16-byte aligned, out as its kind asks (a psm_hit
-// 16 bytes, a count 4); samples (the inside kinds only): 1, 3 or 5
-int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, void* d_out, uint32_t samples = 0) {
-    if (!b) return PSM_ERR_INVALID;
-    if (n == 0) return PSM_OK;
-    psm_ctx* c = b->ctx;
-    const QueryDesc& k = QUERY_DESC[kind];
-    char msg[96];
-    if (!d_in || !d_out) {
-        snprintf(msg, sizeof msg, "%s: NULL pointer", k.name);
-        return set_err(c, PSM_ERR_INVALID, msg);
+// a family's seven kernels by QueryKind (Q_SIGNED: the sign kernel)
+template <class Args>
+struct Kernels {
+    void (*k[7])(Args);
+};
+const Kernels<QueryArgs> BVH_KERNELS = {{bvh_query_closest, bvh_query_any, bvh_query_point, bvh_query_within, bvh_query_count,
+                                         bvh_query_inside, bvh_query_sign}};
+const Kernels<SceneArgs> SCENE_KERNELS = {{scene_query_closest, scene_query_any, scene_query_point, scene_query_within,
+                                           scene_query_count, scene_query_inside, scene_query_sign}};
+const Kernels<InstArgs> INST_KERNELS = {{inst_query_closest, inst_query_any, inst_query_point, inst_query_within, inst_query_count,
+                                         inst_query_inside, inst_query_sign}};
+
+// The launch of every query. Q_SIGNED is two launches: the family's unchanged closest-point kernel, then the sign of what it
+// found (the same stream: in order)
+template <class Args>
+int launch(psm_ctx* c, const Kernels<Args>& kernels, QueryKind kind, uint32_t grid, const Args& a) {
+    if (kind == Q_SIGNED) {
+        kernels.k[Q_POINT]<<<grid, QUERY_BLOCK, 0, c->stream>>>(a);
+        PSM_HIP(c, hipGetLastError());
     }
-    const bool in_bad = ((uintptr_t)d_in & 15u) != 0, out_bad = ((uintptr_t)d_out & (uintptr_t)(k.out_align - 1)) != 0;
-    if (in_bad || out_bad) {
-        if (k.out_align == 16) snprintf(msg, sizeof msg, "%s: %s or %s not 16-byte aligned", k.name, k.in, k.out);
-        else if (in_bad) snprintf(msg, sizeof msg, "%s: %s not 16-byte aligned", k.name, k.in);
-        else snprintf(msg, sizeof msg, "%s: %s not %u-byte aligned", k.name, k.out, k.out_align);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if ((kind == Q_INSIDE || kind == Q_SIGNED) && samples != 1 && samples != 3 && samples != 5) {
-        snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", k.name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    (void)hipSetDevice(c->device);
-    if (!b->built) return set_err(c, PSM_ERR_STATE, k.points ? "point query before build" : "ray query before build");
-    if (63 + ceil_log2(b->cap) > QSTACK_MAX)
-        return set_err(c, PSM_ERR_CAPACITY, k.points ? "point query: hierarchy deeper than the query stack"
-                                                     : "ray query: hierarchy deeper than the query stack");
-    void* spill = nullptr;
-    const int rc = spill_for(c, &spill);   // (a context's first query allocates: a later one can be captured into a graph)
-    if (rc != PSM_OK) return rc;
-    const size_t waves = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;
-    const uint32_t grid = (uint32_t)(waves < QUERY_GRID_CAP ? waves : QUERY_GRID_CAP);
-    QueryArgs qa = {};
-    qa.rays = (const float4*)d_in; qa.n = n;
-    qa.node32 = b->d_node32; qa.tri48 = b->d_tri48; qa.sm = b->d_small; qa.sorted_tri = b->d_sorted_tri;
-    qa.spill = (int*)spill;
-    qa.hits = (float4*)d_out; qa.occluded = (uint8_t*)d_out; qa.count = (uint32_t*)d_out;   // (a kernel reads its own)
-    qa.samples = samples;
-    switch (kind) {
-        case Q_CLOSEST: bvh_query_closest<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
-        case Q_ANY: bvh_query_any<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
-        case Q_POINT: bvh_query_point<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
-        case Q_WITHIN: bvh_query_within<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
-        case Q_COUNT: bvh_query_count<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
-        case Q_INSIDE: bvh_query_inside<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa); break;
-        case Q_SIGNED:   // the unchanged closest-point kernel, then the sign of what it found (the same stream: in order)
-            bvh_query_point<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa);
-            PSM_HIP(c, hipGetLastError());
-            bvh_query_sign<<<grid, QUERY_BLOCK, 0, c->stream>>>(qa);
-            break;
-    }
+    kernels.k[kind]<<<grid, QUERY_BLOCK, 0, c->stream>>>(a);
     PSM_HIP(c, hipGetLastError());
     return PSM_OK;
 }
 
-
-// ---- the scene entry points' checks and launch ---------------------------------------------------------------------------
-const char* const SCENE_NAME[] = {"psm_scene_intersect_dev", "psm_scene_occluded_dev", "psm_scene_closest_point_dev",
-                                  "psm_scene_within_dev", "psm_scene_count_hits_dev", "psm_scene_inside_dev",
-                                  "psm_scene_signed_distance_dev"};
-
-// What scene_query and inst_query do once their list has passed and n > 0: the data pointers (d_geom, called `index` in the
-// messages: the kinds with a psm_hit output only), their alignment and samples; then the context's stack area and the grid, and
-// the scalars of the argument struct (SceneArgs or InstArgs)
-template <class Args>
-int scene_data(psm_ctx* c, const char* name, const char* index, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_geom,
-               uint32_t samples, Args& sa, uint32_t& grid) {
+// The data checks every query shares, under the entry point's name: in / out must be non-NULL, in 16-byte aligned, out as its
+// kind asks (a psm_hit 16 bytes, a count 4); samples (the inside kinds only): 1, 3 or 5. index: what the per-query index array
+// (d_geom: the kinds with a psm_hit output only) is called in the messages, NULL for a query that has none. A batch that passes
+// makes the context's device the current one.
+int check_data(psm_ctx* c, const char* name, const char* index, QueryKind kind, const void* d_in, const void* d_out, const int32_t* d_geom,
+               uint32_t samples) {
     const QueryDesc& k = QUERY_DESC[kind];
     char msg[128];
-    const bool with_geom = k.out_align == 16;
+    const bool with_geom = index && k.out_align == 16;
     if (!d_in || !d_out || (with_geom && !d_geom)) {
         snprintf(msg, sizeof msg, "%s: NULL pointer", name);
         return set_err(c, PSM_ERR_INVALID, msg);
@@ -1261,83 +1241,46 @@ int scene_data(psm_ctx* c, const char* name, const char* index, QueryKind kind, 
         return set_err(c, PSM_ERR_INVALID, msg);
     }
     (void)hipSetDevice(c->device);
+    return PSM_OK;
+}
+
+// The context's stack area (a context's first query allocates: a later one can be captured into a graph), the grid, and the
+// scalars QueryArgs, SceneArgs and InstArgs share
+template <class Args>
+int batch_args(psm_ctx* c, const void* d_in, size_t n, void* d_out, uint32_t samples, Args& a, uint32_t& grid) {
     void* spill = nullptr;
     const int rc = spill_for(c, &spill);
     if (rc != PSM_OK) return rc;
     const size_t waves = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;
     grid = (uint32_t)(waves < QUERY_GRID_CAP ? waves : QUERY_GRID_CAP);
-    sa.rays = (const float4*)d_in; sa.n = n;
-    sa.spill = (int*)spill;
-    sa.hits = (float4*)d_out; sa.occluded = (uint8_t*)d_out; sa.count = (uint32_t*)d_out;
-    sa.geom = d_geom;
-    sa.samples = samples;
+    a.rays = (const float4*)d_in; a.n = n;
+    a.spill = (int*)spill;
+    a.hits = (float4*)d_out; a.occluded = (uint8_t*)d_out; a.count = (uint32_t*)d_out;   // (a kernel reads its own)
+    a.samples = samples;
     return PSM_OK;
 }
 
-// query() for a scene. The list is checked first and whole, also for n == 0: its length, then every entry (NULL, another
-// context than entry 0's, not built, too deep for the stack), the message naming the first failing index. The message goes to
-// the context of the first non-NULL entry (a list of NULLs only has no context to tell: the return code alone). d_geom: the
-// kinds with a psm_hit output only.
-int scene_query(psm_bvh* const* geoms, uint32_t count, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_geom,
-                uint32_t samples = 0) {
-    if (!geoms || count == 0 || count > PSM_SCENE_MAX_GEOMETRIES) return PSM_ERR_INVALID;
-    const char* name = SCENE_NAME[kind];
-    psm_ctx* c = nullptr;
-    for (uint32_t g = 0; g < count && !c; g++)
-        if (geoms[g]) c = geoms[g]->ctx;
-    if (!c) return PSM_ERR_INVALID;
-    char msg[128];
-    for (uint32_t g = 0; g < count; g++) {
-        if (!geoms[g]) {
-            snprintf(msg, sizeof msg, "%s: geometry %u is NULL", name, g);
-            return set_err(c, PSM_ERR_INVALID, msg);
-        }
-        if (geoms[g]->ctx != c) {
-            snprintf(msg, sizeof msg, "%s: geometry %u belongs to another context", name, g);
-            return set_err(c, PSM_ERR_INVALID, msg);
-        }
-    }
-    for (uint32_t g = 0; g < count; g++) {
-        if (!geoms[g]->built) {
-            snprintf(msg, sizeof msg, "%s: geometry %u is not built", name, g);
-            return set_err(c, PSM_ERR_STATE, msg);
-        }
-        if (63 + ceil_log2(geoms[g]->cap) > QSTACK_MAX) {
-            snprintf(msg, sizeof msg, "%s: geometry %u is deeper than the query stack", name, g);
-            return set_err(c, PSM_ERR_CAPACITY, msg);
-        }
-    }
+bool too_deep(const psm_bvh* b) { return 63 + ceil_log2(b->cap) > QSTACK_MAX; }
+
+// A query of one hierarchy: n == 0 is answered before anything else is looked at; then the data, the state, the depth.
+int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, void* d_out, uint32_t samples = 0) {
+    if (!b) return PSM_ERR_INVALID;
     if (n == 0) return PSM_OK;
-    SceneArgs sa = {};
-    uint32_t grid = 0;
-    const int rc = scene_data(c, name, "geom", kind, d_in, n, d_out, d_geom, samples, sa, grid);
+    psm_ctx* c = b->ctx;
+    const bool points = QUERY_DESC[kind].points;
+    int rc = check_data(c, QUERY_DESC[kind].name, nullptr, kind, d_in, d_out, nullptr, samples);
     if (rc != PSM_OK) return rc;
-    sa.geoms = count;
-    for (uint32_t g = 0; g < count; g++) {
-        const psm_bvh* b = geoms[g];
-        sa.g[g] = SceneGeom{b->d_node32, b->d_tri48, b->d_small, b->d_sorted_tri};
-    }
-    switch (kind) {
-        case Q_CLOSEST: scene_query_closest<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa); break;
-        case Q_ANY: scene_query_any<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa); break;
-        case Q_POINT: scene_query_point<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa); break;
-        case Q_WITHIN: scene_query_within<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa); break;
-        case Q_COUNT: scene_query_count<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa); break;
-        case Q_INSIDE: scene_query_inside<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa); break;
-        case Q_SIGNED:   // the scene's closest point, then the scene's sign of what it found (the same stream: in order)
-            scene_query_point<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa);
-            PSM_HIP(c, hipGetLastError());
-            scene_query_sign<<<grid, QUERY_BLOCK, 0, c->stream>>>(sa);
-            break;
-    }
-    PSM_HIP(c, hipGetLastError());
-    return PSM_OK;
+    if (!b->built) return set_err(c, PSM_ERR_STATE, points ? "point query before build" : "ray query before build");
+    if (too_deep(b))
+        return set_err(c, PSM_ERR_CAPACITY, points ? "point query: hierarchy deeper than the query stack"
+                                                   : "ray query: hierarchy deeper than the query stack");
+    QueryArgs qa = {};
+    uint32_t grid = 0;
+    rc = batch_args(c, d_in, n, d_out, samples, qa, grid);
+    if (rc != PSM_OK) return rc;
+    qa.node32 = b->d_node32; qa.tri48 = b->d_tri48; qa.sm = b->d_small; qa.sorted_tri = b->d_sorted_tri;
+    return launch(c, BVH_KERNELS, kind, grid, qa);
 }
-
-// ---- the instanced entry points' checks and launch -------------------------------------------------------------------------
-const char* const INST_NAME[] = {"psm_instances_intersect_dev", "psm_instances_occluded_dev", "psm_instances_closest_point_dev",
-                                 "psm_instances_within_dev", "psm_instances_count_hits_dev", "psm_instances_inside_dev",
-                                 "psm_instances_signed_distance_dev"};
 
 // Why a pose is refused, or NULL (psm_hip.h): in double, on the host. A rigid motion or a reflection has R^T R = 1; the bound
 // leaves room for a matrix that was composed in float32 and refuses every scale or shear a user could mean.
@@ -1353,68 +1296,95 @@ const char* pose_fault(const float* m) {
     return nullptr;
 }
 
-// scene_query() for instances: the same order of checks, with the poses judged between the entries' handles and their state --
-// all of it on the host, before any device is touched
-int inst_query(const psm_instance* insts, uint32_t count, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_inst,
-               uint32_t samples = 0) {
-    if (!insts || count == 0 || count > PSM_SCENE_MAX_GEOMETRIES) return PSM_ERR_INVALID;
-    const char* name = INST_NAME[kind];
+// An entry of a list as the list queries read it: a scene's psm_bvh*, or a psm_instance (a hierarchy and its pose). noun: what
+// the messages call it; fault: why the entry itself is refused, or NULL; fill: its row of the kernel-argument table.
+struct SceneEntry {
+    using Args = SceneArgs;
+    static constexpr const char* noun = "geometry";
+    static psm_bvh* bvh(psm_bvh* e) { return e; }
+    static const char* fault(psm_bvh*) { return nullptr; }
+    static void fill(SceneGeom& t, psm_bvh* b) { t = SceneGeom{b->d_node32, b->d_tri48, b->d_small, b->d_sorted_tri}; }
+};
+struct InstEntry {
+    using Args = InstArgs;
+    static constexpr const char* noun = "instance";
+    static psm_bvh* bvh(const psm_instance& e) { return e.bvh; }
+    static const char* fault(const psm_instance& e) { return pose_fault(e.world_from_object); }
+    static void fill(InstGeom& t, const psm_instance& e) {
+        SceneEntry::fill(t, e.bvh);
+        for (int k = 0; k < 12; k++) t.m[k] = e.world_from_object[k];
+    }
+};
+
+// The list of a scene or an instanced query, checked first and whole, also for n == 0, all of it on the host before any device
+// is touched: its length; then every entry's handle (NULL, another context than the first non-NULL entry's), every entry's own
+// fault (the poses), every entry's state (not built, too deep for the stack) -- the message naming the first failing index. The
+// message goes to the context of the first non-NULL entry, *ctx (a list of NULLs only has no context to tell: the return code alone).
+template <class E, class Entry>
+int check_list(const Entry* list, uint32_t count, const char* name, psm_ctx** ctx) {
+    if (!list || count == 0 || count > PSM_SCENE_MAX_GEOMETRIES) return PSM_ERR_INVALID;
     psm_ctx* c = nullptr;
     for (uint32_t g = 0; g < count && !c; g++)
-        if (insts[g].bvh) c = insts[g].bvh->ctx;
+        if (E::bvh(list[g])) c = E::bvh(list[g])->ctx;
     if (!c) return PSM_ERR_INVALID;
+    *ctx = c;
     char msg[160];
     for (uint32_t g = 0; g < count; g++) {
-        if (!insts[g].bvh) {
-            snprintf(msg, sizeof msg, "%s: instance %u is NULL", name, g);
+        if (!E::bvh(list[g])) {
+            snprintf(msg, sizeof msg, "%s: %s %u is NULL", name, E::noun, g);
             return set_err(c, PSM_ERR_INVALID, msg);
         }
-        if (insts[g].bvh->ctx != c) {
-            snprintf(msg, sizeof msg, "%s: instance %u belongs to another context", name, g);
+        if (E::bvh(list[g])->ctx != c) {
+            snprintf(msg, sizeof msg, "%s: %s %u belongs to another context", name, E::noun, g);
             return set_err(c, PSM_ERR_INVALID, msg);
         }
     }
     for (uint32_t g = 0; g < count; g++)
-        if (const char* why = pose_fault(insts[g].world_from_object)) {
-            snprintf(msg, sizeof msg, "%s: instance %u %s", name, g, why);
+        if (const char* why = E::fault(list[g])) {
+            snprintf(msg, sizeof msg, "%s: %s %u %s", name, E::noun, g, why);
             return set_err(c, PSM_ERR_INVALID, msg);
         }
     for (uint32_t g = 0; g < count; g++) {
-        if (!insts[g].bvh->built) {
-            snprintf(msg, sizeof msg, "%s: instance %u is not built", name, g);
+        if (!E::bvh(list[g])->built) {
+            snprintf(msg, sizeof msg, "%s: %s %u is not built", name, E::noun, g);
             return set_err(c, PSM_ERR_STATE, msg);
         }
-        if (63 + ceil_log2(insts[g].bvh->cap) > QSTACK_MAX) {
-            snprintf(msg, sizeof msg, "%s: instance %u is deeper than the query stack", name, g);
+        if (too_deep(E::bvh(list[g]))) {
+            snprintf(msg, sizeof msg, "%s: %s %u is deeper than the query stack", name, E::noun, g);
             return set_err(c, PSM_ERR_CAPACITY, msg);
         }
     }
-    if (n == 0) return PSM_OK;
-    InstArgs ia = {};
-    uint32_t grid = 0;
-    const int rc = scene_data(c, name, "inst", kind, d_in, n, d_out, d_inst, samples, ia, grid);
-    if (rc != PSM_OK) return rc;
-    ia.geoms = count;
-    for (uint32_t g = 0; g < count; g++) {
-        const psm_bvh* b = insts[g].bvh;
-        ia.g[g].node32 = b->d_node32; ia.g[g].tri48 = b->d_tri48; ia.g[g].sm = b->d_small; ia.g[g].sorted_tri = b->d_sorted_tri;
-        for (int k = 0; k < 12; k++) ia.g[g].m[k] = insts[g].world_from_object[k];
-    }
-    switch (kind) {
-        case Q_CLOSEST: inst_query_closest<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia); break;
-        case Q_ANY: inst_query_any<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia); break;
-        case Q_POINT: inst_query_point<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia); break;
-        case Q_WITHIN: inst_query_within<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia); break;
-        case Q_COUNT: inst_query_count<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia); break;
-        case Q_INSIDE: inst_query_inside<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia); break;
-        case Q_SIGNED:   // the closest point over the instances, then the sign of what it found (the same stream: in order)
-            inst_query_point<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia);
-            PSM_HIP(c, hipGetLastError());
-            inst_query_sign<<<grid, QUERY_BLOCK, 0, c->stream>>>(ia);
-            break;
-    }
-    PSM_HIP(c, hipGetLastError());
     return PSM_OK;
+}
+
+// A query of a list (E: SceneEntry or InstEntry): the list, n == 0, the data, the table, the launch. index: what d_geom is
+// called in the messages ("geom" / "inst").
+template <class E, class Entry>
+int list_query(const Entry* list, uint32_t count, const char* name, const char* index, const Kernels<typename E::Args>& kernels,
+               QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_geom, uint32_t samples) {
+    psm_ctx* c = nullptr;
+    int rc = check_list<E>(list, count, name, &c);
+    if (rc != PSM_OK || n == 0) return rc;
+    rc = check_data(c, name, index, kind, d_in, d_out, d_geom, samples);
+    if (rc != PSM_OK) return rc;
+    typename E::Args a = {};
+    uint32_t grid = 0;
+    rc = batch_args(c, d_in, n, d_out, samples, a, grid);
+    if (rc != PSM_OK) return rc;
+    a.geom = d_geom;
+    a.geoms = count;
+    for (uint32_t g = 0; g < count; g++) E::fill(a.g[g], list[g]);
+    return launch(c, kernels, kind, grid, a);
+}
+
+int scene_query(psm_bvh* const* geoms, uint32_t count, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_geom,
+                uint32_t samples = 0) {
+    return list_query<SceneEntry>(geoms, count, SCENE_NAME[kind], "geom", SCENE_KERNELS, kind, d_in, n, d_out, d_geom, samples);
+}
+
+int inst_query(const psm_instance* insts, uint32_t count, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_inst,
+               uint32_t samples = 0) {
+    return list_query<InstEntry>(insts, count, INST_NAME[kind], "inst", INST_KERNELS, kind, d_in, n, d_out, d_inst, samples);
 }
 
 }  // namespace

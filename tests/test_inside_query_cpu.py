@@ -14,6 +14,7 @@ import pytest
 import inside_query_model as IQ
 import point_query_model as PQ
 import query_model as Q
+from util import QUERY_VGPRS, check_query_kernels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -173,34 +174,9 @@ def test_inside_queries_reject_null_without_device(psm):
         assert fn(None, None, none, ctypes.c_uint32(3), None) == -1
 
 
-# every new kernel within the budget of 8 waves per SIMD (64 VGPRs), nothing spilled; the four existing kernels at their pins
-# (tests/test_query_cpu.py, tests/test_point_query_cpu.py)
-QUERY_VGPRS = {"_ZN3psm15bvh_query_countENS_9QueryArgsE": 64, "_ZN3psm16bvh_query_insideENS_9QueryArgsE": 64,
-               "_ZN3psm14bvh_query_signENS_9QueryArgsE": 64,
-               "_ZN3psm17bvh_query_closestENS_9QueryArgsE": 55, "_ZN3psm13bvh_query_anyENS_9QueryArgsE": 52,
-               "_ZN3psm15bvh_query_pointENS_9QueryArgsE": 59, "_ZN3psm16bvh_query_withinENS_9QueryArgsE": 56}
-
-
-def test_inside_query_kernels_codegen(tmp_path):
-    flags = open(os.path.join(ROOT, "prismarine-core_amd", "csrc", "Makefile")).read()
-    cxx = re.search(r"^CXXFLAGS := (.*)$", flags, re.M).group(1).replace("$(ARCH)", "gfx950").split()
-    out = str(tmp_path / "query.s")
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + [f for f in cxx if not f.startswith("-W")] +
-                          ["-S", "--cuda-device-only", "-o", out, os.path.join(ROOT, "prismarine-core_amd", "csrc", "query.hip")],
-                          stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    for kern, vgprs in QUERY_VGPRS.items():
-        blk = asm[asm.index(".name:           " + kern):]
-        blk = blk[:blk.index(".wavefront_size")]
-        assert int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)) <= vgprs, kern
-        assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)) == 0, kern
-        assert int(re.search(r"\.sgpr_spill_count:\s+(\d+)", blk).group(1)) == 0, kern
-        assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)) == 0, kern
-        body = asm[asm.index(kern + ":"):]
-        body = body[:body.index(".Lfunc_end")]
-        assert "scratch_" not in body, kern
-        if "count" in kern or "inside" in kern or "sign" in kern:
-            assert "v_fma_mix_f32" in body, kern      # the slab planes straight from the fp16 record coordinates, as the ray kernels
+def test_inside_query_kernels_codegen():
+    """the count, inside and sign kernels, and the four earlier kernels still at their ceilings"""
+    check_query_kernels(k for k in QUERY_VGPRS if k.startswith("bvh_"))
 
 
 def test_inside_query_header_layer_compiles_and_links(tmp_path):

@@ -15,8 +15,7 @@ import instance_query_model as NQ
 import point_query_model as PQ
 import query_model as Q
 import scene_query_model as SQ
-from test_inside_query_cpu import QUERY_VGPRS
-from test_scene_query_cpu import SCENE_KERNELS
+from util import QUERY_VGPRS, check_query_kernels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -261,44 +260,11 @@ def test_instanced_queries_refuse_bad_lists_without_a_device(psm):
                         assert fn(lst, u32(count), d_in, n, d_out) == -1
 
 
-# the register ceilings of the seven instanced kernels: what the Makefile's flags give, all within the 64 of
-# __launch_bounds__(64, 8); InstArgs: their one parameter
-# the scene kernels' recorded counts, closest / any / point / within / count / inside / sign: sharing the walk with
-# the instanced kernels must not move them
-SCENE_VGPRS = (57, 52, 62, 56, 51, 50, 51)
-INST_VGPRS = {"_ZN3psm%d%sENS_8InstArgsE" % (len(k), k): v for k, v in (
-    ("inst_query_closest", 59), ("inst_query_any", 54), ("inst_query_point", 63), ("inst_query_within", 58), ("inst_query_count", 53),
-    ("inst_query_inside", 53), ("inst_query_sign", 54))}
-
-
-def test_instanced_query_kernels_codegen(tmp_path):
-    flags = open(os.path.join(ROOT, "prismarine-core_amd", "csrc", "Makefile")).read()
-    cxx = re.search(r"^CXXFLAGS := (.*)$", flags, re.M).group(1).replace("$(ARCH)", "gfx950").split()
-    out = str(tmp_path / "query.s")
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + [f for f in cxx if not f.startswith("-W")] +
-                          ["-S", "--cuda-device-only", "-o", out, os.path.join(ROOT, "prismarine-core_amd", "csrc", "query.hip")],
-                          stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    limits = dict(QUERY_VGPRS)                    # the fourteen existing kernels: still within their ceilings
-    limits.update(dict(zip(SCENE_KERNELS, SCENE_VGPRS)))
-    limits.update(INST_VGPRS)
-    assert len(limits) == 21 and max(INST_VGPRS.values()) <= 64
-    for kern, vgprs in limits.items():
-        blk = asm[asm.index(".name:           " + kern):]
-        blk = blk[:blk.index(".wavefront_size")]
-        assert int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)) <= vgprs, kern
-        assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)) == 0, kern
-        assert int(re.search(r"\.sgpr_spill_count:\s+(\d+)", blk).group(1)) == 0, kern
-        assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)) == 0, kern
-        body = asm[asm.index(kern + ":"):]
-        body = body[:body.index(".Lfunc_end")]
-        assert "scratch_" not in body, kern
-        if kern in INST_VGPRS:
-            # the table of instances (32 x (32 + 48) B) travels in the kernel arguments, which hold 4 KB at most
-            karg = int(re.findall(r"\.kernarg_segment_size:\s+(\d+)", asm[:asm.index(".name:           " + kern)])[-1])
-            assert 2560 <= karg <= 4096, (kern, karg)
-            if "point" not in kern and "within" not in kern:
-                assert "v_fma_mix_f32" in body, kern
+def test_instanced_query_kernels_codegen():
+    """the seven instanced kernels, and the fourteen existing kernels still at their ceilings: sharing the walk with the
+    instanced kernels must not move the scene kernels"""
+    assert len(QUERY_VGPRS) == 21
+    check_query_kernels(QUERY_VGPRS)
 
 
 def test_instanced_query_header_layer_compiles_and_links(tmp_path):

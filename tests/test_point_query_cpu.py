@@ -3,7 +3,6 @@ tests hold the kernels to (tests/point_query_model.py) against a float64 second 
 degenerate triangles, the library's new exports, the kernels' code generation and the header layer."""
 import ctypes
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -11,6 +10,7 @@ import pytest
 
 import point_query_model as PQ
 import query_model as Q
+from util import check_query_kernels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -254,29 +254,9 @@ def test_point_queries_reject_null_without_device(psm):
         assert fn(None, None, ctypes.c_size_t(0), None) == -1
 
 
-# VGPRs the kernels reach (hipcc, Makefile flags): 64 is the budget of 8 waves per SIMD; the ray kernels keep theirs
-QUERY_VGPRS = {"_ZN3psm15bvh_query_pointENS_9QueryArgsE": 64, "_ZN3psm16bvh_query_withinENS_9QueryArgsE": 64,
-               "_ZN3psm17bvh_query_closestENS_9QueryArgsE": 55, "_ZN3psm13bvh_query_anyENS_9QueryArgsE": 52}
-
-
-def test_point_query_kernels_codegen(tmp_path):
-    flags = open(os.path.join(ROOT, "prismarine-core_amd", "csrc", "Makefile")).read()
-    cxx = re.search(r"^CXXFLAGS := (.*)$", flags, re.M).group(1).replace("$(ARCH)", "gfx950").split()
-    out = str(tmp_path / "query.s")
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + [f for f in cxx if not f.startswith("-W")] +
-                          ["-S", "--cuda-device-only", "-o", out, os.path.join(ROOT, "prismarine-core_amd", "csrc", "query.hip")],
-                          stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    for kern, vgprs in QUERY_VGPRS.items():
-        blk = asm[asm.index(".name:           " + kern):]
-        blk = blk[:blk.index(".wavefront_size")]
-        assert int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)) <= vgprs, kern
-        assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)) == 0, kern
-        assert int(re.search(r"\.sgpr_spill_count:\s+(\d+)", blk).group(1)) == 0, kern
-        assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)) == 0, kern
-        body = asm[asm.index(kern + ":"):]
-        body = body[:body.index(".Lfunc_end")]
-        assert "scratch_" not in body, kern
+def test_point_query_kernels_codegen():
+    """the two point kernels, and the ray kernels still at their ceilings"""
+    check_query_kernels(["bvh_query_point", "bvh_query_within", "bvh_query_closest", "bvh_query_any"])
 
 
 def test_point_query_header_layer_compiles_and_links(tmp_path):

@@ -3,14 +3,13 @@ tests hold the kernels to (tests/query_model.py) against the oracle's brute forc
 answer, the library's new exports, the kernels' code generation and the header layer."""
 import ctypes
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
 import query_model as Q
-from util import bits
+from util import bits, check_query_kernels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -136,30 +135,8 @@ def test_queries_reject_null_without_device(psm):
         assert fn(None, None, ctypes.c_size_t(0), None) == -1
 
 
-# VGPRs the two kernels reach (hipcc, Makefile flags): 64 is the budget of 8 waves per SIMD
-QUERY_VGPRS = {"_ZN3psm17bvh_query_closestENS_9QueryArgsE": 55, "_ZN3psm13bvh_query_anyENS_9QueryArgsE": 52}
-
-
-def test_query_kernels_codegen(tmp_path):
-    flags = open(os.path.join(ROOT, "prismarine-core_amd", "csrc", "Makefile")).read()
-    cxx = re.search(r"^CXXFLAGS := (.*)$", flags, re.M).group(1).replace("$(ARCH)", "gfx950").split()
-    assert "query.hip" in re.search(r"^SRC := (.*)$", flags, re.M).group(1).split()
-    out = str(tmp_path / "query.s")
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + [f for f in cxx if not f.startswith("-W")] +
-                          ["-S", "--cuda-device-only", "-o", out, os.path.join(ROOT, "prismarine-core_amd", "csrc", "query.hip")],
-                          stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    for kern, vgprs in QUERY_VGPRS.items():
-        blk = asm[asm.index(".name:           " + kern):]
-        blk = blk[:blk.index(".wavefront_size")]
-        assert int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)) <= vgprs, kern
-        assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)) == 0, kern
-        assert int(re.search(r"\.sgpr_spill_count:\s+(\d+)", blk).group(1)) == 0, kern
-        assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)) == 0, kern
-        body = asm[asm.index(kern + ":"):]
-        body = body[:body.index(".Lfunc_end")]
-        assert "v_fma_mix_f32" in body, kern          # the slab planes straight from the fp16 record coordinates
-        assert "scratch_" not in body, kern
+def test_query_kernels_codegen():
+    check_query_kernels(["bvh_query_closest", "bvh_query_any"])
 
 
 def test_query_header_layer_compiles_and_links(tmp_path):

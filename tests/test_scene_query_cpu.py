@@ -14,7 +14,7 @@ import inside_query_model as IQ
 import point_query_model as PQ
 import query_model as Q
 import scene_query_model as SQ
-from test_inside_query_cpu import QUERY_VGPRS
+from util import QUERY_VGPRS, check_query_kernels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -219,39 +219,11 @@ def test_scene_queries_refuse_bad_lists_without_a_device(psm):
                     assert fn(lst, u32(count), d_in, n, d_out) == -1
 
 
-# the launch bound's register limit (8 waves per SIMD: 64 VGPRs); SceneArgs: the kernels' one parameter
-SCENE_KERNELS = ["_ZN3psm%d%sENS_9SceneArgsE" % (len(k), k) for k in (
-    "scene_query_closest", "scene_query_any", "scene_query_point", "scene_query_within", "scene_query_count", "scene_query_inside",
-    "scene_query_sign")]
-
-
-def test_scene_query_kernels_codegen(tmp_path):
-    flags = open(os.path.join(ROOT, "prismarine-core_amd", "csrc", "Makefile")).read()
-    cxx = re.search(r"^CXXFLAGS := (.*)$", flags, re.M).group(1).replace("$(ARCH)", "gfx950").split()
-    out = str(tmp_path / "query.s")
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + [f for f in cxx if not f.startswith("-W")] +
-                          ["-S", "--cuda-device-only", "-o", out, os.path.join(ROOT, "prismarine-core_amd", "csrc", "query.hip")],
-                          stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    limits = dict(QUERY_VGPRS)                    # the seven single-hierarchy kernels: still within their ceilings
-    limits.update({k: 64 for k in SCENE_KERNELS})
-    assert len(limits) == 14
-    for kern, vgprs in limits.items():
-        blk = asm[asm.index(".name:           " + kern):]
-        blk = blk[:blk.index(".wavefront_size")]
-        assert int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)) <= vgprs, kern
-        assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)) == 0, kern
-        assert int(re.search(r"\.sgpr_spill_count:\s+(\d+)", blk).group(1)) == 0, kern
-        assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)) == 0, kern
-        body = asm[asm.index(kern + ":"):]
-        body = body[:body.index(".Lfunc_end")]
-        assert "scratch_" not in body, kern
-        if kern in SCENE_KERNELS:
-            # the table of geometries (32 x 32 B) travels in the kernel arguments, after the 64 bytes of scalars
-            karg = re.findall(r"\.kernarg_segment_size:\s+(\d+)", asm[:asm.index(".name:           " + kern)])[-1]
-            assert int(karg) >= 32 * 32, kern
-            if "point" not in kern and "within" not in kern:
-                assert "v_fma_mix_f32" in body, kern
+def test_scene_query_kernels_codegen():
+    """the seven scene kernels, and the seven single-hierarchy kernels still at their ceilings"""
+    names = [k for k in QUERY_VGPRS if not k.startswith("inst_")]
+    assert len(names) == 14
+    check_query_kernels(names)
 
 
 def test_scene_query_header_layer_compiles_and_links(tmp_path):

@@ -1,5 +1,12 @@
 """Helpers shared by the parity tests."""
+import os
+import re
+import subprocess
+import tempfile
+
 import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def half2_key(p):
@@ -126,3 +133,66 @@ def random_mesh_descriptions(seed, count):
                "texcoord_accessor": int(rng.randint(-1, len(acc))), "transform": t.reshape(16),
                "transform_inv": np.linalg.inv(t.astype(np.float64)).astype(np.float32).reshape(16), "material_id": int(rng.randint(-1, 5)),
                "index16": int(idx16), "node_count": nodes, "primitive_type": int(quads), "loading_offset": int(rng.randint(0, 30))}
+
+
+# The 21 query kernels of query.hip and the VGPRs each may reach with the Makefile's flags (what they compile
+# to; 64 is the budget of __launch_bounds__(64, 8), 8 waves per SIMD). Per family: the kernels' one parameter, then the ceilings of
+# closest / any / point / within / count / inside / sign.
+QUERY_KINDS = ("closest", "any", "point", "within", "count", "inside", "sign")
+QUERY_FAMILIES = {"bvh": ("QueryArgs", (55, 52, 59, 56, 50, 50, 53)),
+                  "scene": ("SceneArgs", (57, 52, 62, 56, 51, 50, 51)),
+                  "inst": ("InstArgs", (59, 54, 63, 58, 53, 53, 54))}
+QUERY_VGPRS = {"%s_query_%s" % (fam, kind): v for fam, (_, vgprs) in QUERY_FAMILIES.items() for kind, v in zip(QUERY_KINDS, vgprs)}
+
+_query_asm = None
+
+
+def query_asm():
+    """{kernel: (metadata block, body)} of query.hip's kernels, compiled to assembly with the Makefile's flags -- once per test
+    process. Keys are the plain kernel names (bvh_query_closest, ...)."""
+    global _query_asm
+    if _query_asm is None:
+        csrc = os.path.join(ROOT, "prismarine-core_amd", "csrc")
+        flags = open(os.path.join(csrc, "Makefile")).read()
+        cxx = re.search(r"^CXXFLAGS := (.*)$", flags, re.M).group(1).replace("$(ARCH)", "gfx950").split()
+        assert "-fno-slp-vectorize" in cxx and "-ffp-contract=off" in cxx
+        assert "query.hip" in re.search(r"^SRC := (.*)$", flags, re.M).group(1).split()
+        with tempfile.TemporaryDirectory() as tmp:
+            out = os.path.join(tmp, "query.s")
+            subprocess.check_call(["/opt/rocm/bin/hipcc"] + [f for f in cxx if not f.startswith("-W")] +
+                                  ["-S", "--cuda-device-only", "-o", out, os.path.join(csrc, "query.hip")], stderr=subprocess.DEVNULL)
+            asm = open(out).read()
+        kernels = {}
+        for name in QUERY_VGPRS:
+            args = QUERY_FAMILIES[name.split("_")[0]][0]
+            kern = "_ZN3psm%d%sENS_%d%sE" % (len(name), name, len(args), args)
+            at = asm.index(".name:           " + kern)   # inside the kernel's metadata map, .agpr_count to .wavefront_size
+            blk = asm[asm.rindex("  - .agpr_count:", 0, at):]
+            blk = blk[:blk.index(".wavefront_size")]
+            body = asm[asm.index(kern + ":"):]
+            kernels[name] = (blk, body[:body.index(".Lfunc_end")])
+        _query_asm = kernels
+    return _query_asm
+
+
+def check_query_kernels(names):
+    """What every codegen test of the queries holds its kernels to: the VGPR ceiling of the table, nothing spilled, no private
+    segment, no scratch access; the slab planes straight from the fp16 record coordinates (v_fma_mix_f32) in every kernel that
+    walks rays (all but the point / within kernels); the table of a scene (32 x 32 B) or of instances (32 x 80 B, within the 4 KB
+    the segment holds) in the kernel arguments."""
+    asm = query_asm()
+    for name in names:
+        blk, body = asm[name]
+
+        def meta(key):
+            return int(re.search(r"\.%s:\s+(\d+)" % key, blk).group(1))
+        assert meta("vgpr_count") <= QUERY_VGPRS[name] <= 64, name
+        assert meta("vgpr_spill_count") == 0 and meta("sgpr_spill_count") == 0, name
+        assert meta("private_segment_fixed_size") == 0, name
+        assert "scratch_" not in body, name
+        if "point" not in name and "within" not in name:
+            assert "v_fma_mix_f32" in body, name
+        if name.startswith("scene_"):
+            assert meta("kernarg_segment_size") >= 32 * 32, name
+        if name.startswith("inst_"):
+            assert 2560 <= meta("kernarg_segment_size") <= 4096, (name, meta("kernarg_segment_size"))
