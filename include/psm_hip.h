@@ -75,8 +75,9 @@ int psm_sort_u64_u32_dev(psm_ctx* ctx, uint64_t* d_keys, uint32_t* d_vals, size_
  * 2 (default) = hybrid: the LSD passes of the TOP sixteen key bits first (histogram / scan / scatter kernels, two passes),
  * then every workgroup sorts a chunk of whole sixteen-bit bins by the remaining digits in LDS and writes it back once
  * (radix_local): 3 moves of a key through HBM and 7 launches where the reference makes 8 x 3 dispatches (Radix.hpp:57-73).
- * A chunk whose last bin does not fit LDS is sorted through global memory by its workgroup alone (correct, slow) and the
- * context then falls back to algorithm 0 for good (psm_sort_get_algorithm shows it; setting the algorithm again clears it).
+ * A bin too long for a chunk's LDS is sorted through global memory by one workgroup alone, apart from the small bins before it
+ * (slow; correct under every order in which the workgroups run, because a store never shows a neighbour a key of another bin),
+ * and the context then falls back to algorithm 0 for good (psm_sort_get_algorithm shows it; setting the algorithm again clears it).
  * 0 = per pass a histogram, a scan (pfx-work.comp:34-70 as its own launch) and a scatter kernel: 256 B/key, 24 launches.
  * 1 = ONE histogram sweep over the keys for all eight digits (histogram.comp:80-116 once instead of per pass) + one
  * scatter launch per pass that finds its tile's bases by decoupled look-back: 200 B/key, 10 launches -- measured slower

@@ -1,6 +1,7 @@
 // api.hip -- the C ABI of include/psm_hip.h: contexts, buffers, object lifetime, stage order.
 // Host logic only; the kernels live in sort.hip, bvh.hip, trace.hip, shade.hip.
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -123,9 +124,17 @@ static int ctx_create(int device, void* ext_stream, bool use_ext, psm_ctx** out)
     if (const char* t = std::getenv("PSM_SORT_TUNE")) {   // study knob (tools/sort_bench.py): "S_small,S_large,threads[,cap_small,cap_large[,threads_large]]" of radix_local
         unsigned a = 0, b = 0, th = 0, cs = 4096, cl = 4096, thl = 0;
         const int got = std::sscanf(t, "%u,%u,%u,%u,%u,%u", &a, &b, &th, &cs, &cl, &thl);
-        if (got >= 3 && a >= 64 && a < cs && b >= 64 && b < cl && (th == 512 || th == 1024) && (thl == 0 || thl == 512 || thl == 1024)) {
-            c->sort_hybrid_s_small = a; c->sort_hybrid_s_large = b; c->sort_hybrid_threads = th; c->sort_hybrid_threads_large = thl ? thl : th;
+        if (thl == 0) thl = th;
+        // a (cap, threads) pair must be one that radix_local is instantiated for (sort_hybrid's PSM_LOCAL list)
+        auto shape = [](unsigned cap, unsigned threads) { return ((cap == 4096 || cap == 5120) && (threads == 512 || threads == 1024)) || (cap == 6144 && threads == 512); };
+        if (got >= 3 && a >= 64 && a < cs && b >= 64 && b < cl && shape(cs, th) && shape(cl, thl)) {
+            c->sort_hybrid_s_small = a; c->sort_hybrid_s_large = b; c->sort_hybrid_threads = th; c->sort_hybrid_threads_large = thl;
             c->sort_hybrid_cap_small = cs; c->sort_hybrid_cap_large = cl;
+        } else {
+            static std::atomic<bool> warned{false};
+            if (!warned.exchange(true))
+                std::fprintf(stderr, "psm: PSM_SORT_TUNE=\"%s\" ignored (want S_small,S_large,threads[,cap_small,cap_large[,threads_large]] with 64 <= S < cap and "
+                                     "(cap, threads) one of {4096, 5120} x {512, 1024} or (6144, 512)); the hybrid sort keeps its default shapes\n", t);
         }
     }
     *out = c;

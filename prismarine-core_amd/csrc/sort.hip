@@ -346,15 +346,23 @@ __global__ __launch_bounds__(THREADS) void radix_scatter(const uint64_t* __restr
 //      keys differ at all, wave64 match-any ranks as in radix_scatter), then writes the chunk back where it lay.
 // A chunk is at most S keys plus the tail of its last bin; it fits the workgroup's LDS (CAP keys) as long as no bin is longer
 // than CAP - S. Morton codes of meshes spread well over sixteen bits (C3: longest bin 1 876 of 262 267 keys, C5: 723 of 10 M,
-// bits 47..62); for a bin that does not, the workgroup sorts its chunk through global memory on its own (local_slow: correct
-// for every input, slow) and raises `overflow`, a pinned host word launch_sort looks at: a context whose keys overflowed
-// goes back to the eight-pass sort for good. The result is the stable ascending order -- the same bits as the LSD sorts.
+// bits 47..62). For a bin that does not -- the chunk's last bin, the LONG bin, has no end inside the window -- the workgroup
+// splits its chunk: the long bin ALONE goes through global memory (local_slow: LSD passes between the array and the scratch
+// buffer's own stretch, this workgroup alone, slow), the whole small bins before it (fewer than S keys) are an ordinary LDS
+// chunk. It also raises `overflow`, a pinned host word launch_sort looks at: a context whose keys overflowed goes back to the
+// eight-pass sort for good. The result is the stable ascending order -- the same bits as the LSD sorts.
 //
 // In place: a workgroup reads the window [c S - 1, c S + CAP) of the keys -- beyond its own chunk on both sides, to find the
-// bin boundaries -- while its neighbours may already be writing their sorted chunks into the same array. What it looks at in
-// a neighbour's keys is the bin they belong to (key >> pshift), and sorting a chunk never moves a key out of the positions of
-// its bin: whichever version of a neighbour's key a load returns, its bin is the same (pshift >= 32: the bin bits lie in the
-// key's high dword, so even a load torn between two 32-bit halves would agree).
+// bin boundaries -- and, on the overflow path, probes keys past its window for the long bin's end, while its neighbours may
+// already be writing into the same array. What it looks at in a neighbour's keys is the bin they belong to (key >> pshift), so
+// what has to hold is: EVERY state of keys[] that a load can see has, at every position, a key of the bin that the sorted array
+// has there. Two kinds of stores write keys[], and both keep that:
+//   - an LDS chunk is whole bins and is written back once, in its final order;
+//   - local_slow permutes ONE bin: its intermediate states (ordered by the low digits only) still show that bin at every
+//     position of its range. (Run over a whole chunk, as it was until round 6, its second pass left the chunk's bins interleaved
+//     in keys[] and a neighbour could take a false edge for a chunk of its own: tests/sort_local_model.py, test_sort_local_cpu.py.)
+// So whichever version of a neighbour's key a load returns, its bin is the same (pshift >= 32: the bin bits lie in the key's
+// high dword, so even a load torn between two 32-bit halves would agree). Values are read and written inside the own chunk only.
 
 #ifndef PSM_EXP_SORTLOG
 #define PSM_EXP_SORTLOG 0   // 1: an experiment build (make sortlog) whose radix_local workgroups log s_memtime at their phase boundaries (tests/studies/sort_log.py)
@@ -381,8 +389,8 @@ struct LocalLds {
     uint32_t lo, hi;
 };
 
-// the chunk does not fit LDS: stable LSD passes over [gs, gs + m) through global memory, this workgroup alone, the scratch
-// arrays' own [gs, gs + m) as the other buffer
+// a bin that does not fit LDS: stable LSD passes over [gs, gs + m) through global memory, this workgroup alone, the scratch
+// arrays' own [gs, gs + m) as the other buffer. [gs, gs + m) must be ONE bin (see "In place" above)
 template <int CAP, int THREADS>
 PSM_D void local_slow(LocalLds<CAP, THREADS>& S, uint64_t* keys, uint32_t* vals, uint64_t* altk, uint32_t* altv, uint32_t gs, uint32_t m) {
     constexpr int ITEMS = CAP / THREADS, NW = THREADS / 64;
@@ -474,6 +482,37 @@ PSM_D void local_slow(LocalLds<CAP, THREADS>& S, uint64_t* keys, uint32_t* vals,
     }
 }
 
+// radix_local's overflow path: the chunk's last bin has no end inside the window. Sorts that long bin ALONE through global memory
+// (it is one bin: whatever order local_slow leaves between its passes, every position of its range shows the same bin to the
+// neighbours -- and to the search below of another workgroup on this path), raises the overflow word, and returns where the long
+// bin starts in the window, jl in [js, S): [js, jl) is what is left of the chunk.
+// (Inlined: as a call it costs every radix_local 72-200 bytes of scratch for the callee's frame; inlined none, and no spill.)
+template <int CAP, int THREADS>
+PSM_D uint32_t radix_local_overflow(LocalLds<CAP, THREADS>& L, uint64_t* keys, uint32_t* vals, uint64_t* altk, uint32_t* altv,
+                                                      uint32_t n, uint32_t a, uint32_t winN, uint32_t js, uint32_t S, int pshift, uint32_t* overflow) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t bin = key_bin(L.sk[winN - 1], pshift);
+    // its end is the first key of a later bin (the keys are ordered by bin)
+    uint32_t lo = a + winN, hi = n;   // first position with a later bin lies in [lo, hi]
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (key_bin(keys[mid], pshift) > bin) hi = mid; else lo = mid + 1u;
+    }
+    __syncthreads();   // every thread has read L.hi (radix_local's `je`) before it changes
+    // its start: no bin boundary in [S, winN), so key S - 1 is of the long bin and the bin starts in [js, S - 1] (L.hi is 0xFFFFFFFF here)
+    for (uint32_t j = js + tid; j < S; j += THREADS)
+        if (key_bin(L.sk[j], pshift) == bin) { atomicMin(&L.hi, j); break; }
+    __syncthreads();
+    const uint32_t jl = L.hi;
+    const uint32_t gs = a + jl, m = lo - gs;
+    local_slow<CAP, THREADS>(L, keys, vals, altk, altv, gs, m);
+    if (tid == 0 && overflow) __hip_atomic_fetch_add(overflow, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __syncthreads();   // every thread has read local_slow's L.diff
+    if (tid == 0) { L.diff[0] = 0; L.diff[1] = 0; }   // the chunk's own, below
+    __syncthreads();
+    return jl;
+}
+
 // (second launch bound: waves per SIMD such that two workgroups share a CU while their LDS -- 160 KB a CU -- allows it)
 template <int CAP, int THREADS>
 __global__ __launch_bounds__(THREADS, (2 * sizeof(LocalLds<CAP, THREADS>) <= 160 * 1024 ? 2 : 1) * THREADS / 256) void radix_local(uint64_t* keys, uint32_t* vals, uint64_t* altk, uint32_t* altv,
@@ -542,18 +581,10 @@ __global__ __launch_bounds__(THREADS, (2 * sizeof(LocalLds<CAP, THREADS>) <= 160
     uint32_t je = L.hi;
     if (je == 0xFFFFFFFFu && a + winN >= n) je = winN;   // the array ends inside the window
     if (je == 0xFFFFFFFFu) {
-        // the chunk's last bin runs past the window: its end is the first key of a later bin (the keys are ordered by bin)
-        const uint32_t bin = key_bin(L.sk[winN - 1], pshift);
-        uint32_t lo = a + winN, hi = n;   // first position with a later bin lies in [lo, hi]
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if (key_bin(keys[mid], pshift) > bin) hi = mid; else lo = mid + 1u;
-        }
-        const uint32_t gs = a + js, m = lo - gs;
-        __syncthreads();
-        local_slow<CAP, THREADS>(L, keys, vals, altk, altv, gs, m);
-        if (tid == 0 && overflow) __hip_atomic_fetch_add(overflow, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        return;
+        // the chunk's last bin -- the long bin -- runs past the window
+        je = radix_local_overflow<CAP, THREADS>(L, keys, vals, altk, altv, n, a, winN, js, S, pshift, overflow);
+        if (je == js) return;   // nothing precedes the long bin
+        // ... else the whole small bins [js, je) before it: an ordinary chunk
     }
     const uint32_t size = je - js, gs = a + js;
     // wave w works on slots [w per, (w + 1) per) of the chunk, 64 per round

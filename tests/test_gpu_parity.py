@@ -5,10 +5,14 @@ queues the shading kernel emits; accumulated radiance within 1e-4 relative (the 
 difference left is the order of the float atomic adds into a texel).
 """
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 
+import sort_layouts
+import sort_local_model
 from util import bits, canonical_nodes
 
 pytestmark = pytest.mark.gpu
@@ -165,6 +169,66 @@ def test_hybrid_sort_chunk_edges(psm, ctx, case):
         assert np.array_equal(gk, ek) and np.array_equal(gv, ev)
         rs.setAlgorithm(2)
         assert rs.getAlgorithm() == (2, 2)
+
+
+def _overflow_cases():
+    out = []
+    for shape, n in (("small", 20000), ("large", 2 ** 19 + 4099)):   # sort_hybrid's two shapes; 2^19 + 4099 is the smallest size of the large one that holds every layout
+        S, CAP = sort_local_model.default_shape(n)
+        for name in sort_layouts.NAMES:
+            for where, c0 in sort_layouts.stretches(name, n, S, CAP).items():
+                out.append(pytest.param(name, n, c0, id="%s-%s-%s" % (shape, name, where)))
+    return out
+
+
+@pytest.mark.parametrize("name,n,c0", _overflow_cases())
+def test_hybrid_sort_overflow_layouts(psm, ctx, name, n, c0):
+    """radix_local's overflow path (sort_layouts.py lists the layouts): the long bin goes through global memory alone, the small
+    bins before it are an LDS chunk. One sort each, bit for bit the stable order; whether the context must have fallen back is
+    what the model of the kernel (sort_local_model.py) says of the same keys. The ORDER of the workgroups' loads and stores is
+    test_sort_local_cpu.py's business, not this test's."""
+    S, CAP = sort_local_model.default_shape(n)
+    rng = np.random.RandomState(c0 + 7 * len(name))
+    keys = sort_layouts.layout(name, n, S, CAP, c0, 48, seed=c0 + len(name))[rng.permutation(n)]   # the global passes bring the bins back together
+    vals = rng.randint(0, 2 ** 32, size=n, dtype=np.int64).astype(np.uint32)
+    overflow = sort_local_model.overflows(keys)
+    if name != "end_at_window_minus_1":
+        assert overflow
+    rs = psm.RadixSort(ctx)
+    gk, gv = rs.sort_arrays(keys, vals)
+    ek, ev = _stable(keys, vals)
+    assert np.array_equal(gk, ek) and np.array_equal(gv, ev)
+    assert rs.getAlgorithm() == (2, 0 if overflow else 2)
+    if overflow:   # the context now sorts with the eight passes; asking for the hybrid sort again re-arms it
+        gk, gv = rs.sort_arrays(keys, vals)
+        assert np.array_equal(gk, ek) and np.array_equal(gv, ev)
+        rs.setAlgorithm(2)
+        assert rs.getAlgorithm() == (2, 2)
+
+
+def _sort_tune_child(tune, *args):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "tests", "sort_tune_child.py")] + list(args), env=dict(os.environ, PSM_SORT_TUNE=tune),
+                         capture_output=True, text=True, timeout=120, cwd=root)
+    assert out.returncode == 0, out.stderr[-3000:]
+    return out
+
+
+def test_sort_tune_without_a_kernel_of_that_shape_is_refused():
+    """PSM_SORT_TUNE with 8 192 keys of LDS, for which no radix_local exists: one warning, the default shapes, every sort right
+    (it used to be accepted, and every hybrid sort of the context then failed)."""
+    out = _sort_tune_child("1024,2048,1024,8192,4096", "rejected")
+    assert "sorted 2 x 20000 keys" in out.stdout
+    assert out.stderr.count("PSM_SORT_TUNE") == 1 and "ignored" in out.stderr
+
+
+def test_sort_tune_5120_keys_of_lds_overflow_layouts():
+    """A shape that exists (stretches of 3 072 bin starts, 5 120 keys of LDS, 1 024 threads): a long bin at every offset of its
+    stretch, and two in one launch."""
+    out = _sort_tune_child("3072,3072,1024,5120,5120", "layouts", "3072", "5120")
+    want = sum(len(sort_layouts.stretches(name, 20000, 3072, 5120)) for name in sort_layouts.NAMES if name.startswith("long_at_") or name == "two_long")
+    assert want >= 5 and "sorted %d layouts, %d overflowed" % (want, want) in out.stdout, out.stdout
+    assert "PSM_SORT_TUNE" not in out.stderr
 
 
 # ---------------------------------------------------------------------------- build
