@@ -3,4 +3,5 @@
 #include "TriangleHierarchy.inl"
 #include "QueryScene.inl"
 #include "InstancedScene.inl"
+#include "InstanceWorld.inl"
 #include "Pipeline.inl"

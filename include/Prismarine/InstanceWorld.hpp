@@ -1,0 +1,39 @@
+#pragma once
+// Prismarine/InstanceWorld.hpp -- psm::InstanceWorld (not in the reference): InstancedScene's seven queries over up to
+// PSM_WORLD_MAX_INSTANCES instances under a top-level tree on the device (psm_world_*, include/psm_hip.h "instance worlds").
+// A query enters only the instances it can reach; the answers are those of an InstancedScene over the same list. The list is
+// uploaded by commit(); setTransform() moves bodies without rebuilding a hierarchy. Poses are glm::mat4 as in InstancedScene.
+
+#include "InstancedScene.hpp"
+
+namespace NSM {
+
+    class InstanceWorld : public InstancedScene {
+    protected:
+        psm_world * world = nullptr;
+
+    public:
+        explicit InstanceWorld(uint32_t capacity = PSM_WORLD_MAX_INSTANCES) { world = psm_world_create(context(), capacity); }
+        ~InstanceWorld() { if (world) psm_world_destroy(world); }
+        InstanceWorld(const InstanceWorld &) = delete;
+        InstanceWorld & operator=(const InstanceWorld &) = delete;
+        psm_world * handle() const { return world; }
+
+        // upload the list built with add() / clear(): table, boxes and tree (psm_world_set_instances)
+        int commit();
+        // place instances first .. first + count - 1 anew, on the host list and on the device (psm_world_set_transforms)
+        int setTransforms(size_t first, const glm::mat4 * worldFromObject, size_t count);
+        int setTransform(size_t i, const glm::mat4 &worldFromObject) { return setTransforms(i, &worldFromObject, 1); }
+        // after a member hierarchy was refitted: boxes and tree from the triangles as they now are
+        int refresh() { return poses.empty() ? int(PSM_OK) : setTransforms(0, poses.data(), poses.size()); }
+        uint32_t count() const { return psm_world_count(world); }
+
+        int intersect(const psm_query_ray * d_rays, size_t n, psm_hit * d_hits, int32_t * d_inst);
+        int occluded(const psm_query_ray * d_rays, size_t n, uint8_t * d_hit);
+        int countHits(const psm_query_ray * d_rays, size_t n, uint32_t * d_count);
+        int closestPoint(const psm_point_query * d_points, size_t n, psm_hit * d_hits, int32_t * d_inst);
+        int within(const psm_point_query * d_points, size_t n, uint8_t * d_hit);
+        int inside(const psm_point_query * d_points, size_t n, uint8_t * d_inside, uint32_t samples = 3);
+        int signedDistance(const psm_point_query * d_points, size_t n, psm_hit * d_hits, int32_t * d_inst, uint32_t samples = 3);
+    };
+}

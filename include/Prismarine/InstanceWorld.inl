@@ -1,0 +1,59 @@
+// Prismarine/InstanceWorld.inl -- implementation of psm::InstanceWorld over the C ABI (psm_world_*): thin checked wrappers.
+#include "InstanceWorld.hpp"
+
+namespace NSM {
+
+    inline int InstanceWorld::commit() {
+        const std::vector<psm_instance> v = instances();
+        const int rc = v.size() != geometries.size() ? int(PSM_ERR_INVALID) : psm_world_set_instances(world, v.data(), uint32_t(v.size()));
+        check(rc, "InstanceWorld::commit");
+        return rc;
+    }
+    inline int InstanceWorld::setTransforms(size_t first, const glm::mat4 * m, size_t count) {
+        std::vector<float> m12(12 * count);
+        for (size_t k = 0; k < count; k++) {
+            if (m[k][0][3] != 0.0f || m[k][1][3] != 0.0f || m[k][2][3] != 0.0f || m[k][3][3] != 1.0f) return int(PSM_ERR_INVALID);
+            for (int row = 0; row < 3; row++)
+                for (int col = 0; col < 4; col++) m12[12 * k + 4 * row + col] = m[k][col][row];
+        }
+        const int rc = psm_world_set_transforms(world, uint32_t(first), uint32_t(count), m12.data());
+        check(rc, "InstanceWorld::setTransforms");
+        for (size_t k = 0; rc == PSM_OK && k < count; k++) poses.at(first + k) = m[k];
+        return rc;
+    }
+    inline int InstanceWorld::intersect(const psm_query_ray * d_rays, size_t n, psm_hit * d_hits, int32_t * d_inst) {
+        const int rc = psm_world_intersect_dev(world, d_rays, n, d_hits, d_inst);
+        check(rc, "InstanceWorld::intersect");
+        return rc;
+    }
+    inline int InstanceWorld::occluded(const psm_query_ray * d_rays, size_t n, uint8_t * d_hit) {
+        const int rc = psm_world_occluded_dev(world, d_rays, n, d_hit);
+        check(rc, "InstanceWorld::occluded");
+        return rc;
+    }
+    inline int InstanceWorld::countHits(const psm_query_ray * d_rays, size_t n, uint32_t * d_count) {
+        const int rc = psm_world_count_hits_dev(world, d_rays, n, d_count);
+        check(rc, "InstanceWorld::countHits");
+        return rc;
+    }
+    inline int InstanceWorld::closestPoint(const psm_point_query * d_points, size_t n, psm_hit * d_hits, int32_t * d_inst) {
+        const int rc = psm_world_closest_point_dev(world, d_points, n, d_hits, d_inst);
+        check(rc, "InstanceWorld::closestPoint");
+        return rc;
+    }
+    inline int InstanceWorld::within(const psm_point_query * d_points, size_t n, uint8_t * d_hit) {
+        const int rc = psm_world_within_dev(world, d_points, n, d_hit);
+        check(rc, "InstanceWorld::within");
+        return rc;
+    }
+    inline int InstanceWorld::inside(const psm_point_query * d_points, size_t n, uint8_t * d_inside, uint32_t samples) {
+        const int rc = psm_world_inside_dev(world, d_points, n, samples, d_inside);
+        check(rc, "InstanceWorld::inside");
+        return rc;
+    }
+    inline int InstanceWorld::signedDistance(const psm_point_query * d_points, size_t n, psm_hit * d_hits, int32_t * d_inst, uint32_t samples) {
+        const int rc = psm_world_signed_distance_dev(world, d_points, n, samples, d_hits, d_inst);
+        check(rc, "InstanceWorld::signedDistance");
+        return rc;
+    }
+}

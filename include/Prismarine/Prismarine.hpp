@@ -9,5 +9,6 @@
 #include "TriangleHierarchy.hpp"
 #include "QueryScene.hpp"          // addition: the queries over several hierarchies at once (psm_scene_*_dev)
 #include "InstancedScene.hpp"      // addition: the same over instances, a hierarchy and a rigid pose each (psm_instances_*_dev)
+#include "InstanceWorld.hpp"       // addition: the same without the limit of 32, under a top-level tree on the device (psm_world_*)
 #include "Pipeline.hpp"
 #include "FrameBatch.hpp"   // addition: several frames in flight (psm_lanes_render)

@@ -527,6 +527,52 @@ int psm_instances_inside_dev(const psm_instance* insts, uint32_t count, const ps
 int psm_instances_signed_distance_dev(const psm_instance* insts, uint32_t count, const psm_point_query* d_points, size_t n,
                                       uint32_t samples, psm_hit* d_hits, int32_t* d_inst);
 
+/* instance worlds: the seven queries over a top-level tree of instances (new; no reference counterpart).
+ * The instanced queries above enter every instance for every query and end at 32 entries. A world is a handle that owns, on
+ * the device, the table of up to PSM_WORLD_MAX_INSTANCES instances and a binary tree over their padded world-space boxes; a
+ * query walks the tree and enters only the instances it can reach. Semantics, in one sentence: a world of N instances answers
+ * every query exactly as psm_instances_*_dev would over the same ordered list if that list could be N long -- candidates,
+ * windows, rmax, validity per instance on the moved query, the float32 move, inside summing each ray's crossings over all
+ * instances before the vote, the record (the winning instance's object-space u, v, t, tri; d_inst its index in the list) and
+ * ties going to the lexicographically lowest (inst, tri). The tree never shows in an answer: every box is padded and every
+ * prune slackened beyond the worst difference between the world-space box test and the object-space candidate test.
+ *   - psm_world_create(ctx, capacity): capacity 1 .. PSM_WORLD_MAX_INSTANCES; NULL on failure (psm_last_error says why)
+ *   - psm_world_set_instances(world, insts, count): the list checks of the instanced queries with the same messages (a NULL
+ *     bvh, another context than the world's, a pose that is non-finite or not rigid -- in double --, a hierarchy that is not
+ *     built or too deep), all before any device work; count > capacity: PSM_ERR_CAPACITY; count == 0 empties the world. Then
+ *     the table is uploaded, every instance's box is computed on the device from its hierarchy's triangles (nothing is read
+ *     back), and the tree is built on the context's stream: Morton keys of the box centres with the instance index as the
+ *     tie-break, the library's sort, one emit kernel, one bottom-up box pass. Synchronises once, to read the tree's depth
+ *   - depth: a walk uses one stack for both levels. A world whose tree depth plus its deepest hierarchy's depth bound plus one
+ *     exceeds the 96 entries of the query stack is refused (PSM_ERR_CAPACITY) and LEFT EMPTY
+ *   - psm_world_set_transforms(world, first, count, m12): new poses (12 floats each) for instances first .. first + count - 1,
+ *     checked as above; boxes and tree are rebuilt, no hierarchy is
+ *   - staleness: the table holds device pointers. Every hierarchy carries a generation that each build bumps (a load or a clear
+ *     leaves the hierarchy un-built until its next build or refit); the world records it at psm_world_set_instances, and every
+ *     query (and psm_world_set_transforms) looks, once per distinct hierarchy, for a generation that differs or a hierarchy
+ *     that is not built: PSM_ERR_STATE with a message naming the first stale instance, and nothing is launched. Set the
+ *     instances again. A hierarchy must outlive the worlds that hold it. A REFIT (reload the same count, psm_bvh_refit) does
+ *     not bump the generation but moves the triangles out of the boxes: call psm_world_set_transforms over the whole range
+ *     (with the poses as they are) after it, and the world is exact again
+ *   - an empty world (never set, emptied, or refused for its depth) answers every query with misses; no query kernel runs
+ *   - the seven queries: data arguments, their checks and n == 0 as the psm_instances_* forms; stream-ordered on the world's
+ *     context, no host synchronisation, one launch (signed distance: two) */
+#define PSM_WORLD_MAX_INSTANCES 65536
+typedef struct psm_world psm_world;
+psm_world* psm_world_create(psm_ctx* ctx, uint32_t capacity);
+int psm_world_destroy(psm_world* world);
+int psm_world_set_instances(psm_world* world, const psm_instance* insts, uint32_t count);
+int psm_world_set_transforms(psm_world* world, uint32_t first, uint32_t count, const float* m12);
+uint32_t psm_world_count(const psm_world* world);
+int psm_world_intersect_dev(psm_world* world, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits, int32_t* d_inst);
+int psm_world_occluded_dev(psm_world* world, const psm_query_ray* d_rays, size_t n, uint8_t* d_hit);
+int psm_world_count_hits_dev(psm_world* world, const psm_query_ray* d_rays, size_t n, uint32_t* d_count);
+int psm_world_closest_point_dev(psm_world* world, const psm_point_query* d_points, size_t n, psm_hit* d_hits, int32_t* d_inst);
+int psm_world_within_dev(psm_world* world, const psm_point_query* d_points, size_t n, uint8_t* d_hit);
+int psm_world_inside_dev(psm_world* world, const psm_point_query* d_points, size_t n, uint32_t samples, uint8_t* d_inside);
+int psm_world_signed_distance_dev(psm_world* world, const psm_point_query* d_points, size_t n, uint32_t samples, psm_hit* d_hits,
+                                  int32_t* d_inst);
+
 /* ---------------------------------------------------------------------------------------------
  * several frames in flight (new; DESIGN.md "lanes")
  * `frames` x GltfViewer::process() (Viewer.cpp:296-312) with up to `lanes` of them in flight: lane s =

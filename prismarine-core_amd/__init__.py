@@ -31,6 +31,9 @@ EXPORTS = [
     "psm_scene_inside_dev", "psm_scene_signed_distance_dev",
     "psm_instances_intersect_dev", "psm_instances_occluded_dev", "psm_instances_count_hits_dev", "psm_instances_closest_point_dev",
     "psm_instances_within_dev", "psm_instances_inside_dev", "psm_instances_signed_distance_dev",
+    "psm_world_create", "psm_world_destroy", "psm_world_set_instances", "psm_world_set_transforms", "psm_world_count",
+    "psm_world_intersect_dev", "psm_world_occluded_dev", "psm_world_count_hits_dev", "psm_world_closest_point_dev", "psm_world_within_dev",
+    "psm_world_inside_dev", "psm_world_signed_distance_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -55,6 +58,8 @@ HIT_DT = np.dtype([("u", "<f4"), ("v", "<f4"), ("t", "<f4"), ("tri", "<i4")])
 QUERY_RAY_DT = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direct", "<f4", 3), ("tmax", "<f4")])   # psm_query_ray
 POINT_QUERY_DT = np.dtype([("p", "<f4", 3), ("rmax", "<f4")])   # psm_point_query
 SCENE_MAX_GEOMETRIES = 32   # psm_hip.h PSM_SCENE_MAX_GEOMETRIES
+WORLD_MAX_INSTANCES = 65536   # psm_hip.h PSM_WORLD_MAX_INSTANCES
+INSTANCE_DT = np.dtype([("bvh", "<u8"), ("world_from_object", "<f4", 12)])   # psm_instance
 # PSM_INSIDE_DIRECTIONS (include/psm_hip.h): ray k of TriangleHierarchy.inside / .signedDistance goes along row k
 INSIDE_DIRECTIONS = np.array([[0.4082483, 0.57735026, 0.70710677], [-0.7905694, 0.35355338, 0.5],
                               [0.52223295, -0.797724, 0.30151135], [-0.35355338, -0.4330127, -0.8291562],
@@ -119,6 +124,8 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.psm_last_error.restype = C.c_char_p
         _lib.psm_ctx_stream.restype = C.c_void_p
+        _lib.psm_world_create.restype = C.c_void_p
+        _lib.psm_world_count.restype = C.c_uint32
         for name in EXPORTS:
             getattr(_lib, name)  # AttributeError if an export is missing
     return _lib
@@ -734,6 +741,86 @@ class InstancedScene(QueryScene):
             insts[k].world_from_object[:] = self._poses[k].reshape(12).tolist()
         tail = () if d_geom is None else (C.c_void_p(d_geom),)
         self.ctx.check(getattr(lib(), name)(insts, C.c_uint32(g), C.c_void_p(d_in), C.c_size_t(n), *extra, C.c_void_p(d_out), *tail), name)
+
+
+class InstanceWorld(QueryScene):
+    """InstancedScene without its limit of 32 and without its cost per instance (psm_world_*; not in the reference): up to
+    WORLD_MAX_INSTANCES instances (TriangleHierarchy, matrix) in a table on the device under a tree over their world-space boxes.
+    A query walks the tree and enters only the instances it can reach; the answers are exactly those an InstancedScene over the
+    same ordered list would give if it could be that long (ties: the lowest (instance, triangle)). Moving bodies is
+    setTransform() / setTransforms(): boxes and tree are redone on the device, no hierarchy is rebuilt. The world records its
+    hierarchies as they are when set: after a member was rebuilt, reloaded or reallocated the next query raises PsmError until
+    setInstances() is called again; after a member was REFITTED call refresh(). Methods, arguments and numpy / torch placement:
+    QueryScene's; QueryHits.geom is the index of the winning instance."""
+
+    def __init__(self, ctx, entries, capacity=None):
+        self.ctx = ctx
+        pairs = list(entries)
+        cap = max(len(pairs), 1) if capacity is None else int(capacity)
+        self._w = C.c_void_p(lib().psm_world_create(ctx._h, C.c_uint32(cap)))
+        if not self._w:
+            raise PsmError("psm_world_create: %s" % lib().psm_last_error(ctx._h).decode())
+        self.hierarchies, self._poses, self._handles = [], np.zeros((0, 3, 4), np.float32), []
+        try:
+            self.setInstances(pairs)
+        except Exception:
+            self.close()
+            raise
+
+    def setInstances(self, entries):
+        """Set the whole list anew (psm_world_set_instances): table, boxes and tree; an empty list empties the world."""
+        pairs = list(entries)
+        poses = np.stack([_pose(m, "InstanceWorld") for _, m in pairs]) if pairs else np.zeros((0, 3, 4), np.float32)
+        handles = [th._h.value if isinstance(th._h, C.c_void_p) else th._h for th, _ in pairs]
+        insts = np.zeros(len(pairs), INSTANCE_DT)
+        insts["bvh"] = [h or 0 for h in handles]
+        insts["world_from_object"] = poses.reshape(-1, 12)
+        self.hierarchies, self._poses, self._handles = [], np.zeros((0, 3, 4), np.float32), []   # (a refused list leaves what the library leaves)
+        self.ctx.check(lib().psm_world_set_instances(self._w, _p(insts), C.c_uint32(len(pairs))), "psm_world_set_instances")
+        self.hierarchies, self._poses, self._handles = [th for th, _ in pairs], poses, handles
+
+    def __len__(self):
+        return int(lib().psm_world_count(self._w))
+
+    def setTransform(self, i, matrix):
+        """Place instance i anew (psm_world_set_transforms): no hierarchy is rebuilt."""
+        i = range(len(self.hierarchies))[i]
+        self.setTransforms(i, [matrix])
+
+    def setTransforms(self, first, matrices):
+        """Place instances first .. first + len(matrices) - 1 anew."""
+        ms = np.stack([_pose(m, "InstanceWorld.setTransforms") for m in matrices]) if len(matrices) else np.zeros((0, 3, 4), np.float32)
+        if first < 0 or first + ms.shape[0] > len(self.hierarchies):
+            raise IndexError("InstanceWorld.setTransforms: instances %d .. %d of %d" % (first, first + ms.shape[0], len(self.hierarchies)))
+        self._fresh("psm_world_set_transforms")
+        self.ctx.check(lib().psm_world_set_transforms(self._w, C.c_uint32(first), C.c_uint32(ms.shape[0]), _p(np.ascontiguousarray(ms))),
+                       "psm_world_set_transforms")
+        self._poses[first:first + ms.shape[0]] = ms
+
+    def refresh(self):
+        """After a member hierarchy was refitted: the boxes and the tree are redone from the triangles as they now are."""
+        self.setTransforms(0, self._poses)
+
+    def transforms(self):
+        """The poses, float32 [instances, 3, 4] (a copy)."""
+        return self._poses.copy()
+
+    def _fresh(self, name):
+        """a hierarchy whose handle is no longer the one recorded was reallocated: the library must not be given the old one"""
+        for k, (th, h) in enumerate(zip(self.hierarchies, self._handles)):
+            if (th._h.value if isinstance(th._h, C.c_void_p) else th._h) != h:
+                raise PsmError("%s: instance %d's hierarchy was reallocated after the instances were set (set the instances again)" % (name, k))
+
+    def _call(self, name, d_in, n, extra, d_out, d_geom):
+        name = name.replace("psm_bvh_", "psm_world_")
+        self._fresh(name)
+        tail = () if d_geom is None else (C.c_void_p(d_geom),)
+        self.ctx.check(getattr(lib(), name)(self._w, C.c_void_p(d_in), C.c_size_t(n), *extra, C.c_void_p(d_out), *tail), name)
+
+    def close(self):
+        if self._w:
+            lib().psm_world_destroy(self._w)
+            self._w = C.c_void_p()
 
 
 class TextureSet:

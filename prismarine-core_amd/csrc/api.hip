@@ -4,7 +4,9 @@
 #include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <new>
+#include <unordered_map>
 
 #include "psm_common.h"
 #include "psm_internal.h"
@@ -81,6 +83,27 @@ static void dev_free(T*& p) {
     p = nullptr;
 }
 
+}  // namespace psm
+
+// The generation of a hierarchy: bumped by every build (not by a refit; a load or a clear leaves `built` false until the next
+// build or refit). What a psm_world (world.hip) recorded of a hierarchy is stale when the generation differs. Kept beside the
+// handles, not in them: the layout of psm_bvh is part of what the traversal counters were collected with.
+namespace psm {
+static std::mutex gen_mu;
+static std::unordered_map<const psm_bvh*, uint64_t> gen_of;
+uint64_t bvh_generation(const psm_bvh* b) {
+    std::lock_guard<std::mutex> lk(gen_mu);
+    auto it = gen_of.find(b);
+    return it == gen_of.end() ? 0 : it->second;
+}
+static void bvh_bump_generation(const psm_bvh* b) {
+    std::lock_guard<std::mutex> lk(gen_mu);
+    gen_of[b]++;
+}
+static void bvh_forget_generation(const psm_bvh* b) {
+    std::lock_guard<std::mutex> lk(gen_mu);
+    gen_of.erase(b);
+}
 }  // namespace psm
 
 using namespace psm;
@@ -295,6 +318,7 @@ int psm_bvh_destroy(psm_bvh* b) {
     dev_free(b->d_block); dev_free(b->d_small); dev_free(b->d_opt); dev_free(b->d_seg);
     dev_free(b->d_sorted_tri); dev_free(b->d_pairbox); dev_free(b->d_link); dev_free(b->d_range); dev_free(b->d_node32);
     if (b->build_graph) (void)hipGraphExecDestroy(b->build_graph);
+    bvh_forget_generation(b);
     delete b;
     return PSM_OK;
 }
@@ -443,6 +467,7 @@ int psm_bvh_stage_bounds(psm_bvh* b, const double* opt) {
     if (b->tri_count == 0) return set_err(c, PSM_ERR_STATE, "build: no triangles");
     { int rc = bvh_upload_opt(b, opt); if (rc != PSM_OK) return rc; }
     b->built = false;  // a new build has begun: the node records of the last one can no longer be produced (psm_bvh_download)
+    bvh_bump_generation(b);   // ... and what a psm_world holds of this hierarchy is stale
     b->topo_tris = 0;  // ... nor can it be refitted: its transform and keys are being replaced
     int rc = launch_bvh_bounds(b);
     if (rc == PSM_OK) b->bounds_done = true;
@@ -560,6 +585,7 @@ int psm_bvh_build(psm_bvh* b, const double* opt) {
         return bvh_build_plain(b, opt);
     }
     c->sort_error_word = b->graph_error_word;
+    bvh_bump_generation(b);
     b->topo_tris = b->tri_count;
     b->bounds_done = b->morton_done = b->sort_done = b->built = true;
     b->records_valid = false;

@@ -1398,6 +1398,9 @@ void query_release(psm_ctx* c) {
     spill_area.erase(it);
 }
 
+// world.hip: the context's stack area serves the world queries too (their launches use the same grid cap)
+int query_spill(psm_ctx* c, void** out) { return spill_for(c, out); }
+
 }  // namespace psm
 
 int psm_bvh_intersect_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits) {

@@ -1,0 +1,1304 @@
+// world.hip -- instance worlds: the seven queries of query.hip over a top-level tree of posed instances (new; no reference
+// counterpart; include/psm_hip.h "instance worlds").
+//
+// A world is a handle that owns, on the device, a table of instances (a hierarchy's four pointers and a rigid pose: the row of
+// query.hip's InstGeom, now in memory) and a binary tree over the instances' padded world-space boxes. A world of N instances
+// answers every query exactly as psm_instances_*_dev would over the same ordered list if that list could be N long: the tree
+// only decides which instances a query enters, and every box test is padded and slackened so that it never drops an instance
+// that holds a counting candidate (the bounds: WORLD_PAD below). What a query does inside an instance is the instanced bodies'
+// code, copied: query.hip's 21 kernels keep their instruction streams (the file is touched for one host function only).
+//
+// The walk is one loop over one stack ([depth][lane] in LDS, the rest in the context's spill area). A stack entry is a link:
+//   link < 0               instance ~link of the world: the lane enters it (loads its row, moves the query, sets up)
+//   link & WORLD_TOP       node (link & ~WORLD_TOP) of the tree over the instances
+//   otherwise              an internal node of the hierarchy the lane is in (query.hip's links; leaves are never pushed)
+// A lane is "inside an instance" exactly while its current link is of the third kind; when its pop brings up a link of the first
+// two kinds it is back at the top level -- the tag does what a marker entry would, without the entry (the host still budgets
+// one). Lanes of a wave may be at different levels: the loop body holds the three steps under one branch each.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <unordered_map>
+#include <vector>
+
+#include "psm_common.h"
+#include "psm_internal.h"
+
+namespace psm {
+
+int query_spill(psm_ctx* c, void** out);   // query.hip: the context's stack area beyond the LDS part
+uint64_t bvh_generation(const psm_bvh* b);   // api.hip: bumped by every build of the hierarchy
+
+// one instance as the kernels read it: 80 B, 16-byte aligned (five 16-byte loads)
+struct WorldRow {
+    const uint4* node32;
+    const float4* tri48;
+    const uint32_t* sm;
+    const int32_t* sorted_tri;
+    float m[12];   // psm_instance.world_from_object
+};
+static_assert(sizeof(WorldRow) == 80, "a table row is 80 bytes");
+
+// a node of the tree over the instances, 64 B: both children's float32 boxes and two links (>= 0: a node, < 0: ~instance)
+//   w0 = L.lo.xyz L.hi.x | w1 = L.hi.yz R.lo.xy | w2 = R.lo.z R.hi.xyz | w3 = linkL linkR 0 0
+struct WorldNode {
+    float4 w0, w1, w2;
+    int4 w3;
+};
+static_assert(sizeof(WorldNode) == 64, "a node record is 64 bytes");
+
+struct WorldArgs {
+    const float4* rays;      // as QueryArgs
+    size_t n;
+    int* spill;
+    float4* hits;
+    uint8_t* occluded;
+    uint32_t* count;
+    int32_t* geom;           // the winning instance per query, -1 on a miss
+    uint32_t samples;
+    int root;                // 0: the tree's root node; < 0: ~instance of a world of one
+    const WorldRow* rows;
+    const WorldNode* nodes;
+};
+
+namespace {
+
+constexpr int SM_M = 0, SM_COUNT = 24, SM_ROOT = 25;   // bvh.hip: d_small
+constexpr int QUERY_BLOCK = 64, QSTACK_LDS = 16, QSTACK_MAX = 96;   // query.hip
+#ifndef PSM_QUERY_GRID_CAP
+#define PSM_QUERY_GRID_CAP 8192
+#endif
+constexpr uint32_t QUERY_GRID_CAP = PSM_QUERY_GRID_CAP;
+constexpr int WORLD_TOP = 0x40000000;   // tag of a top-level node link (hierarchy node links stay below 2^28)
+
+// The padding and the slacks (DESIGN.md 4.11 has the derivation). The box test works on the world query and the forward image
+// of the object box, T + R box; the candidate test on the query moved by inst_point / inst_rotate, R^T (x - T). They differ by
+//   * the move's rounding: one subtraction, three products, two sums per coordinate: <= 4 eps sqrt 3 (|x| + |T|) ~ 4.2e-7 (...)
+//   * R^T R = 1 + E, |E_ij| <= 1e-5 (pose_fault): R^-T - R = -R E (1 + E)^-1, a displacement of <= 3e-5 sqrt 3 = 5.2e-5 times
+//     the largest object coordinate, and |R^T d| = 1 +- 1.5e-5: world distances are object distances to 1.5e-5 (squares: 3e-5)
+//   * tri_query's 1e-5 tolerance on u, v, u + v: a counted crossing lies within 1e-5 of an edge length (<= 2 sqrt 3 times the
+//     largest object coordinate) of its triangle: 3.5e-5
+// in all <= 8.8e-5 S in position, S the largest of: the object box's largest |coordinate|, |T|, the world box's largest
+// |coordinate| -- plus 4.2e-7 of the query's largest |coordinate|. WORLD_PAD = WORLD_QSLACK = 2^-11 = 4.9e-4 (5.5x and > 1000x).
+// Distances: WORLD_TSLACK = 2^-12 = 2.4e-4 on t (16x 1.5e-5), WORLD_PSLACK = 2^-11 on d2 (16x 3e-5).
+constexpr float WORLD_PAD = 0x1p-11f;      // a leaf box grows by WORLD_PAD * S + WORLD_FLOOR on every side
+constexpr float WORLD_FLOOR = 0x1p-100f;   // ... so no box is ever degenerate (the NaN argument at WorldRay::slab)
+constexpr float WORLD_QSLACK = 0x1p-11f;   // ... and by WORLD_QSLACK * the query's largest |coordinate| at the test
+constexpr float WORLD_TSLACK = 0x1p-12f;   // a ray's prune against best / tmax / tmin: relative
+constexpr float WORLD_PSLACK = 0x1p-11f;   // a point's prune against best d2 / rmax^2: relative
+
+// ---- copied from query.hip (its kernels keep their code; see the comments there) ---------------------------------------------
+
+PSM_D bool w_tri_query(const float4* __restrict__ tri48, int tri, v3 orig, v3 dir, float& T, float& U, float& V) {
+    const float4 a = tri48[(size_t)3 * tri + 0], b = tri48[(size_t)3 * tri + 1], c = tri48[(size_t)3 * tri + 2];
+    const v3 v0 = mk3(a.x, a.y, a.z), e1 = mk3(b.x, b.y, b.z), e2 = mk3(c.x, c.y, c.z);
+    const v3 pvec = cross3(dir, e2);
+    const float det = dot3(e1, pvec);
+    if (pabs(det) <= 0.0f) return false;
+    const float invDev = 1.f / det;
+    const v3 tvec = orig - v0;
+    const float u = dot3(tvec, pvec) * invDev;
+    if (u < -0.00001f || u > 1.00001f) return false;
+    const v3 qvec = cross3(tvec, e1);
+    const float v = dot3(dir, qvec) * invDev;
+    if (v < -0.00001f || (u + v) > 1.00001f) return false;
+    T = dot3(e2, qvec) * invDev;
+    U = u;
+    V = v;
+    return true;
+}
+
+PSM_D bool finite3(v3 a) { return __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z); }
+
+struct Row {
+    float P, h;
+};
+PSM_D Row affine_row(const float* M, int k, v3 x) {
+    const float m0 = M[4 * k + 0], m1 = M[4 * k + 1], m2 = M[4 * k + 2], m3 = M[4 * k + 3];
+    Row r;
+    r.P = ((m0 * x.x + m1 * x.y) + m2 * x.z) + m3;
+    const float S = ((pabs(m0 * x.x) + pabs(m1 * x.y)) + pabs(m2 * x.z)) + pabs(m3);
+    r.h = (2.0f + S) * 0x1p-16f;
+    return r;
+}
+
+struct Axis {
+    float inv, nlo, nhi;
+};
+PSM_D Axis ray_axis(const float* M, int k, v3 o, v3 d) {
+    const float m0 = M[4 * k + 0], m1 = M[4 * k + 1], m2 = M[4 * k + 2];
+    const Row r = affine_row(M, k, o);
+    float D = (m0 * d.x + m1 * d.y) + m2 * d.z;
+    if (!(pabs(D) >= 1e-20f)) D = __builtin_copysignf(1e-20f, D);
+    Axis a;
+    a.inv = 1.0f / D;
+    a.nlo = -(r.P + r.h) * a.inv;
+    a.nhi = (r.h - r.P) * a.inv;
+    return a;
+}
+
+PSM_D void slab(const Axis& X, const Axis& Y, const Axis& Z, float mnx, float mny, float mnz, float mxx, float mxy, float mxz,
+                float& tNear, float& tFar) {
+    const float ax = fmaf(mnx, X.inv, X.nlo), bx = fmaf(mxx, X.inv, X.nhi);
+    const float ay = fmaf(mny, Y.inv, Y.nlo), by = fmaf(mxy, Y.inv, Y.nhi);
+    const float az = fmaf(mnz, Z.inv, Z.nlo), bz = fmaf(mxz, Z.inv, Z.nhi);
+    tNear = smaxf(smaxf(sminf(ax, bx), sminf(ay, by)), sminf(az, bz));
+    tFar = sminf(sminf(smaxf(ax, bx), smaxf(ay, by)), smaxf(az, bz));
+}
+
+PSM_D float4 miss_hit() { return make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1)); }
+
+PSM_D float clamp01(float x) {
+    x = x > 0.f ? x : 0.f;
+    return x < 1.f ? x : 1.f;
+}
+
+PSM_D float closest_on_tri(v3 v0, v3 e1, v3 e2, v3 p, float& U, float& V) {
+    const v3 ap = p - v0;
+    const float aa = dot3(e1, e1), ab = dot3(e1, e2), bb = dot3(e2, e2);
+    const float d1 = dot3(e1, ap), d2 = dot3(e2, ap);
+    const float d3 = d1 - aa, d4 = d2 - ab, d5 = d1 - ab, d6 = d2 - bb;
+    const float vc = aa * d2 - ab * d1;
+    const float vb = bb * d1 - ab * d2;
+    const float va = d3 * d6 - d5 * d4;
+    const float e43 = d4 - d3, e56 = d5 - d6;
+    const float det = aa * bb - ab * ab;
+    const v3 e21 = e2 - e1;
+    const float cc = dot3(e21, e21);
+    const bool sa = aa >= bb && aa >= cc, sb = bb >= cc;
+    int reg = sa ? 7 : (sb ? 8 : 9);
+    float n1 = sa ? d1 : (sb ? d2 : e43), q1d = sa ? aa : (sb ? bb : cc);
+    if (det > (aa * bb) * 0x1p-16f) { reg = 6; n1 = vb; q1d = det; }
+    if (va <= 0.f && e43 >= 0.f && e56 >= 0.f && e43 + e56 > 0.f) { reg = 5; n1 = e43; q1d = e43 + e56; }
+    if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f && d2 - d6 > 0.f) { reg = 4; n1 = d2; q1d = d2 - d6; }
+    if (d6 >= 0.f && d5 <= d6) { reg = 3; n1 = 0.f; q1d = 1.f; }
+    if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f && d1 - d3 > 0.f) { reg = 2; n1 = d1; q1d = d1 - d3; }
+    if (d3 >= 0.f && d4 <= d3) { reg = 1; n1 = 0.f; q1d = 1.f; }
+    if (d1 <= 0.f && d2 <= 0.f) { reg = 0; n1 = 0.f; q1d = 1.f; }
+    const float q1 = n1 / q1d;
+    const float q2 = (reg == 6 ? vc : 0.f) / (reg == 6 ? det : 1.f);
+    const float c1 = clamp01(q1);
+    float u = 0.f, v = 0.f;
+    if (reg == 1) u = 1.f;
+    if (reg == 2) u = q1;
+    if (reg == 3) v = 1.f;
+    if (reg == 4) v = q1;
+    if (reg == 5) { u = 1.f - q1; v = q1; }
+    if (reg == 6) {
+        u = c1;
+        const float f = q2 > 0.f ? q2 : 0.f, lim = 1.f - c1;
+        v = f < lim ? f : lim;
+    }
+    if (reg == 7) u = c1;
+    if (reg == 8) v = c1;
+    if (reg == 9) { u = 1.f - c1; v = c1; }
+    const v3 c = mk3((v0.x + u * e1.x) + v * e2.x, (v0.y + u * e1.y) + v * e2.y, (v0.z + u * e1.z) + v * e2.z);
+    const v3 dp = p - c;
+    U = u;
+    V = v;
+    return dot3(dp, dp);
+}
+
+struct PointBound {
+    float il0, il1, il2;
+    float wf;
+    bool orth;
+};
+PSM_D PointBound point_bound(const float* M) {
+    PointBound b;
+    float il[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float lam = sqrtf(dot3(mk3(M[4 * k], M[4 * k + 1], M[4 * k + 2]), mk3(M[4 * k], M[4 * k + 1], M[4 * k + 2])));
+        il[k] = lam > 0.f ? 1.0f / lam : 0.f;
+    }
+    const v3 r0 = mk3(M[0], M[1], M[2]), r1 = mk3(M[4], M[5], M[6]), r2 = mk3(M[8], M[9], M[10]);
+    const float c01 = pabs(dot3(r0, r1)) * il[0] * il[1], c02 = pabs(dot3(r0, r2)) * il[0] * il[2];
+    const float c12 = pabs(dot3(r1, r2)) * il[1] * il[2];
+    const float cmax = smaxf(smaxf(c01, c02), c12) + 0x1p-20f;
+    b.il0 = il[0];
+    b.il1 = il[1];
+    b.il2 = il[2];
+    b.orth = cmax <= 0x1p-11f && il[0] > 0.f && il[1] > 0.f && il[2] > 0.f;
+    b.wf = b.orth ? (1.0f - 0x1p-18f) / (1.0f + 2.0f * cmax) : (1.0f - 0x1p-18f);
+    return b;
+}
+
+struct PointImage {
+    float Px, Py, Pz, h;
+
+    PSM_D void set(const float* M, v3 p) {
+        const Row X = affine_row(M, 0, p), Y = affine_row(M, 1, p), Z = affine_row(M, 2, p);
+        Px = X.P;
+        Py = Y.P;
+        Pz = Z.P;
+        h = smaxf(smaxf(X.h, Y.h), Z.h);
+    }
+    PSM_D float lb2(const PointBound& B, float mnx, float mny, float mnz, float mxx, float mxy, float mxz) const {
+        const float tx = smaxf(smaxf(mnx - Px, Px - mxx) - h, 0.f) * B.il0;
+        const float ty = smaxf(smaxf(mny - Py, Py - mxy) - h, 0.f) * B.il1;
+        const float tz = smaxf(smaxf(mnz - Pz, Pz - mxz) - h, 0.f) * B.il2;
+        const float m = smaxf(smaxf(tx, ty), tz);
+        return (B.orth ? ((tx * tx + ty * ty) + tz * tz) : m * m) * B.wf;
+    }
+    PSM_D void children(const PointBound& B, uint4 n0, uint4 n1, float best, bool& okL, bool& okR, float& kL, float& kR) const {
+        kL = lb2(B, half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z));
+        kR = lb2(B, half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y));
+        okL = kL <= best;
+        okR = kR <= best;
+    }
+};
+
+__device__ const float W_INSIDE_DIR[PSM_INSIDE_MAX_SAMPLES][3] = PSM_INSIDE_DIRECTIONS;
+
+PSM_D v3 inst_rotate(const float* m, v3 d) {
+    return mk3((m[0] * d.x + m[4] * d.y) + m[8] * d.z, (m[1] * d.x + m[5] * d.y) + m[9] * d.z, (m[2] * d.x + m[6] * d.y) + m[10] * d.z);
+}
+PSM_D v3 inst_point(const float* m, v3 x) { return inst_rotate(m, mk3(x.x - m[3], x.y - m[7], x.z - m[11])); }
+
+// ---- the two-level walk --------------------------------------------------------------------------------------------------------
+
+// The body:
+//   bool begin(i, alive)     load query i, clear the running state, set up the WORLD query the top level tests; false: a miss
+//   void top(w0, w1, w2, okL, okR, kL, kR)   a top-level node's two boxes: kept or not, and the order key (nearer first)
+//   int  enter(inst)         load the instance's row, move the query (re-read from memory, as 4.9), do the per-geometry set-up,
+//                            test the lone leaf of a one-leaf hierarchy; returns the hierarchy's root to walk, -1 for none
+//                            (fewer than two leaves, or the moved query is invalid in this instance)
+//   children, leaf, done, again, finish: as query.hip's scene_walk
+// Every loop here is bounded: the node loop by the two trees (each iteration visits a node or an instance once per walk), the
+// leaf loop by two, the outer ones by the batch and the sample count.
+template <class Body>
+PSM_D void world_walk(const WorldArgs& w, Body& q) {
+    __shared__ int stack[QSTACK_LDS][QUERY_BLOCK];
+    const int lane = (int)threadIdx.x;
+    __builtin_assume(lane >= 0 && lane < QUERY_BLOCK);
+    const size_t spill_stride = (size_t)gridDim.x * QUERY_BLOCK;
+    int* __restrict__ spill = w.spill + (size_t)blockIdx.x * QUERY_BLOCK + lane;
+    for (size_t i = (size_t)blockIdx.x * QUERY_BLOCK + (size_t)lane; i - (size_t)lane < w.n; i += spill_stride) {
+        const bool alive = i < w.n;
+        const bool valid = q.begin(i, alive);
+        do {
+            int cur = w.root < 0 ? w.root : (w.root | WORLD_TOP), sp = 0;
+            bool walking = valid;
+            while (walking) {
+                bool pop = false;
+                if (cur < 0) {
+                    const int r = q.enter(~cur);
+                    pop = r < 0;
+                    cur = r;
+                } else if (cur & WORLD_TOP) {
+                    const WorldNode* np = (const WorldNode*)((const char*)w.nodes + ((size_t)(uint32_t)(cur & ~WORLD_TOP) << 6));
+                    const float4 w0 = np->w0, w1 = np->w1, w2 = np->w2;
+                    const int4 w3 = np->w3;
+                    bool okL, okR;
+                    float kL, kR;
+                    q.top(w0, w1, w2, okL, okR, kL, kR);
+                    const int lkL = w3.x < 0 ? w3.x : (w3.x | WORLD_TOP), lkR = w3.y < 0 ? w3.y : (w3.y | WORLD_TOP);
+                    const bool leftFirst = okL && (!okR || kL <= kR);   // nearer child first
+                    const int first = leftFirst ? lkL : lkR, second = leftFirst ? lkR : lkL;
+                    if (okL && okR) {
+                        // (sp < QSTACK_MAX always: psm_world_set_instances refuses a world whose two depths exceed it)
+                        if (sp < QSTACK_LDS) stack[sp][lane] = second;
+                        else if (sp < QSTACK_MAX) spill[(size_t)(sp - QSTACK_LDS) * spill_stride] = second;
+                        sp++;
+                    }
+                    cur = first;
+                    pop = !(okL || okR);
+                } else {
+                    const uint4* np = (const uint4*)((const char*)q.node32 + ((uint32_t)cur << 5));
+                    const uint4 n0 = np[0], n1 = np[1];
+                    const int lkx = (int)n1.z, lky = (int)n1.w;
+                    bool okL, okR;
+                    float kL, kR;
+                    q.children(n0, n1, okL, okR, kL, kR);
+                    const bool leafL = okL && lkx < 0, leafR = okR && lky < 0;
+                    int t0 = leafL ? ~lkx : (leafR ? ~lky : -1);
+                    int t1 = (leafL && leafR) ? ~lky : -1;
+                    while (t0 >= 0) {
+                        q.leaf(t0);
+                        t0 = t1;
+                        t1 = -1;
+                    }
+                    const bool intL = okL && !leafL, intR = okR && !leafR;
+                    const bool leftFirst = intL && (!intR || kL <= kR);
+                    const int first = leftFirst ? lkx : lky, second = leftFirst ? lky : lkx;
+                    if (intL && intR) {
+                        if (sp < QSTACK_LDS) stack[sp][lane] = second;
+                        else if (sp < QSTACK_MAX) spill[(size_t)(sp - QSTACK_LDS) * spill_stride] = second;
+                        sp++;
+                    }
+                    cur = first;
+                    pop = !(intL || intR);
+                }
+                if (q.done()) break;
+                if (pop) {
+                    if (sp == 0) break;
+                    sp--;
+                    cur = sp < QSTACK_LDS ? stack[sp][lane] : spill[(size_t)(sp - QSTACK_LDS) * spill_stride];
+                }
+            }
+        } while (q.again());
+        if (alive) q.finish(i);
+    }
+}
+
+// The best record of a world (closest hit and closest point; `best` is t or d2). The tree visits the instances in tree order,
+// so SceneBest's one-key trick does not carry over: a candidate (x, inst, tri) wins iff x < best, or x == best and (inst, tri)
+// is lexicographically lower than the record's (no record: binst = btri = -1, the largest as unsigned). Boxes are kept with <=.
+struct WorldBest {
+    float best, bu, bv;
+    int btri, binst;
+    PSM_D void clear(float bound) {
+        best = bound;
+        bu = 0.f;
+        bv = 0.f;
+        btri = -1;
+        binst = -1;
+    }
+    PSM_D bool wins(float x, int inst, int tri) const {
+        return x < best || (x == best && ((uint32_t)inst < (uint32_t)binst || (inst == binst && (uint32_t)tri < (uint32_t)btri)));
+    }
+    PSM_D void take(float x, float u, float v, int inst, int tri) {
+        best = x;
+        bu = u;
+        bv = v;
+        btri = tri;
+        binst = inst;
+    }
+};
+
+// the row of instance `in`, by five aligned 16-byte loads; the lane keeps the two pointers its walk needs
+struct RowLoad {
+    const uint32_t* sm;
+    const int32_t* sorted_tri;
+    float m[12];
+};
+template <class Q>
+PSM_D RowLoad load_row(const WorldArgs& w, int in, Q& q) {
+    const uint4* rp = (const uint4*)(w.rows + in);
+    const uint4 a = rp[0], b = rp[1], c = rp[2], d = rp[3], e = rp[4];
+    q.node32 = (const uint4*)(((uint64_t)a.y << 32) | a.x);
+    q.tri48 = (const float4*)(((uint64_t)a.w << 32) | a.z);
+    q.inst = in;
+    RowLoad r;
+    r.sm = (const uint32_t*)(((uint64_t)b.y << 32) | b.x);
+    r.sorted_tri = (const int32_t*)(((uint64_t)b.w << 32) | b.z);
+    r.m[0] = u2f(c.x); r.m[1] = u2f(c.y); r.m[2] = u2f(c.z); r.m[3] = u2f(c.w);
+    r.m[4] = u2f(d.x); r.m[5] = u2f(d.y); r.m[6] = u2f(d.z); r.m[7] = u2f(d.w);
+    r.m[8] = u2f(e.x); r.m[9] = u2f(e.y); r.m[10] = u2f(e.z); r.m[11] = u2f(e.w);
+    return r;
+}
+
+// A ray in a world: the object-space ray of the instance the lane is in (query.hip's SceneRay) and the WORLD ray the top level
+// tests: origin, reciprocal of the unit direction (normalize3 of the direction as given: SceneRay::aim's), the query's pad.
+struct WorldRay {
+    const uint4* node32;
+    const float4* tri48;
+    int inst;
+    v3 o, d;
+    float tmin, tmax;
+    Axis X, Y, Z;
+    v3 wo, wiv;
+    float qpad;
+    bool nocull;   // the world direction is no unit vector (zero, non-finite, overflowed): every box is kept
+
+    PSM_D void world_ray(v3 orig, v3 dir) {
+        wo = orig;
+        const v3 dn = normalize3(dir);
+        nocull = !(finite3(dn) && dot3(dn, dn) > 0.5f);
+        wiv = mk3(1.0f / dn.x, 1.0f / dn.y, 1.0f / dn.z);   // (+-inf for an axis-aligned ray)
+        qpad = WORLD_QSLACK * smaxf(smaxf(pabs(orig.x), pabs(orig.y)), pabs(orig.z));
+    }
+    // The slab test of a world box, grown by qpad. minNum / maxNum: on an axis the ray is parallel to, wiv is
+    // +-inf and a plane distance is -inf, +inf or (the origin exactly in the plane: 0 x inf) NaN, which sminf / smaxf ignore.
+    // "Passes a leaf's box => passes every ancestor's": an inner box is the exact min / max union of leaf boxes, float
+    // subtraction and multiplication by one factor are monotone, so on an axis with a finite wiv an ancestor's interval
+    // contains the leaf's. On a parallel axis a leaf passes only with its origin strictly between the grown planes (-inf, +inf:
+    // no constraint) -- a leaf box has lo < hi on every axis (WORLD_FLOOR), so one NaN always comes with an infinity of the
+    // failing sign, and two NaN never -- and strictly between a leaf's planes is strictly between every ancestor's.
+    PSM_D void slab(float lx, float ly, float lz, float hx, float hy, float hz, float& tNear, float& tFar) const {
+        const float ax = ((lx - qpad) - wo.x) * wiv.x, bx = ((hx + qpad) - wo.x) * wiv.x;
+        const float ay = ((ly - qpad) - wo.y) * wiv.y, by = ((hy + qpad) - wo.y) * wiv.y;
+        const float az = ((lz - qpad) - wo.z) * wiv.z, bz = ((hz + qpad) - wo.z) * wiv.z;
+        tNear = smaxf(smaxf(sminf(ax, bx), sminf(ay, by)), sminf(az, bz));
+        tFar = sminf(sminf(smaxf(ax, bx), smaxf(ay, by)), smaxf(az, bz));
+    }
+    // both boxes of a top-level node against [tmin, lim], slackened; written as negations so that a NaN bound keeps the box
+    PSM_D void top_boxes(float4 w0, float4 w1, float4 w2, float lim, bool& okL, bool& okR, float& nL, float& nR) const {
+        float fL, fR;
+        slab(w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, nL, fL);
+        slab(w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, nR, fR);
+        const float hi = lim + WORLD_TSLACK * pabs(lim), lo = tmin - WORLD_TSLACK * pabs(tmin);
+        okL = nocull | (!(nL > fL) & !(nL > hi) & !(fL < lo));
+        okR = nocull | (!(nR > fR) & !(nR > hi) & !(fR < lo));
+    }
+    // enter(): the world ray (orig, dir as given) moved into instance `in` as query.hip's inst_ray moves it, then the axes
+    PSM_D int enter_ray(const WorldArgs& w, int in, v3 orig, v3 dir, const int32_t*& sorted_tri, uint32_t& count) {
+        const RowLoad r = load_row(w, in, *this);
+        o = inst_point(r.m, orig);
+        d = normalize3(inst_rotate(r.m, dir));
+        float M[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) M[k] = u2f(r.sm[SM_M + k]);
+        X = ray_axis(M, 0, o, d);
+        Y = ray_axis(M, 1, o, d);
+        Z = ray_axis(M, 2, o, d);
+        sorted_tri = r.sorted_tri;
+        count = r.sm[SM_COUNT];
+        const int root = (int)r.sm[SM_ROOT];
+        return (finite3(o) && finite3(d)) ? (root >= 0 ? root : -2) : -1;   // -2: valid here, no tree (0 or 1 leaves)
+    }
+    PSM_D void boxes(uint4 n0, uint4 n1, float lim, bool& okL, bool& okR, float& nL, float& nR) const {
+        float fL, fR;
+        psm::slab(X, Y, Z, half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z), nL, fL);
+        psm::slab(X, Y, Z, half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y), nR, fR);
+        okL = (nL <= fL) & (nL <= lim) & (fL >= tmin);
+        okR = (nR <= fR) & (nR <= lim) & (fR >= tmin);
+    }
+};
+
+// closest hit (ANY = false) and any hit (ANY = true)
+template <bool ANY>
+struct WorldRayBody : WorldRay {
+    const WorldArgs& w;
+    WorldBest b;
+    bool found, alive;
+    size_t idx;
+
+    PSM_D WorldRayBody(const WorldArgs& a) : w(a) {}
+    PSM_D bool begin(size_t i, bool al) {
+        idx = i;
+        alive = al;
+        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(1.f, 0.f, 0.f, -1.f);
+        if (al) { r0 = w.rays[2 * i]; r1 = w.rays[2 * i + 1]; }
+        tmin = r0.w;
+        tmax = r1.w;
+        world_ray(mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z));
+        b.clear(tmax);
+        found = false;
+        return al && tmin <= tmax;
+    }
+    PSM_D void top(float4 w0, float4 w1, float4 w2, bool& okL, bool& okR, float& nL, float& nR) const {
+        top_boxes(w0, w1, w2, ANY ? tmax : b.best, okL, okR, nL, nR);
+    }
+    PSM_D int enter(int in) {
+        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(1.f, 0.f, 0.f, 0.f);
+        if (alive) { r0 = w.rays[2 * idx]; r1 = w.rays[2 * idx + 1]; }
+        const int32_t* st;
+        uint32_t count;
+        const int r = enter_ray(w, in, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), st, count);
+        if (r != -1 && count == 1u) leaf(st[0]);
+        return r;
+    }
+    PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& nL, float& nR) const {
+        boxes(n0, n1, ANY ? tmax : b.best, okL, okR, nL, nR);
+    }
+    PSM_D void leaf(int tri) {
+        float t, u, v;
+        if (w_tri_query(tri48, tri, o, d, t, u, v) && t >= tmin && b.wins(t, inst, tri)) {
+            found = true;
+            if (!ANY) b.take(t, u, v, inst, tri);
+        }
+    }
+    PSM_D bool done() const { return ANY && found; }
+    PSM_D bool again() const { return false; }
+    PSM_D void finish(size_t i) const {
+        if (ANY) {
+            w.occluded[i] = found ? 1 : 0;
+        } else {
+            w.hits[i] = found ? make_float4(b.bu, b.bv, b.best, __int_as_float(b.btri)) : miss_hit();
+            w.geom[i] = b.binst;
+        }
+    }
+};
+
+// the counting ray (query.hip's CountRay): every candidate inside the window, summed over the instances entered
+struct WorldCountRay : WorldRay {
+    uint32_t count;
+    PSM_D void top(float4 w0, float4 w1, float4 w2, bool& okL, bool& okR, float& nL, float& nR) const {
+        top_boxes(w0, w1, w2, tmax, okL, okR, nL, nR);
+    }
+    PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& nL, float& nR) const { boxes(n0, n1, tmax, okL, okR, nL, nR); }
+    PSM_D void leaf(int tri) {
+        float t, u, v;
+        if (w_tri_query(tri48, tri, o, d, t, u, v) && t >= tmin && t <= tmax) count++;
+    }
+    PSM_D bool done() const { return false; }
+};
+
+struct WorldCountBody : WorldCountRay {
+    const WorldArgs& w;
+    bool alive;
+    size_t idx;
+    PSM_D WorldCountBody(const WorldArgs& a) : w(a) {}
+    PSM_D bool begin(size_t i, bool al) {
+        idx = i;
+        alive = al;
+        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(1.f, 0.f, 0.f, -1.f);
+        if (al) { r0 = w.rays[2 * i]; r1 = w.rays[2 * i + 1]; }
+        tmin = r0.w;
+        tmax = r1.w;
+        world_ray(mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z));
+        count = 0u;
+        return al && tmin <= tmax;
+    }
+    PSM_D int enter(int in) {
+        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(1.f, 0.f, 0.f, 0.f);
+        if (alive) { r0 = w.rays[2 * idx]; r1 = w.rays[2 * idx + 1]; }
+        const int32_t* st;
+        uint32_t cnt;
+        const int r = enter_ray(w, in, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), st, cnt);
+        if (r != -1 && cnt == 1u) leaf(st[0]);
+        return r;
+    }
+    PSM_D bool again() const { return false; }
+    PSM_D void finish(size_t i) const { w.count[i] = count; }
+};
+
+// inside / the sign of a closest-point result: ray k is the WORLD ray {p, 0, PSM_INSIDE_DIRECTIONS[k], +inf}; its crossings are
+// summed over every instance it reaches before it votes; again() restarts the top-level walk for the next direction
+template <bool SIGN>
+struct WorldInsideBody : WorldCountRay {
+    const WorldArgs& w;
+    uint32_t k, votes;
+    float dist;
+    bool valid, alive;
+    size_t idx;
+
+    PSM_D WorldInsideBody(const WorldArgs& a) : w(a) {}
+    PSM_D v3 dir() const {
+        const int r = __builtin_amdgcn_readfirstlane((int)k);   // (every lane of the wave is at the same k)
+        return mk3(W_INSIDE_DIR[r][0], W_INSIDE_DIR[r][1], W_INSIDE_DIR[r][2]);
+    }
+    PSM_D float4 point() const {
+        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
+        if (alive) q = w.rays[idx];
+        return q;
+    }
+    PSM_D bool begin(size_t i, bool al) {
+        idx = i;
+        alive = al;
+        const float4 q = point();
+        k = 0u;
+        votes = 0u;
+        count = 0u;
+        dist = 0.f;
+        tmin = 0.f;
+        tmax = __builtin_inff();
+        valid = al;
+        if (SIGN) {
+            float4 h = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+            if (al) h = w.hits[i];
+            dist = h.z;
+            valid = __float_as_int(h.w) >= 0;
+        }
+        valid = finite3(mk3(q.x, q.y, q.z)) && valid;   // (a non-finite p: outside)
+        world_ray(mk3(q.x, q.y, q.z), dir());
+        return valid;
+    }
+    PSM_D int enter(int in) {
+        const float4 q = point();
+        const int32_t* st;
+        uint32_t cnt;
+        const int r = enter_ray(w, in, mk3(q.x, q.y, q.z), dir(), st, cnt);
+        if (r != -1 && cnt == 1u) leaf(st[0]);
+        return r;
+    }
+    PSM_D bool again() {
+        votes += count & 1u;
+        k++;
+        if (!valid || k >= w.samples) return false;
+        count = 0u;
+        const float4 q = point();
+        world_ray(mk3(q.x, q.y, q.z), dir());
+        return true;
+    }
+    PSM_D void finish(size_t i) const {
+        const bool in = 2u * votes > w.samples;
+        if (!SIGN) w.occluded[i] = in ? 1 : 0;
+        else if (in) ((float*)(w.hits + i))[2] = __uint_as_float(__float_as_uint(dist) | 0x80000000u);
+    }
+};
+
+// closest point (WITHIN = false) and within radius (WITHIN = true): query.hip's InstPointBody; the top level tests the WORLD
+// point's squared distance to a box grown by qpad against the best d2 (an object-space value: equal to the world one to 3e-5)
+template <bool WITHIN>
+struct WorldPointBody {
+    const WorldArgs& w;
+    const uint4* node32;
+    const float4* tri48;
+    int inst;
+    PointBound B;
+    v3 p, wp;
+    float rmax, qpad;
+    WorldBest b;
+    bool found, alive;
+    size_t idx;
+    PointImage P;
+
+    PSM_D WorldPointBody(const WorldArgs& a) : w(a) {}
+    PSM_D float4 point() const {
+        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
+        if (alive) q = w.rays[idx];
+        return q;
+    }
+    PSM_D bool begin(size_t i, bool al) {
+        idx = i;
+        alive = al;
+        const float4 q = point();
+        wp = mk3(q.x, q.y, q.z);
+        qpad = WORLD_QSLACK * smaxf(smaxf(pabs(q.x), pabs(q.y)), pabs(q.z));
+        rmax = q.w;
+        b.clear((q.w * q.w) * 1.00000095367431640625f + 0x1p-126f);   // (query.hip PointBody::begin)
+        found = false;
+        return al && finite3(wp) && q.w >= 0.f;
+    }
+    PSM_D float gap2(float lx, float ly, float lz, float hx, float hy, float hz) const {
+        const float tx = smaxf(smaxf((lx - qpad) - wp.x, wp.x - (hx + qpad)), 0.f);
+        const float ty = smaxf(smaxf((ly - qpad) - wp.y, wp.y - (hy + qpad)), 0.f);
+        const float tz = smaxf(smaxf((lz - qpad) - wp.z, wp.z - (hz + qpad)), 0.f);
+        return (tx * tx + ty * ty) + tz * tz;
+    }
+    PSM_D void top(float4 w0, float4 w1, float4 w2, bool& okL, bool& okR, float& kL, float& kR) const {
+        kL = gap2(w0.x, w0.y, w0.z, w0.w, w1.x, w1.y);
+        kR = gap2(w1.z, w1.w, w2.x, w2.y, w2.z, w2.w);
+        const float lim = b.best + WORLD_PSLACK * b.best;
+        okL = !(kL > lim);
+        okR = !(kR > lim);
+    }
+    PSM_D int enter(int in) {
+        const float4 q = point();
+        const RowLoad r = load_row(w, in, *this);
+        p = inst_point(r.m, mk3(q.x, q.y, q.z));
+        float M[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) M[k] = u2f(r.sm[SM_M + k]);
+        B = point_bound(M);
+        P.set(M, p);
+        if (!finite3(p)) return -1;
+        if (r.sm[SM_COUNT] == 1u) leaf(r.sorted_tri[0]);
+        const int root = (int)r.sm[SM_ROOT];
+        return root >= 0 ? root : -2;
+    }
+    PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& kL, float& kR) const {
+        P.children(B, n0, n1, b.best, okL, okR, kL, kR);
+    }
+    PSM_D void leaf(int tri) {
+        const float4 A = tri48[(size_t)3 * tri + 0], Bv = tri48[(size_t)3 * tri + 1], Cv = tri48[(size_t)3 * tri + 2];
+        float u, v;
+        const float d2 = closest_on_tri(mk3(A.x, A.y, A.z), mk3(Bv.x, Bv.y, Bv.z), mk3(Cv.x, Cv.y, Cv.z), p, u, v);
+        if (sqrtf(d2) <= rmax && b.wins(d2, inst, tri)) {
+            found = true;
+            if (!WITHIN) b.take(d2, u, v, inst, tri);
+        }
+    }
+    PSM_D bool done() const { return WITHIN && found; }
+    PSM_D bool again() const { return false; }
+    PSM_D void finish(size_t i) const {
+        if (WITHIN) {
+            w.occluded[i] = found ? 1 : 0;
+        } else {
+            w.hits[i] = found ? make_float4(b.bu, b.bv, sqrtf(b.best), __int_as_float(b.btri)) : miss_hit();
+            w.geom[i] = b.binst;
+        }
+    }
+};
+
+template <class Body>
+PSM_D void world_body(const WorldArgs& w) {
+    Body q(w);
+    world_walk(w, q);
+}
+
+}  // namespace
+
+// The lane's two hierarchy pointers, its instance index and the world ray beside the object ray do not fit 64 VGPRs: the
+// kernels are built for 4 waves per SIMD (128 VGPRs), without spills or scratch (tests/test_world_query_cpu.py holds the counts).
+__global__ __launch_bounds__(QUERY_BLOCK, 4) void world_query_closest(WorldArgs w) { world_body<WorldRayBody<false>>(w); }
+__global__ __launch_bounds__(QUERY_BLOCK, 4) void world_query_any(WorldArgs w) { world_body<WorldRayBody<true>>(w); }
+__global__ __launch_bounds__(QUERY_BLOCK, 4) void world_query_point(WorldArgs w) { world_body<WorldPointBody<false>>(w); }
+__global__ __launch_bounds__(QUERY_BLOCK, 4) void world_query_within(WorldArgs w) { world_body<WorldPointBody<true>>(w); }
+__global__ __launch_bounds__(QUERY_BLOCK, 4) void world_query_count(WorldArgs w) { world_body<WorldCountBody>(w); }
+__global__ __launch_bounds__(QUERY_BLOCK, 4) void world_query_inside(WorldArgs w) { world_body<WorldInsideBody<false>>(w); }
+__global__ __launch_bounds__(QUERY_BLOCK, 4) void world_query_sign(WorldArgs w) { world_body<WorldInsideBody<true>>(w); }
+
+// ---- set-up kernels: boxes, Morton keys, the tree, its boxes (correct and free of host round trips; not tuned) -----------------
+
+struct WorldSrc {   // a distinct hierarchy of a world: its triangles as the candidate tests read them
+    const float4* tri48;
+    uint32_t tris;
+    uint32_t pad;
+};
+
+// the object-space box of each distinct hierarchy: min / max over v0, v0 + e1, v0 + e2 of ALL its loaded triangles -- a superset
+// of the kept ones (a triangle the build dropped only widens the box); a NaN coordinate is ignored (fminf / fmaxf)
+__global__ __launch_bounds__(256) void world_obj_boxes(const WorldSrc* __restrict__ src, float4* __restrict__ obox) {
+    __shared__ float red[6][256];
+    const WorldSrc s = src[blockIdx.x];
+    const float inf = __builtin_inff();
+    float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
+    for (uint32_t t = threadIdx.x; t < s.tris; t += 256u) {
+        const float4 a = s.tri48[(size_t)3 * t], b = s.tri48[(size_t)3 * t + 1], c = s.tri48[(size_t)3 * t + 2];
+        const float v[3][3] = {{a.x, a.y, a.z}, {a.x + b.x, a.y + b.y, a.z + b.z}, {a.x + c.x, a.y + c.y, a.z + c.z}};
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) { lo[j] = fminf(lo[j], v[k][j]); hi[j] = fmaxf(hi[j], v[k][j]); }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; j++) { red[j][threadIdx.x] = lo[j]; red[3 + j][threadIdx.x] = hi[j]; }
+    __syncthreads();
+    for (int s2 = 128; s2 > 0; s2 >>= 1) {
+        if ((int)threadIdx.x < s2)
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                red[j][threadIdx.x] = fminf(red[j][threadIdx.x], red[j][threadIdx.x + s2]);
+                red[3 + j][threadIdx.x] = fmaxf(red[3 + j][threadIdx.x], red[3 + j][threadIdx.x + s2]);
+            }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        obox[2 * blockIdx.x] = make_float4(red[0][0], red[1][0], red[2][0], 0.f);
+        obox[2 * blockIdx.x + 1] = make_float4(red[3][0], red[4][0], red[5][0], 0.f);
+    }
+}
+
+// the padded world box of each instance: centre R c + T, half extent |R| e, grown by WORLD_PAD * S + WORLD_FLOOR. A hierarchy
+// without triangles (lo = +inf, hi = -inf) gets an inverted box that no query passes.
+__global__ __launch_bounds__(256) void world_inst_boxes(const WorldRow* __restrict__ rows, const uint32_t* __restrict__ slot,
+                                                        const float4* __restrict__ obox, uint32_t n, float4* __restrict__ box) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 lo = obox[2 * slot[i]], hi = obox[2 * slot[i] + 1];
+    const float* m = rows[i].m;
+    if (!(lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z)) {
+        box[2 * i] = make_float4(__builtin_inff(), __builtin_inff(), __builtin_inff(), 0.f);
+        box[2 * i + 1] = make_float4(-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), 0.f);
+        return;
+    }
+    const float c[3] = {0.5f * lo.x + 0.5f * hi.x, 0.5f * lo.y + 0.5f * hi.y, 0.5f * lo.z + 0.5f * hi.z};
+    const float e[3] = {0.5f * hi.x - 0.5f * lo.x, 0.5f * hi.y - 0.5f * lo.y, 0.5f * hi.z - 0.5f * lo.z};
+    float S = fmaxf(fmaxf(fmaxf(pabs(lo.x), pabs(hi.x)), fmaxf(pabs(lo.y), pabs(hi.y))), fmaxf(pabs(lo.z), pabs(hi.z)));
+    S = fmaxf(S, fmaxf(fmaxf(pabs(m[3]), pabs(m[7])), pabs(m[11])));
+    float cw[3], ew[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        cw[k] = ((m[4 * k] * c[0] + m[4 * k + 1] * c[1]) + m[4 * k + 2] * c[2]) + m[4 * k + 3];
+        ew[k] = (pabs(m[4 * k]) * e[0] + pabs(m[4 * k + 1]) * e[1]) + pabs(m[4 * k + 2]) * e[2];
+        S = fmaxf(S, pabs(cw[k]) + ew[k]);
+    }
+    const float pad = WORLD_PAD * S + WORLD_FLOOR;
+    box[2 * i] = make_float4((cw[0] - ew[0]) - pad, (cw[1] - ew[1]) - pad, (cw[2] - ew[2]) - pad, 0.f);
+    box[2 * i + 1] = make_float4((cw[0] + ew[0]) + pad, (cw[1] + ew[1]) + pad, (cw[2] + ew[2]) + pad, 0.f);
+}
+
+PSM_D float finite_or(float x, float y) { return __builtin_isfinite(x) ? x : y; }
+
+// the bounds of the finite box centres (one workgroup; at most 65 536 instances)
+__global__ __launch_bounds__(1024) void world_centre_bounds(const float4* __restrict__ box, uint32_t n, float4* __restrict__ bounds) {
+    __shared__ float red[6][1024];
+    const float inf = __builtin_inff();
+    float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
+    for (uint32_t i = threadIdx.x; i < n; i += 1024u) {
+        const float4 a = box[2 * i], b = box[2 * i + 1];
+        const float c[3] = {0.5f * a.x + 0.5f * b.x, 0.5f * a.y + 0.5f * b.y, 0.5f * a.z + 0.5f * b.z};
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+            if (__builtin_isfinite(c[j])) { lo[j] = fminf(lo[j], c[j]); hi[j] = fmaxf(hi[j], c[j]); }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; j++) { red[j][threadIdx.x] = lo[j]; red[3 + j][threadIdx.x] = hi[j]; }
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                red[j][threadIdx.x] = fminf(red[j][threadIdx.x], red[j][threadIdx.x + s]);
+                red[3 + j][threadIdx.x] = fmaxf(red[3 + j][threadIdx.x], red[3 + j][threadIdx.x + s]);
+            }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        bounds[0] = make_float4(red[0][0], red[1][0], red[2][0], 0.f);
+        bounds[1] = make_float4(red[3][0], red[4][0], red[5][0], 0.f);
+    }
+}
+
+// key = the 48-bit Morton code of the box centre (16 bits per axis over the centres' bounds) << 16 | the instance index: the
+// keys are distinct, the index breaks ties, and the tree over them is at most 64 levels deep
+__global__ __launch_bounds__(256) void world_morton(const float4* __restrict__ box, const float4* __restrict__ bounds, uint32_t n,
+                                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ idx) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = box[2 * i], b = box[2 * i + 1], lo = bounds[0], hi = bounds[1];
+    const float c[3] = {0.5f * a.x + 0.5f * b.x, 0.5f * a.y + 0.5f * b.y, 0.5f * a.z + 0.5f * b.z};
+    const float l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z};
+    uint32_t q[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const float ext = h[j] - l[j];
+        float f = (ext > 0.f && __builtin_isfinite(ext)) ? (finite_or(c[j], l[j]) - l[j]) / ext : 0.f;
+        f = f > 0.f ? f : 0.f;   // (NaN: 0)
+        f = f < 1.f ? f : 1.f;
+        const uint32_t v = (uint32_t)(f * 65536.0f);
+        q[j] = v < 65535u ? v : 65535u;
+    }
+    keys[i] = (morton3_64(q[0], q[1], q[2]) << 16) | (uint64_t)i;
+    idx[i] = i;
+}
+
+// the radix tree over the sorted distinct keys (Karras 2012): thread i makes internal node i; node 0 is the root. parent[]:
+// (node << 1 | side) for every internal node (entry i) and every leaf position (entry n - 1 + p); the root's is -1
+PSM_D int key_delta(const uint64_t* __restrict__ keys, int n, int i, int j) {
+    if (j < 0 || j >= n) return -1;
+    return __builtin_clzll(keys[i] ^ keys[j]);
+}
+__global__ __launch_bounds__(256) void world_emit(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx, uint32_t n,
+                                                  WorldNode* __restrict__ nodes, int* __restrict__ parent) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x), N = (int)n;
+    if (i >= N - 1) return;
+    const int d = key_delta(keys, N, i, i + 1) - key_delta(keys, N, i, i - 1) >= 0 ? 1 : -1;
+    const int dmin = key_delta(keys, N, i, i - d);
+    int lmax = 2;
+    while (lmax < 2 * N && key_delta(keys, N, i, i + lmax * d) > dmin) lmax *= 2;
+    int l = 0;
+    for (int t = lmax / 2; t >= 1; t /= 2)
+        if (key_delta(keys, N, i, i + (l + t) * d) > dmin) l += t;
+    const int j = i + l * d;
+    const int dnode = key_delta(keys, N, i, j);
+    int s = 0;
+    for (int t = l; t > 1;) {
+        t = (t + 1) >> 1;
+        if (key_delta(keys, N, i, i + (s + t) * d) > dnode) s += t;
+    }
+    const int gamma = i + s * d + (d < 0 ? -1 : 0);
+    const int lo = i < j ? i : j, hi = i < j ? j : i;
+    const bool leafL = lo == gamma, leafR = hi == gamma + 1;
+    nodes[i].w3 = make_int4(leafL ? ~(int)idx[gamma] : gamma, leafR ? ~(int)idx[gamma + 1] : gamma + 1, 0, 0);
+    parent[leafL ? N - 1 + gamma : gamma] = i << 1;
+    parent[leafR ? N - 1 + gamma + 1 : gamma + 1] = (i << 1) | 1;
+    if (i == 0) parent[0] = -1;
+}
+
+// The boxes, bottom-up: a thread per leaf position carries its subtree's box (and height) to the parent's record; the first
+// of a node's two children to arrive stops there, the second reads its sibling's half (written before the sibling's fence and
+// counter increment; read with agent-scope atomic loads, past this CU's vector cache) and carries the exact min / max union
+// further. Nobody waits for anybody: a thread leaves or goes on. Bounded by the tree's height.
+PSM_D float load_agent(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__global__ __launch_bounds__(256) void world_fit(const float4* __restrict__ box, const uint32_t* __restrict__ idx, uint32_t n,
+                                                 WorldNode* nodes, const int* __restrict__ parent, uint32_t* arrived, int* height,
+                                                 int* depth) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= n) return;
+    const float4 a = box[2 * idx[p]], b = box[2 * idx[p] + 1];
+    float lo[3] = {a.x, a.y, a.z}, hi[3] = {b.x, b.y, b.z};
+    int h = 0;
+    int par = parent[n - 1 + p];
+    while (par >= 0) {
+        const int node = par >> 1, side = par & 1;
+        float* rec = (float*)(nodes + node);
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            __hip_atomic_store(rec + 6 * side + j, lo[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(rec + 6 * side + 3 + j, hi[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __hip_atomic_store(height + 2 * node + side, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        if (atomicAdd(arrived + node, 1u) == 0u) return;
+        __threadfence();
+        const int other = side ^ 1;
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            lo[j] = fminf(lo[j], load_agent(rec + 6 * other + j));
+            hi[j] = fmaxf(hi[j], load_agent(rec + 6 * other + 3 + j));
+        }
+        const int ho = __hip_atomic_load(height + 2 * node + other, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        h = (h > ho ? h : ho) + 1;
+        if (node == 0) *depth = h;
+        par = parent[node];
+    }
+}
+
+// a query of an empty world: every record a miss
+__global__ __launch_bounds__(256) void world_fill_miss(float4* hits, int32_t* geom, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    hits[i] = make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1));
+    geom[i] = -1;
+}
+
+}  // namespace psm
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------
+
+struct psm_world {
+    psm_ctx* ctx = nullptr;
+    uint32_t cap = 0, count = 0;
+    int depth = 0;                          // of the tree over the instances (internal nodes on the longest root-to-leaf path)
+    std::vector<psm_instance> insts;        // the list as set
+    std::vector<uint32_t> slot;             // per instance: its hierarchy's index in `distinct`
+    std::vector<psm_bvh*> distinct;         // the hierarchies of the list, each once, in order of first appearance
+    std::vector<uint64_t> gens;             // ... and the generation each had at psm_world_set_instances
+    std::vector<uint32_t> first_of;         // ... and the first instance that uses it
+    std::vector<psm::WorldRow> rows;        // staging of d_rows
+    std::vector<psm::WorldSrc> srcs;        // staging of d_src
+    psm::WorldRow* d_rows = nullptr;
+    uint32_t* d_slot = nullptr;
+    psm::WorldSrc* d_src = nullptr;
+    float4* d_obox = nullptr;               // 2 per distinct hierarchy
+    float4* d_box = nullptr;                // 2 per instance: the padded world box
+    float4* d_bounds = nullptr;             // 2
+    uint64_t* d_keys = nullptr;
+    uint32_t* d_idx = nullptr;
+    psm::WorldNode* d_nodes = nullptr;
+    int* d_parent = nullptr;                // 2 cap
+    uint32_t* d_arrived = nullptr;
+    int* d_height = nullptr;                // 2 cap
+    int* d_depth = nullptr;
+};
+
+namespace psm {
+namespace {
+
+enum QueryKind { Q_CLOSEST, Q_ANY, Q_POINT, Q_WITHIN, Q_COUNT, Q_INSIDE, Q_SIGNED };
+struct QueryDesc {
+    const char* name;
+    const char* in;
+    const char* out;
+    unsigned out_align;
+};
+const QueryDesc WORLD_DESC[] = {{"psm_world_intersect_dev", "rays", "hits", 16},
+                                {"psm_world_occluded_dev", "rays", nullptr, 1},
+                                {"psm_world_closest_point_dev", "points", "hits", 16},
+                                {"psm_world_within_dev", "points", nullptr, 1},
+                                {"psm_world_count_hits_dev", "rays", "counts", 4},
+                                {"psm_world_inside_dev", "points", nullptr, 1},
+                                {"psm_world_signed_distance_dev", "points", "hits", 16}};
+void (*const WORLD_KERNELS[7])(WorldArgs) = {world_query_closest, world_query_any, world_query_point, world_query_within,
+                                             world_query_count, world_query_inside, world_query_sign};
+
+int ceil_log2(size_t n) {
+    int k = 0;
+    while (((size_t)1 << k) < n) k++;
+    return k;
+}
+// what a walk of the hierarchy can hold on the stack: query.hip's bound (too_deep), and never more than its internal nodes
+int hier_depth(const psm_bvh* b) {
+    const int bound = 63 + ceil_log2(b->cap);
+    const int nodes = b->tri_count > 0 ? (int)(b->tri_count < (1u << 30) ? b->tri_count : (1u << 30)) - 1 : 0;
+    return nodes < bound ? nodes : bound;
+}
+
+// query.hip's pose_fault
+const char* pose_fault(const float* m) {
+    for (int k = 0; k < 12; k++)
+        if (!std::isfinite(m[k])) return "has a non-finite transform";
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) {
+            double dot = 0.0;
+            for (int i = 0; i < 3; i++) dot += (double)m[4 * i + a] * (double)m[4 * i + b];
+            if (std::fabs(dot - (a == b ? 1.0 : 0.0)) > 1e-5) return "has a transform that is not rigid (R^T R differs from 1 by more than 1e-5)";
+        }
+    return nullptr;
+}
+
+// query.hip's check_data, with d_inst as the index array
+int check_data(psm_ctx* c, QueryKind kind, const void* d_in, const void* d_out, const int32_t* d_inst, uint32_t samples) {
+    const QueryDesc& k = WORLD_DESC[kind];
+    char msg[128];
+    const bool with_inst = k.out_align == 16;
+    if (!d_in || !d_out || (with_inst && !d_inst)) {
+        snprintf(msg, sizeof msg, "%s: NULL pointer", k.name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    const bool in_bad = ((uintptr_t)d_in & 15u) != 0, out_bad = ((uintptr_t)d_out & (uintptr_t)(k.out_align - 1)) != 0;
+    if (in_bad || out_bad) {
+        if (k.out_align == 16) snprintf(msg, sizeof msg, "%s: %s or %s not 16-byte aligned", k.name, k.in, k.out);
+        else if (in_bad) snprintf(msg, sizeof msg, "%s: %s not 16-byte aligned", k.name, k.in);
+        else snprintf(msg, sizeof msg, "%s: %s not %u-byte aligned", k.name, k.out, k.out_align);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (with_inst && ((uintptr_t)d_inst & 3u) != 0) {
+        snprintf(msg, sizeof msg, "%s: inst not 4-byte aligned", k.name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if ((kind == Q_INSIDE || kind == Q_SIGNED) && samples != 1 && samples != 3 && samples != 5) {
+        snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", k.name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    (void)hipSetDevice(c->device);
+    return PSM_OK;
+}
+
+// the first instance whose hierarchy is no longer what the world recorded, or -1
+int first_stale(const psm_world* w) {
+    int first = -1;
+    for (size_t h = 0; h < w->distinct.size(); h++)
+        if ((bvh_generation(w->distinct[h]) != w->gens[h] || !w->distinct[h]->built) && (first < 0 || (int)w->first_of[h] < first))
+            first = (int)w->first_of[h];
+    return first;
+}
+int refuse_stale(const psm_world* w, const char* name, int inst) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: instance %d's hierarchy was rebuilt, or reloaded and not refitted, after psm_world_set_instances (set the instances again)", name, inst);
+    return set_err(w->ctx, PSM_ERR_STATE, msg);
+}
+
+void world_clear(psm_world* w) {
+    w->count = 0;
+    w->depth = 0;
+    w->insts.clear(); w->slot.clear(); w->distinct.clear(); w->gens.clear(); w->first_of.clear(); w->rows.clear(); w->srcs.clear();
+}
+
+// boxes and tree from the table on the device (the context's stream); reads the tree's depth back (one synchronisation)
+int world_rebuild(psm_world* w) {
+    psm_ctx* c = w->ctx;
+    const uint32_t n = w->count, nh = (uint32_t)w->distinct.size();
+    w->depth = 0;
+    if (n < 2) return PSM_OK;   // a world of one: no tree, the instance is entered by every query
+    const uint32_t grid = (n + 255u) / 256u;
+    world_obj_boxes<<<nh, 256, 0, c->stream>>>(w->d_src, w->d_obox);
+    world_inst_boxes<<<grid, 256, 0, c->stream>>>(w->d_rows, w->d_slot, w->d_obox, n, w->d_box);
+    world_centre_bounds<<<1, 1024, 0, c->stream>>>(w->d_box, n, w->d_bounds);
+    world_morton<<<grid, 256, 0, c->stream>>>(w->d_box, w->d_bounds, n, w->d_keys, w->d_idx);
+    PSM_HIP(c, hipGetLastError());
+    int rc = launch_sort(c, w->d_keys, w->d_idx, n, nullptr, 64);
+    if (rc != PSM_OK) return rc;
+    PSM_HIP(c, hipMemsetAsync(w->d_arrived, 0, (size_t)n * sizeof(uint32_t), c->stream));
+    world_emit<<<grid, 256, 0, c->stream>>>(w->d_keys, w->d_idx, n, w->d_nodes, w->d_parent);
+    world_fit<<<grid, 256, 0, c->stream>>>(w->d_box, w->d_idx, n, w->d_nodes, w->d_parent, w->d_arrived, w->d_height, w->d_depth);
+    PSM_HIP(c, hipGetLastError());
+    int depth = 0;
+    PSM_HIP(c, hipMemcpyAsync(&depth, w->d_depth, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    PSM_HIP(c, hipStreamSynchronize(c->stream));
+    rc = sort_check(c);
+    if (rc != PSM_OK) return rc;
+    w->depth = depth;
+    return PSM_OK;
+}
+
+// the depth rule: the tree's depth, one entry for the way back, the deepest hierarchy's bound
+int check_depth(psm_world* w, const char* name) {
+    int deepest = 0;
+    uint32_t which = 0;
+    for (size_t h = 0; h < w->distinct.size(); h++)
+        if (hier_depth(w->distinct[h]) > deepest) { deepest = hier_depth(w->distinct[h]); which = w->first_of[h]; }
+    if (w->depth + deepest + 1 <= QSTACK_MAX) return PSM_OK;
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: the tree over the instances (depth %d) and instance %u's hierarchy (depth bound %d) are together deeper than the query stack (%d); the world is left empty",
+             name, w->depth, which, deepest, QSTACK_MAX);
+    world_clear(w);
+    return set_err(w->ctx, PSM_ERR_CAPACITY, msg);
+}
+
+int world_upload_and_build(psm_world* w, const char* name) {
+    psm_ctx* c = w->ctx;
+    (void)hipSetDevice(c->device);
+    const uint32_t n = w->count;
+    PSM_HIP(c, hipMemcpyAsync(w->d_rows, w->rows.data(), (size_t)n * sizeof(WorldRow), hipMemcpyHostToDevice, c->stream));
+    PSM_HIP(c, hipMemcpyAsync(w->d_slot, w->slot.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    PSM_HIP(c, hipMemcpyAsync(w->d_src, w->srcs.data(), w->srcs.size() * sizeof(WorldSrc), hipMemcpyHostToDevice, c->stream));
+    PSM_HIP(c, hipStreamSynchronize(c->stream));   // (the staging vectors are pageable and the caller's to change)
+    int rc = world_rebuild(w);
+    if (rc != PSM_OK) { world_clear(w); return rc; }
+    return check_depth(w, name);
+}
+
+int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_inst, uint32_t samples = 0) {
+    if (!w) return PSM_ERR_INVALID;
+    if (n == 0) return PSM_OK;
+    psm_ctx* c = w->ctx;
+    const char* name = WORLD_DESC[kind].name;
+    int rc = check_data(c, kind, d_in, d_out, d_inst, samples);
+    if (rc != PSM_OK) return rc;
+    if (w->count == 0) {   // an empty world: every query misses, no query kernel runs
+        const unsigned per = WORLD_DESC[kind].out_align;
+        if (per == 16) world_fill_miss<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>((float4*)d_out, d_inst, n);
+        else PSM_HIP(c, hipMemsetAsync(d_out, 0, n * per, c->stream));
+        PSM_HIP(c, hipGetLastError());
+        return PSM_OK;
+    }
+    const int stale = first_stale(w);
+    if (stale >= 0) return refuse_stale(w, name, stale);
+    void* spill = nullptr;
+    rc = query_spill(c, &spill);
+    if (rc != PSM_OK) return rc;
+    const size_t waves = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;
+    const uint32_t grid = (uint32_t)(waves < QUERY_GRID_CAP ? waves : QUERY_GRID_CAP);
+    WorldArgs a = {};
+    a.rays = (const float4*)d_in; a.n = n;
+    a.spill = (int*)spill;
+    a.hits = (float4*)d_out; a.occluded = (uint8_t*)d_out; a.count = (uint32_t*)d_out;
+    a.geom = d_inst;
+    a.samples = samples;
+    a.root = w->count == 1 ? ~0 : 0;
+    a.rows = w->d_rows;
+    a.nodes = w->d_nodes;
+    if (kind == Q_SIGNED) {
+        WORLD_KERNELS[Q_POINT]<<<grid, QUERY_BLOCK, 0, c->stream>>>(a);
+        PSM_HIP(c, hipGetLastError());
+    }
+    WORLD_KERNELS[kind]<<<grid, QUERY_BLOCK, 0, c->stream>>>(a);
+    PSM_HIP(c, hipGetLastError());
+    return PSM_OK;
+}
+
+template <class T>
+int world_alloc(psm_ctx* c, T** p, size_t n) {
+    PSM_HIP(c, hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
+    return PSM_OK;
+}
+
+}  // namespace
+}  // namespace psm
+
+psm_world* psm_world_create(psm_ctx* c, uint32_t capacity) {
+    using namespace psm;
+    if (!c) return nullptr;
+    if (capacity == 0 || capacity > PSM_WORLD_MAX_INSTANCES) {
+        set_err(c, PSM_ERR_INVALID, "psm_world_create: capacity must be 1 .. PSM_WORLD_MAX_INSTANCES");
+        return nullptr;
+    }
+    (void)hipSetDevice(c->device);
+    psm_world* w = new (std::nothrow) psm_world();
+    if (!w) return nullptr;
+    w->ctx = c;
+    w->cap = capacity;
+    const size_t n = capacity;
+    int rc = PSM_OK;
+    auto A = [&](int r) { if (rc == PSM_OK) rc = r; };
+    A(world_alloc(c, &w->d_rows, n)); A(world_alloc(c, &w->d_slot, n)); A(world_alloc(c, &w->d_src, n));
+    A(world_alloc(c, &w->d_obox, 2 * n)); A(world_alloc(c, &w->d_box, 2 * n)); A(world_alloc(c, &w->d_bounds, 2));
+    A(world_alloc(c, &w->d_keys, n)); A(world_alloc(c, &w->d_idx, n)); A(world_alloc(c, &w->d_nodes, n));
+    A(world_alloc(c, &w->d_parent, 2 * n)); A(world_alloc(c, &w->d_arrived, n)); A(world_alloc(c, &w->d_height, 2 * n));
+    A(world_alloc(c, &w->d_depth, 1));
+    if (rc != PSM_OK) { psm_world_destroy(w); return nullptr; }
+    return w;
+}
+
+int psm_world_destroy(psm_world* w) {
+    if (!w) return PSM_ERR_INVALID;
+    (void)hipSetDevice(w->ctx->device);
+    (void)hipStreamSynchronize(w->ctx->stream);
+    void* all[] = {w->d_rows, w->d_slot, w->d_src, w->d_obox, w->d_box, w->d_bounds, w->d_keys, w->d_idx, w->d_nodes, w->d_parent,
+                   w->d_arrived, w->d_height, w->d_depth};
+    for (void* p : all)
+        if (p) (void)hipFree(p);
+    delete w;
+    return PSM_OK;
+}
+
+uint32_t psm_world_count(const psm_world* w) { return w ? w->count : 0u; }
+
+int psm_world_set_instances(psm_world* w, const psm_instance* insts, uint32_t count) {
+    using namespace psm;
+    if (!w) return PSM_ERR_INVALID;
+    psm_ctx* c = w->ctx;
+    const char* name = "psm_world_set_instances";
+    char msg[160];
+    if (count == 0) { world_clear(w); return PSM_OK; }
+    if (!insts) return set_err(c, PSM_ERR_INVALID, "psm_world_set_instances: NULL list");
+    if (count > w->cap) {
+        snprintf(msg, sizeof msg, "%s: %u instances exceed the world's capacity of %u", name, count, w->cap);
+        return set_err(c, PSM_ERR_CAPACITY, msg);
+    }
+    // the list checks of the instanced queries (query.hip check_list<InstEntry>), in their order, all before any device work
+    for (uint32_t g = 0; g < count; g++) {
+        if (!insts[g].bvh) {
+            snprintf(msg, sizeof msg, "%s: instance %u is NULL", name, g);
+            return set_err(c, PSM_ERR_INVALID, msg);
+        }
+        if (insts[g].bvh->ctx != c) {
+            snprintf(msg, sizeof msg, "%s: instance %u belongs to another context", name, g);
+            return set_err(c, PSM_ERR_INVALID, msg);
+        }
+    }
+    for (uint32_t g = 0; g < count; g++)
+        if (const char* why = pose_fault(insts[g].world_from_object)) {
+            snprintf(msg, sizeof msg, "%s: instance %u %s", name, g, why);
+            return set_err(c, PSM_ERR_INVALID, msg);
+        }
+    for (uint32_t g = 0; g < count; g++) {
+        if (!insts[g].bvh->built) {
+            snprintf(msg, sizeof msg, "%s: instance %u is not built", name, g);
+            return set_err(c, PSM_ERR_STATE, msg);
+        }
+        if (63 + ceil_log2(insts[g].bvh->cap) > QSTACK_MAX) {
+            snprintf(msg, sizeof msg, "%s: instance %u is deeper than the query stack", name, g);
+            return set_err(c, PSM_ERR_CAPACITY, msg);
+        }
+    }
+    world_clear(w);
+    w->count = count;
+    w->insts.assign(insts, insts + count);
+    w->rows.resize(count);
+    w->slot.resize(count);
+    std::unordered_map<const psm_bvh*, uint32_t> seen;
+    for (uint32_t g = 0; g < count; g++) {
+        psm_bvh* b = insts[g].bvh;
+        auto it = seen.find(b);
+        if (it == seen.end()) {
+            it = seen.emplace(b, (uint32_t)w->distinct.size()).first;
+            w->distinct.push_back(b);
+            w->gens.push_back(bvh_generation(b));
+            w->first_of.push_back(g);
+            w->srcs.push_back(WorldSrc{b->d_tri48, b->tri_count, 0u});
+        }
+        w->slot[g] = it->second;
+        WorldRow& r = w->rows[g];
+        r.node32 = b->d_node32; r.tri48 = b->d_tri48; r.sm = b->d_small; r.sorted_tri = b->d_sorted_tri;
+        memcpy(r.m, insts[g].world_from_object, sizeof r.m);
+    }
+    return world_upload_and_build(w, name);
+}
+
+int psm_world_set_transforms(psm_world* w, uint32_t first, uint32_t count, const float* m12) {
+    using namespace psm;
+    if (!w) return PSM_ERR_INVALID;
+    psm_ctx* c = w->ctx;
+    const char* name = "psm_world_set_transforms";
+    char msg[160];
+    if ((uint64_t)first + count > w->count) {
+        snprintf(msg, sizeof msg, "%s: instances %u .. %llu of a world of %u", name, first, (unsigned long long)first + count, w->count);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (count == 0) return PSM_OK;
+    if (!m12) return set_err(c, PSM_ERR_INVALID, "psm_world_set_transforms: NULL matrices");
+    for (uint32_t k = 0; k < count; k++)
+        if (const char* why = pose_fault(m12 + 12 * (size_t)k)) {
+            snprintf(msg, sizeof msg, "%s: instance %u %s", name, first + k, why);
+            return set_err(c, PSM_ERR_INVALID, msg);
+        }
+    const int stale = first_stale(w);
+    if (stale >= 0) return refuse_stale(w, name, stale);
+    for (uint32_t k = 0; k < count; k++) {
+        memcpy(w->insts[first + k].world_from_object, m12 + 12 * (size_t)k, 12 * sizeof(float));
+        memcpy(w->rows[first + k].m, m12 + 12 * (size_t)k, 12 * sizeof(float));
+    }
+    for (size_t h = 0; h < w->distinct.size(); h++) w->srcs[h].tris = w->distinct[h]->tri_count;
+    return world_upload_and_build(w, name);
+}
+
+int psm_world_intersect_dev(psm_world* w, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits, int32_t* d_inst) {
+    return psm::world_query(w, psm::Q_CLOSEST, d_rays, n, d_hits, d_inst);
+}
+int psm_world_occluded_dev(psm_world* w, const psm_query_ray* d_rays, size_t n, uint8_t* d_hit) {
+    return psm::world_query(w, psm::Q_ANY, d_rays, n, d_hit, nullptr);
+}
+int psm_world_count_hits_dev(psm_world* w, const psm_query_ray* d_rays, size_t n, uint32_t* d_count) {
+    return psm::world_query(w, psm::Q_COUNT, d_rays, n, d_count, nullptr);
+}
+int psm_world_closest_point_dev(psm_world* w, const psm_point_query* d_points, size_t n, psm_hit* d_hits, int32_t* d_inst) {
+    return psm::world_query(w, psm::Q_POINT, d_points, n, d_hits, d_inst);
+}
+int psm_world_within_dev(psm_world* w, const psm_point_query* d_points, size_t n, uint8_t* d_hit) {
+    return psm::world_query(w, psm::Q_WITHIN, d_points, n, d_hit, nullptr);
+}
+int psm_world_inside_dev(psm_world* w, const psm_point_query* d_points, size_t n, uint32_t samples, uint8_t* d_inside) {
+    return psm::world_query(w, psm::Q_INSIDE, d_points, n, d_inside, nullptr, samples);
+}
+int psm_world_signed_distance_dev(psm_world* w, const psm_point_query* d_points, size_t n, uint32_t samples, psm_hit* d_hits,
+                                  int32_t* d_inst) {
+    return psm::world_query(w, psm::Q_SIGNED, d_points, n, d_hits, d_inst, samples);
+}

@@ -19,6 +19,10 @@ a scene query against rebuild of the merged hierarchy + a plain query.
 points: (a) identity instances against `scene` on the same hierarchies (the merged one; 8 slabs): the cost of the move; (b) ONE torus
 hierarchy (MOVING_NU x MOVING_NV) at 2, 8 and 32 poses on a lattice inside the scene's bounds; (c) the static scene plus a moving
 10 000-triangle torus: a pose update + an instanced query against a re-upload and rebuild of the small mesh + a scene query.
+`query_bench.py world`: the instance worlds (psm_world_*) through the package's InstanceWorld, device arrays in and out:
+(a) N = 32 separated tori, world against InstancedScene on the same library, interleaved A B A B; (b) one torus at 256, 4096
+and 65 536 grid poses: absolute throughput of local rays and points; (c) a pose update plus a world query against re-baking the
+posed triangles into one hierarchy (upload + build) plus a plain query. WORLD_N = queries per batch (default 2^18).
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -486,6 +490,84 @@ def instances():
     print(json.dumps(out))
 
 
+def world():
+    import torch
+    n = int(os.environ.get("WORLD_N", str(1 << 18)))
+    ctx = psm.Context(0, stream=torch.cuda.current_stream().cuda_stream)
+    tor = torus(48, 24, 0.7, 0.25)
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(tor.shape[0])
+    th.loadTriangles(tor)
+    th.build()
+    rng = np.random.RandomState(1)
+    dev = torch.device("cuda", 0)
+    out = {"mode": "world", "queries": n, "torus_triangles": int(tor.shape[0]), "reps": REPS}
+
+    def grid_poses(count):
+        side = int(np.ceil(np.sqrt(count)))
+        m = np.zeros((count, 3, 4), np.float32)
+        m[:, 0, 0] = m[:, 1, 1] = m[:, 2, 2] = 1.0
+        k = np.arange(count)
+        m[:, 0, 3], m[:, 1, 3] = 2.5 * (k % side), 2.5 * (k // side)
+        return m
+
+    def local_queries(poses):
+        c = poses[rng.randint(0, poses.shape[0], n), :, 3]
+        o = (c + rng.uniform(-1.5, 1.5, (n, 3))).astype(np.float32)
+        d = (c + rng.uniform(-0.6, 0.6, (n, 3)) - o).astype(np.float32)
+        p = (c + rng.uniform(-1.2, 1.2, (n, 3))).astype(np.float32)
+        return [torch.from_numpy(a).to(dev) for a in (o, d, p)]
+
+    # (a) 32 separated bodies: the world against the flat list, A B A B
+    poses = grid_poses(32)
+    o, d, p = local_queries(poses)
+    flat = psm.InstancedScene(ctx, [(th, m) for m in poses])
+    wd = psm.InstanceWorld(ctx, [(th, m) for m in poses])
+    for name, fa, fb in (("intersect", lambda: flat.intersect(o, d), lambda: wd.intersect(o, d)),
+                         ("closest_point", lambda: flat.closestPoint(p), lambda: wd.closestPoint(p)),
+                         ("inside", lambda: flat.inside(p, 3), lambda: wd.inside(p, 3))):
+        a1, b1, a2, b2 = median_ms(ctx, fa), median_ms(ctx, fb), median_ms(ctx, fa), median_ms(ctx, fb)
+        out["n32_%s_instanced_ms" % name] = [round(a1, 4), round(a2, 4)]
+        out["n32_%s_world_ms" % name] = [round(b1, 4), round(b2, 4)]
+        out["n32_%s_world_over_instanced" % name] = round((b1 + b2) / (a1 + a2), 3)
+    wd.close()
+    # (b) one torus at many poses
+    for count in (256, 4096, 65536):
+        poses = grid_poses(count)
+        o, d, p = local_queries(poses)
+        t0 = time.perf_counter()
+        wd = psm.InstanceWorld(ctx, [(th, m) for m in poses])
+        ctx.sync()
+        out["poses%d_set_instances_ms" % count] = round((time.perf_counter() - t0) * 1e3, 3)
+        out["poses%d_set_transforms_ms" % count] = round(median_ms(ctx, wd.refresh), 3)
+        for name, fn in (("intersect", lambda: wd.intersect(o, d)), ("closest_point", lambda: wd.closestPoint(p)), ("inside", lambda: wd.inside(p, 3))):
+            ms = median_ms(ctx, fn)
+            out["poses%d_%s_ms" % (count, name)] = round(ms, 4)
+            out["poses%d_%s_Mq_per_s" % (count, name)] = round(n / ms / 1e3, 2)
+        if count == 256:
+            # (c) a body moves: pose update + world query against re-bake (posed triangles, upload, build) + plain query
+            baked = psm.TriangleHierarchy(ctx)
+            baked.allocate(count * tor.shape[0])
+
+            def rebake():
+                tris = (tor[None] + poses[:, None, None, :, 3]).reshape(-1, 3, 3)
+                baked.clearTribuffer()
+                baked.loadTriangles(tris)
+                baked.build()
+                return baked.intersect(o, d)
+
+            def move():
+                wd.setTransform(7, poses[7])
+                return wd.intersect(o, d)
+            a1, b1, a2, b2 = median_ms(ctx, rebake), median_ms(ctx, move), median_ms(ctx, rebake), median_ms(ctx, move)
+            out["moving_rebake_plus_query_ms"] = [round(a1, 3), round(a2, 3)]
+            out["moving_pose_plus_world_query_ms"] = [round(b1, 3), round(b2, 3)]
+            baked.close()
+        wd.close()
+    th.close()
+    print(json.dumps(out))
+
+
 def main():
     sc = scenes.sponza_like()
     ctx = psm.Context(0)
@@ -551,4 +633,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world}.get(" ".join(sys.argv[1:]), main)()
