@@ -56,6 +56,11 @@ namespace NSM {
         int countHits(const psm_query_ray * d_rays, size_t n, uint32_t * d_count);
         int inside(const psm_point_query * d_points, size_t n, uint8_t * d_inside, uint32_t samples = 3);
         int signedDistance(const psm_point_query * d_points, size_t n, psm_hit * d_hits, uint32_t samples = 3);
+        // not in the reference: the first k hits of n rays in the order (t, tri) / the k nearest triangles of n points in the order
+        // (d2, tri), 1 <= k <= PSM_QUERY_K_MAX: d_hits [n][k] records, d_count [n] = the slots of a row that hold one, the rest
+        // are misses (psm_bvh_first_hits_dev / psm_bvh_nearest_dev), stream-ordered on the context; returns the psm_status
+        int firstHits(const psm_query_ray * d_rays, size_t n, uint32_t k, psm_hit * d_hits, uint32_t * d_count);
+        int nearest(const psm_point_query * d_points, size_t n, uint32_t k, psm_hit * d_hits, uint32_t * d_count);
         psm_bvh * handle() { return bvh; }
     };
 }

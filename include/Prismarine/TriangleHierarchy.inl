@@ -67,6 +67,16 @@ namespace NSM {
         check(rc, "TriangleHierarchy::signedDistance");
         return rc;
     }
+    inline int TriangleHierarchy::firstHits(const psm_query_ray * d_rays, size_t n, uint32_t k, psm_hit * d_hits, uint32_t * d_count) {
+        const int rc = psm_bvh_first_hits_dev(bvh, d_rays, n, k, d_hits, d_count);
+        check(rc, "TriangleHierarchy::firstHits");
+        return rc;
+    }
+    inline int TriangleHierarchy::nearest(const psm_point_query * d_points, size_t n, uint32_t k, psm_hit * d_hits, uint32_t * d_count) {
+        const int rc = psm_bvh_nearest_dev(bvh, d_points, n, k, d_hits, d_count);
+        check(rc, "TriangleHierarchy::nearest");
+        return rc;
+    }
     inline void TriangleHierarchy::setBuildGraph(bool enable) { if (bvh) check(psm_bvh_set_build_graph(bvh, enable ? 1 : 0), "TriangleHierarchy::setBuildGraph"); }
     inline void TriangleHierarchy::configureIntersection(bool clearDepth) { (void)clearDepth; }  // ignored by the reference's shaders too
 

@@ -436,6 +436,31 @@ int psm_bvh_count_hits_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, 
 int psm_bvh_inside_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, uint32_t samples, uint8_t* d_inside);
 int psm_bvh_signed_distance_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, uint32_t samples, psm_hit* d_hits);
 
+/* k-best queries against a built hierarchy (new; no reference counterpart): the first k hits of a ray and the k
+ * nearest triangles of a point, k fixed by the caller, 1 <= k <= PSM_QUERY_K_MAX. The output is n rows of k psm_hit records
+ * (d_hits[i * k + s], slot s of query i) and a count per query; there is no allocation, no overflow and no second pass, and with
+ * k >= the ray's hit count the row is the complete list. A single hierarchy only: scenes, instances and worlds have no k-best
+ * queries. Semantics:
+ *   - first hits: the candidates, the validity of a ray, the triangle test and the window tmin <= t <= tmax are those of
+ *     psm_bvh_intersect_dev / psm_bvh_count_hits_dev, unchanged. With c the number psm_bvh_count_hits_dev gives for the ray,
+ *     row i holds the min(k, c) counting candidates that are smallest in the lexicographic order (t, tri), ascending: t compared
+ *     as floats (-0 == +0, the id then decides), tri unsigned. Each record is {u, v, t, tri} as psm_bvh_intersect_dev writes it
+ *   - nearest: the candidates, the validity of a point, closest_on_tri, d2 and dist = sqrtf(d2) <= rmax are those of
+ *     psm_bvh_closest_point_dev, unchanged. Row i holds the min(k, c) counting triangles that are smallest in (d2, tri),
+ *     ascending -- the key is d2, not dist: two different d2 may share a sqrtf. Each record is {u, v, dist, tri}
+ *   - d_count[i] = min(k, c); the slots from d_count[i] on are the miss record {0, 0, +inf, -1}; an invalid query has count 0
+ *     and a row of misses
+ *   - what follows: slot 0 is bit for bit the record psm_bvh_intersect_dev / psm_bvh_closest_point_dev writes for the query
+ *     (bit-equal t / d2 of several triangles -- coincident triangles, a ray within 1e-5 of a shared edge -- are all listed, in id
+ *     order); d_count > 0 iff psm_bvh_occluded_dev / psm_bvh_within_dev say 1; the row for k is the first k slots of the row for
+ *     any larger k; nothing depends on the traversal order
+ *   - k == 0 or k > PSM_QUERY_K_MAX: PSM_ERR_INVALID, nothing is launched. d_hits 16-byte and d_count 4-byte aligned;
+ *     everything else (alignment of the inputs, NULL checks, n = 0, PSM_ERR_STATE before the first build, stream order,
+ *     capture, refit, 0 / 1 leaves) as for the queries above */
+#define PSM_QUERY_K_MAX 16
+int psm_bvh_first_hits_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, uint32_t k, psm_hit* d_hits, uint32_t* d_count);
+int psm_bvh_nearest_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, uint32_t k, psm_hit* d_hits, uint32_t* d_count);
+
 /* scene queries: the seven queries above over several hierarchies at once (new; no reference counterpart).
  * A scene is an ordered list of G built hierarchies of ONE context, 1 <= G <= PSM_SCENE_MAX_GEOMETRIES, passed per call (there
  * is no scene handle). The limit is 32 because the per-geometry table then travels with the launch (32 x four pointers = 1 KB

@@ -27,6 +27,7 @@ EXPORTS = [
     "psm_bvh_get_info", "psm_bvh_stage_bounds", "psm_bvh_stage_morton", "psm_bvh_stage_sort",
     "psm_bvh_stage_emit", "psm_bvh_download", "psm_bvh_intersect_dev", "psm_bvh_occluded_dev",
     "psm_bvh_closest_point_dev", "psm_bvh_within_dev", "psm_bvh_count_hits_dev", "psm_bvh_inside_dev", "psm_bvh_signed_distance_dev",
+    "psm_bvh_first_hits_dev", "psm_bvh_nearest_dev",
     "psm_scene_intersect_dev", "psm_scene_occluded_dev", "psm_scene_count_hits_dev", "psm_scene_closest_point_dev", "psm_scene_within_dev",
     "psm_scene_inside_dev", "psm_scene_signed_distance_dev",
     "psm_instances_intersect_dev", "psm_instances_occluded_dev", "psm_instances_count_hits_dev", "psm_instances_closest_point_dev",
@@ -57,6 +58,7 @@ RAY_DT = np.dtype([("origin", "<f4", 3), ("direct", "<f4", 3), ("color", "<f4", 
 HIT_DT = np.dtype([("u", "<f4"), ("v", "<f4"), ("t", "<f4"), ("tri", "<i4")])
 QUERY_RAY_DT = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direct", "<f4", 3), ("tmax", "<f4")])   # psm_query_ray
 POINT_QUERY_DT = np.dtype([("p", "<f4", 3), ("rmax", "<f4")])   # psm_point_query
+QUERY_K_MAX = 16   # psm_hip.h PSM_QUERY_K_MAX
 SCENE_MAX_GEOMETRIES = 32   # psm_hip.h PSM_SCENE_MAX_GEOMETRIES
 WORLD_MAX_INSTANCES = 65536   # psm_hip.h PSM_WORLD_MAX_INSTANCES
 INSTANCE_DT = np.dtype([("bvh", "<u8"), ("world_from_object", "<f4", 12)])   # psm_instance
@@ -397,9 +399,25 @@ class TriangleHierarchy:
         placement as intersect()."""
         return self._query(origins, directions, tmin, tmax, "bool")
 
-    def _query(self, origins, directions, tmin, tmax, out):
+    def firstHits(self, origins, directions, k, tmin=0.0, tmax=np.inf):
+        """The first k hits of every ray, in order (psm_bvh_first_hits_dev; not in the reference): of the triangles countHits()
+        counts, the min(k, count) smallest in (t, tri) -- bit-equal t (coincident triangles, a shared edge) are all listed, by id.
+        k: 1 .. QUERY_K_MAX. Returns QueryHitLists: u, v, t, tri [n, k] (slot 0 is intersect()'s record; the slots past count are
+        misses: tri = -1, t = +inf) and count [n]. Arguments and placement as intersect(). A single hierarchy only: QueryScene,
+        InstancedScene and InstanceWorld have no such query."""
+        return self._query(origins, directions, tmin, tmax, "lists", "psm_bvh_first_hits_dev", k)
+
+    def nearest(self, points, k, rmax=np.inf):
+        """The k nearest triangles of every point within rmax (psm_bvh_nearest_dev; not in the reference): the min(k, count)
+        smallest in (d2, tri). k: 1 .. QUERY_K_MAX. Returns QueryHitLists: t = the distance, and u, v as closestPoint()'s (slot 0
+        is closestPoint()'s record). Arguments and placement as closestPoint()."""
+        return self._point_query(points, rmax, "lists", "psm_bvh_nearest_dev", k=k)
+
+    def _query(self, origins, directions, tmin, tmax, out, name=None, k=None):
+        name = name or _RAY_QUERIES[out]
+        extra = () if k is None else (C.c_uint32(_k(k, name)),)
         if type(origins).__module__.split(".")[0] == "torch":
-            return _query_torch(self, origins, directions, tmin, tmax, out)
+            return _query_torch(self, origins, directions, tmin, tmax, out, name, *extra)
         o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
         n = o.shape[0]
@@ -407,7 +425,7 @@ class TriangleHierarchy:
             raise ValueError("origins and directions: %d against %d rays" % (n, d.shape[0]))
         rays = np.empty((n, 8), np.float32)
         rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7] = o, tmin, d, tmax
-        return self._launch_np(rays, out, _RAY_QUERIES[out])
+        return self._launch_np(rays, out, name, *extra)
 
     def countHits(self, origins, directions, tmin=0.0, tmax=np.inf):
         """The number of triangles each ray hits inside [tmin, tmax] (psm_bvh_count_hits_dev; not in the reference): what occluded()
@@ -441,10 +459,12 @@ class TriangleHierarchy:
         reference): a bool array / tensor. Arguments and placement as closestPoint()."""
         return self._point_query(points, radius, "bool", "psm_bvh_within_dev")
 
-    def _point_query(self, points, rmax, out, name, samples=None):
+    def _point_query(self, points, rmax, out, name, samples=None, k=None):
         """points [n, 3] with rmax, or (the inside queries only) [n, 4] records already packed; samples: the inside queries' extra
-        argument"""
+        argument, k: the k-best queries'"""
         extra = () if samples is None else (C.c_uint32(_samples(samples, name)),)
+        if k is not None:
+            extra = (C.c_uint32(_k(k, name)),)
         packed = samples is not None and getattr(points, "ndim", 0) == 2 and points.shape[1] == 4
         if type(points).__module__.split(".")[0] == "torch":
             import torch
@@ -469,8 +489,9 @@ class TriangleHierarchy:
         return _launch_np(self, packed, out, name, *extra)
 
     def _call(self, name, d_in, n, extra, d_out, d_geom):
-        """the native call of one query launch (d_geom: unused -- a single hierarchy reports no geometry)"""
-        self.ctx.check(getattr(lib(), name)(self._h, C.c_void_p(d_in), C.c_size_t(n), *extra, C.c_void_p(d_out)), name)
+        """the native call of one query launch (d_geom: a single hierarchy reports no geometry; the k-best queries' counts)"""
+        tail = () if d_geom is None else (C.c_void_p(d_geom),)
+        self.ctx.check(getattr(lib(), name)(self._h, C.c_void_p(d_in), C.c_size_t(n), *extra, C.c_void_p(d_out), *tail), name)
 
     _scene = False   # (QueryScene: True -- a "hits" result then carries QueryHits.geom)
 
@@ -504,8 +525,9 @@ class TriangleHierarchy:
             self._h = C.c_void_p()
 
 
-# a query's result by kind: bytes per query and the numpy type of the array returned ("hits": QueryHits over float32 [n, 4])
-_QUERY_OUT = {"hits": (16, np.float32), "bool": (1, np.bool_), "count": (4, np.uint32)}
+# a query's result by kind: bytes per query and the numpy type of the array returned ("hits": QueryHits over float32 [n, 4];
+# "lists": QueryHitLists over float32 [n, k, 4] -- 16 bytes per slot, k the launch's extra argument -- and a count per query)
+_QUERY_OUT = {"hits": (16, np.float32), "bool": (1, np.bool_), "count": (4, np.uint32), "lists": (16, np.float32)}
 _RAY_QUERIES = {"hits": "psm_bvh_intersect_dev", "bool": "psm_bvh_occluded_dev", "count": "psm_bvh_count_hits_dev"}
 
 
@@ -515,6 +537,33 @@ def _samples(samples, name):
     if s != samples or not 0 <= s < 1 << 32:
         raise ValueError("%s: samples must be 1, 3 or 5" % name)
     return s
+
+
+def _k(k, name):
+    """the k-best queries' k as the C ABI takes it (a uint32; the library refuses 0 and k > QUERY_K_MAX)"""
+    v = int(k)
+    if v != k or not 0 <= v < 1 << 32:
+        raise ValueError("%s: k must be 1 .. %d" % (name, QUERY_K_MAX))
+    return v
+
+
+class QueryHitLists:
+    """The rows of TriangleHierarchy.firstHits / .nearest: `buffer` [n, k, 4] float32 (numpy array or torch tensor) holds psm_hit
+    records (u, v, t, tri); u, v, t and tri (int32) [n, k] are views of it. count [n]: the slots of a row that hold a record
+    (uint32; an int32 tensor for torch), the rest are misses (tri = -1, t = +inf)."""
+
+    def __init__(self, buffer, count):
+        self.buffer = buffer
+        self.count = count
+        self.u, self.v, self.t = buffer[:, :, 0], buffer[:, :, 1], buffer[:, :, 2]
+        if isinstance(buffer, np.ndarray):
+            self.tri = buffer.view(np.int32)[:, :, 3]
+        else:
+            import torch
+            self.tri = buffer.view(torch.int32)[:, :, 3]
+
+    def __len__(self):
+        return self.buffer.shape[0]
 
 
 class QueryHits:
@@ -542,8 +591,10 @@ def _launch_np(th, packed, out, name, *extra):
     ctx = th.ctx
     n = packed.shape[0]
     per, dtype = _QUERY_OUT[out]
-    geom = th._scene and out == "hits"
-    hr, ho = ctx.buf_alloc(max(packed.nbytes, 32)), ctx.buf_alloc(max(per * n, 16))
+    lists = out == "lists"   # (k rows per query, and the counts travel where a scene's geometry indices do)
+    k = extra[0].value if lists else 1
+    geom = (th._scene and out == "hits") or lists
+    hr, ho = ctx.buf_alloc(max(packed.nbytes, 32)), ctx.buf_alloc(max(per * k * n, 16))
     hg = ctx.buf_alloc(max(4 * n, 16)) if geom else None
     try:
         if n:
@@ -551,6 +602,8 @@ def _launch_np(th, packed, out, name, *extra):
         th._call(name, ctx.buf_ptr(hr)[0], n, extra, ctx.buf_ptr(ho)[0], ctx.buf_ptr(hg)[0] if geom else None)
         if n == 0:
             ctx.sync()
+            if lists:
+                return QueryHitLists(np.zeros((0, k, 4), np.float32), np.zeros(0, np.uint32))
             if out == "hits":
                 return QueryHits(np.zeros((0, 4), np.float32), np.zeros(0, np.int32) if geom else None)
             return np.zeros(0, dtype)
@@ -558,6 +611,8 @@ def _launch_np(th, packed, out, name, *extra):
             return ctx.buf_download(ho, np.uint8, n).view(np.bool_)
         if out == "count":
             return ctx.buf_download(ho, np.uint32, n)
+        if lists:
+            return QueryHitLists(ctx.buf_download(ho, np.float32, 4 * k * n).reshape(n, k, 4), ctx.buf_download(hg, np.uint32, n))
         return QueryHits(ctx.buf_download(ho, np.float32, 4 * n).reshape(n, 4), ctx.buf_download(hg, np.int32, n) if geom else None)
     finally:
         ctx.buf_free(hr)
@@ -584,7 +639,7 @@ def _hip_check(rc, what):
         raise PsmError("%s failed (%d)" % (what, rc))
 
 
-def _query_torch(th, origins, directions, tmin, tmax, out):
+def _query_torch(th, origins, directions, tmin, tmax, out, name, *extra):
     """TriangleHierarchy.intersect / occluded on torch device tensors: rays packed on torch's current stream, the kernel on the
     context's stream, the two ordered by events when they differ -- no host synchronisation."""
     import torch
@@ -601,7 +656,7 @@ def _query_torch(th, origins, directions, tmin, tmax, out):
     rays[:, 3] = torch.as_tensor(tmin, dtype=torch.float32, device=dev)
     rays[:, 4:7] = d
     rays[:, 7] = torch.as_tensor(tmax, dtype=torch.float32, device=dev)
-    return _launch_torch(th, rays, out, _RAY_QUERIES[out])
+    return _launch_torch(th, rays, out, name, *extra)
 
 
 def _launch_torch(th, packed, kind, name, *extra):
@@ -611,9 +666,11 @@ def _launch_torch(th, packed, kind, name, *extra):
     import torch
     dev = packed.device
     n = packed.shape[0]
-    shape, dtype = {"hits": ((n, 4), torch.float32), "bool": ((n,), torch.uint8), "count": ((n,), torch.int32)}[kind]
+    lists = kind == "lists"
+    shape, dtype = {"hits": ((n, 4), torch.float32), "bool": ((n,), torch.uint8), "count": ((n,), torch.int32),
+                    "lists": ((n, extra[0].value if lists else 1, 4), torch.float32)}[kind]
     out = torch.empty(shape, dtype=dtype, device=dev)
-    geom = torch.empty((n,), dtype=torch.int32, device=dev) if th._scene and kind == "hits" else None
+    geom = torch.empty((n,), dtype=torch.int32, device=dev) if (th._scene and kind == "hits") or lists else None
     cur = torch.cuda.current_stream(dev)
     mine = th.ctx.stream or 0   # (NULL: the device's null stream, torch's default stream)
     other = mine != cur.cuda_stream
@@ -628,6 +685,8 @@ def _launch_torch(th, packed, kind, name, *extra):
         _hip_check(hip.hipEventRecord(ev, C.c_void_p(mine)), "hipEventRecord")
         _hip_check(hip.hipStreamWaitEvent(C.c_void_p(cur.cuda_stream), ev, C.c_uint(0)), "hipStreamWaitEvent")
         _hip_check(hip.hipEventDestroy(ev), "hipEventDestroy")
+    if lists:
+        return QueryHitLists(out, geom)
     return QueryHits(out, geom) if kind == "hits" else (out.view(torch.bool) if kind == "bool" else out)
 
 

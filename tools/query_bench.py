@@ -23,6 +23,10 @@ hierarchy (MOVING_NU x MOVING_NV) at 2, 8 and 32 poses on a lattice inside the s
 (a) N = 32 separated tori, world against InstancedScene on the same library, interleaved A B A B; (b) one torus at 256, 4096
 and 65 536 grid poses: absolute throughput of local rays and points; (c) a pose update plus a world query against re-baking the
 posed triangles into one hierarchy (upload + build) plus a plain query. WORLD_N = queries per batch (default 2^18).
+`query_bench.py kbest`: the k-best queries (psm_bvh_first_hits_dev / psm_bvh_nearest_dev) for k = 1, 4 and 16, every pair
+alternated A B A B with medians of REPS: on the ray mode's primary and bounce-like rays firstHits against intersect, against
+countHits, and against what a caller does without it -- k intersect launches, tmin moved past the last t between them (a torch
+operation on the same stream; it loses hits at a bit-equal t); on the point mode's two sets nearest against closestPoint.
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -568,6 +572,113 @@ def world():
     print(json.dumps(out))
 
 
+def abab(ctx, fa, fb):
+    """medians (ms) of fa and fb, alternated A B A B after a warm-up call of each"""
+    fa()
+    fb()
+    ctx.sync()
+    ta, tb = [], []
+    for _ in range(REPS):
+        for fn, ts in ((fa, ta), (fb, tb)):
+            t0 = time.perf_counter()
+            fn()
+            ctx.sync()
+            ts.append((time.perf_counter() - t0) * 1e3)
+    return round(float(np.median(ta)), 4), round(float(np.median(tb)), 4)
+
+
+def kbest():
+    import torch   # (before the library loads its HIP runtime)
+    dev = torch.device("cuda", 0)
+    sc = scenes.sponza_like()
+    ctx = psm.Context(0, stream=torch.cuda.current_stream(dev).cuda_stream)   # torch's tmin update and the launches: one stream
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(sc["tris"].shape[0])
+    th.loadTriangles(sc["tris"], sc["normals"], sc["mats"])
+    th.build()
+    rt = psm.Pipeline(ctx, seed=1000)
+    rt.resizeBuffers(W, H)
+    rt.resize(W, H)
+    cam = scenes.camera_matrices(sc["eye"], sc["view"], W, H)
+    rt.camera_matrices(cam[0], cam[1])
+    prim = rt.download_rays()
+    rt.close()
+    n = prim.shape[0]
+    o, d = prim["origin"].copy(), prim["direct"].copy()
+    lib = psm.lib()
+    size = C.c_size_t(n)
+    rays = torch.zeros((n, 8), dtype=torch.float32, device=dev)
+    hits = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+    rows = torch.zeros((n, 16, 4), dtype=torch.float32, device=dev)
+    count = torch.zeros((n,), dtype=torch.int32, device=dev)
+    p_rays, p_hits, p_rows, p_count = (C.c_void_p(x.data_ptr()) for x in (rays, hits, rows, count))
+    inf = torch.tensor(float("inf"), device=dev)
+
+    def pack(o, d, tmin):
+        r = np.zeros((n, 8), np.float32)
+        r[:, 0:3], r[:, 3], r[:, 4:7], r[:, 7] = o, tmin, d, np.inf
+        rays.copy_(torch.from_numpy(r))
+
+    def closest():
+        ctx.check(lib.psm_bvh_intersect_dev(th._h, p_rays, size, p_hits), "psm_bvh_intersect_dev")
+
+    def counting():
+        ctx.check(lib.psm_bvh_count_hits_dev(th._h, p_rays, size, p_count), "psm_bvh_count_hits_dev")
+
+    def first(k):
+        return lambda: ctx.check(lib.psm_bvh_first_hits_dev(th._h, p_rays, size, C.c_uint32(k), p_rows, p_count), "psm_bvh_first_hits_dev")
+
+    def emulation(k, tmin0):
+        def run():
+            for j in range(k):
+                closest()
+                if j + 1 < k:
+                    rays[:, 3] = torch.nextafter(hits[:, 2], inf)
+            rays[:, 3] = tmin0
+        return run
+
+    out = {"rays": n, "points": NPTS, "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+    pack(o, d, 0.0)
+    closest()
+    ctx.sync()
+    bo, bd = bounce_rays(sc, o, d, hits.cpu().numpy())
+    for name, (ro, rd, tmin0) in (("primary", (o, d, 0.0)), ("bounce", (bo, bd, 1e-3))):
+        pack(ro, rd, tmin0)
+        out[name + "_intersect_ms"], out[name + "_count_hits_ms"] = abab(ctx, closest, counting)
+        out[name + "_mean_hits"] = round(float(count.float().mean().item()), 2)
+        for k in (1, 4, 16):
+            a, b = abab(ctx, first(k), closest)
+            out["%s_first_hits_k%d_ms" % (name, k)], out["%s_intersect_beside_k%d_ms" % (name, k)] = a, b
+            a, b = abab(ctx, first(k), emulation(k, tmin0))
+            out["%s_first_hits_k%d_again_ms" % (name, k)], out["%s_%dx_intersect_ms" % (name, k, )] = a, b
+
+    tris = sc["tris"].reshape(-1, 3, 3)
+    lo, hi = tris.reshape(-1, 3).min(0), tris.reshape(-1, 3).max(0)
+    diag = float(np.linalg.norm(hi - lo))
+    rng = np.random.RandomState(7)
+    m = min(NPTS, n)
+    w = rng.dirichlet([1, 1, 1], m).astype(np.float32)
+    surf = np.einsum("ij,ijk->ik", w, tris[rng.randint(0, tris.shape[0], m)])
+    sets = {"surface_noise": (surf + rng.normal(0, 0.01 * diag, (m, 3))).astype(np.float32),
+            "uniform": rng.uniform(lo, hi, (m, 3)).astype(np.float32)}
+    msize = C.c_size_t(m)
+    out["points"] = m
+    for name, pts in sets.items():
+        q = np.empty((m, 4), np.float32)
+        q[:, 0:3], q[:, 3] = pts, np.inf
+        rays.view(-1, 4)[:m].copy_(torch.from_numpy(q))
+
+        def point():
+            ctx.check(lib.psm_bvh_closest_point_dev(th._h, p_rays, msize, p_hits), "psm_bvh_closest_point_dev")
+        for k in (1, 4, 16):
+            a, b = abab(ctx, lambda: ctx.check(lib.psm_bvh_nearest_dev(th._h, p_rays, msize, C.c_uint32(k), p_rows, p_count),
+                                               "psm_bvh_nearest_dev"), point)
+            out["%s_nearest_k%d_ms" % (name, k)], out["%s_closest_point_beside_k%d_ms" % (name, k)] = a, b
+    th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def main():
     sc = scenes.sponza_like()
     ctx = psm.Context(0)
@@ -633,4 +744,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest}.get(" ".join(sys.argv[1:]), main)()
