@@ -10,10 +10,10 @@
 
 #include "psm_common.h"
 #include "psm_internal.h"
+#define PSM_QUERY_HOST_DECLARATIONS_ONLY   // query_release, bvh_generation
+#include "psm_query_host.h"
 
 namespace psm {
-
-void query_release(psm_ctx* c);   // query.hip
 
 constexpr int SM_COUNT = 24;
 constexpr int SM_ROOT = 25;

@@ -1,6 +1,8 @@
-// psm_query_dev.h -- the device pieces every query kernel file shares (query.hip, kbest.hip): the constants of the walk, the
-// kernel arguments, the triangle and box tests of rays and points, and the walk itself. Moved here from query.hip as they
-// were; query.hip's 21 kernels compile to the same instructions (tests/test_world_query_cpu.py hashes them).
+// psm_query_dev.h -- the device pieces every query kernel file shares (query.hip, kbest.hip, world.hip): the constants of the
+// walk, the kernel arguments, the triangle and box tests of rays and points, the move into an instance's object space, the
+// directions of the inside test, and the single-hierarchy walk itself. Moved here from query.hip as they were; every kernel of
+// the three files compiles to the same instructions as with the pieces in its own file (tools/kernel_diff.py; query.hip's 21
+// are hashed by tests/test_world_query_cpu.py).
 #pragma once
 #include "psm_common.h"
 #include "psm_internal.h"
@@ -346,6 +348,19 @@ struct PointImage {
         okR = kR <= best;
     }
 };
+
+// ---- what the inside queries and the posed queries (instances, worlds) share ------------------------------------------------
+
+// The rays of the inside test (psm_hip.h PSM_INSIDE_DIRECTIONS: written there once): ray k of a point p is {p, 0, row k, +inf}.
+__device__ const float INSIDE_DIR[PSM_INSIDE_MAX_SAMPLES][3] = PSM_INSIDE_DIRECTIONS;
+
+// The canonical move into an instance's object space (psm_hip.h; tests/instance_query_model.py states it in numpy): a direction
+// goes through R^T, x'_j = (R[0][j] d.x + R[1][j] d.y) + R[2][j] d.z, a point through the same after d = x - T per component.
+// One float32 operation order (the build contracts nothing: -ffp-contract=off).
+PSM_D v3 inst_rotate(const float* m, v3 d) {
+    return mk3((m[0] * d.x + m[4] * d.y) + m[8] * d.z, (m[1] * d.x + m[5] * d.y) + m[9] * d.z, (m[2] * d.x + m[6] * d.y) + m[10] * d.z);
+}
+PSM_D v3 inst_point(const float* m, v3 x) { return inst_rotate(m, mk3(x.x - m[3], x.y - m[7], x.z - m[11])); }
 
 }  // namespace
 

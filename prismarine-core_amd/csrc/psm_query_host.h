@@ -1,0 +1,84 @@
+// psm_query_host.h -- the host path every query entry point shares (query.hip, world.hip): the kinds, what
+// their messages call things, the data and list checks, the context's stack area, the launch. The functions are defined once,
+// in query.hip. api.hip takes the declarations alone (PSM_QUERY_HOST_DECLARATIONS_ONLY): it holds no kernels, and the
+// templates below need the walk's constants of psm_query_dev.h.
+#pragma once
+#include "psm_internal.h"
+
+namespace psm {
+
+void query_release(psm_ctx* c);               // query.hip, for psm_ctx_destroy: the context's stack area goes with it
+uint64_t bvh_generation(const psm_bvh* b);    // api.hip: bumped by every build of the hierarchy
+
+// (Q_FIRST_HITS, Q_NEAREST: the k-best queries of kbest.hip, single hierarchies only: no entry in the kernel tables)
+enum QueryKind { Q_CLOSEST, Q_ANY, Q_POINT, Q_WITHIN, Q_COUNT, Q_INSIDE, Q_SIGNED, Q_FIRST_HITS, Q_NEAREST };
+// per kind: the single-hierarchy entry point, what the input and the output are called in its messages (out: NULL when its
+// alignment is not checked: a byte per query), the output's alignment, the family in the state / capacity texts
+struct QueryDesc {
+    const char* name;
+    const char* in;
+    const char* out;
+    unsigned out_align;
+    bool points;
+};
+extern const QueryDesc QUERY_DESC[];
+
+// the context's stack entries beyond the LDS part (allocated on the context's first query)
+int spill_for(psm_ctx* c, void** out);
+// ceil(log2(n)) for n >= 1
+int ceil_log2(size_t n);
+// the builder's height bound of a hierarchy (QSTACK_MAX in psm_query_dev.h): 63 + ceil(log2(capacity))
+int depth_bound(const psm_bvh* b);
+// Why a pose is refused, or NULL (psm_hip.h)
+const char* pose_fault(const float* m);
+// The data checks every query shares, under the entry point's name (query.hip has the rules)
+int check_data(psm_ctx* c, const char* name, const char* index, QueryKind kind, const void* d_in, const void* d_out, const int32_t* d_geom,
+               uint32_t samples);
+// The per-entry checks of a list of instances against the context c, the message naming the first failing index: every handle
+// (NULL, another context), every pose, every hierarchy's state (not built, too deep for the stack); all on the host
+int check_instances(psm_ctx* c, const psm_instance* list, uint32_t count, const char* name);
+
+}  // namespace psm
+
+#ifndef PSM_QUERY_HOST_DECLARATIONS_ONLY
+#include "psm_query_dev.h"
+
+namespace psm {
+
+// a family's seven kernels by QueryKind (Q_SIGNED: the sign kernel)
+template <class Args>
+struct Kernels {
+    void (*k[7])(Args);
+};
+
+// The launch of every query. Q_SIGNED is two launches: the family's unchanged closest-point kernel, then the sign of what it
+// found (the same stream: in order)
+template <class Args>
+int launch(psm_ctx* c, const Kernels<Args>& kernels, QueryKind kind, uint32_t grid, const Args& a) {
+    if (kind == Q_SIGNED) {
+        kernels.k[Q_POINT]<<<grid, QUERY_BLOCK, 0, c->stream>>>(a);
+        PSM_HIP(c, hipGetLastError());
+    }
+    kernels.k[kind]<<<grid, QUERY_BLOCK, 0, c->stream>>>(a);
+    PSM_HIP(c, hipGetLastError());
+    return PSM_OK;
+}
+
+// The context's stack area (a context's first query allocates: a later one can be captured into a graph), the grid, and the
+// scalars QueryArgs, SceneArgs, InstArgs and WorldArgs share
+template <class Args>
+int batch_args(psm_ctx* c, const void* d_in, size_t n, void* d_out, uint32_t samples, Args& a, uint32_t& grid) {
+    void* spill = nullptr;
+    const int rc = spill_for(c, &spill);
+    if (rc != PSM_OK) return rc;
+    const size_t waves = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;
+    grid = (uint32_t)(waves < QUERY_GRID_CAP ? waves : QUERY_GRID_CAP);
+    a.rays = (const float4*)d_in; a.n = n;
+    a.spill = (int*)spill;
+    a.hits = (float4*)d_out; a.occluded = (uint8_t*)d_out; a.count = (uint32_t*)d_out;   // (a kernel reads its own)
+    a.samples = samples;
+    return PSM_OK;
+}
+
+}  // namespace psm
+#endif

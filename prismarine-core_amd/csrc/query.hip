@@ -13,7 +13,8 @@
 // child boxes by fmaf on the fp16 record coordinates (v_fma_mix_f32), nearer child first. The kernels are grid-stride. The walk
 // (query_walk: grid-stride loop, stack, leaf scheduling) is shared by the ray and the point kernels; a body says what a query is.
 // The same seven queries over a list of hierarchies (scene_walk) and over posed instances (4.9) follow. The host
-// side is one path for all 21 entry points: check_list / check_data / batch_args / launch over a per-family kernel table (4.10).
+// side is one path for all 21 entry points: check_list / check_data / batch_args / launch over a per-family kernel table (4.10);
+// psm_query_host.h declares the parts of it that world.hip's seven entry points go through as well (4.13).
 #include <cmath>
 #include <cstdio>
 #include <mutex>
@@ -22,7 +23,8 @@
 
 #include "psm_common.h"
 #include "psm_internal.h"
-#include "psm_query_dev.h"   // the constants, QueryArgs, the triangle / box / point tests and query_walk (shared with kbest.hip)
+#include "psm_query_dev.h"    // the constants, QueryArgs, the triangle / box / point tests and query_walk (shared with kbest.hip, world.hip)
+#include "psm_query_host.h"   // QueryKind, QueryDesc, Kernels, launch, batch_args; the checks defined below (shared with world.hip)
 
 namespace psm {
 
@@ -202,9 +204,6 @@ struct CountBody : CountRay {
     PSM_D bool again() const { return false; }
     PSM_D void finish(size_t i) const { a.count[i] = count; }
 };
-
-// The rays of the inside test (psm_hip.h PSM_INSIDE_DIRECTIONS: written there once): ray k of a point p is {p, 0, row k, +inf}.
-__device__ const float INSIDE_DIR[PSM_INSIDE_MAX_SAMPLES][3] = PSM_INSIDE_DIRECTIONS;
 
 // inside / outside of a point (SIGN = false: psm_bvh_inside_dev) and the sign of a closest-point result (SIGN = true: the second
 // kernel of psm_bvh_signed_distance_dev, after bvh_query_point has written hits[i]). One point per lane; its `samples` rays are
@@ -659,14 +658,6 @@ static_assert(sizeof(InstGeom) == 80 && sizeof(InstArgs) <= 4096, "the instance 
 
 namespace {
 
-// The canonical move into an instance's object space (psm_hip.h; tests/instance_query_model.py states it in numpy): a direction
-// goes through R^T, x'_j = (R[0][j] d.x + R[1][j] d.y) + R[2][j] d.z, a point through the same after d = x - T per component.
-// One float32 operation order (the build contracts nothing: -ffp-contract=off).
-PSM_D v3 inst_rotate(const float* m, v3 d) {
-    return mk3((m[0] * d.x + m[4] * d.y) + m[8] * d.z, (m[1] * d.x + m[5] * d.y) + m[9] * d.z, (m[2] * d.x + m[6] * d.y) + m[10] * d.z);
-}
-PSM_D v3 inst_point(const float* m, v3 x) { return inst_rotate(m, mk3(x.x - m[3], x.y - m[7], x.z - m[11])); }
-
 // The instanced bodies are the scene bodies over InstArgs with begin() and enter() replaced. begin() keeps what passes through
 // unchanged (the window, rmax) and the query's index; enter() reads the query again from memory (16 or 32 B, resident in L2),
 // moves it into the instance's object space, then does the scene body's per-geometry set-up. The world query is therefore never
@@ -808,10 +799,12 @@ __global__ __launch_bounds__(QUERY_BLOCK, 8) void inst_query_sign(InstArgs s) { 
 namespace {
 
 // the stack entries beyond the LDS part, per context, shared by every query kind (all run on the context's stream, never at
-// once): one column per lane of a launch (allocated on the context's first query)
+// once; the world queries' launches use the same grid cap): one column per lane of a launch (allocated on the context's first query)
 constexpr size_t SPILL_BYTES = (size_t)(QSTACK_MAX - QSTACK_LDS) * QUERY_GRID_CAP * QUERY_BLOCK * sizeof(int);
 std::mutex spill_mu;
 std::unordered_map<const psm_ctx*, void*> spill_area;
+
+}  // namespace
 
 int spill_for(psm_ctx* c, void** out) {
     std::lock_guard<std::mutex> lk(spill_mu);
@@ -828,17 +821,9 @@ int ceil_log2(size_t n) {
     return k;
 }
 
-// (Q_FIRST_HITS, Q_NEAREST: the k-best queries of kbest.hip, single hierarchies only: no entry in the kernel tables)
-enum QueryKind { Q_CLOSEST, Q_ANY, Q_POINT, Q_WITHIN, Q_COUNT, Q_INSIDE, Q_SIGNED, Q_FIRST_HITS, Q_NEAREST };
-// per kind: the single-hierarchy entry point, what the input and the output are called in its messages (out: NULL when its
-// alignment is not checked: a byte per query), the output's alignment, the family in the state / capacity texts
-struct QueryDesc {
-    const char* name;
-    const char* in;
-    const char* out;
-    unsigned out_align;
-    bool points;
-};
+// the builder's height bound of a hierarchy (QSTACK_MAX)
+int depth_bound(const psm_bvh* b) { return 63 + ceil_log2(b->cap); }
+
 const QueryDesc QUERY_DESC[] = {{"psm_bvh_intersect_dev", "rays", "hits", 16, false},
                                 {"psm_bvh_occluded_dev", "rays", nullptr, 1, false},
                                 {"psm_bvh_closest_point_dev", "points", "hits", 16, true},
@@ -848,37 +833,6 @@ const QueryDesc QUERY_DESC[] = {{"psm_bvh_intersect_dev", "rays", "hits", 16, fa
                                 {"psm_bvh_signed_distance_dev", "points", "hits", 16, true},
                                 {"psm_bvh_first_hits_dev", "rays", "hits", 16, false},
                                 {"psm_bvh_nearest_dev", "points", "hits", 16, true}};
-const char* const SCENE_NAME[] = {"psm_scene_intersect_dev", "psm_scene_occluded_dev", "psm_scene_closest_point_dev",
-                                  "psm_scene_within_dev", "psm_scene_count_hits_dev", "psm_scene_inside_dev",
-                                  "psm_scene_signed_distance_dev"};
-const char* const INST_NAME[] = {"psm_instances_intersect_dev", "psm_instances_occluded_dev", "psm_instances_closest_point_dev",
-                                 "psm_instances_within_dev", "psm_instances_count_hits_dev", "psm_instances_inside_dev",
-                                 "psm_instances_signed_distance_dev"};
-
-// a family's seven kernels by QueryKind (Q_SIGNED: the sign kernel)
-template <class Args>
-struct Kernels {
-    void (*k[7])(Args);
-};
-const Kernels<QueryArgs> BVH_KERNELS = {{bvh_query_closest, bvh_query_any, bvh_query_point, bvh_query_within, bvh_query_count,
-                                         bvh_query_inside, bvh_query_sign}};
-const Kernels<SceneArgs> SCENE_KERNELS = {{scene_query_closest, scene_query_any, scene_query_point, scene_query_within,
-                                           scene_query_count, scene_query_inside, scene_query_sign}};
-const Kernels<InstArgs> INST_KERNELS = {{inst_query_closest, inst_query_any, inst_query_point, inst_query_within, inst_query_count,
-                                         inst_query_inside, inst_query_sign}};
-
-// The launch of every query. Q_SIGNED is two launches: the family's unchanged closest-point kernel, then the sign of what it
-// found (the same stream: in order)
-template <class Args>
-int launch(psm_ctx* c, const Kernels<Args>& kernels, QueryKind kind, uint32_t grid, const Args& a) {
-    if (kind == Q_SIGNED) {
-        kernels.k[Q_POINT]<<<grid, QUERY_BLOCK, 0, c->stream>>>(a);
-        PSM_HIP(c, hipGetLastError());
-    }
-    kernels.k[kind]<<<grid, QUERY_BLOCK, 0, c->stream>>>(a);
-    PSM_HIP(c, hipGetLastError());
-    return PSM_OK;
-}
 
 // The data checks every query shares, under the entry point's name: in / out must be non-NULL, in 16-byte aligned, out as its
 // kind asks (a psm_hit 16 bytes, a count 4); samples (the inside kinds only): 1, 3 or 5; the k-best kinds' k travels as
@@ -917,23 +871,37 @@ int check_data(psm_ctx* c, const char* name, const char* index, QueryKind kind, 
     return PSM_OK;
 }
 
-// The context's stack area (a context's first query allocates: a later one can be captured into a graph), the grid, and the
-// scalars QueryArgs, SceneArgs and InstArgs share
-template <class Args>
-int batch_args(psm_ctx* c, const void* d_in, size_t n, void* d_out, uint32_t samples, Args& a, uint32_t& grid) {
-    void* spill = nullptr;
-    const int rc = spill_for(c, &spill);
-    if (rc != PSM_OK) return rc;
-    const size_t waves = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;
-    grid = (uint32_t)(waves < QUERY_GRID_CAP ? waves : QUERY_GRID_CAP);
-    a.rays = (const float4*)d_in; a.n = n;
-    a.spill = (int*)spill;
-    a.hits = (float4*)d_out; a.occluded = (uint8_t*)d_out; a.count = (uint32_t*)d_out;   // (a kernel reads its own)
-    a.samples = samples;
-    return PSM_OK;
+// Why a pose is refused, or NULL (psm_hip.h): in double, on the host. A rigid motion or a reflection has R^T R = 1; the bound
+// leaves room for a matrix that was composed in float32 and refuses every scale or shear a user could mean.
+const char* pose_fault(const float* m) {
+    for (int k = 0; k < 12; k++)
+        if (!std::isfinite(m[k])) return "has a non-finite transform";
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) {
+            double dot = 0.0;
+            for (int i = 0; i < 3; i++) dot += (double)m[4 * i + a] * (double)m[4 * i + b];
+            if (std::fabs(dot - (a == b ? 1.0 : 0.0)) > 1e-5) return "has a transform that is not rigid (R^T R differs from 1 by more than 1e-5)";
+        }
+    return nullptr;
 }
 
-bool too_deep(const psm_bvh* b) { return 63 + ceil_log2(b->cap) > QSTACK_MAX; }
+namespace {
+
+const char* const SCENE_NAME[] = {"psm_scene_intersect_dev", "psm_scene_occluded_dev", "psm_scene_closest_point_dev",
+                                  "psm_scene_within_dev", "psm_scene_count_hits_dev", "psm_scene_inside_dev",
+                                  "psm_scene_signed_distance_dev"};
+const char* const INST_NAME[] = {"psm_instances_intersect_dev", "psm_instances_occluded_dev", "psm_instances_closest_point_dev",
+                                 "psm_instances_within_dev", "psm_instances_count_hits_dev", "psm_instances_inside_dev",
+                                 "psm_instances_signed_distance_dev"};
+
+const Kernels<QueryArgs> BVH_KERNELS = {{bvh_query_closest, bvh_query_any, bvh_query_point, bvh_query_within, bvh_query_count,
+                                         bvh_query_inside, bvh_query_sign}};
+const Kernels<SceneArgs> SCENE_KERNELS = {{scene_query_closest, scene_query_any, scene_query_point, scene_query_within,
+                                           scene_query_count, scene_query_inside, scene_query_sign}};
+const Kernels<InstArgs> INST_KERNELS = {{inst_query_closest, inst_query_any, inst_query_point, inst_query_within, inst_query_count,
+                                         inst_query_inside, inst_query_sign}};
+
+bool too_deep(const psm_bvh* b) { return depth_bound(b) > QSTACK_MAX; }
 
 // A query of one hierarchy: n == 0 is answered before anything else is looked at; then the data, the state, the depth.
 // The k-best kinds (kbest.hip) come through here too: samples is their k, d_out their [n][k] records, d_count their counts.
@@ -960,20 +928,6 @@ int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, void* d_out, u
     return launch(c, BVH_KERNELS, kind, grid, qa);
 }
 
-// Why a pose is refused, or NULL (psm_hip.h): in double, on the host. A rigid motion or a reflection has R^T R = 1; the bound
-// leaves room for a matrix that was composed in float32 and refuses every scale or shear a user could mean.
-const char* pose_fault(const float* m) {
-    for (int k = 0; k < 12; k++)
-        if (!std::isfinite(m[k])) return "has a non-finite transform";
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) {
-            double dot = 0.0;
-            for (int i = 0; i < 3; i++) dot += (double)m[4 * i + a] * (double)m[4 * i + b];
-            if (std::fabs(dot - (a == b ? 1.0 : 0.0)) > 1e-5) return "has a transform that is not rigid (R^T R differs from 1 by more than 1e-5)";
-        }
-    return nullptr;
-}
-
 // An entry of a list as the list queries read it: a scene's psm_bvh*, or a psm_instance (a hierarchy and its pose). noun: what
 // the messages call it; fault: why the entry itself is refused, or NULL; fill: its row of the kernel-argument table.
 struct SceneEntry {
@@ -994,18 +948,10 @@ struct InstEntry {
     }
 };
 
-// The list of a scene or an instanced query, checked first and whole, also for n == 0, all of it on the host before any device
-// is touched: its length; then every entry's handle (NULL, another context than the first non-NULL entry's), every entry's own
-// fault (the poses), every entry's state (not built, too deep for the stack) -- the message naming the first failing index. The
-// message goes to the context of the first non-NULL entry, *ctx (a list of NULLs only has no context to tell: the return code alone).
+// The per-entry checks of a list against its context c, the message naming the first failing index: every entry's handle
+// (NULL, another context than c), every entry's own fault (the poses), every entry's state (not built, too deep for the stack).
 template <class E, class Entry>
-int check_list(const Entry* list, uint32_t count, const char* name, psm_ctx** ctx) {
-    if (!list || count == 0 || count > PSM_SCENE_MAX_GEOMETRIES) return PSM_ERR_INVALID;
-    psm_ctx* c = nullptr;
-    for (uint32_t g = 0; g < count && !c; g++)
-        if (E::bvh(list[g])) c = E::bvh(list[g])->ctx;
-    if (!c) return PSM_ERR_INVALID;
-    *ctx = c;
+int check_entries(psm_ctx* c, const Entry* list, uint32_t count, const char* name) {
     char msg[160];
     for (uint32_t g = 0; g < count; g++) {
         if (!E::bvh(list[g])) {
@@ -1033,6 +979,20 @@ int check_list(const Entry* list, uint32_t count, const char* name, psm_ctx** ct
         }
     }
     return PSM_OK;
+}
+
+// The list of a scene or an instanced query, checked first and whole, also for n == 0, all of it on the host before any device
+// is touched: its length, then its entries (check_entries). The message goes to the context of the first non-NULL entry, *ctx
+// (a list of NULLs only has no context to tell: the return code alone).
+template <class E, class Entry>
+int check_list(const Entry* list, uint32_t count, const char* name, psm_ctx** ctx) {
+    if (!list || count == 0 || count > PSM_SCENE_MAX_GEOMETRIES) return PSM_ERR_INVALID;
+    psm_ctx* c = nullptr;
+    for (uint32_t g = 0; g < count && !c; g++)
+        if (E::bvh(list[g])) c = E::bvh(list[g])->ctx;
+    if (!c) return PSM_ERR_INVALID;
+    *ctx = c;
+    return check_entries<E>(c, list, count, name);
 }
 
 // A query of a list (E: SceneEntry or InstEntry): the list, n == 0, the data, the table, the launch. index: what d_geom is
@@ -1076,8 +1036,10 @@ void query_release(psm_ctx* c) {
     spill_area.erase(it);
 }
 
-// world.hip: the context's stack area serves the world queries too (their launches use the same grid cap)
-int query_spill(psm_ctx* c, void** out) { return spill_for(c, out); }
+// psm_world_set_instances (world.hip): the instanced queries' per-entry checks, against the world's context
+int check_instances(psm_ctx* c, const psm_instance* list, uint32_t count, const char* name) {
+    return check_entries<InstEntry>(c, list, count, name);
+}
 
 }  // namespace psm
 

@@ -5,8 +5,9 @@
 // query.hip's InstGeom, now in memory) and a binary tree over the instances' padded world-space boxes. A world of N instances
 // answers every query exactly as psm_instances_*_dev would over the same ordered list if that list could be N long: the tree
 // only decides which instances a query enters, and every box test is padded and slackened so that it never drops an instance
-// that holds a counting candidate (the bounds: WORLD_PAD below). What a query does inside an instance is the instanced bodies'
-// code, copied: query.hip's 21 kernels keep their instruction streams (the file is touched for one host function only).
+// that holds a counting candidate (the bounds: WORLD_PAD below). What a query does inside an instance is what the instanced
+// bodies of query.hip do, from the same pieces: the tests, the move and the constants of psm_query_dev.h, the checks and the
+// launch of psm_query_host.h. This file holds what is a world's own: rows, tree, walk, stale check, depth rule.
 //
 // The walk is one loop over one stack ([depth][lane] in LDS, the rest in the context's spill area). A stack entry is a link:
 //   link < 0               instance ~link of the world: the lane enters it (loads its row, moves the query, sets up)
@@ -24,11 +25,10 @@
 
 #include "psm_common.h"
 #include "psm_internal.h"
+#include "psm_query_dev.h"    // the constants, the triangle / box / point tests, inst_point / inst_rotate, INSIDE_DIR
+#include "psm_query_host.h"   // QueryKind, check_data / check_instances, batch_args / launch
 
 namespace psm {
-
-int query_spill(psm_ctx* c, void** out);   // query.hip: the context's stack area beyond the LDS part
-uint64_t bvh_generation(const psm_bvh* b);   // api.hip: bumped by every build of the hierarchy
 
 // one instance as the kernels read it: 80 B, 16-byte aligned (five 16-byte loads)
 struct WorldRow {
@@ -64,12 +64,6 @@ struct WorldArgs {
 
 namespace {
 
-constexpr int SM_M = 0, SM_COUNT = 24, SM_ROOT = 25;   // bvh.hip: d_small
-constexpr int QUERY_BLOCK = 64, QSTACK_LDS = 16, QSTACK_MAX = 96;   // query.hip
-#ifndef PSM_QUERY_GRID_CAP
-#define PSM_QUERY_GRID_CAP 8192
-#endif
-constexpr uint32_t QUERY_GRID_CAP = PSM_QUERY_GRID_CAP;
 constexpr int WORLD_TOP = 0x40000000;   // tag of a top-level node link (hierarchy node links stay below 2^28)
 
 // The padding and the slacks (DESIGN.md 4.11 has the derivation). The box test works on the world query and the forward image
@@ -87,175 +81,6 @@ constexpr float WORLD_FLOOR = 0x1p-100f;   // ... so no box is ever degenerate (
 constexpr float WORLD_QSLACK = 0x1p-11f;   // ... and by WORLD_QSLACK * the query's largest |coordinate| at the test
 constexpr float WORLD_TSLACK = 0x1p-12f;   // a ray's prune against best / tmax / tmin: relative
 constexpr float WORLD_PSLACK = 0x1p-11f;   // a point's prune against best d2 / rmax^2: relative
-
-// ---- copied from query.hip (its kernels keep their code; see the comments there) ---------------------------------------------
-
-PSM_D bool w_tri_query(const float4* __restrict__ tri48, int tri, v3 orig, v3 dir, float& T, float& U, float& V) {
-    const float4 a = tri48[(size_t)3 * tri + 0], b = tri48[(size_t)3 * tri + 1], c = tri48[(size_t)3 * tri + 2];
-    const v3 v0 = mk3(a.x, a.y, a.z), e1 = mk3(b.x, b.y, b.z), e2 = mk3(c.x, c.y, c.z);
-    const v3 pvec = cross3(dir, e2);
-    const float det = dot3(e1, pvec);
-    if (pabs(det) <= 0.0f) return false;
-    const float invDev = 1.f / det;
-    const v3 tvec = orig - v0;
-    const float u = dot3(tvec, pvec) * invDev;
-    if (u < -0.00001f || u > 1.00001f) return false;
-    const v3 qvec = cross3(tvec, e1);
-    const float v = dot3(dir, qvec) * invDev;
-    if (v < -0.00001f || (u + v) > 1.00001f) return false;
-    T = dot3(e2, qvec) * invDev;
-    U = u;
-    V = v;
-    return true;
-}
-
-PSM_D bool finite3(v3 a) { return __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z); }
-
-struct Row {
-    float P, h;
-};
-PSM_D Row affine_row(const float* M, int k, v3 x) {
-    const float m0 = M[4 * k + 0], m1 = M[4 * k + 1], m2 = M[4 * k + 2], m3 = M[4 * k + 3];
-    Row r;
-    r.P = ((m0 * x.x + m1 * x.y) + m2 * x.z) + m3;
-    const float S = ((pabs(m0 * x.x) + pabs(m1 * x.y)) + pabs(m2 * x.z)) + pabs(m3);
-    r.h = (2.0f + S) * 0x1p-16f;
-    return r;
-}
-
-struct Axis {
-    float inv, nlo, nhi;
-};
-PSM_D Axis ray_axis(const float* M, int k, v3 o, v3 d) {
-    const float m0 = M[4 * k + 0], m1 = M[4 * k + 1], m2 = M[4 * k + 2];
-    const Row r = affine_row(M, k, o);
-    float D = (m0 * d.x + m1 * d.y) + m2 * d.z;
-    if (!(pabs(D) >= 1e-20f)) D = __builtin_copysignf(1e-20f, D);
-    Axis a;
-    a.inv = 1.0f / D;
-    a.nlo = -(r.P + r.h) * a.inv;
-    a.nhi = (r.h - r.P) * a.inv;
-    return a;
-}
-
-PSM_D void slab(const Axis& X, const Axis& Y, const Axis& Z, float mnx, float mny, float mnz, float mxx, float mxy, float mxz,
-                float& tNear, float& tFar) {
-    const float ax = fmaf(mnx, X.inv, X.nlo), bx = fmaf(mxx, X.inv, X.nhi);
-    const float ay = fmaf(mny, Y.inv, Y.nlo), by = fmaf(mxy, Y.inv, Y.nhi);
-    const float az = fmaf(mnz, Z.inv, Z.nlo), bz = fmaf(mxz, Z.inv, Z.nhi);
-    tNear = smaxf(smaxf(sminf(ax, bx), sminf(ay, by)), sminf(az, bz));
-    tFar = sminf(sminf(smaxf(ax, bx), smaxf(ay, by)), smaxf(az, bz));
-}
-
-PSM_D float4 miss_hit() { return make_float4(0.f, 0.f, __builtin_inff(), __int_as_float(-1)); }
-
-PSM_D float clamp01(float x) {
-    x = x > 0.f ? x : 0.f;
-    return x < 1.f ? x : 1.f;
-}
-
-PSM_D float closest_on_tri(v3 v0, v3 e1, v3 e2, v3 p, float& U, float& V) {
-    const v3 ap = p - v0;
-    const float aa = dot3(e1, e1), ab = dot3(e1, e2), bb = dot3(e2, e2);
-    const float d1 = dot3(e1, ap), d2 = dot3(e2, ap);
-    const float d3 = d1 - aa, d4 = d2 - ab, d5 = d1 - ab, d6 = d2 - bb;
-    const float vc = aa * d2 - ab * d1;
-    const float vb = bb * d1 - ab * d2;
-    const float va = d3 * d6 - d5 * d4;
-    const float e43 = d4 - d3, e56 = d5 - d6;
-    const float det = aa * bb - ab * ab;
-    const v3 e21 = e2 - e1;
-    const float cc = dot3(e21, e21);
-    const bool sa = aa >= bb && aa >= cc, sb = bb >= cc;
-    int reg = sa ? 7 : (sb ? 8 : 9);
-    float n1 = sa ? d1 : (sb ? d2 : e43), q1d = sa ? aa : (sb ? bb : cc);
-    if (det > (aa * bb) * 0x1p-16f) { reg = 6; n1 = vb; q1d = det; }
-    if (va <= 0.f && e43 >= 0.f && e56 >= 0.f && e43 + e56 > 0.f) { reg = 5; n1 = e43; q1d = e43 + e56; }
-    if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f && d2 - d6 > 0.f) { reg = 4; n1 = d2; q1d = d2 - d6; }
-    if (d6 >= 0.f && d5 <= d6) { reg = 3; n1 = 0.f; q1d = 1.f; }
-    if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f && d1 - d3 > 0.f) { reg = 2; n1 = d1; q1d = d1 - d3; }
-    if (d3 >= 0.f && d4 <= d3) { reg = 1; n1 = 0.f; q1d = 1.f; }
-    if (d1 <= 0.f && d2 <= 0.f) { reg = 0; n1 = 0.f; q1d = 1.f; }
-    const float q1 = n1 / q1d;
-    const float q2 = (reg == 6 ? vc : 0.f) / (reg == 6 ? det : 1.f);
-    const float c1 = clamp01(q1);
-    float u = 0.f, v = 0.f;
-    if (reg == 1) u = 1.f;
-    if (reg == 2) u = q1;
-    if (reg == 3) v = 1.f;
-    if (reg == 4) v = q1;
-    if (reg == 5) { u = 1.f - q1; v = q1; }
-    if (reg == 6) {
-        u = c1;
-        const float f = q2 > 0.f ? q2 : 0.f, lim = 1.f - c1;
-        v = f < lim ? f : lim;
-    }
-    if (reg == 7) u = c1;
-    if (reg == 8) v = c1;
-    if (reg == 9) { u = 1.f - c1; v = c1; }
-    const v3 c = mk3((v0.x + u * e1.x) + v * e2.x, (v0.y + u * e1.y) + v * e2.y, (v0.z + u * e1.z) + v * e2.z);
-    const v3 dp = p - c;
-    U = u;
-    V = v;
-    return dot3(dp, dp);
-}
-
-struct PointBound {
-    float il0, il1, il2;
-    float wf;
-    bool orth;
-};
-PSM_D PointBound point_bound(const float* M) {
-    PointBound b;
-    float il[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float lam = sqrtf(dot3(mk3(M[4 * k], M[4 * k + 1], M[4 * k + 2]), mk3(M[4 * k], M[4 * k + 1], M[4 * k + 2])));
-        il[k] = lam > 0.f ? 1.0f / lam : 0.f;
-    }
-    const v3 r0 = mk3(M[0], M[1], M[2]), r1 = mk3(M[4], M[5], M[6]), r2 = mk3(M[8], M[9], M[10]);
-    const float c01 = pabs(dot3(r0, r1)) * il[0] * il[1], c02 = pabs(dot3(r0, r2)) * il[0] * il[2];
-    const float c12 = pabs(dot3(r1, r2)) * il[1] * il[2];
-    const float cmax = smaxf(smaxf(c01, c02), c12) + 0x1p-20f;
-    b.il0 = il[0];
-    b.il1 = il[1];
-    b.il2 = il[2];
-    b.orth = cmax <= 0x1p-11f && il[0] > 0.f && il[1] > 0.f && il[2] > 0.f;
-    b.wf = b.orth ? (1.0f - 0x1p-18f) / (1.0f + 2.0f * cmax) : (1.0f - 0x1p-18f);
-    return b;
-}
-
-struct PointImage {
-    float Px, Py, Pz, h;
-
-    PSM_D void set(const float* M, v3 p) {
-        const Row X = affine_row(M, 0, p), Y = affine_row(M, 1, p), Z = affine_row(M, 2, p);
-        Px = X.P;
-        Py = Y.P;
-        Pz = Z.P;
-        h = smaxf(smaxf(X.h, Y.h), Z.h);
-    }
-    PSM_D float lb2(const PointBound& B, float mnx, float mny, float mnz, float mxx, float mxy, float mxz) const {
-        const float tx = smaxf(smaxf(mnx - Px, Px - mxx) - h, 0.f) * B.il0;
-        const float ty = smaxf(smaxf(mny - Py, Py - mxy) - h, 0.f) * B.il1;
-        const float tz = smaxf(smaxf(mnz - Pz, Pz - mxz) - h, 0.f) * B.il2;
-        const float m = smaxf(smaxf(tx, ty), tz);
-        return (B.orth ? ((tx * tx + ty * ty) + tz * tz) : m * m) * B.wf;
-    }
-    PSM_D void children(const PointBound& B, uint4 n0, uint4 n1, float best, bool& okL, bool& okR, float& kL, float& kR) const {
-        kL = lb2(B, half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z));
-        kR = lb2(B, half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y));
-        okL = kL <= best;
-        okR = kR <= best;
-    }
-};
-
-__device__ const float W_INSIDE_DIR[PSM_INSIDE_MAX_SAMPLES][3] = PSM_INSIDE_DIRECTIONS;
-
-PSM_D v3 inst_rotate(const float* m, v3 d) {
-    return mk3((m[0] * d.x + m[4] * d.y) + m[8] * d.z, (m[1] * d.x + m[5] * d.y) + m[9] * d.z, (m[2] * d.x + m[6] * d.y) + m[10] * d.z);
-}
-PSM_D v3 inst_point(const float* m, v3 x) { return inst_rotate(m, mk3(x.x - m[3], x.y - m[7], x.z - m[11])); }
 
 // ---- the two-level walk --------------------------------------------------------------------------------------------------------
 
@@ -449,6 +274,14 @@ struct WorldRay {
         const int root = (int)r.sm[SM_ROOT];
         return (finite3(o) && finite3(d)) ? (root >= 0 ? root : -2) : -1;   // -2: valid here, no tree (0 or 1 leaves)
     }
+    // begin() of the bodies whose query is a ray: the window and the world ray (a dead lane: an empty window)
+    PSM_D void begin_ray(const WorldArgs& w, size_t i, bool al) {
+        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(1.f, 0.f, 0.f, -1.f);
+        if (al) { r0 = w.rays[2 * i]; r1 = w.rays[2 * i + 1]; }
+        tmin = r0.w;
+        tmax = r1.w;
+        world_ray(mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z));
+    }
     PSM_D void boxes(uint4 n0, uint4 n1, float lim, bool& okL, bool& okR, float& nL, float& nR) const {
         float fL, fR;
         psm::slab(X, Y, Z, half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z), nL, fL);
@@ -470,11 +303,7 @@ struct WorldRayBody : WorldRay {
     PSM_D bool begin(size_t i, bool al) {
         idx = i;
         alive = al;
-        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(1.f, 0.f, 0.f, -1.f);
-        if (al) { r0 = w.rays[2 * i]; r1 = w.rays[2 * i + 1]; }
-        tmin = r0.w;
-        tmax = r1.w;
-        world_ray(mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z));
+        begin_ray(w, i, al);
         b.clear(tmax);
         found = false;
         return al && tmin <= tmax;
@@ -496,7 +325,7 @@ struct WorldRayBody : WorldRay {
     }
     PSM_D void leaf(int tri) {
         float t, u, v;
-        if (w_tri_query(tri48, tri, o, d, t, u, v) && t >= tmin && b.wins(t, inst, tri)) {
+        if (tri_query(tri48, tri, o, d, t, u, v) && t >= tmin && b.wins(t, inst, tri)) {
             found = true;
             if (!ANY) b.take(t, u, v, inst, tri);
         }
@@ -522,7 +351,7 @@ struct WorldCountRay : WorldRay {
     PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& nL, float& nR) const { boxes(n0, n1, tmax, okL, okR, nL, nR); }
     PSM_D void leaf(int tri) {
         float t, u, v;
-        if (w_tri_query(tri48, tri, o, d, t, u, v) && t >= tmin && t <= tmax) count++;
+        if (tri_query(tri48, tri, o, d, t, u, v) && t >= tmin && t <= tmax) count++;
     }
     PSM_D bool done() const { return false; }
 };
@@ -535,11 +364,7 @@ struct WorldCountBody : WorldCountRay {
     PSM_D bool begin(size_t i, bool al) {
         idx = i;
         alive = al;
-        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(1.f, 0.f, 0.f, -1.f);
-        if (al) { r0 = w.rays[2 * i]; r1 = w.rays[2 * i + 1]; }
-        tmin = r0.w;
-        tmax = r1.w;
-        world_ray(mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z));
+        begin_ray(w, i, al);
         count = 0u;
         return al && tmin <= tmax;
     }
@@ -569,7 +394,7 @@ struct WorldInsideBody : WorldCountRay {
     PSM_D WorldInsideBody(const WorldArgs& a) : w(a) {}
     PSM_D v3 dir() const {
         const int r = __builtin_amdgcn_readfirstlane((int)k);   // (every lane of the wave is at the same k)
-        return mk3(W_INSIDE_DIR[r][0], W_INSIDE_DIR[r][1], W_INSIDE_DIR[r][2]);
+        return mk3(INSIDE_DIR[r][0], INSIDE_DIR[r][1], INSIDE_DIR[r][2]);
     }
     PSM_D float4 point() const {
         float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
@@ -961,74 +786,17 @@ struct psm_world {
 namespace psm {
 namespace {
 
-enum QueryKind { Q_CLOSEST, Q_ANY, Q_POINT, Q_WITHIN, Q_COUNT, Q_INSIDE, Q_SIGNED };
-struct QueryDesc {
-    const char* name;
-    const char* in;
-    const char* out;
-    unsigned out_align;
-};
-const QueryDesc WORLD_DESC[] = {{"psm_world_intersect_dev", "rays", "hits", 16},
-                                {"psm_world_occluded_dev", "rays", nullptr, 1},
-                                {"psm_world_closest_point_dev", "points", "hits", 16},
-                                {"psm_world_within_dev", "points", nullptr, 1},
-                                {"psm_world_count_hits_dev", "rays", "counts", 4},
-                                {"psm_world_inside_dev", "points", nullptr, 1},
-                                {"psm_world_signed_distance_dev", "points", "hits", 16}};
-void (*const WORLD_KERNELS[7])(WorldArgs) = {world_query_closest, world_query_any, world_query_point, world_query_within,
-                                             world_query_count, world_query_inside, world_query_sign};
+const char* const WORLD_NAME[7] = {"psm_world_intersect_dev", "psm_world_occluded_dev", "psm_world_closest_point_dev",
+                                   "psm_world_within_dev", "psm_world_count_hits_dev", "psm_world_inside_dev",
+                                   "psm_world_signed_distance_dev"};
+const Kernels<WorldArgs> WORLD_KERNELS = {{world_query_closest, world_query_any, world_query_point, world_query_within,
+                                           world_query_count, world_query_inside, world_query_sign}};
 
-int ceil_log2(size_t n) {
-    int k = 0;
-    while (((size_t)1 << k) < n) k++;
-    return k;
-}
-// what a walk of the hierarchy can hold on the stack: query.hip's bound (too_deep), and never more than its internal nodes
+// what a walk of the hierarchy can hold on the stack: the builder's bound (depth_bound), and never more than its internal nodes
 int hier_depth(const psm_bvh* b) {
-    const int bound = 63 + ceil_log2(b->cap);
+    const int bound = depth_bound(b);
     const int nodes = b->tri_count > 0 ? (int)(b->tri_count < (1u << 30) ? b->tri_count : (1u << 30)) - 1 : 0;
     return nodes < bound ? nodes : bound;
-}
-
-// query.hip's pose_fault
-const char* pose_fault(const float* m) {
-    for (int k = 0; k < 12; k++)
-        if (!std::isfinite(m[k])) return "has a non-finite transform";
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) {
-            double dot = 0.0;
-            for (int i = 0; i < 3; i++) dot += (double)m[4 * i + a] * (double)m[4 * i + b];
-            if (std::fabs(dot - (a == b ? 1.0 : 0.0)) > 1e-5) return "has a transform that is not rigid (R^T R differs from 1 by more than 1e-5)";
-        }
-    return nullptr;
-}
-
-// query.hip's check_data, with d_inst as the index array
-int check_data(psm_ctx* c, QueryKind kind, const void* d_in, const void* d_out, const int32_t* d_inst, uint32_t samples) {
-    const QueryDesc& k = WORLD_DESC[kind];
-    char msg[128];
-    const bool with_inst = k.out_align == 16;
-    if (!d_in || !d_out || (with_inst && !d_inst)) {
-        snprintf(msg, sizeof msg, "%s: NULL pointer", k.name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    const bool in_bad = ((uintptr_t)d_in & 15u) != 0, out_bad = ((uintptr_t)d_out & (uintptr_t)(k.out_align - 1)) != 0;
-    if (in_bad || out_bad) {
-        if (k.out_align == 16) snprintf(msg, sizeof msg, "%s: %s or %s not 16-byte aligned", k.name, k.in, k.out);
-        else if (in_bad) snprintf(msg, sizeof msg, "%s: %s not 16-byte aligned", k.name, k.in);
-        else snprintf(msg, sizeof msg, "%s: %s not %u-byte aligned", k.name, k.out, k.out_align);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (with_inst && ((uintptr_t)d_inst & 3u) != 0) {
-        snprintf(msg, sizeof msg, "%s: inst not 4-byte aligned", k.name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if ((kind == Q_INSIDE || kind == Q_SIGNED) && samples != 1 && samples != 3 && samples != 5) {
-        snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", k.name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    (void)hipSetDevice(c->device);
-    return PSM_OK;
 }
 
 // the first instance whose hierarchy is no longer what the world recorded, or -1
@@ -1105,15 +873,16 @@ int world_upload_and_build(psm_world* w, const char* name) {
     return check_depth(w, name);
 }
 
+// A query of a world: the data (check_data, as every query's), the empty world's answer, the stale check, the launch
 int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_inst, uint32_t samples = 0) {
     if (!w) return PSM_ERR_INVALID;
     if (n == 0) return PSM_OK;
     psm_ctx* c = w->ctx;
-    const char* name = WORLD_DESC[kind].name;
-    int rc = check_data(c, kind, d_in, d_out, d_inst, samples);
+    const char* name = WORLD_NAME[kind];
+    int rc = check_data(c, name, "inst", kind, d_in, d_out, d_inst, samples);
     if (rc != PSM_OK) return rc;
     if (w->count == 0) {   // an empty world: every query misses, no query kernel runs
-        const unsigned per = WORLD_DESC[kind].out_align;
+        const unsigned per = QUERY_DESC[kind].out_align;
         if (per == 16) world_fill_miss<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>((float4*)d_out, d_inst, n);
         else PSM_HIP(c, hipMemsetAsync(d_out, 0, n * per, c->stream));
         PSM_HIP(c, hipGetLastError());
@@ -1121,27 +890,15 @@ int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* 
     }
     const int stale = first_stale(w);
     if (stale >= 0) return refuse_stale(w, name, stale);
-    void* spill = nullptr;
-    rc = query_spill(c, &spill);
-    if (rc != PSM_OK) return rc;
-    const size_t waves = (n + QUERY_BLOCK - 1) / QUERY_BLOCK;
-    const uint32_t grid = (uint32_t)(waves < QUERY_GRID_CAP ? waves : QUERY_GRID_CAP);
     WorldArgs a = {};
-    a.rays = (const float4*)d_in; a.n = n;
-    a.spill = (int*)spill;
-    a.hits = (float4*)d_out; a.occluded = (uint8_t*)d_out; a.count = (uint32_t*)d_out;
+    uint32_t grid = 0;
+    rc = batch_args(c, d_in, n, d_out, samples, a, grid);
+    if (rc != PSM_OK) return rc;
     a.geom = d_inst;
-    a.samples = samples;
     a.root = w->count == 1 ? ~0 : 0;
     a.rows = w->d_rows;
     a.nodes = w->d_nodes;
-    if (kind == Q_SIGNED) {
-        WORLD_KERNELS[Q_POINT]<<<grid, QUERY_BLOCK, 0, c->stream>>>(a);
-        PSM_HIP(c, hipGetLastError());
-    }
-    WORLD_KERNELS[kind]<<<grid, QUERY_BLOCK, 0, c->stream>>>(a);
-    PSM_HIP(c, hipGetLastError());
-    return PSM_OK;
+    return launch(c, WORLD_KERNELS, kind, grid, a);
 }
 
 template <class T>
@@ -1203,32 +960,9 @@ int psm_world_set_instances(psm_world* w, const psm_instance* insts, uint32_t co
         snprintf(msg, sizeof msg, "%s: %u instances exceed the world's capacity of %u", name, count, w->cap);
         return set_err(c, PSM_ERR_CAPACITY, msg);
     }
-    // the list checks of the instanced queries (query.hip check_list<InstEntry>), in their order, all before any device work
-    for (uint32_t g = 0; g < count; g++) {
-        if (!insts[g].bvh) {
-            snprintf(msg, sizeof msg, "%s: instance %u is NULL", name, g);
-            return set_err(c, PSM_ERR_INVALID, msg);
-        }
-        if (insts[g].bvh->ctx != c) {
-            snprintf(msg, sizeof msg, "%s: instance %u belongs to another context", name, g);
-            return set_err(c, PSM_ERR_INVALID, msg);
-        }
-    }
-    for (uint32_t g = 0; g < count; g++)
-        if (const char* why = pose_fault(insts[g].world_from_object)) {
-            snprintf(msg, sizeof msg, "%s: instance %u %s", name, g, why);
-            return set_err(c, PSM_ERR_INVALID, msg);
-        }
-    for (uint32_t g = 0; g < count; g++) {
-        if (!insts[g].bvh->built) {
-            snprintf(msg, sizeof msg, "%s: instance %u is not built", name, g);
-            return set_err(c, PSM_ERR_STATE, msg);
-        }
-        if (63 + ceil_log2(insts[g].bvh->cap) > QSTACK_MAX) {
-            snprintf(msg, sizeof msg, "%s: instance %u is deeper than the query stack", name, g);
-            return set_err(c, PSM_ERR_CAPACITY, msg);
-        }
-    }
+    // the per-entry checks of the instanced queries, in their order, all before any device work
+    const int rc = check_instances(c, insts, count, name);
+    if (rc != PSM_OK) return rc;
     world_clear(w);
     w->count = count;
     w->insts.assign(insts, insts + count);

@@ -307,3 +307,91 @@ def test_65536_poses_of_one_icosphere(psm, ctx):
     finally:
         world.close()
         th.close()
+
+
+def test_world_host_checks_by_their_exact_messages(psm, ctx):
+    """every refusal of a world query's data and of psm_world_set_instances' list, by return code and text: all of them are
+    made on the host before any launch, and a refused list leaves the world as it was"""
+    two = np.asarray([[0, 0, 0, 1, 0, 0, 0, 1, 0], [0, 0, 1, 1, 0, 1, 0, 1, 1]], F)
+    a, b = _hier(psm, ctx, two), _hier(psm, ctx, two + F(2))
+    unbuilt = psm.TriangleHierarchy(ctx)
+    unbuilt.allocate(4)
+    unbuilt.loadTriangles(two)
+    other_ctx = psm.Context(0)
+    foreign = _hier(psm, other_ctx, two)
+    world = psm.InstanceWorld(ctx, [(a, NQ.IDENTITY), (b, NQ.IDENTITY)], capacity=4)
+    try:
+        lib = psm.lib()
+        h = ctx.buf_alloc(256)
+        p = ctx.buf_ptr(h)[0]
+        P, one, three, u32, w = ctypes.c_void_p, ctypes.c_size_t(1), ctypes.c_uint32(3), ctypes.c_uint32, world._w
+        err = lambda: lib.psm_last_error(ctx._h).decode()
+        assert lib.psm_world_intersect_dev(w, None, one, P(p + 32), P(p + 64)) == -1
+        assert err() == "psm_world_intersect_dev: NULL pointer"
+        assert lib.psm_world_closest_point_dev(w, P(p), one, P(p + 32), None) == -1      # inst must not be NULL
+        assert err() == "psm_world_closest_point_dev: NULL pointer"
+        assert lib.psm_world_within_dev(w, P(p), one, None) == -1
+        assert err() == "psm_world_within_dev: NULL pointer"
+        assert lib.psm_world_intersect_dev(w, P(p), one, P(p + 36), P(p + 64)) == -1
+        assert err() == "psm_world_intersect_dev: rays or hits not 16-byte aligned"
+        assert lib.psm_world_closest_point_dev(w, P(p + 8), one, P(p + 32), P(p + 64)) == -1
+        assert err() == "psm_world_closest_point_dev: points or hits not 16-byte aligned"
+        assert lib.psm_world_occluded_dev(w, P(p + 4), one, P(p + 64)) == -1
+        assert err() == "psm_world_occluded_dev: rays not 16-byte aligned"
+        assert lib.psm_world_count_hits_dev(w, P(p), one, P(p + 34)) == -1
+        assert err() == "psm_world_count_hits_dev: counts not 4-byte aligned"
+        assert lib.psm_world_intersect_dev(w, P(p), one, P(p + 32), P(p + 66)) == -1
+        assert err() == "psm_world_intersect_dev: inst not 4-byte aligned"
+        for s in (0, 2, 4, 6):
+            assert lib.psm_world_inside_dev(w, P(p), one, u32(s), P(p + 64)) == -1
+            assert err() == "psm_world_inside_dev: samples must be 1, 3 or 5"
+            assert lib.psm_world_signed_distance_dev(w, P(p), one, u32(s), P(p + 32), P(p + 64)) == -1
+            assert err() == "psm_world_signed_distance_dev: samples must be 1, 3 or 5"
+        # the data is judged before the samples, and a NULL before an alignment
+        assert lib.psm_world_signed_distance_dev(w, P(p), one, u32(2), P(p + 32), P(p + 66)) == -1
+        assert err() == "psm_world_signed_distance_dev: inst not 4-byte aligned"
+        assert lib.psm_world_intersect_dev(w, P(p + 4), one, P(p + 32), None) == -1
+        assert err() == "psm_world_intersect_dev: NULL pointer"
+
+        eye = [1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]
+
+        def lst(*entries):
+            v = (psm.Instance * len(entries))()
+            for k, e in enumerate(entries):
+                th, m = e if isinstance(e, tuple) else (e, eye)
+                v[k].bvh = th._h.value if th is not None else None
+                v[k].world_from_object[:] = m
+            return v
+
+        scaled, sheared, nan, mirror = list(eye), list(eye), list(eye), list(eye)
+        scaled[0], sheared[1], nan[11], mirror[5] = 1.0001, 1e-4, float("nan"), -1
+        name = "psm_world_set_instances"
+        assert lib.psm_world_set_instances(w, None, u32(2)) == -1
+        assert err() == name + ": NULL list"
+        assert lib.psm_world_set_instances(w, lst(a, b, a, b, a), u32(5)) == -4
+        assert err() == name + ": 5 instances exceed the world's capacity of 4"
+        assert lib.psm_world_set_instances(w, lst(a, None), u32(2)) == -1
+        assert err() == name + ": instance 1 is NULL"
+        assert lib.psm_world_set_instances(w, lst(a, b, foreign), u32(3)) == -1
+        assert err() == name + ": instance 2 belongs to another context"
+        assert lib.psm_world_set_instances(w, lst(a, (b, nan)), u32(2)) == -1
+        assert err() == name + ": instance 1 has a non-finite transform"
+        for bad in (scaled, sheared):
+            assert lib.psm_world_set_instances(w, lst((a, mirror), b, (b, bad)), u32(3)) == -1
+            assert err().startswith(name + ": instance 2 has a transform that is not rigid")
+        assert lib.psm_world_set_instances(w, lst(a, unbuilt), u32(2)) == -5
+        assert err() == name + ": instance 1 is not built"
+        # in the list's order of checks: every handle, then every pose, then every hierarchy's state
+        assert lib.psm_world_set_instances(w, lst(unbuilt, (b, scaled), None), u32(3)) == -1
+        assert err() == name + ": instance 2 is NULL"
+        assert lib.psm_world_set_instances(w, lst(unbuilt, (b, scaled)), u32(2)) == -1
+        assert err().startswith(name + ": instance 1 has a transform that is not rigid")
+        assert lib.psm_world_count(w) == 2
+        ctx.buf_free(h)
+    finally:
+        world.close()
+        foreign.close()
+        other_ctx.close()
+        unbuilt.close()
+        b.close()
+        a.close()

@@ -4,11 +4,9 @@ for bit, its rows are prefixes of one another and its counts are min(k, brute co
 two kernels compile within their ceilings, and the header layer compiles against the new methods. The largest k of every test is
 the library's own limit (the kmax fixture)."""
 import ctypes
-import functools
 import os
 import re
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -17,7 +15,7 @@ import inside_query_model as IQ
 import kbest_query_model as KQ
 import point_query_model as PQ
 import query_model as Q
-from util import ROOT
+from util import ROOT, csrc_asm, kernel_asm, kernel_meta
 
 F = np.float32
 U = np.uint32
@@ -167,31 +165,13 @@ def test_library_exports_the_kbest_queries(psm, kmax):
 KBEST_VGPRS = {"bvh_query_first_hits": 60, "bvh_query_nearest": 62}
 
 
-@functools.lru_cache(maxsize=None)
-def kbest_asm():
-    csrc = os.path.join(ROOT, "prismarine-core_amd", "csrc")
-    flags = open(os.path.join(csrc, "Makefile")).read()
-    cxx = re.search(r"^CXXFLAGS := (.*)$", flags, re.M).group(1).replace("$(ARCH)", "gfx950").split()
-    assert "kbest.hip" in re.search(r"^SRC := (.*)$", flags, re.M).group(1).split()
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "kbest.s")
-        subprocess.check_call(["/opt/rocm/bin/hipcc"] + [f for f in cxx if not f.startswith("-W")] +
-                              ["-S", "--cuda-device-only", "-o", out, os.path.join(csrc, "kbest.hip")], stderr=subprocess.DEVNULL)
-        return open(out).read()
-
-
 def test_kbest_kernels_codegen(kmax):
-    asm = kbest_asm()
+    asm = csrc_asm("kbest.hip")
     for name, ceiling in KBEST_VGPRS.items():
-        kern = "_ZN3psm%d%sENS_9QueryArgsE" % (len(name), name)
-        at = asm.index(".name:           " + kern)
-        blk = asm[asm.rindex("  - .agpr_count:", 0, at):]
-        blk = blk[:blk.index(".wavefront_size")]
-        body = asm[asm.index(kern + ":"):]
-        body = body[:body.index(".Lfunc_end")]
+        blk, body = kernel_asm(asm, "_ZN3psm%d%sENS_9QueryArgsE" % (len(name), name))
 
         def meta(key):
-            return int(re.search(r"\.%s:\s+(\d+)" % key, blk).group(1))
+            return kernel_meta(blk, key)
         assert meta("vgpr_count") <= ceiling <= 64, (name, meta("vgpr_count"))
         assert meta("vgpr_spill_count") == 0 and meta("sgpr_spill_count") == 0, name
         assert meta("private_segment_fixed_size") == 0 and "scratch_" not in body, name

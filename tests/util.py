@@ -1,4 +1,5 @@
 """Helpers shared by the parity tests."""
+import functools
 import os
 import re
 import subprocess
@@ -144,35 +145,45 @@ QUERY_FAMILIES = {"bvh": ("QueryArgs", (55, 52, 59, 56, 50, 50, 53)),
                   "inst": ("InstArgs", (59, 54, 63, 58, 53, 53, 54))}
 QUERY_VGPRS = {"%s_query_%s" % (fam, kind): v for fam, (_, vgprs) in QUERY_FAMILIES.items() for kind, v in zip(QUERY_KINDS, vgprs)}
 
-_query_asm = None
+@functools.lru_cache(maxsize=None)
+def csrc_asm(source):
+    """The device assembly of prismarine-core_amd/csrc/<source>, compiled with the Makefile's flags for gfx950 -- once per test
+    process."""
+    csrc = os.path.join(ROOT, "prismarine-core_amd", "csrc")
+    flags = open(os.path.join(csrc, "Makefile")).read()
+    cxx = re.search(r"^CXXFLAGS := (.*)$", flags, re.M).group(1).replace("$(ARCH)", "gfx950").split()
+    assert "-fno-slp-vectorize" in cxx and "-ffp-contract=off" in cxx
+    assert source in re.search(r"^SRC := (.*)$", flags, re.M).group(1).split()
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, source.replace(".hip", ".s"))
+        subprocess.check_call(["/opt/rocm/bin/hipcc"] + [f for f in cxx if not f.startswith("-W")] +
+                              ["-S", "--cuda-device-only", "-o", out, os.path.join(csrc, source)], stderr=subprocess.DEVNULL)
+        return open(out).read()
 
 
+def kernel_asm(asm, mangled):
+    """(metadata block, body) of the kernel `mangled` in an assembly text: the block is the kernel's metadata map from
+    .agpr_count to .wavefront_size, the body runs from its label to the end of the function"""
+    at = asm.index(".name:           " + mangled)
+    blk = asm[asm.rindex("  - .agpr_count:", 0, at):]
+    body = asm[asm.index(mangled + ":"):]
+    return blk[:blk.index(".wavefront_size")], body[:body.index(".Lfunc_end")]
+
+
+def kernel_meta(blk, key):
+    """an integer entry of a kernel's metadata block"""
+    return int(re.search(r"\.%s:\s+(\d+)" % key, blk).group(1))
+
+
+@functools.lru_cache(maxsize=None)
 def query_asm():
-    """{kernel: (metadata block, body)} of query.hip's kernels, compiled to assembly with the Makefile's flags -- once per test
-    process. Keys are the plain kernel names (bvh_query_closest, ...)."""
-    global _query_asm
-    if _query_asm is None:
-        csrc = os.path.join(ROOT, "prismarine-core_amd", "csrc")
-        flags = open(os.path.join(csrc, "Makefile")).read()
-        cxx = re.search(r"^CXXFLAGS := (.*)$", flags, re.M).group(1).replace("$(ARCH)", "gfx950").split()
-        assert "-fno-slp-vectorize" in cxx and "-ffp-contract=off" in cxx
-        assert "query.hip" in re.search(r"^SRC := (.*)$", flags, re.M).group(1).split()
-        with tempfile.TemporaryDirectory() as tmp:
-            out = os.path.join(tmp, "query.s")
-            subprocess.check_call(["/opt/rocm/bin/hipcc"] + [f for f in cxx if not f.startswith("-W")] +
-                                  ["-S", "--cuda-device-only", "-o", out, os.path.join(csrc, "query.hip")], stderr=subprocess.DEVNULL)
-            asm = open(out).read()
-        kernels = {}
-        for name in QUERY_VGPRS:
-            args = QUERY_FAMILIES[name.split("_")[0]][0]
-            kern = "_ZN3psm%d%sENS_%d%sE" % (len(name), name, len(args), args)
-            at = asm.index(".name:           " + kern)   # inside the kernel's metadata map, .agpr_count to .wavefront_size
-            blk = asm[asm.rindex("  - .agpr_count:", 0, at):]
-            blk = blk[:blk.index(".wavefront_size")]
-            body = asm[asm.index(kern + ":"):]
-            kernels[name] = (blk, body[:body.index(".Lfunc_end")])
-        _query_asm = kernels
-    return _query_asm
+    """{kernel: (metadata block, body)} of query.hip's kernels. Keys are the plain kernel names (bvh_query_closest, ...)."""
+    asm = csrc_asm("query.hip")
+    kernels = {}
+    for name in QUERY_VGPRS:
+        args = QUERY_FAMILIES[name.split("_")[0]][0]
+        kernels[name] = kernel_asm(asm, "_ZN3psm%d%sENS_%d%sE" % (len(name), name, len(args), args))
+    return kernels
 
 
 def check_query_kernels(names):
@@ -185,7 +196,7 @@ def check_query_kernels(names):
         blk, body = asm[name]
 
         def meta(key):
-            return int(re.search(r"\.%s:\s+(\d+)" % key, blk).group(1))
+            return kernel_meta(blk, key)
         assert meta("vgpr_count") <= QUERY_VGPRS[name] <= 64, name
         assert meta("vgpr_spill_count") == 0 and meta("sgpr_spill_count") == 0, name
         assert meta("private_segment_fixed_size") == 0, name
