@@ -35,5 +35,10 @@ namespace NSM {
         int within(const psm_point_query * d_points, size_t n, uint8_t * d_hit);
         int inside(const psm_point_query * d_points, size_t n, uint8_t * d_inside, uint32_t samples = 3);
         int signedDistance(const psm_point_query * d_points, size_t n, psm_hit * d_hits, int32_t * d_inst, uint32_t samples = 3);
+        // the first k hits of n rays in the order (t, inst, tri) / the k nearest triangles of n points in the order (d2, inst, tri)
+        // over the whole world, 1 <= k <= PSM_QUERY_K_MAX: d_hits and d_inst [n][k], d_count [n] = the slots filled, the rest are
+        // misses with inst = -1 (psm_world_first_hits_dev / psm_world_nearest_dev); the flat lists have no such query
+        int firstHits(const psm_query_ray * d_rays, size_t n, uint32_t k, psm_hit * d_hits, int32_t * d_inst, uint32_t * d_count);
+        int nearest(const psm_point_query * d_points, size_t n, uint32_t k, psm_hit * d_hits, int32_t * d_inst, uint32_t * d_count);
     };
 }

@@ -56,4 +56,14 @@ namespace NSM {
         check(rc, "InstanceWorld::signedDistance");
         return rc;
     }
+    inline int InstanceWorld::firstHits(const psm_query_ray * d_rays, size_t n, uint32_t k, psm_hit * d_hits, int32_t * d_inst, uint32_t * d_count) {
+        const int rc = psm_world_first_hits_dev(world, d_rays, n, k, d_hits, d_inst, d_count);
+        check(rc, "InstanceWorld::firstHits");
+        return rc;
+    }
+    inline int InstanceWorld::nearest(const psm_point_query * d_points, size_t n, uint32_t k, psm_hit * d_hits, int32_t * d_inst, uint32_t * d_count) {
+        const int rc = psm_world_nearest_dev(world, d_points, n, k, d_hits, d_inst, d_count);
+        check(rc, "InstanceWorld::nearest");
+        return rc;
+    }
 }

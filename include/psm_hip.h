@@ -439,8 +439,8 @@ int psm_bvh_signed_distance_dev(psm_bvh* bvh, const psm_point_query* d_points, s
 /* k-best queries against a built hierarchy (new; no reference counterpart): the first k hits of a ray and the k
  * nearest triangles of a point, k fixed by the caller, 1 <= k <= PSM_QUERY_K_MAX. The output is n rows of k psm_hit records
  * (d_hits[i * k + s], slot s of query i) and a count per query; there is no allocation, no overflow and no second pass, and with
- * k >= the ray's hit count the row is the complete list. A single hierarchy only: scenes, instances and worlds have no k-best
- * queries. Semantics:
+ * k >= the ray's hit count the row is the complete list. Flat scenes and instanced lists have none; worlds: below
+ * (psm_world_first_hits_dev / psm_world_nearest_dev). Semantics:
  *   - first hits: the candidates, the validity of a ray, the triangle test and the window tmin <= t <= tmax are those of
  *     psm_bvh_intersect_dev / psm_bvh_count_hits_dev, unchanged. With c the number psm_bvh_count_hits_dev gives for the ray,
  *     row i holds the min(k, c) counting candidates that are smallest in the lexicographic order (t, tri), ascending: t compared
@@ -597,6 +597,33 @@ int psm_world_within_dev(psm_world* world, const psm_point_query* d_points, size
 int psm_world_inside_dev(psm_world* world, const psm_point_query* d_points, size_t n, uint32_t samples, uint8_t* d_inside);
 int psm_world_signed_distance_dev(psm_world* world, const psm_point_query* d_points, size_t n, uint32_t samples, psm_hit* d_hits,
                                   int32_t* d_inst);
+
+/* k-best queries over a world (new; no reference counterpart): a ray's first k hits and a point's k nearest
+ * triangles over every instance of the world, in one launch, 1 <= k <= PSM_QUERY_K_MAX. d_hits[i * k + s] and d_inst[i * k + s]
+ * are slot s of query i, d_count[i] the number of filled slots. Flat scenes and instanced lists (psm_scene_*, psm_instances_*)
+ * have no k-best query: a world over the same ordered list answers as they would. Semantics:
+ *   - candidates: exactly those of psm_world_count_hits_dev / psm_world_within_dev. Per instance the query is moved by the
+ *     canonical float32 move and its validity is judged on the moved query; a ray candidate passes the triangle test with
+ *     tmin <= t <= tmax, a point candidate passes closest_on_tri with sqrtf(d2) <= rmax, d2 the instance's own value for its
+ *     own moved point
+ *   - rows: with c the world's count of candidates, row i holds the min(k, c) candidates smallest in the lexicographic order
+ *     (value, inst, tri), ascending: value is t (resp. d2, not the distance), compared as a float (-0 == +0); inst and tri are
+ *     compared unsigned. A record is the winning instance's object-space {u, v, t | dist, tri}, as psm_world_intersect_dev /
+ *     psm_world_closest_point_dev write it, and d_inst the instance's index in the list
+ *   - d_count[i] = min(k, c); the slots from d_count[i] on hold {0, 0, +inf, -1} and inst = -1; an invalid query has count 0
+ *     and a row of misses
+ *   - what follows: slot 0 and its inst are bit for bit the record and d_inst of psm_world_intersect_dev /
+ *     psm_world_closest_point_dev; the count is min(k, psm_world_count_hits_dev); it is positive iff psm_world_occluded_dev /
+ *     psm_world_within_dev say 1; the row for k is a prefix of the row for any larger k; nothing depends on the tree or the
+ *     visit order (coincident instances tie on every hit and are listed inst ascending); a world of N instances answers as
+ *     the flat instanced list would if it could be N long and had the query
+ *   - k == 0 or k > PSM_QUERY_K_MAX: PSM_ERR_INVALID, nothing is launched. d_hits 16-byte, d_inst and d_count 4-byte aligned,
+ *     none NULL; the stale check, n == 0, stream order and capture as for the other world queries; an empty world answers
+ *     without a query kernel: n x k miss records, inst = -1, counts 0 */
+int psm_world_first_hits_dev(psm_world* world, const psm_query_ray* d_rays, size_t n, uint32_t k, psm_hit* d_hits, int32_t* d_inst,
+                             uint32_t* d_count);
+int psm_world_nearest_dev(psm_world* world, const psm_point_query* d_points, size_t n, uint32_t k, psm_hit* d_hits, int32_t* d_inst,
+                          uint32_t* d_count);
 
 /* ---------------------------------------------------------------------------------------------
  * several frames in flight (new; DESIGN.md "lanes")

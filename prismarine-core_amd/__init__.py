@@ -34,7 +34,7 @@ EXPORTS = [
     "psm_instances_within_dev", "psm_instances_inside_dev", "psm_instances_signed_distance_dev",
     "psm_world_create", "psm_world_destroy", "psm_world_set_instances", "psm_world_set_transforms", "psm_world_count",
     "psm_world_intersect_dev", "psm_world_occluded_dev", "psm_world_count_hits_dev", "psm_world_closest_point_dev", "psm_world_within_dev",
-    "psm_world_inside_dev", "psm_world_signed_distance_dev",
+    "psm_world_inside_dev", "psm_world_signed_distance_dev", "psm_world_first_hits_dev", "psm_world_nearest_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -403,8 +403,8 @@ class TriangleHierarchy:
         """The first k hits of every ray, in order (psm_bvh_first_hits_dev; not in the reference): of the triangles countHits()
         counts, the min(k, count) smallest in (t, tri) -- bit-equal t (coincident triangles, a shared edge) are all listed, by id.
         k: 1 .. QUERY_K_MAX. Returns QueryHitLists: u, v, t, tri [n, k] (slot 0 is intersect()'s record; the slots past count are
-        misses: tri = -1, t = +inf) and count [n]. Arguments and placement as intersect(). A single hierarchy only: QueryScene,
-        InstancedScene and InstanceWorld have no such query."""
+        misses: tri = -1, t = +inf) and count [n]. Arguments and placement as intersect(). QueryScene and InstancedScene have
+        no such query; InstanceWorld has (InstanceWorld.firstHits)."""
         return self._query(origins, directions, tmin, tmax, "lists", "psm_bvh_first_hits_dev", k)
 
     def nearest(self, points, k, rmax=np.inf):
@@ -489,7 +489,8 @@ class TriangleHierarchy:
         return _launch_np(self, packed, out, name, *extra)
 
     def _call(self, name, d_in, n, extra, d_out, d_geom):
-        """the native call of one query launch (d_geom: a single hierarchy reports no geometry; the k-best queries' counts)"""
+        """the native call of one query launch (d_geom: a single hierarchy reports no geometry; the k-best queries' counts; a
+        world's k-best queries: the pair (instances, counts))"""
         tail = () if d_geom is None else (C.c_void_p(d_geom),)
         self.ctx.check(getattr(lib(), name)(self._h, C.c_void_p(d_in), C.c_size_t(n), *extra, C.c_void_p(d_out), *tail), name)
 
@@ -548,13 +549,16 @@ def _k(k, name):
 
 
 class QueryHitLists:
-    """The rows of TriangleHierarchy.firstHits / .nearest: `buffer` [n, k, 4] float32 (numpy array or torch tensor) holds psm_hit
-    records (u, v, t, tri); u, v, t and tri (int32) [n, k] are views of it. count [n]: the slots of a row that hold a record
-    (uint32; an int32 tensor for torch), the rest are misses (tri = -1, t = +inf)."""
+    """The rows of TriangleHierarchy.firstHits / .nearest and InstanceWorld.firstHits / .nearest: `buffer` [n, k, 4] float32 (numpy
+    array or torch tensor) holds psm_hit records (u, v, t, tri); u, v, t and tri (int32) [n, k] are views of it. count [n]: the
+    slots of a row that hold a record (uint32; an int32 tensor for torch), the rest are misses (tri = -1, t = +inf). geom: for an
+    InstanceWorld's rows the int32 [n, k] array / tensor of each slot's instance (-1 in a miss slot; tri is that instance's id);
+    None for a single hierarchy's."""
 
-    def __init__(self, buffer, count):
+    def __init__(self, buffer, count, geom=None):
         self.buffer = buffer
         self.count = count
+        self.geom = geom
         self.u, self.v, self.t = buffer[:, :, 0], buffer[:, :, 1], buffer[:, :, 2]
         if isinstance(buffer, np.ndarray):
             self.tri = buffer.view(np.int32)[:, :, 3]
@@ -596,14 +600,16 @@ def _launch_np(th, packed, out, name, *extra):
     geom = (th._scene and out == "hits") or lists
     hr, ho = ctx.buf_alloc(max(packed.nbytes, 32)), ctx.buf_alloc(max(per * k * n, 16))
     hg = ctx.buf_alloc(max(4 * n, 16)) if geom else None
+    hi = ctx.buf_alloc(max(4 * k * n, 16)) if lists and th._scene else None   # (a world's rows: the instance of every slot)
     try:
         if n:
             ctx.buf_upload(hr, packed)
-        th._call(name, ctx.buf_ptr(hr)[0], n, extra, ctx.buf_ptr(ho)[0], ctx.buf_ptr(hg)[0] if geom else None)
+        d_geom = ctx.buf_ptr(hg)[0] if geom else None
+        th._call(name, ctx.buf_ptr(hr)[0], n, extra, ctx.buf_ptr(ho)[0], d_geom if hi is None else (ctx.buf_ptr(hi)[0], d_geom))
         if n == 0:
             ctx.sync()
             if lists:
-                return QueryHitLists(np.zeros((0, k, 4), np.float32), np.zeros(0, np.uint32))
+                return QueryHitLists(np.zeros((0, k, 4), np.float32), np.zeros(0, np.uint32), None if hi is None else np.zeros((0, k), np.int32))
             if out == "hits":
                 return QueryHits(np.zeros((0, 4), np.float32), np.zeros(0, np.int32) if geom else None)
             return np.zeros(0, dtype)
@@ -612,13 +618,16 @@ def _launch_np(th, packed, out, name, *extra):
         if out == "count":
             return ctx.buf_download(ho, np.uint32, n)
         if lists:
-            return QueryHitLists(ctx.buf_download(ho, np.float32, 4 * k * n).reshape(n, k, 4), ctx.buf_download(hg, np.uint32, n))
+            return QueryHitLists(ctx.buf_download(ho, np.float32, 4 * k * n).reshape(n, k, 4), ctx.buf_download(hg, np.uint32, n),
+                                 None if hi is None else ctx.buf_download(hi, np.int32, k * n).reshape(n, k))
         return QueryHits(ctx.buf_download(ho, np.float32, 4 * n).reshape(n, 4), ctx.buf_download(hg, np.int32, n) if geom else None)
     finally:
         ctx.buf_free(hr)
         ctx.buf_free(ho)
         if geom:
             ctx.buf_free(hg)
+        if hi is not None:
+            ctx.buf_free(hi)
 
 
 _hip_lib = None
@@ -671,6 +680,7 @@ def _launch_torch(th, packed, kind, name, *extra):
                     "lists": ((n, extra[0].value if lists else 1, 4), torch.float32)}[kind]
     out = torch.empty(shape, dtype=dtype, device=dev)
     geom = torch.empty((n,), dtype=torch.int32, device=dev) if (th._scene and kind == "hits") or lists else None
+    inst = torch.empty(shape[:2], dtype=torch.int32, device=dev) if lists and th._scene else None   # (a world's rows)
     cur = torch.cuda.current_stream(dev)
     mine = th.ctx.stream or 0   # (NULL: the device's null stream, torch's default stream)
     other = mine != cur.cuda_stream
@@ -678,7 +688,8 @@ def _launch_torch(th, packed, kind, name, *extra):
         ev_in = torch.cuda.Event()
         ev_in.record(cur)
         _hip_check(_hip().hipStreamWaitEvent(C.c_void_p(mine), C.c_void_p(ev_in.cuda_event), C.c_uint(0)), "hipStreamWaitEvent")
-    th._call(name, packed.data_ptr(), n, extra, out.data_ptr(), None if geom is None else geom.data_ptr())
+    d_geom = None if geom is None else geom.data_ptr()
+    th._call(name, packed.data_ptr(), n, extra, out.data_ptr(), d_geom if inst is None else (inst.data_ptr(), d_geom))
     if other:   # ... and torch's stream for the kernel: every later use of `out`, and of the memory of `packed`, comes after it
         hip, ev = _hip(), C.c_void_p()
         _hip_check(hip.hipEventCreateWithFlags(C.byref(ev), C.c_uint(2)), "hipEventCreateWithFlags")   # hipEventDisableTiming
@@ -686,7 +697,7 @@ def _launch_torch(th, packed, kind, name, *extra):
         _hip_check(hip.hipStreamWaitEvent(C.c_void_p(cur.cuda_stream), ev, C.c_uint(0)), "hipStreamWaitEvent")
         _hip_check(hip.hipEventDestroy(ev), "hipEventDestroy")
     if lists:
-        return QueryHitLists(out, geom)
+        return QueryHitLists(out, geom, inst)
     return QueryHits(out, geom) if kind == "hits" else (out.view(torch.bool) if kind == "bool" else out)
 
 
@@ -810,7 +821,8 @@ class InstanceWorld(QueryScene):
     setTransform() / setTransforms(): boxes and tree are redone on the device, no hierarchy is rebuilt. The world records its
     hierarchies as they are when set: after a member was rebuilt, reloaded or reallocated the next query raises PsmError until
     setInstances() is called again; after a member was REFITTED call refresh(). Methods, arguments and numpy / torch placement:
-    QueryScene's; QueryHits.geom is the index of the winning instance."""
+    QueryScene's; QueryHits.geom is the index of the winning instance. A world also has the k-best queries, firstHits() and
+    nearest(), which the flat lists (QueryScene, InstancedScene) have not."""
 
     def __init__(self, ctx, entries, capacity=None):
         self.ctx = ctx
@@ -870,10 +882,29 @@ class InstanceWorld(QueryScene):
             if (th._h.value if isinstance(th._h, C.c_void_p) else th._h) != h:
                 raise PsmError("%s: instance %d's hierarchy was reallocated after the instances were set (set the instances again)" % (name, k))
 
+    def firstHits(self, origins, directions, k, tmin=0.0, tmax=np.inf):
+        """The first k hits of every ray over the whole world, in order (psm_world_first_hits_dev): of the candidates countHits()
+        counts, the min(k, count) smallest in (t, instance, tri) -- bit-equal t (coincident instances, coincident triangles, a
+        shared edge) are all listed, the lowest instance first. k: 1 .. QUERY_K_MAX. Returns QueryHitLists: u, v, t, tri and geom
+        (the slot's instance) [n, k], each record the instance's object-space values (slot 0 and geom[:, 0] are intersect()'s
+        record and geom; the slots past count are misses: tri = -1, t = +inf, geom = -1) and count [n]. Arguments and placement
+        as intersect()."""
+        return self._query(origins, directions, tmin, tmax, "lists", "psm_bvh_first_hits_dev", k)
+
+    def nearest(self, points, k, rmax=np.inf):
+        """The k nearest triangles of every point within rmax over the whole world (psm_world_nearest_dev): the min(k, count)
+        smallest in (d2, instance, tri), d2 each instance's own squared distance to its moved point. k: 1 .. QUERY_K_MAX. Returns
+        QueryHitLists with geom: t = the distance, u, v as closestPoint()'s (slot 0 and geom[:, 0] are closestPoint()'s record
+        and geom). Arguments and placement as closestPoint()."""
+        return self._point_query(points, rmax, "lists", "psm_bvh_nearest_dev", k=k)
+
     def _call(self, name, d_in, n, extra, d_out, d_geom):
         name = name.replace("psm_bvh_", "psm_world_")
         self._fresh(name)
-        tail = () if d_geom is None else (C.c_void_p(d_geom),)
+        if isinstance(d_geom, tuple):   # (the k-best queries: the instances [n, k], then the counts [n])
+            tail = tuple(C.c_void_p(p) for p in d_geom)
+        else:
+            tail = () if d_geom is None else (C.c_void_p(d_geom),)
         self.ctx.check(getattr(lib(), name)(self._w, C.c_void_p(d_in), C.c_size_t(n), *extra, C.c_void_p(d_out), *tail), name)
 
     def close(self):

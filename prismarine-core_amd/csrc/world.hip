@@ -8,6 +8,8 @@
 // that holds a counting candidate (the bounds: WORLD_PAD below). What a query does inside an instance is what the instanced
 // bodies of query.hip do, from the same pieces: the tests, the move and the constants of psm_query_dev.h, the checks and the
 // launch of psm_query_host.h. This file holds what is a world's own: rows, tree, walk, stale check, depth rule.
+// The k-best queries of a world (a ray's first k hits, a point's k nearest triangles over all instances) are
+// here too: two more bodies for the same walk, with the sorted list of psm_world_klist.h in the place of the one best record.
 //
 // The walk is one loop over one stack ([depth][lane] in LDS, the rest in the context's spill area). A stack entry is a link:
 //   link < 0               instance ~link of the world: the lane enters it (loads its row, moves the query, sets up)
@@ -27,6 +29,8 @@
 #include "psm_internal.h"
 #include "psm_query_dev.h"    // the constants, the triangle / box / point tests, inst_point / inst_rotate, INSIDE_DIR
 #include "psm_query_host.h"   // QueryKind, check_data / check_instances, batch_args / launch
+#define PSM_KLIST_FN PSM_D
+#include "psm_world_klist.h"  // WorldKList: the sorted list of the k-best queries (also compiled for the host by a test)
 
 namespace psm {
 
@@ -536,6 +540,199 @@ PSM_D void world_body(const WorldArgs& w) {
     world_walk(w, q);
 }
 
+// ---- k-best: a ray's first k hits, a point's k nearest triangles, over the whole world ------------------------
+
+// The sorted list of one query (psm_world_klist.h: kbest.hip's KList with a third key word), its two columns in the wave's
+// dynamic LDS: the k x 64 keys {value bits, tri}, then the k x 64 instances, both [slot][lane]
+struct WorldList : WorldKList<uint2, QUERY_BLOCK> {
+    PSM_D static uint2* keys() {
+        extern __shared__ uint2 world_list[];
+        return world_list;
+    }
+    PSM_D WorldList(uint32_t slots)
+        : WorldKList<uint2, QUERY_BLOCK>(keys() + threadIdx.x, (uint32_t*)(keys() + (size_t)slots * QUERY_BLOCK) + threadIdx.x, slots) {}
+};
+
+// what finish() needs of the row of instance `in`: the triangles and the pose
+PSM_D const float4* load_pose(const WorldArgs& w, uint32_t in, float* m) {
+    const uint4* rp = (const uint4*)(w.rows + in);
+    const uint4 a = rp[0], c = rp[2], d = rp[3], e = rp[4];
+    m[0] = u2f(c.x); m[1] = u2f(c.y); m[2] = u2f(c.z); m[3] = u2f(c.w);
+    m[4] = u2f(d.x); m[5] = u2f(d.y); m[6] = u2f(d.z); m[7] = u2f(d.w);
+    m[8] = u2f(e.x); m[9] = u2f(e.y); m[10] = u2f(e.z); m[11] = u2f(e.w);
+    return (const float4*)(((uint64_t)a.w << 32) | a.z);
+}
+
+// the first k hits of a ray over the world: WorldRayBody<false> with the list in the place of its one best record. lim: the
+// bound of both levels of boxes -- tmax until the list is full, then the last slot's t (kept with <=, and at the top level
+// slackened: a candidate at the last slot's t of a lower (inst, tri) must still be reached)
+struct WorldFirstHitsBody : WorldRay {
+    const WorldArgs& w;
+    WorldList L;
+    float lim;
+    bool alive;
+    size_t idx;
+
+    PSM_D WorldFirstHitsBody(const WorldArgs& a) : w(a), L(a.samples) {}
+    PSM_D void ray(float4& r0, float4& r1) const {
+        r0 = make_float4(0.f, 0.f, 0.f, 0.f);
+        r1 = make_float4(1.f, 0.f, 0.f, 0.f);
+        if (alive) { r0 = w.rays[2 * idx]; r1 = w.rays[2 * idx + 1]; }
+    }
+    PSM_D bool begin(size_t i, bool al) {
+        idx = i;
+        alive = al;
+        begin_ray(w, i, al);
+        lim = tmax;
+        L.clear();   // per query: the grid-stride loop comes here again
+        return al && tmin <= tmax;
+    }
+    PSM_D void top(float4 w0, float4 w1, float4 w2, bool& okL, bool& okR, float& nL, float& nR) const {
+        top_boxes(w0, w1, w2, lim, okL, okR, nL, nR);
+    }
+    PSM_D int enter(int in) {
+        float4 r0, r1;
+        ray(r0, r1);
+        const int32_t* st;
+        uint32_t count;
+        const int r = enter_ray(w, in, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), st, count);
+        if (r != -1 && count == 1u) leaf(st[0]);
+        return r;
+    }
+    PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& nL, float& nR) const { boxes(n0, n1, lim, okL, okR, nL, nR); }
+    PSM_D void leaf(int tri) {
+        float t, u, v;
+        if (tri_query(tri48, tri, o, d, t, u, v) && t >= tmin && t <= tmax) lim = L.offer(t, (uint32_t)inst, (uint32_t)tri, lim);
+    }
+    PSM_D bool done() const { return false; }
+    PSM_D bool again() const { return false; }
+    // u, v are not kept: per stored (inst, tri) the ray is re-read and moved exactly as enter() moves it and the same test is
+    // run again -- the same function on the same inputs gives the same bits (-ffp-contract=off)
+    PSM_D void finish(size_t i) const {
+        float4 r0, r1;
+        ray(r0, r1);
+        float4* __restrict__ row = w.hits + i * L.k;
+        int32_t* __restrict__ irow = w.geom + i * L.k;
+        for (uint32_t s = 0; s < L.k; s++) {
+            float4 h = miss_hit();
+            int32_t hin = -1;
+            if (s < L.cnt) {
+                const uint2 e = L.key[(size_t)s * QUERY_BLOCK];
+                const uint32_t in = L.ins[(size_t)s * QUERY_BLOCK];
+                float m[12];
+                const float4* tris = load_pose(w, in, m);
+                const v3 oo = inst_point(m, mk3(r0.x, r0.y, r0.z));
+                const v3 dd = normalize3(inst_rotate(m, mk3(r1.x, r1.y, r1.z)));
+                float t = 0.f, u = 0.f, v = 0.f;
+                (void)tri_query(tris, (int)e.y, oo, dd, t, u, v);
+                h = make_float4(u, v, __uint_as_float(e.x), __uint_as_float(e.y));
+                hin = (int32_t)in;
+            }
+            row[s] = h;
+            irow[s] = hin;
+        }
+        w.count[i] = L.cnt;
+    }
+};
+
+// the k nearest triangles of a point over the world: WorldPointBody<false> with the list in the place of its one best record.
+// best: the bound of both levels of boxes -- the rmax bound until the list is full, then the last slot's d2. The key is d2, each
+// instance's own value for its own moved point (not the distance: two d2 may share a sqrtf)
+struct WorldNearestBody {
+    const WorldArgs& w;
+    const uint4* node32;
+    const float4* tri48;
+    int inst;
+    PointBound B;
+    v3 p, wp;
+    float rmax, qpad, best;
+    WorldList L;
+    bool alive;
+    size_t idx;
+    PointImage P;
+
+    PSM_D WorldNearestBody(const WorldArgs& a) : w(a), L(a.samples) {}
+    PSM_D float4 point() const {
+        float4 q = make_float4(0.f, 0.f, 0.f, -1.f);
+        if (alive) q = w.rays[idx];
+        return q;
+    }
+    PSM_D bool begin(size_t i, bool al) {
+        idx = i;
+        alive = al;
+        const float4 q = point();
+        wp = mk3(q.x, q.y, q.z);
+        qpad = WORLD_QSLACK * smaxf(smaxf(pabs(q.x), pabs(q.y)), pabs(q.z));
+        rmax = q.w;
+        best = (q.w * q.w) * 1.00000095367431640625f + 0x1p-126f;   // (query.hip PointBody::begin)
+        L.clear();
+        return al && finite3(wp) && q.w >= 0.f;
+    }
+    PSM_D float gap2(float lx, float ly, float lz, float hx, float hy, float hz) const {
+        const float tx = smaxf(smaxf((lx - qpad) - wp.x, wp.x - (hx + qpad)), 0.f);
+        const float ty = smaxf(smaxf((ly - qpad) - wp.y, wp.y - (hy + qpad)), 0.f);
+        const float tz = smaxf(smaxf((lz - qpad) - wp.z, wp.z - (hz + qpad)), 0.f);
+        return (tx * tx + ty * ty) + tz * tz;
+    }
+    PSM_D void top(float4 w0, float4 w1, float4 w2, bool& okL, bool& okR, float& kL, float& kR) const {
+        kL = gap2(w0.x, w0.y, w0.z, w0.w, w1.x, w1.y);
+        kR = gap2(w1.z, w1.w, w2.x, w2.y, w2.z, w2.w);
+        const float lim = best + WORLD_PSLACK * best;
+        okL = !(kL > lim);
+        okR = !(kR > lim);
+    }
+    PSM_D int enter(int in) {
+        const float4 q = point();
+        const RowLoad r = load_row(w, in, *this);
+        p = inst_point(r.m, mk3(q.x, q.y, q.z));
+        float M[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) M[k] = u2f(r.sm[SM_M + k]);
+        B = point_bound(M);
+        P.set(M, p);
+        if (!finite3(p)) return -1;
+        if (r.sm[SM_COUNT] == 1u) leaf(r.sorted_tri[0]);
+        const int root = (int)r.sm[SM_ROOT];
+        return root >= 0 ? root : -2;
+    }
+    PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& kL, float& kR) const {
+        P.children(B, n0, n1, best, okL, okR, kL, kR);
+    }
+    PSM_D static float test(const float4* tris, int tri, v3 at, float& u, float& v) {
+        const float4 A = tris[(size_t)3 * tri + 0], Bv = tris[(size_t)3 * tri + 1], Cv = tris[(size_t)3 * tri + 2];
+        return closest_on_tri(mk3(A.x, A.y, A.z), mk3(Bv.x, Bv.y, Bv.z), mk3(Cv.x, Cv.y, Cv.z), at, u, v);
+    }
+    PSM_D void leaf(int tri) {
+        float u, v;
+        const float d2 = test(tri48, tri, p, u, v);
+        if (sqrtf(d2) <= rmax) best = L.offer(d2, (uint32_t)inst, (uint32_t)tri, best);
+    }
+    PSM_D bool done() const { return false; }
+    PSM_D bool again() const { return false; }
+    PSM_D void finish(size_t i) const {
+        const float4 q = point();
+        float4* __restrict__ row = w.hits + i * L.k;
+        int32_t* __restrict__ irow = w.geom + i * L.k;
+        for (uint32_t s = 0; s < L.k; s++) {
+            float4 h = miss_hit();
+            int32_t hin = -1;
+            if (s < L.cnt) {
+                const uint2 e = L.key[(size_t)s * QUERY_BLOCK];
+                const uint32_t in = L.ins[(size_t)s * QUERY_BLOCK];
+                float m[12];
+                const float4* tris = load_pose(w, in, m);
+                float u, v;
+                (void)test(tris, (int)e.y, inst_point(m, mk3(q.x, q.y, q.z)), u, v);
+                h = make_float4(u, v, sqrtf(__uint_as_float(e.x)), __uint_as_float(e.y));
+                hin = (int32_t)in;
+            }
+            row[s] = h;
+            irow[s] = hin;
+        }
+        w.count[i] = L.cnt;
+    }
+};
+
 }  // namespace
 
 // The lane's two hierarchy pointers, its instance index and the world ray beside the object ray do not fit 64 VGPRs: the
@@ -547,6 +744,11 @@ __global__ __launch_bounds__(QUERY_BLOCK, 4) void world_query_within(WorldArgs w
 __global__ __launch_bounds__(QUERY_BLOCK, 4) void world_query_count(WorldArgs w) { world_body<WorldCountBody>(w); }
 __global__ __launch_bounds__(QUERY_BLOCK, 4) void world_query_inside(WorldArgs w) { world_body<WorldInsideBody<false>>(w); }
 __global__ __launch_bounds__(QUERY_BLOCK, 4) void world_query_sign(WorldArgs w) { world_body<WorldInsideBody<true>>(w); }
+
+// WorldArgs as the closest-hit / closest-point kernels read it, and: hits and geom [n][k], count [n], samples = k; the launch
+// gives k x 64 x 12 B of dynamic LDS beside the stack (DESIGN.md 4.14 has the budget and the register counts)
+__global__ __launch_bounds__(QUERY_BLOCK, 4) void world_query_first_hits(WorldArgs w) { world_body<WorldFirstHitsBody>(w); }
+__global__ __launch_bounds__(QUERY_BLOCK, 4) void world_query_nearest(WorldArgs w) { world_body<WorldNearestBody>(w); }
 
 // ---- set-up kernels: boxes, Morton keys, the tree, its boxes (correct and free of host round trips; not tuned) -----------------
 
@@ -786,9 +988,9 @@ struct psm_world {
 namespace psm {
 namespace {
 
-const char* const WORLD_NAME[7] = {"psm_world_intersect_dev", "psm_world_occluded_dev", "psm_world_closest_point_dev",
+const char* const WORLD_NAME[9] = {"psm_world_intersect_dev", "psm_world_occluded_dev", "psm_world_closest_point_dev",
                                    "psm_world_within_dev", "psm_world_count_hits_dev", "psm_world_inside_dev",
-                                   "psm_world_signed_distance_dev"};
+                                   "psm_world_signed_distance_dev", "psm_world_first_hits_dev", "psm_world_nearest_dev"};
 const Kernels<WorldArgs> WORLD_KERNELS = {{world_query_closest, world_query_any, world_query_point, world_query_within,
                                            world_query_count, world_query_inside, world_query_sign}};
 
@@ -873,19 +1075,31 @@ int world_upload_and_build(psm_world* w, const char* name) {
     return check_depth(w, name);
 }
 
-// A query of a world: the data (check_data, as every query's), the empty world's answer, the stale check, the launch
-int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_inst, uint32_t samples = 0) {
+// A query of a world: the data (check_data, as every query's), the empty world's answer, the stale check, the launch. The
+// k-best kinds come through here too: samples is their k, d_out and d_inst their [n][k] rows, d_count their counts (which go
+// through check_data's index slot as "counts", as in query.hip's query(); d_inst is then checked here)
+int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_inst, uint32_t samples = 0,
+                uint32_t* d_count = nullptr) {
     if (!w) return PSM_ERR_INVALID;
     if (n == 0) return PSM_OK;
     psm_ctx* c = w->ctx;
     const char* name = WORLD_NAME[kind];
-    int rc = check_data(c, name, "inst", kind, d_in, d_out, d_inst, samples);
+    const bool kbest = kind == Q_FIRST_HITS || kind == Q_NEAREST;
+    int rc = kbest ? check_data(c, name, "counts", kind, d_in, d_out, (const int32_t*)d_count, samples)
+                   : check_data(c, name, "inst", kind, d_in, d_out, d_inst, samples);
     if (rc != PSM_OK) return rc;
+    if (kbest && (!d_inst || ((uintptr_t)d_inst & 3u) != 0)) {
+        char msg[128];
+        snprintf(msg, sizeof msg, d_inst ? "%s: inst not 4-byte aligned" : "%s: NULL pointer", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    const size_t rows = kbest ? n * samples : n;   // (samples <= PSM_QUERY_K_MAX here)
     if (w->count == 0) {   // an empty world: every query misses, no query kernel runs
         const unsigned per = QUERY_DESC[kind].out_align;
-        if (per == 16) world_fill_miss<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>((float4*)d_out, d_inst, n);
+        if (per == 16) world_fill_miss<<<(unsigned)((rows + 255) / 256), 256, 0, c->stream>>>((float4*)d_out, d_inst, rows);
         else PSM_HIP(c, hipMemsetAsync(d_out, 0, n * per, c->stream));
         PSM_HIP(c, hipGetLastError());
+        if (kbest) PSM_HIP(c, hipMemsetAsync(d_count, 0, n * sizeof(uint32_t), c->stream));
         return PSM_OK;
     }
     const int stale = first_stale(w);
@@ -898,6 +1112,14 @@ int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* 
     a.root = w->count == 1 ? ~0 : 0;
     a.rows = w->d_rows;
     a.nodes = w->d_nodes;
+    if (kbest) {   // the list: k x 64 x (8 + 4) B of dynamic LDS per wave, beside the stack
+        a.count = d_count;
+        const size_t lds = (size_t)samples * QUERY_BLOCK * (sizeof(uint2) + sizeof(uint32_t));
+        if (kind == Q_NEAREST) world_query_nearest<<<grid, QUERY_BLOCK, lds, c->stream>>>(a);
+        else world_query_first_hits<<<grid, QUERY_BLOCK, lds, c->stream>>>(a);
+        PSM_HIP(c, hipGetLastError());
+        return PSM_OK;
+    }
     return launch(c, WORLD_KERNELS, kind, grid, a);
 }
 
@@ -1035,4 +1257,12 @@ int psm_world_inside_dev(psm_world* w, const psm_point_query* d_points, size_t n
 int psm_world_signed_distance_dev(psm_world* w, const psm_point_query* d_points, size_t n, uint32_t samples, psm_hit* d_hits,
                                   int32_t* d_inst) {
     return psm::world_query(w, psm::Q_SIGNED, d_points, n, d_hits, d_inst, samples);
+}
+int psm_world_first_hits_dev(psm_world* w, const psm_query_ray* d_rays, size_t n, uint32_t k, psm_hit* d_hits, int32_t* d_inst,
+                             uint32_t* d_count) {
+    return psm::world_query(w, psm::Q_FIRST_HITS, d_rays, n, d_hits, d_inst, k, d_count);
+}
+int psm_world_nearest_dev(psm_world* w, const psm_point_query* d_points, size_t n, uint32_t k, psm_hit* d_hits, int32_t* d_inst,
+                          uint32_t* d_count) {
+    return psm::world_query(w, psm::Q_NEAREST, d_points, n, d_hits, d_inst, k, d_count);
 }

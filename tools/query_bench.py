@@ -27,6 +27,10 @@ posed triangles into one hierarchy (upload + build) plus a plain query. WORLD_N 
 alternated A B A B with medians of REPS: on the ray mode's primary and bounce-like rays firstHits against intersect, against
 countHits, and against what a caller does without it -- k intersect launches, tmin moved past the last t between them (a torch
 operation on the same stream; it loses hits at a bit-equal t); on the point mode's two sets nearest against closestPoint.
+`query_bench.py worldkbest`: the k-best queries of an instance world (psm_world_first_hits_dev / psm_world_nearest_dev) on the world
+mode's scenes (one torus at 32, 256, 4096 and 65 536 grid poses, local rays and points), k = 1, 4 and 16, every pair alternated
+A B A B with medians of REPS: firstHits against intersect, and against k intersect launches with tmin moved past the last t
+between them (it loses hits at a bit-equal t); nearest against closestPoint. WORLD_N = queries per batch (default 2^18).
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -587,6 +591,83 @@ def abab(ctx, fa, fb):
     return round(float(np.median(ta)), 4), round(float(np.median(tb)), 4)
 
 
+def worldkbest():
+    import torch   # (before the library loads its HIP runtime)
+    n = int(os.environ.get("WORLD_N", str(1 << 18)))
+    dev = torch.device("cuda", 0)
+    ctx = psm.Context(0, stream=torch.cuda.current_stream(dev).cuda_stream)   # torch's tmin update and the launches: one stream
+    tor = torus(48, 24, 0.7, 0.25)
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(tor.shape[0])
+    th.loadTriangles(tor)
+    th.build()
+    rng = np.random.RandomState(1)
+    lib = psm.lib()
+    size = C.c_size_t(n)
+    rays = torch.zeros((n, 8), dtype=torch.float32, device=dev)
+    pts = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+    hits = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+    geom = torch.zeros((n,), dtype=torch.int32, device=dev)
+    rows = torch.zeros((n, 16, 4), dtype=torch.float32, device=dev)
+    inst = torch.zeros((n, 16), dtype=torch.int32, device=dev)
+    count = torch.zeros((n,), dtype=torch.int32, device=dev)
+    p_rays, p_pts, p_hits, p_geom, p_rows, p_inst, p_count = (C.c_void_p(x.data_ptr()) for x in (rays, pts, hits, geom, rows, inst, count))
+    inf = torch.tensor(float("inf"), device=dev)
+    out = {"mode": "worldkbest", "queries": n, "torus_triangles": int(tor.shape[0]), "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+    for poses_n in (32, 256, 4096, 65536):
+        side = int(np.ceil(np.sqrt(poses_n)))      # the world mode's grid of poses and its local queries
+        poses = np.zeros((poses_n, 3, 4), np.float32)
+        poses[:, 0, 0] = poses[:, 1, 1] = poses[:, 2, 2] = 1.0
+        k_ = np.arange(poses_n)
+        poses[:, 0, 3], poses[:, 1, 3] = 2.5 * (k_ % side), 2.5 * (k_ // side)
+        c = poses[rng.randint(0, poses_n, n), :, 3]
+        o = (c + rng.uniform(-1.5, 1.5, (n, 3))).astype(np.float32)
+        r = np.zeros((n, 8), np.float32)
+        r[:, 0:3], r[:, 4:7], r[:, 7] = o, (c + rng.uniform(-0.6, 0.6, (n, 3)) - o).astype(np.float32), np.inf
+        rays.copy_(torch.from_numpy(r))
+        q = np.empty((n, 4), np.float32)
+        q[:, 0:3], q[:, 3] = (c + rng.uniform(-1.2, 1.2, (n, 3))).astype(np.float32), np.inf
+        pts.copy_(torch.from_numpy(q))
+        wd = psm.InstanceWorld(ctx, [(th, m) for m in poses])
+        w = wd._w
+
+        def closest():
+            ctx.check(lib.psm_world_intersect_dev(w, p_rays, size, p_hits, p_geom), "psm_world_intersect_dev")
+
+        def point():
+            ctx.check(lib.psm_world_closest_point_dev(w, p_pts, size, p_hits, p_geom), "psm_world_closest_point_dev")
+
+        def first(k):
+            return lambda: ctx.check(lib.psm_world_first_hits_dev(w, p_rays, size, C.c_uint32(k), p_rows, p_inst, p_count), "psm_world_first_hits_dev")
+
+        def near(k):
+            return lambda: ctx.check(lib.psm_world_nearest_dev(w, p_pts, size, C.c_uint32(k), p_rows, p_inst, p_count), "psm_world_nearest_dev")
+
+        def emulation(k):
+            def run():
+                for j in range(k):
+                    closest()
+                    if j + 1 < k:
+                        rays[:, 3] = torch.nextafter(hits[:, 2], inf)
+                rays[:, 3] = 0.0
+            return run
+
+        tag = "poses%d" % poses_n
+        ctx.check(lib.psm_world_count_hits_dev(w, p_rays, size, p_count), "psm_world_count_hits_dev")
+        out[tag + "_mean_hits"] = round(float(count.float().mean().item()), 2)
+        for k in (1, 4, 16):
+            a, b = abab(ctx, first(k), closest)
+            out["%s_first_hits_k%d_ms" % (tag, k)], out["%s_intersect_beside_k%d_ms" % (tag, k)] = a, b
+            a, b = abab(ctx, first(k), emulation(k))
+            out["%s_first_hits_k%d_again_ms" % (tag, k)], out["%s_%dx_intersect_ms" % (tag, k)] = a, b
+            a, b = abab(ctx, near(k), point)
+            out["%s_nearest_k%d_ms" % (tag, k)], out["%s_closest_point_beside_k%d_ms" % (tag, k)] = a, b
+        wd.close()
+    th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def kbest():
     import torch   # (before the library loads its HIP runtime)
     dev = torch.device("cuda", 0)
@@ -744,4 +825,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest}.get(" ".join(sys.argv[1:]), main)()
