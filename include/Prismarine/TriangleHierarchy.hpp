@@ -61,6 +61,13 @@ namespace NSM {
         // are misses (psm_bvh_first_hits_dev / psm_bvh_nearest_dev), stream-ordered on the context; returns the psm_status
         int firstHits(const psm_query_ray * d_rays, size_t n, uint32_t k, psm_hit * d_hits, uint32_t * d_count);
         int nearest(const psm_point_query * d_points, size_t n, uint32_t k, psm_hit * d_hits, uint32_t * d_count);
+        // not in the reference: whether / how many / which triangles overlap each of n axis-aligned boxes (closed: touching counts);
+        // boxTriangles: 1 <= k <= PSM_QUERY_K_MAX, d_tris [n][k] = the lowest ids that count, ascending, then -1, d_count [n] = the
+        // slots that hold one (psm_bvh_box_overlaps_dev / psm_bvh_box_count_dev / psm_bvh_box_triangles_dev), stream-ordered on
+        // the context; returns the psm_status
+        int boxOverlaps(const psm_box_query * d_boxes, size_t n, uint8_t * d_hit);
+        int boxCount(const psm_box_query * d_boxes, size_t n, uint32_t * d_count);
+        int boxTriangles(const psm_box_query * d_boxes, size_t n, uint32_t k, int32_t * d_tris, uint32_t * d_count);
         psm_bvh * handle() { return bvh; }
     };
 }

@@ -77,6 +77,21 @@ namespace NSM {
         check(rc, "TriangleHierarchy::nearest");
         return rc;
     }
+    inline int TriangleHierarchy::boxOverlaps(const psm_box_query * d_boxes, size_t n, uint8_t * d_hit) {
+        const int rc = psm_bvh_box_overlaps_dev(bvh, d_boxes, n, d_hit);
+        check(rc, "TriangleHierarchy::boxOverlaps");
+        return rc;
+    }
+    inline int TriangleHierarchy::boxCount(const psm_box_query * d_boxes, size_t n, uint32_t * d_count) {
+        const int rc = psm_bvh_box_count_dev(bvh, d_boxes, n, d_count);
+        check(rc, "TriangleHierarchy::boxCount");
+        return rc;
+    }
+    inline int TriangleHierarchy::boxTriangles(const psm_box_query * d_boxes, size_t n, uint32_t k, int32_t * d_tris, uint32_t * d_count) {
+        const int rc = psm_bvh_box_triangles_dev(bvh, d_boxes, n, k, d_tris, d_count);
+        check(rc, "TriangleHierarchy::boxTriangles");
+        return rc;
+    }
     inline void TriangleHierarchy::setBuildGraph(bool enable) { if (bvh) check(psm_bvh_set_build_graph(bvh, enable ? 1 : 0), "TriangleHierarchy::setBuildGraph"); }
     inline void TriangleHierarchy::configureIntersection(bool clearDepth) { (void)clearDepth; }  // ignored by the reference's shaders too
 

@@ -461,6 +461,46 @@ int psm_bvh_signed_distance_dev(psm_bvh* bvh, const psm_point_query* d_points, s
 int psm_bvh_first_hits_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, uint32_t k, psm_hit* d_hits, uint32_t* d_count);
 int psm_bvh_nearest_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, uint32_t k, psm_hit* d_hits, uint32_t* d_count);
 
+/* box queries against a built hierarchy (new; no reference counterpart): whether, how many and which of the
+ * hierarchy's triangles overlap an axis-aligned box, on the same leaves, stack, context and checks as the queries above. Flat
+ * scenes, instanced lists and worlds have none (a posed box is an oriented box in object space). Semantics:
+ *   - a box {lo, hi} is valid iff its six numbers are finite and lo[k] <= hi[k] on every axis; a point (lo == hi) is valid. An
+ *     invalid box answers 0, 0, or count 0 with a row of -1: never an error, as for invalid rays and points. The pads are not read
+ *   - the candidates are the hierarchy's leaves (PSM_BVH_LEAF_TRI) by load-order triangle id, a triangle read as the build
+ *     stores it: v0, e1 = v1 - v0, e2 = v2 - v0. A triangle the build dropped stays dropped
+ *   - a candidate counts iff box_tri(v0, e1, e2, lo, hi): the 13 separating axes of a triangle and a box, in float32, one fixed
+ *     operation order, multiplications, additions and compares only (box.hip box_tri; tests/box_query_model.py restates it),
+ *     closed: touching counts -- as float32 decides it: where every operation is exact (coordinates on a lattice) contact counts;
+ *     elsewhere contact that is exact in real numbers is found or missed by the rounding of the sums.
+ *       L = lo - v0, H = hi - v0 per component; f3 = e2 - e1 per component; dot(a, b) = (a0 b0 + a1 b1) + a2 b2
+ *       for an axis a: bmin(a) = the sum over a's components of (a_j >= 0 ? a_j L_j : a_j H_j), bmax(a) the same with L and H
+ *         swapped; three terms as (s0 + s1) + s2; a component that is zero by construction is left out of the sums and of dot
+ *         (the two other terms only, in component order)
+ *       an axis with the triangle's projections P (relative to v0) separates iff !(max P >= bmin && min P <= bmax)
+ *       the three unit axes k: P = {0, e1_k, e2_k} against [L_k, H_k] directly, no product
+ *       the nine edge axes unit_k x f, f = e1, e2, f3: k = x: (0, -f_z, f_y); k = y: (f_z, 0, -f_x); k = z: (-f_y, f_x, 0);
+ *         P = {0, dot(a, e2)} for f = e1, P = {0, dot(a, e1)} for f = e2 and for f = f3
+ *       the normal axis n = cross3(e1, e2) (psm_math.h): P = {0}
+ *       box_tri holds iff no axis separates. max / min of P are selections (p > 0 ? p : 0, p < 0 ? p : 0). A degenerate triangle
+ *       gets a finite, deterministic answer: its zero axes separate nothing
+ *   - overlaps: d_hit[i] = 1 iff some candidate counts, else 0 (uint8_t, torch.bool-compatible)
+ *   - count: d_count[i] = the number c of candidates that count
+ *   - triangles: 1 <= k <= PSM_QUERY_K_MAX; row i of d_tris ([n][k]) holds the min(k, c) LOWEST triangle ids that count,
+ *     ascending, then -1; d_count[i] = min(k, c). With k >= c the row is the complete list; the row for k is the first k slots of
+ *     the row for any larger k
+ *   - nothing depends on the traversal order: a flag, a sum, the lowest ids
+ *   - k == 0 or k > PSM_QUERY_K_MAX: PSM_ERR_INVALID, nothing is launched, as for the k-best queries. d_boxes 16-byte, d_count
+ *     and d_tris 4-byte aligned; everything else (NULL checks, n = 0, PSM_ERR_STATE before the first build -- "box query before
+ *     build" --, PSM_ERR_CAPACITY for a hierarchy deeper than the query stack, stream order, capture, refit, 0 / 1 leaves) as
+ *     for the queries above. A refused call launches nothing and leaves the output buffers untouched */
+typedef struct {
+    float lo[3], pad0;
+    float hi[3], pad1;
+} psm_box_query; /* 32 B: two 16-byte loads */
+int psm_bvh_box_overlaps_dev(psm_bvh* bvh, const psm_box_query* d_boxes, size_t n, uint8_t* d_hit);
+int psm_bvh_box_count_dev(psm_bvh* bvh, const psm_box_query* d_boxes, size_t n, uint32_t* d_count);
+int psm_bvh_box_triangles_dev(psm_bvh* bvh, const psm_box_query* d_boxes, size_t n, uint32_t k, int32_t* d_tris, uint32_t* d_count);
+
 /* scene queries: the seven queries above over several hierarchies at once (new; no reference counterpart).
  * A scene is an ordered list of G built hierarchies of ONE context, 1 <= G <= PSM_SCENE_MAX_GEOMETRIES, passed per call (there
  * is no scene handle). The limit is 32 because the per-geometry table then travels with the launch (32 x four pointers = 1 KB

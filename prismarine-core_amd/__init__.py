@@ -28,6 +28,7 @@ EXPORTS = [
     "psm_bvh_stage_emit", "psm_bvh_download", "psm_bvh_intersect_dev", "psm_bvh_occluded_dev",
     "psm_bvh_closest_point_dev", "psm_bvh_within_dev", "psm_bvh_count_hits_dev", "psm_bvh_inside_dev", "psm_bvh_signed_distance_dev",
     "psm_bvh_first_hits_dev", "psm_bvh_nearest_dev",
+    "psm_bvh_box_overlaps_dev", "psm_bvh_box_count_dev", "psm_bvh_box_triangles_dev",
     "psm_scene_intersect_dev", "psm_scene_occluded_dev", "psm_scene_count_hits_dev", "psm_scene_closest_point_dev", "psm_scene_within_dev",
     "psm_scene_inside_dev", "psm_scene_signed_distance_dev",
     "psm_instances_intersect_dev", "psm_instances_occluded_dev", "psm_instances_count_hits_dev", "psm_instances_closest_point_dev",
@@ -58,6 +59,7 @@ RAY_DT = np.dtype([("origin", "<f4", 3), ("direct", "<f4", 3), ("color", "<f4", 
 HIT_DT = np.dtype([("u", "<f4"), ("v", "<f4"), ("t", "<f4"), ("tri", "<i4")])
 QUERY_RAY_DT = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direct", "<f4", 3), ("tmax", "<f4")])   # psm_query_ray
 POINT_QUERY_DT = np.dtype([("p", "<f4", 3), ("rmax", "<f4")])   # psm_point_query
+BOX_QUERY_DT = np.dtype([("lo", "<f4", 3), ("pad0", "<f4"), ("hi", "<f4", 3), ("pad1", "<f4")])   # psm_box_query
 QUERY_K_MAX = 16   # psm_hip.h PSM_QUERY_K_MAX
 SCENE_MAX_GEOMETRIES = 32   # psm_hip.h PSM_SCENE_MAX_GEOMETRIES
 WORLD_MAX_INSTANCES = 65536   # psm_hip.h PSM_WORLD_MAX_INSTANCES
@@ -413,6 +415,52 @@ class TriangleHierarchy:
         is closestPoint()'s record). Arguments and placement as closestPoint()."""
         return self._point_query(points, rmax, "lists", "psm_bvh_nearest_dev", k=k)
 
+    def boxOverlaps(self, lo, hi):
+        """Whether some triangle overlaps each axis-aligned box [lo, hi] (psm_bvh_box_overlaps_dev; not in the reference): lo, hi
+        [n, 3]; the box is closed (touching counts), a point (lo == hi) is a box, and a box with a non-finite number or lo > hi on
+        an axis overlaps nothing. The test is the 13 separating axes of a triangle and a box in float32 (psm_hip.h "box queries").
+        A bool array / tensor. numpy in: numpy out; torch device tensors in: torch tensors out on the same device, ordered against
+        torch's current stream without synchronising (as intersect()). QueryScene, InstancedScene and InstanceWorld have no box
+        queries."""
+        return self._box_query(lo, hi, "bool", "psm_bvh_box_overlaps_dev")
+
+    def boxCount(self, lo, hi):
+        """The number of triangles that overlap each box (psm_bvh_box_count_dev; not in the reference): what boxOverlaps() asks
+        "is there one?" about, counted. A uint32 array, or an int32 tensor for torch tensors. Arguments and placement as
+        boxOverlaps()."""
+        return self._box_query(lo, hi, "count", "psm_bvh_box_count_dev")
+
+    def boxTriangles(self, lo, hi, k):
+        """Which triangles overlap each box (psm_bvh_box_triangles_dev; not in the reference): of the triangles boxCount() counts,
+        the min(k, count) lowest ids, ascending. k: 1 .. QUERY_K_MAX. Returns QueryTriLists: tri [n, k] int32 (-1 past count) and
+        count [n]; with k >= boxCount() the row is the complete list. Arguments and placement as boxOverlaps()."""
+        if not 1 <= _k(k, "psm_bvh_box_triangles_dev") <= QUERY_K_MAX:   # (refused here: no call is made)
+            raise PsmError("psm_bvh_box_triangles_dev: k must be 1 .. %d" % QUERY_K_MAX)
+        return self._box_query(lo, hi, "tris", "psm_bvh_box_triangles_dev", k)
+
+    def _box_query(self, lo, hi, out, name, k=None):
+        """lo, hi [n, 3] packed into psm_box_query records (the pads are 0) on the side the arguments live on"""
+        extra = () if k is None else (C.c_uint32(int(k)),)
+        if type(lo).__module__.split(".")[0] == "torch":
+            import torch
+            dev = lo.device
+            if dev.type != "cuda" or getattr(hi, "device", None) != dev:
+                raise ValueError("box queries: lo and hi must be tensors on the context's device")
+            a, b = lo.reshape(-1, 3), hi.reshape(-1, 3)
+            if a.shape[0] != b.shape[0]:
+                raise ValueError("lo and hi: %d against %d boxes" % (a.shape[0], b.shape[0]))
+            boxes = torch.zeros((a.shape[0], 8), dtype=torch.float32, device=dev)
+            boxes[:, 0:3] = a
+            boxes[:, 4:7] = b
+            return _launch_torch(self, boxes, out, name, *extra)
+        a = np.ascontiguousarray(lo, np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(hi, np.float32).reshape(-1, 3)
+        if a.shape[0] != b.shape[0]:
+            raise ValueError("lo and hi: %d against %d boxes" % (a.shape[0], b.shape[0]))
+        boxes = np.zeros((a.shape[0], 8), np.float32)
+        boxes[:, 0:3], boxes[:, 4:7] = a, b
+        return self._launch_np(boxes, out, name, *extra)
+
     def _query(self, origins, directions, tmin, tmax, out, name=None, k=None):
         name = name or _RAY_QUERIES[out]
         extra = () if k is None else (C.c_uint32(_k(k, name)),)
@@ -527,8 +575,9 @@ class TriangleHierarchy:
 
 
 # a query's result by kind: bytes per query and the numpy type of the array returned ("hits": QueryHits over float32 [n, 4];
-# "lists": QueryHitLists over float32 [n, k, 4] -- 16 bytes per slot, k the launch's extra argument -- and a count per query)
-_QUERY_OUT = {"hits": (16, np.float32), "bool": (1, np.bool_), "count": (4, np.uint32), "lists": (16, np.float32)}
+# "lists": QueryHitLists over float32 [n, k, 4] -- 16 bytes per slot, k the launch's extra argument -- and a count per query;
+# "tris": QueryTriLists over int32 [n, k] -- 4 bytes per slot -- and a count per query)
+_QUERY_OUT = {"hits": (16, np.float32), "bool": (1, np.bool_), "count": (4, np.uint32), "lists": (16, np.float32), "tris": (4, np.int32)}
 _RAY_QUERIES = {"hits": "psm_bvh_intersect_dev", "bool": "psm_bvh_occluded_dev", "count": "psm_bvh_count_hits_dev"}
 
 
@@ -570,6 +619,18 @@ class QueryHitLists:
         return self.buffer.shape[0]
 
 
+class QueryTriLists:
+    """The rows of TriangleHierarchy.boxTriangles: tri [n, k] int32 (numpy array or torch tensor), the lowest triangle ids that
+    overlap the box, ascending, -1 in the slots past count; count [n] (uint32; an int32 tensor for torch)."""
+
+    def __init__(self, tri, count):
+        self.tri = tri
+        self.count = count
+
+    def __len__(self):
+        return self.tri.shape[0]
+
+
 class QueryHits:
     """Closest hits of TriangleHierarchy.intersect (closest points of .closestPoint and .signedDistance: t is the distance): `buffer` [n, 4] float32 (numpy array or torch tensor) holds psm_hit records
     (u, v, t, tri); t, u, v and tri (int32) are views of it. geom: for a QueryScene's results the int32 array / tensor of the
@@ -595,9 +656,10 @@ def _launch_np(th, packed, out, name, *extra):
     ctx = th.ctx
     n = packed.shape[0]
     per, dtype = _QUERY_OUT[out]
+    tris = out == "tris"     # (a box query's id rows: k slots per query and the counts, as the lists')
     lists = out == "lists"   # (k rows per query, and the counts travel where a scene's geometry indices do)
-    k = extra[0].value if lists else 1
-    geom = (th._scene and out == "hits") or lists
+    k = extra[0].value if lists or tris else 1
+    geom = (th._scene and out == "hits") or lists or tris
     hr, ho = ctx.buf_alloc(max(packed.nbytes, 32)), ctx.buf_alloc(max(per * k * n, 16))
     hg = ctx.buf_alloc(max(4 * n, 16)) if geom else None
     hi = ctx.buf_alloc(max(4 * k * n, 16)) if lists and th._scene else None   # (a world's rows: the instance of every slot)
@@ -610,6 +672,8 @@ def _launch_np(th, packed, out, name, *extra):
             ctx.sync()
             if lists:
                 return QueryHitLists(np.zeros((0, k, 4), np.float32), np.zeros(0, np.uint32), None if hi is None else np.zeros((0, k), np.int32))
+            if tris:
+                return QueryTriLists(np.zeros((0, k), np.int32), np.zeros(0, np.uint32))
             if out == "hits":
                 return QueryHits(np.zeros((0, 4), np.float32), np.zeros(0, np.int32) if geom else None)
             return np.zeros(0, dtype)
@@ -617,6 +681,8 @@ def _launch_np(th, packed, out, name, *extra):
             return ctx.buf_download(ho, np.uint8, n).view(np.bool_)
         if out == "count":
             return ctx.buf_download(ho, np.uint32, n)
+        if tris:
+            return QueryTriLists(ctx.buf_download(ho, np.int32, k * n).reshape(n, k), ctx.buf_download(hg, np.uint32, n))
         if lists:
             return QueryHitLists(ctx.buf_download(ho, np.float32, 4 * k * n).reshape(n, k, 4), ctx.buf_download(hg, np.uint32, n),
                                  None if hi is None else ctx.buf_download(hi, np.int32, k * n).reshape(n, k))
@@ -675,11 +741,12 @@ def _launch_torch(th, packed, kind, name, *extra):
     import torch
     dev = packed.device
     n = packed.shape[0]
-    lists = kind == "lists"
+    lists, tris = kind == "lists", kind == "tris"
     shape, dtype = {"hits": ((n, 4), torch.float32), "bool": ((n,), torch.uint8), "count": ((n,), torch.int32),
-                    "lists": ((n, extra[0].value if lists else 1, 4), torch.float32)}[kind]
+                    "lists": ((n, extra[0].value if lists else 1, 4), torch.float32),
+                    "tris": ((n, extra[0].value if tris else 1), torch.int32)}[kind]
     out = torch.empty(shape, dtype=dtype, device=dev)
-    geom = torch.empty((n,), dtype=torch.int32, device=dev) if (th._scene and kind == "hits") or lists else None
+    geom = torch.empty((n,), dtype=torch.int32, device=dev) if (th._scene and kind == "hits") or lists or tris else None
     inst = torch.empty(shape[:2], dtype=torch.int32, device=dev) if lists and th._scene else None   # (a world's rows)
     cur = torch.cuda.current_stream(dev)
     mine = th.ctx.stream or 0   # (NULL: the device's null stream, torch's default stream)
@@ -698,6 +765,8 @@ def _launch_torch(th, packed, kind, name, *extra):
         _hip_check(hip.hipEventDestroy(ev), "hipEventDestroy")
     if lists:
         return QueryHitLists(out, geom, inst)
+    if tris:
+        return QueryTriLists(out, geom)
     return QueryHits(out, geom) if kind == "hits" else (out.view(torch.bool) if kind == "bool" else out)
 
 

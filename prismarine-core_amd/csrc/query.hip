@@ -832,18 +832,21 @@ const QueryDesc QUERY_DESC[] = {{"psm_bvh_intersect_dev", "rays", "hits", 16, fa
                                 {"psm_bvh_inside_dev", "points", nullptr, 1, true},
                                 {"psm_bvh_signed_distance_dev", "points", "hits", 16, true},
                                 {"psm_bvh_first_hits_dev", "rays", "hits", 16, false},
-                                {"psm_bvh_nearest_dev", "points", "hits", 16, true}};
+                                {"psm_bvh_nearest_dev", "points", "hits", 16, true},
+                                {"psm_bvh_box_overlaps_dev", "boxes", nullptr, 1, false},
+                                {"psm_bvh_box_count_dev", "boxes", "counts", 4, false},
+                                {"psm_bvh_box_triangles_dev", "boxes", "tris", 4, false}};
 
 // The data checks every query shares, under the entry point's name: in / out must be non-NULL, in 16-byte aligned, out as its
 // kind asks (a psm_hit 16 bytes, a count 4); samples (the inside kinds only): 1, 3 or 5; the k-best kinds' k travels as
 // samples: 1 .. PSM_QUERY_K_MAX. index: what the per-query index array (d_geom: the kinds with a psm_hit output only; the
-// k-best kinds' d_count) is called in the messages, NULL for a query that has none. A batch that passes makes the context's
+// k-best kinds' and the box triangles query's d_count) is called in the messages, NULL for a query that has none. A batch that passes makes the context's
 // device the current one.
 int check_data(psm_ctx* c, const char* name, const char* index, QueryKind kind, const void* d_in, const void* d_out, const int32_t* d_geom,
                uint32_t samples) {
     const QueryDesc& k = QUERY_DESC[kind];
     char msg[128];
-    const bool with_geom = index && k.out_align == 16;
+    const bool with_geom = index && (k.out_align == 16 || kind == Q_BOX_TRIS);   // (the triangles query: int32 rows and counts)
     if (!d_in || !d_out || (with_geom && !d_geom)) {
         snprintf(msg, sizeof msg, "%s: NULL pointer", name);
         return set_err(c, PSM_ERR_INVALID, msg);
@@ -863,7 +866,7 @@ int check_data(psm_ctx* c, const char* name, const char* index, QueryKind kind, 
         snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", name);
         return set_err(c, PSM_ERR_INVALID, msg);
     }
-    if ((kind == Q_FIRST_HITS || kind == Q_NEAREST) && (samples == 0 || samples > PSM_QUERY_K_MAX)) {
+    if ((kind == Q_FIRST_HITS || kind == Q_NEAREST || kind == Q_BOX_TRIS) && (samples == 0 || samples > PSM_QUERY_K_MAX)) {
         snprintf(msg, sizeof msg, "%s: k must be 1 .. %d", name, PSM_QUERY_K_MAX);
         return set_err(c, PSM_ERR_INVALID, msg);
     }
@@ -904,18 +907,22 @@ const Kernels<InstArgs> INST_KERNELS = {{inst_query_closest, inst_query_any, ins
 bool too_deep(const psm_bvh* b) { return depth_bound(b) > QSTACK_MAX; }
 
 // A query of one hierarchy: n == 0 is answered before anything else is looked at; then the data, the state, the depth.
-// The k-best kinds (kbest.hip) come through here too: samples is their k, d_out their [n][k] records, d_count their counts.
+// The k-best kinds (kbest.hip) come through here too: samples is their k, d_out their [n][k] records, d_count their counts;
+// and the box kinds (box.hip): d_in the boxes, and for the triangles query samples = k, d_out the [n][k] ids, d_count the counts.
 int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, void* d_out, uint32_t samples = 0, uint32_t* d_count = nullptr) {
     if (!b) return PSM_ERR_INVALID;
     if (n == 0) return PSM_OK;
     psm_ctx* c = b->ctx;
-    const bool points = QUERY_DESC[kind].points, kbest = kind == Q_FIRST_HITS || kind == Q_NEAREST;
-    int rc = check_data(c, QUERY_DESC[kind].name, kbest ? "counts" : nullptr, kind, d_in, d_out, (const int32_t*)d_count, samples);
+    const bool points = QUERY_DESC[kind].points, kbest = kind == Q_FIRST_HITS || kind == Q_NEAREST, box = kind >= Q_BOX_ANY;
+    const bool counted = kbest || kind == Q_BOX_TRIS;
+    int rc = check_data(c, QUERY_DESC[kind].name, counted ? "counts" : nullptr, kind, d_in, d_out, (const int32_t*)d_count, samples);
     if (rc != PSM_OK) return rc;
-    if (!b->built) return set_err(c, PSM_ERR_STATE, points ? "point query before build" : "ray query before build");
+    if (!b->built)
+        return set_err(c, PSM_ERR_STATE, box ? "box query before build" : points ? "point query before build" : "ray query before build");
     if (too_deep(b))
-        return set_err(c, PSM_ERR_CAPACITY, points ? "point query: hierarchy deeper than the query stack"
-                                                   : "ray query: hierarchy deeper than the query stack");
+        return set_err(c, PSM_ERR_CAPACITY, box      ? "box query: hierarchy deeper than the query stack"
+                                            : points ? "point query: hierarchy deeper than the query stack"
+                                                     : "ray query: hierarchy deeper than the query stack");
     QueryArgs qa = {};
     uint32_t grid = 0;
     rc = batch_args(c, d_in, n, d_out, samples, qa, grid);
@@ -924,6 +931,10 @@ int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, void* d_out, u
     if (kbest) {
         qa.count = d_count;
         return kbest_launch(c, points, grid, qa);
+    }
+    if (box) {   // (box.hip; the triangles query's rows are d_out, its counts d_count)
+        if (kind == Q_BOX_TRIS) qa.count = d_count;
+        return box_launch(c, (int)kind - (int)Q_BOX_ANY, grid, qa);
     }
     return launch(c, BVH_KERNELS, kind, grid, qa);
 }
@@ -1077,6 +1088,18 @@ int psm_bvh_first_hits_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, 
 
 int psm_bvh_nearest_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, uint32_t k, psm_hit* d_hits, uint32_t* d_count) {
     return psm::query(bvh, psm::Q_NEAREST, d_points, n, d_hits, k, d_count);
+}
+
+int psm_bvh_box_overlaps_dev(psm_bvh* bvh, const psm_box_query* d_boxes, size_t n, uint8_t* d_hit) {
+    return psm::query(bvh, psm::Q_BOX_ANY, d_boxes, n, d_hit);
+}
+
+int psm_bvh_box_count_dev(psm_bvh* bvh, const psm_box_query* d_boxes, size_t n, uint32_t* d_count) {
+    return psm::query(bvh, psm::Q_BOX_COUNT, d_boxes, n, d_count);
+}
+
+int psm_bvh_box_triangles_dev(psm_bvh* bvh, const psm_box_query* d_boxes, size_t n, uint32_t k, int32_t* d_tris, uint32_t* d_count) {
+    return psm::query(bvh, psm::Q_BOX_TRIS, d_boxes, n, d_tris, k, d_count);
 }
 
 int psm_scene_intersect_dev(psm_bvh* const* geoms, uint32_t count, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits, int32_t* d_geom) {

@@ -31,6 +31,11 @@ operation on the same stream; it loses hits at a bit-equal t); on the point mode
 mode's scenes (one torus at 32, 256, 4096 and 65 536 grid poses, local rays and points), k = 1, 4 and 16, every pair alternated
 A B A B with medians of REPS: firstHits against intersect, and against k intersect launches with tmin moved past the last t
 between them (it loses hits at a bit-equal t); nearest against closestPoint. WORLD_N = queries per batch (default 2^18).
+`query_bench.py boxes`: the box queries (psm_bvh_box_overlaps_dev / psm_bvh_box_count_dev / psm_bvh_box_triangles_dev) on the
+Sponza-class scene and the stress scene (STRESS_TRIS triangles, default 10 M): the three queries (triangles at k = 4 and 16) over
+the cell boxes of a 64^3 and a 128^3 grid of the scene's bounds, each alternated A B A B (medians of REPS) with what a caller had
+before them: psm_bvh_within_dev with the cell's half-diagonal as radius (a sphere around the cell: it over-reports); and
+boxCount for ONE box around half the scene (the case an early acceptance of contained subtrees would serve).
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -760,6 +765,72 @@ def kbest():
     print(json.dumps(out))
 
 
+def boxes():
+    lib = psm.lib()
+    out = {"reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+    stress_tris = int(os.environ.get("STRESS_TRIS", "10000000"))
+    for scene_name, sc in (("sponza", scenes.sponza_like()), ("stress", scenes.stress(stress_tris))):
+        ctx = psm.Context(0)
+        th = psm.TriangleHierarchy(ctx)
+        th.allocate(sc["tris"].shape[0])
+        th.loadTriangles(sc["tris"], sc["normals"], sc["mats"])
+        th.build()
+        v = sc["tris"].reshape(-1, 3)
+        lo, hi = v.min(0).astype(np.float64), v.max(0).astype(np.float64)
+        out[scene_name + "_tris"] = int(th.info().leaf_count)
+        for g in (64, 128):
+            n = g ** 3
+            idx = np.stack(np.meshgrid(np.arange(g), np.arange(g), np.arange(g), indexing="ij"), axis=-1).reshape(-1, 3)
+            cell = (hi - lo) / g
+            b = np.zeros((n, 8), np.float32)
+            b[:, 0:3], b[:, 4:7] = lo + idx * cell, lo + (idx + 1) * cell
+            q = np.zeros((n, 4), np.float32)
+            q[:, 0:3], q[:, 3] = lo + (idx + 0.5) * cell, 0.5 * float(np.linalg.norm(cell))
+            hs = [ctx.buf_alloc(x) for x in (32 * n, 16 * n, n, 4 * n, 4 * 16 * n)]
+            p_box, p_pts, p_flag, p_count, p_rows = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in hs)
+            ctx.buf_upload(hs[0], b)
+            ctx.buf_upload(hs[1], q)
+            size = C.c_size_t(n)
+
+            def within():
+                ctx.check(lib.psm_bvh_within_dev(th._h, p_pts, size, p_flag), "psm_bvh_within_dev")
+
+            def overlaps():
+                ctx.check(lib.psm_bvh_box_overlaps_dev(th._h, p_box, size, p_flag), "psm_bvh_box_overlaps_dev")
+
+            def count():
+                ctx.check(lib.psm_bvh_box_count_dev(th._h, p_box, size, p_count), "psm_bvh_box_count_dev")
+
+            def triangles(k):
+                return lambda: ctx.check(lib.psm_bvh_box_triangles_dev(th._h, p_box, size, C.c_uint32(k), p_rows, p_count),
+                                         "psm_bvh_box_triangles_dev")
+            key = "%s_%d_" % (scene_name, g)
+            for name, fn in (("overlaps", overlaps), ("count", count), ("triangles_k4", triangles(4)), ("triangles_k16", triangles(16))):
+                out[key + name + "_ms"], out[key + "within_beside_" + name + "_ms"] = abab(ctx, fn, within)
+            within()
+            sphere = float(ctx.buf_download(hs[2], np.uint8, n).mean())
+            overlaps()
+            out[key + "within_fraction"], out[key + "overlaps_fraction"] = round(sphere, 4), round(float(ctx.buf_download(hs[2], np.uint8, n).mean()), 4)
+            count()
+            out[key + "mean_count"] = round(float(ctx.buf_download(hs[3], np.uint32, n).mean()), 2)
+            for h in hs:
+                ctx.buf_free(h)
+        # one box around half the scene (the lower half along x)
+        hb, hc = ctx.buf_alloc(32), ctx.buf_alloc(16)
+        b = np.zeros((1, 8), np.float32)
+        b[0, 0:3], b[0, 4:7] = lo, [0.5 * (lo[0] + hi[0]), hi[1], hi[2]]
+        ctx.buf_upload(hb, b)
+        p_b, p_c = C.c_void_p(ctx.buf_ptr(hb)[0]), C.c_void_p(ctx.buf_ptr(hc)[0])
+        out[scene_name + "_half_scene_count_ms"] = round(median_ms(ctx, lambda: ctx.check(lib.psm_bvh_box_count_dev(th._h, p_b, C.c_size_t(1), p_c),
+                                                                                        "psm_bvh_box_count_dev")), 4)
+        out[scene_name + "_half_scene_count"] = int(ctx.buf_download(hc, np.uint32, 1)[0])
+        ctx.buf_free(hb)
+        ctx.buf_free(hc)
+        th.close()
+        ctx.close()
+    print(json.dumps(out))
+
+
 def main():
     sc = scenes.sponza_like()
     ctx = psm.Context(0)
@@ -825,4 +896,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes}.get(" ".join(sys.argv[1:]), main)()
