@@ -40,5 +40,13 @@ namespace NSM {
         // misses with inst = -1 (psm_world_first_hits_dev / psm_world_nearest_dev); the flat lists have no such query
         int firstHits(const psm_query_ray * d_rays, size_t n, uint32_t k, psm_hit * d_hits, int32_t * d_inst, uint32_t * d_count);
         int nearest(const psm_point_query * d_points, size_t n, uint32_t k, psm_hit * d_hits, int32_t * d_inst, uint32_t * d_count);
+        // whether / how many / which (instance, triangle) pairs overlap each of n axis-aligned WORLD boxes (closed: touching
+        // counts): the box is never moved, each candidate triangle is posed forward and judged by the single hierarchy's box test;
+        // trianglesInBox: 1 <= k <= PSM_QUERY_K_MAX, d_tri and d_inst [n][k] = the lowest (inst, tri) that count, ascending, then
+        // -1 in both, d_count [n] = the slots filled (psm_world_box_overlaps_dev / psm_world_box_count_dev /
+        // psm_world_box_triangles_dev); the flat lists have no such query
+        int overlapsBox(const psm_box_query * d_boxes, size_t n, uint8_t * d_hit);
+        int countInBox(const psm_box_query * d_boxes, size_t n, uint32_t * d_count);
+        int trianglesInBox(const psm_box_query * d_boxes, size_t n, uint32_t k, int32_t * d_tri, int32_t * d_inst, uint32_t * d_count);
     };
 }

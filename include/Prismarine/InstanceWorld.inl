@@ -66,4 +66,19 @@ namespace NSM {
         check(rc, "InstanceWorld::nearest");
         return rc;
     }
+    inline int InstanceWorld::overlapsBox(const psm_box_query * d_boxes, size_t n, uint8_t * d_hit) {
+        const int rc = psm_world_box_overlaps_dev(world, d_boxes, n, d_hit);
+        check(rc, "InstanceWorld::overlapsBox");
+        return rc;
+    }
+    inline int InstanceWorld::countInBox(const psm_box_query * d_boxes, size_t n, uint32_t * d_count) {
+        const int rc = psm_world_box_count_dev(world, d_boxes, n, d_count);
+        check(rc, "InstanceWorld::countInBox");
+        return rc;
+    }
+    inline int InstanceWorld::trianglesInBox(const psm_box_query * d_boxes, size_t n, uint32_t k, int32_t * d_tri, int32_t * d_inst, uint32_t * d_count) {
+        const int rc = psm_world_box_triangles_dev(world, d_boxes, n, k, d_tri, d_inst, d_count);
+        check(rc, "InstanceWorld::trianglesInBox");
+        return rc;
+    }
 }

@@ -463,7 +463,7 @@ int psm_bvh_nearest_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n,
 
 /* box queries against a built hierarchy (new; no reference counterpart): whether, how many and which of the
  * hierarchy's triangles overlap an axis-aligned box, on the same leaves, stack, context and checks as the queries above. Flat
- * scenes, instanced lists and worlds have none (a posed box is an oriented box in object space). Semantics:
+ * scenes and instanced lists have none; worlds: below (psm_world_box_*_dev: the box stays in world space). Semantics:
  *   - a box {lo, hi} is valid iff its six numbers are finite and lo[k] <= hi[k] on every axis; a point (lo == hi) is valid. An
  *     invalid box answers 0, 0, or count 0 with a row of -1: never an error, as for invalid rays and points. The pads are not read
  *   - the candidates are the hierarchy's leaves (PSM_BVH_LEAF_TRI) by load-order triangle id, a triangle read as the build
@@ -664,6 +664,38 @@ int psm_world_first_hits_dev(psm_world* world, const psm_query_ray* d_rays, size
                              uint32_t* d_count);
 int psm_world_nearest_dev(psm_world* world, const psm_point_query* d_points, size_t n, uint32_t k, psm_hit* d_hits, int32_t* d_inst,
                           uint32_t* d_count);
+
+/* box queries over a world (new; no reference counterpart): whether, how many and which (instance, triangle)
+ * pairs of a world overlap an axis-aligned box given in WORLD space, in one launch. A posed box would be an oriented box in
+ * object space; the contract avoids it: the box stays in world space and is never moved, the candidate triangle is posed
+ * forward. Flat scenes and instanced lists (psm_scene_*, psm_instances_*) have no box query. Semantics:
+ *   - box validity, closedness and the answer for an invalid box are those of the box queries against a built hierarchy:
+ *     six finite numbers, lo[k] <= hi[k]; a point is a box; an invalid box answers 0, 0, or count 0 with rows of -1. The box is
+ *     not moved, so there is no per-instance validity
+ *   - the candidates are the pairs (inst, tri): inst an index of the world's ordered list, tri a leaf of that instance's
+ *     hierarchy (PSM_BVH_LEAF_TRI), stored as v0, e1, e2
+ *   - with m = world_from_object[12] of the instance, in float32, one rounding per operation, nothing fused (the order
+ *     the world's instance boxes are made in):
+ *       fwd_point(m, x)_k = ((m[4k] * x.x + m[4k+1] * x.y) + m[4k+2] * x.z) + m[4k+3]
+ *       fwd_vec  (m, d)_k =  (m[4k] * d.x + m[4k+1] * d.y) + m[4k+2] * d.z
+ *     the candidate counts iff box_tri(fwd_point(m, v0), fwd_vec(m, e1), fwd_vec(m, e2), lo, hi), box_tri the function of the
+ *     box queries above, unchanged, bit for bit. The edges are R e1 and R e2 -- not differences of posed vertices
+ *   - the flat answer, which a world reproduces exactly, is taken over the ordered instance list and all leaves of every member:
+ *       overlaps: d_hit[i] = 1 iff some candidate counts, else 0
+ *       count: d_count[i] = the number c of candidates that count, summed over the instances (uint32)
+ *       triangles: 1 <= k <= PSM_QUERY_K_MAX; rows i of d_tri and d_inst ([n][k] int32 each) hold the min(k, c) LOWEST pairs
+ *         (inst, tri) that count in lexicographic order, ascending (inst and tri compared unsigned); the slots past
+ *         d_count[i] = min(k, c) hold -1 in both. The row for k is a prefix of the row for any larger k; coincident instances
+ *         list every shared triangle once per instance, the lowest instance first
+ *   - nothing depends on the tree, its prune or the order of the walk: a flag, a sum, the lowest pairs
+ *   - k == 0 or k > PSM_QUERY_K_MAX: PSM_ERR_INVALID, nothing is launched, as for the k-best queries. d_boxes 16-byte, d_count,
+ *     d_tri and d_inst 4-byte aligned, none NULL; the stale check, the depth budget, n == 0, stream order and capture as for the
+ *     other world queries; an empty world answers 0 / 0 / count 0 and rows of -1 without a query kernel. A refused call
+ *     launches nothing and leaves the output buffers untouched */
+int psm_world_box_overlaps_dev(psm_world* world, const psm_box_query* d_boxes, size_t n, uint8_t* d_hit);
+int psm_world_box_count_dev(psm_world* world, const psm_box_query* d_boxes, size_t n, uint32_t* d_count);
+int psm_world_box_triangles_dev(psm_world* world, const psm_box_query* d_boxes, size_t n, uint32_t k, int32_t* d_tri, int32_t* d_inst,
+                                uint32_t* d_count);
 
 /* ---------------------------------------------------------------------------------------------
  * several frames in flight (new; DESIGN.md "lanes")

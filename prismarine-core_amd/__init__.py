@@ -36,6 +36,7 @@ EXPORTS = [
     "psm_world_create", "psm_world_destroy", "psm_world_set_instances", "psm_world_set_transforms", "psm_world_count",
     "psm_world_intersect_dev", "psm_world_occluded_dev", "psm_world_count_hits_dev", "psm_world_closest_point_dev", "psm_world_within_dev",
     "psm_world_inside_dev", "psm_world_signed_distance_dev", "psm_world_first_hits_dev", "psm_world_nearest_dev",
+    "psm_world_box_overlaps_dev", "psm_world_box_count_dev", "psm_world_box_triangles_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -420,8 +421,8 @@ class TriangleHierarchy:
         [n, 3]; the box is closed (touching counts), a point (lo == hi) is a box, and a box with a non-finite number or lo > hi on
         an axis overlaps nothing. The test is the 13 separating axes of a triangle and a box in float32 (psm_hip.h "box queries").
         A bool array / tensor. numpy in: numpy out; torch device tensors in: torch tensors out on the same device, ordered against
-        torch's current stream without synchronising (as intersect()). QueryScene, InstancedScene and InstanceWorld have no box
-        queries."""
+        torch's current stream without synchronising (as intersect()). QueryScene and InstancedScene have no box queries;
+        InstanceWorld has its own (overlapsBox / countInBox / trianglesInBox: the box in world space)."""
         return self._box_query(lo, hi, "bool", "psm_bvh_box_overlaps_dev")
 
     def boxCount(self, lo, hi):
@@ -621,11 +622,14 @@ class QueryHitLists:
 
 class QueryTriLists:
     """The rows of TriangleHierarchy.boxTriangles: tri [n, k] int32 (numpy array or torch tensor), the lowest triangle ids that
-    overlap the box, ascending, -1 in the slots past count; count [n] (uint32; an int32 tensor for torch)."""
+    overlap the box, ascending, -1 in the slots past count; count [n] (uint32; an int32 tensor for torch). geom: for the rows of
+    InstanceWorld.trianglesInBox the int32 [n, k] array / tensor of each slot's instance (-1 past count; tri is that instance's
+    id; the rows ascend in (geom, tri)); None for a single hierarchy's."""
 
-    def __init__(self, tri, count):
+    def __init__(self, tri, count, geom=None):
         self.tri = tri
         self.count = count
+        self.geom = geom
 
     def __len__(self):
         return self.tri.shape[0]
@@ -662,7 +666,7 @@ def _launch_np(th, packed, out, name, *extra):
     geom = (th._scene and out == "hits") or lists or tris
     hr, ho = ctx.buf_alloc(max(packed.nbytes, 32)), ctx.buf_alloc(max(per * k * n, 16))
     hg = ctx.buf_alloc(max(4 * n, 16)) if geom else None
-    hi = ctx.buf_alloc(max(4 * k * n, 16)) if lists and th._scene else None   # (a world's rows: the instance of every slot)
+    hi = ctx.buf_alloc(max(4 * k * n, 16)) if (lists or tris) and th._scene else None   # (a world's rows: the instance of every slot)
     try:
         if n:
             ctx.buf_upload(hr, packed)
@@ -673,7 +677,7 @@ def _launch_np(th, packed, out, name, *extra):
             if lists:
                 return QueryHitLists(np.zeros((0, k, 4), np.float32), np.zeros(0, np.uint32), None if hi is None else np.zeros((0, k), np.int32))
             if tris:
-                return QueryTriLists(np.zeros((0, k), np.int32), np.zeros(0, np.uint32))
+                return QueryTriLists(np.zeros((0, k), np.int32), np.zeros(0, np.uint32), None if hi is None else np.zeros((0, k), np.int32))
             if out == "hits":
                 return QueryHits(np.zeros((0, 4), np.float32), np.zeros(0, np.int32) if geom else None)
             return np.zeros(0, dtype)
@@ -682,7 +686,8 @@ def _launch_np(th, packed, out, name, *extra):
         if out == "count":
             return ctx.buf_download(ho, np.uint32, n)
         if tris:
-            return QueryTriLists(ctx.buf_download(ho, np.int32, k * n).reshape(n, k), ctx.buf_download(hg, np.uint32, n))
+            return QueryTriLists(ctx.buf_download(ho, np.int32, k * n).reshape(n, k), ctx.buf_download(hg, np.uint32, n),
+                                 None if hi is None else ctx.buf_download(hi, np.int32, k * n).reshape(n, k))
         if lists:
             return QueryHitLists(ctx.buf_download(ho, np.float32, 4 * k * n).reshape(n, k, 4), ctx.buf_download(hg, np.uint32, n),
                                  None if hi is None else ctx.buf_download(hi, np.int32, k * n).reshape(n, k))
@@ -747,7 +752,7 @@ def _launch_torch(th, packed, kind, name, *extra):
                     "tris": ((n, extra[0].value if tris else 1), torch.int32)}[kind]
     out = torch.empty(shape, dtype=dtype, device=dev)
     geom = torch.empty((n,), dtype=torch.int32, device=dev) if (th._scene and kind == "hits") or lists or tris else None
-    inst = torch.empty(shape[:2], dtype=torch.int32, device=dev) if lists and th._scene else None   # (a world's rows)
+    inst = torch.empty(shape[:2], dtype=torch.int32, device=dev) if (lists or tris) and th._scene else None   # (a world's rows)
     cur = torch.cuda.current_stream(dev)
     mine = th.ctx.stream or 0   # (NULL: the device's null stream, torch's default stream)
     other = mine != cur.cuda_stream
@@ -766,7 +771,7 @@ def _launch_torch(th, packed, kind, name, *extra):
     if lists:
         return QueryHitLists(out, geom, inst)
     if tris:
-        return QueryTriLists(out, geom)
+        return QueryTriLists(out, geom, inst)
     return QueryHits(out, geom) if kind == "hits" else (out.view(torch.bool) if kind == "bool" else out)
 
 
@@ -891,7 +896,8 @@ class InstanceWorld(QueryScene):
     hierarchies as they are when set: after a member was rebuilt, reloaded or reallocated the next query raises PsmError until
     setInstances() is called again; after a member was REFITTED call refresh(). Methods, arguments and numpy / torch placement:
     QueryScene's; QueryHits.geom is the index of the winning instance. A world also has the k-best queries, firstHits() and
-    nearest(), which the flat lists (QueryScene, InstancedScene) have not."""
+    nearest(), and the box queries overlapsBox(), countInBox() and trianglesInBox() over world-space boxes, which the flat lists
+    (QueryScene, InstancedScene) have not."""
 
     def __init__(self, ctx, entries, capacity=None):
         self.ctx = ctx
@@ -966,6 +972,29 @@ class InstanceWorld(QueryScene):
         QueryHitLists with geom: t = the distance, u, v as closestPoint()'s (slot 0 and geom[:, 0] are closestPoint()'s record
         and geom). Arguments and placement as closestPoint()."""
         return self._point_query(points, rmax, "lists", "psm_bvh_nearest_dev", k=k)
+
+    def overlapsBox(self, lo, hi):
+        """Whether some triangle of some instance overlaps each axis-aligned WORLD box [lo, hi] (psm_world_box_overlaps_dev): lo,
+        hi [n, 3]. The box stays in world space; each candidate triangle is posed forward in float32 (v0' = R v0 + T, e1' = R e1,
+        e2' = R e2) and judged by boxOverlaps()'s test (psm_hip.h "box queries over a world"). Closed; a point is a box; a box with
+        a non-finite number or lo > hi overlaps nothing. A bool array / tensor; numpy / torch placement as intersect()."""
+        return self._box_query(lo, hi, "bool", "psm_bvh_box_overlaps_dev")
+
+    def countInBox(self, lo, hi):
+        """The number of (instance, triangle) pairs that overlap each world box, summed over the instances
+        (psm_world_box_count_dev). A uint32 array, or an int32 tensor for torch tensors. Arguments as overlapsBox()."""
+        return self._box_query(lo, hi, "count", "psm_bvh_box_count_dev")
+
+    def trianglesInBox(self, lo, hi, k):
+        """Which triangles of which instances overlap each world box (psm_world_box_triangles_dev): of the pairs countInBox()
+        counts, the min(k, count) lowest in (instance, tri), ascending -- coincident instances list a shared triangle once per
+        instance, the lowest instance first. k: 1 .. QUERY_K_MAX. Returns QueryTriLists: tri and geom (the slot's instance)
+        [n, k] int32, -1 in both past count, and count [n]. Arguments as overlapsBox()."""
+        if not 1 <= _k(k, "psm_world_box_triangles_dev") <= QUERY_K_MAX:   # (refused here: no call is made)
+            raise PsmError("psm_world_box_triangles_dev: k must be 1 .. %d" % QUERY_K_MAX)
+        return self._box_query(lo, hi, "tris", "psm_bvh_box_triangles_dev", k)
+
+    _box_query = TriangleHierarchy._box_query
 
     def _call(self, name, d_in, n, extra, d_out, d_geom):
         name = name.replace("psm_bvh_", "psm_world_")

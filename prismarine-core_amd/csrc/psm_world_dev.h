@@ -1,0 +1,189 @@
+// psm_world_dev.h -- the device pieces the kernel files of a world share (world.hip, world_box.hip): the
+// table row, the node of the tree over the instances, the kernel arguments, the padding and the slacks, the two-level walk, and
+// the loads of a row. Moved here from world.hip as they were; every kernel of world.hip compiles to the same instructions as
+// with the pieces in its own file (tools/kernel_diff.py; the digests of tests/test_world_kbest_cpu.py).
+#pragma once
+#include "psm_common.h"
+#include "psm_internal.h"
+#include "psm_query_dev.h"
+
+namespace psm {
+
+// one instance as the kernels read it: 80 B, 16-byte aligned (five 16-byte loads)
+struct WorldRow {
+    const uint4* node32;
+    const float4* tri48;
+    const uint32_t* sm;
+    const int32_t* sorted_tri;
+    float m[12];   // psm_instance.world_from_object
+};
+static_assert(sizeof(WorldRow) == 80, "a table row is 80 bytes");
+
+// a node of the tree over the instances, 64 B: both children's float32 boxes and two links (>= 0: a node, < 0: ~instance)
+//   w0 = L.lo.xyz L.hi.x | w1 = L.hi.yz R.lo.xy | w2 = R.lo.z R.hi.xyz | w3 = linkL linkR 0 0
+struct WorldNode {
+    float4 w0, w1, w2;
+    int4 w3;
+};
+static_assert(sizeof(WorldNode) == 64, "a node record is 64 bytes");
+
+struct WorldArgs {
+    const float4* rays;      // as QueryArgs
+    size_t n;
+    int* spill;
+    float4* hits;
+    uint8_t* occluded;
+    uint32_t* count;
+    int32_t* geom;           // the winning instance per query, -1 on a miss
+    uint32_t samples;
+    int root;                // 0: the tree's root node; < 0: ~instance of a world of one
+    const WorldRow* rows;
+    const WorldNode* nodes;
+};
+
+// world_box.hip: the launch of a world's box kernel (mode: 0 overlaps, 1 count, 2 triangles) for world.hip's host path; a.rays
+// holds the boxes where a ray's two float4 are, a.samples is the triangles query's k, a.hits its [n][k] int32 triangle rows,
+// a.geom its [n][k] instance rows, a.count the counts
+int world_box_launch(psm_ctx* c, int mode, uint32_t grid, const WorldArgs& a);
+
+namespace {
+
+constexpr int WORLD_TOP = 0x40000000;   // tag of a top-level node link (hierarchy node links stay below 2^28)
+
+// The padding and the slacks (DESIGN.md 4.11 has the derivation). The box test works on the world query and the forward image
+// of the object box, T + R box; the candidate test on the query moved by inst_point / inst_rotate, R^T (x - T). They differ by
+//   * the move's rounding: one subtraction, three products, two sums per coordinate: <= 4 eps sqrt 3 (|x| + |T|) ~ 4.2e-7 (...)
+//   * R^T R = 1 + E, |E_ij| <= 1e-5 (pose_fault): R^-T - R = -R E (1 + E)^-1, a displacement of <= 3e-5 sqrt 3 = 5.2e-5 times
+//     the largest object coordinate, and |R^T d| = 1 +- 1.5e-5: world distances are object distances to 1.5e-5 (squares: 3e-5)
+//   * tri_query's 1e-5 tolerance on u, v, u + v: a counted crossing lies within 1e-5 of an edge length (<= 2 sqrt 3 times the
+//     largest object coordinate) of its triangle: 3.5e-5
+// in all <= 8.8e-5 S in position, S the largest of: the object box's largest |coordinate|, |T|, the world box's largest
+// |coordinate| -- plus 4.2e-7 of the query's largest |coordinate|. WORLD_PAD = WORLD_QSLACK = 2^-11 = 4.9e-4 (5.5x and > 1000x).
+// Distances: WORLD_TSLACK = 2^-12 = 2.4e-4 on t (16x 1.5e-5), WORLD_PSLACK = 2^-11 on d2 (16x 3e-5).
+constexpr float WORLD_PAD = 0x1p-11f;      // a leaf box grows by WORLD_PAD * S + WORLD_FLOOR on every side
+constexpr float WORLD_FLOOR = 0x1p-100f;   // ... so no box is ever degenerate (the NaN argument at WorldRay::slab)
+constexpr float WORLD_QSLACK = 0x1p-11f;   // ... and by WORLD_QSLACK * the query's largest |coordinate| at the test
+constexpr float WORLD_TSLACK = 0x1p-12f;   // a ray's prune against best / tmax / tmin: relative
+constexpr float WORLD_PSLACK = 0x1p-11f;   // a point's prune against best d2 / rmax^2: relative
+
+// ---- the two-level walk --------------------------------------------------------------------------------------------------------
+
+// The body:
+//   bool begin(i, alive)     load query i, clear the running state, set up the WORLD query the top level tests; false: a miss
+//   void top(w0, w1, w2, okL, okR, kL, kR)   a top-level node's two boxes: kept or not, and the order key (nearer first)
+//   int  enter(inst)         load the instance's row, move the query (re-read from memory, as 4.9), do the per-geometry set-up,
+//                            test the lone leaf of a one-leaf hierarchy; returns the hierarchy's root to walk, -1 for none
+//                            (fewer than two leaves, or the moved query is invalid in this instance)
+//   children, leaf, done, again, finish: as query.hip's scene_walk
+// Every loop here is bounded: the node loop by the two trees (each iteration visits a node or an instance once per walk), the
+// leaf loop by two, the outer ones by the batch and the sample count.
+template <class Body>
+PSM_D void world_walk(const WorldArgs& w, Body& q) {
+    __shared__ int stack[QSTACK_LDS][QUERY_BLOCK];
+    const int lane = (int)threadIdx.x;
+    __builtin_assume(lane >= 0 && lane < QUERY_BLOCK);
+    const size_t spill_stride = (size_t)gridDim.x * QUERY_BLOCK;
+    int* __restrict__ spill = w.spill + (size_t)blockIdx.x * QUERY_BLOCK + lane;
+    for (size_t i = (size_t)blockIdx.x * QUERY_BLOCK + (size_t)lane; i - (size_t)lane < w.n; i += spill_stride) {
+        const bool alive = i < w.n;
+        const bool valid = q.begin(i, alive);
+        do {
+            int cur = w.root < 0 ? w.root : (w.root | WORLD_TOP), sp = 0;
+            bool walking = valid;
+            while (walking) {
+                bool pop = false;
+                if (cur < 0) {
+                    const int r = q.enter(~cur);
+                    pop = r < 0;
+                    cur = r;
+                } else if (cur & WORLD_TOP) {
+                    const WorldNode* np = (const WorldNode*)((const char*)w.nodes + ((size_t)(uint32_t)(cur & ~WORLD_TOP) << 6));
+                    const float4 w0 = np->w0, w1 = np->w1, w2 = np->w2;
+                    const int4 w3 = np->w3;
+                    bool okL, okR;
+                    float kL, kR;
+                    q.top(w0, w1, w2, okL, okR, kL, kR);
+                    const int lkL = w3.x < 0 ? w3.x : (w3.x | WORLD_TOP), lkR = w3.y < 0 ? w3.y : (w3.y | WORLD_TOP);
+                    const bool leftFirst = okL && (!okR || kL <= kR);   // nearer child first
+                    const int first = leftFirst ? lkL : lkR, second = leftFirst ? lkR : lkL;
+                    if (okL && okR) {
+                        // (sp < QSTACK_MAX always: psm_world_set_instances refuses a world whose two depths exceed it)
+                        if (sp < QSTACK_LDS) stack[sp][lane] = second;
+                        else if (sp < QSTACK_MAX) spill[(size_t)(sp - QSTACK_LDS) * spill_stride] = second;
+                        sp++;
+                    }
+                    cur = first;
+                    pop = !(okL || okR);
+                } else {
+                    const uint4* np = (const uint4*)((const char*)q.node32 + ((uint32_t)cur << 5));
+                    const uint4 n0 = np[0], n1 = np[1];
+                    const int lkx = (int)n1.z, lky = (int)n1.w;
+                    bool okL, okR;
+                    float kL, kR;
+                    q.children(n0, n1, okL, okR, kL, kR);
+                    const bool leafL = okL && lkx < 0, leafR = okR && lky < 0;
+                    int t0 = leafL ? ~lkx : (leafR ? ~lky : -1);
+                    int t1 = (leafL && leafR) ? ~lky : -1;
+                    while (t0 >= 0) {
+                        q.leaf(t0);
+                        t0 = t1;
+                        t1 = -1;
+                    }
+                    const bool intL = okL && !leafL, intR = okR && !leafR;
+                    const bool leftFirst = intL && (!intR || kL <= kR);
+                    const int first = leftFirst ? lkx : lky, second = leftFirst ? lky : lkx;
+                    if (intL && intR) {
+                        if (sp < QSTACK_LDS) stack[sp][lane] = second;
+                        else if (sp < QSTACK_MAX) spill[(size_t)(sp - QSTACK_LDS) * spill_stride] = second;
+                        sp++;
+                    }
+                    cur = first;
+                    pop = !(intL || intR);
+                }
+                if (q.done()) break;
+                if (pop) {
+                    if (sp == 0) break;
+                    sp--;
+                    cur = sp < QSTACK_LDS ? stack[sp][lane] : spill[(size_t)(sp - QSTACK_LDS) * spill_stride];
+                }
+            }
+        } while (q.again());
+        if (alive) q.finish(i);
+    }
+}
+
+// the row of instance `in`, by five aligned 16-byte loads; the lane keeps the two pointers its walk needs
+struct RowLoad {
+    const uint32_t* sm;
+    const int32_t* sorted_tri;
+    float m[12];
+};
+template <class Q>
+PSM_D RowLoad load_row(const WorldArgs& w, int in, Q& q) {
+    const uint4* rp = (const uint4*)(w.rows + in);
+    const uint4 a = rp[0], b = rp[1], c = rp[2], d = rp[3], e = rp[4];
+    q.node32 = (const uint4*)(((uint64_t)a.y << 32) | a.x);
+    q.tri48 = (const float4*)(((uint64_t)a.w << 32) | a.z);
+    q.inst = in;
+    RowLoad r;
+    r.sm = (const uint32_t*)(((uint64_t)b.y << 32) | b.x);
+    r.sorted_tri = (const int32_t*)(((uint64_t)b.w << 32) | b.z);
+    r.m[0] = u2f(c.x); r.m[1] = u2f(c.y); r.m[2] = u2f(c.z); r.m[3] = u2f(c.w);
+    r.m[4] = u2f(d.x); r.m[5] = u2f(d.y); r.m[6] = u2f(d.z); r.m[7] = u2f(d.w);
+    r.m[8] = u2f(e.x); r.m[9] = u2f(e.y); r.m[10] = u2f(e.z); r.m[11] = u2f(e.w);
+    return r;
+}
+
+// what finish() needs of the row of instance `in`: the triangles and the pose
+PSM_D const float4* load_pose(const WorldArgs& w, uint32_t in, float* m) {
+    const uint4* rp = (const uint4*)(w.rows + in);
+    const uint4 a = rp[0], c = rp[2], d = rp[3], e = rp[4];
+    m[0] = u2f(c.x); m[1] = u2f(c.y); m[2] = u2f(c.z); m[3] = u2f(c.w);
+    m[4] = u2f(d.x); m[5] = u2f(d.y); m[6] = u2f(d.z); m[7] = u2f(d.w);
+    m[8] = u2f(e.x); m[9] = u2f(e.y); m[10] = u2f(e.z); m[11] = u2f(e.w);
+    return (const float4*)(((uint64_t)a.w << 32) | a.z);
+}
+
+}  // namespace
+
+}  // namespace psm

@@ -36,6 +36,10 @@ Sponza-class scene and the stress scene (STRESS_TRIS triangles, default 10 M): t
 the cell boxes of a 64^3 and a 128^3 grid of the scene's bounds, each alternated A B A B (medians of REPS) with what a caller had
 before them: psm_bvh_within_dev with the cell's half-diagonal as radius (a sphere around the cell: it over-reports); and
 boxCount for ONE box around half the scene (the case an early acceptance of contained subtrees would serve).
+`query_bench.py worldboxes`: the box queries of an instance world (psm_world_box_overlaps_dev / psm_world_box_count_dev /
+psm_world_box_triangles_dev) on the world mode's torus at 256 and 4 096 grid poses: the three queries (triangles at k = 4 and 16)
+over the cell boxes of a 64^3 grid of the world's bounds, each alternated A B A B (medians of REPS) with psm_world_within_dev at
+the cell's half-diagonal -- the stand-in a caller had --; and countInBox for ONE box around half the world.
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -831,6 +835,82 @@ def boxes():
     print(json.dumps(out))
 
 
+def worldboxes():
+    lib = psm.lib()
+    ctx = psm.Context(0)
+    tor = torus(48, 24, 0.7, 0.25)
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(tor.shape[0])
+    th.loadTriangles(tor)
+    th.build()
+    rng = np.random.RandomState(1)
+    g = 64
+    n = g ** 3
+    idx = np.stack(np.meshgrid(np.arange(g), np.arange(g), np.arange(g), indexing="ij"), axis=-1).reshape(-1, 3)
+    out = {"mode": "worldboxes", "grid": g, "queries": n, "torus_triangles": int(tor.shape[0]), "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+    hs = [ctx.buf_alloc(x) for x in (32 * n, 16 * n, n, 4 * n, 4 * 16 * n, 4 * 16 * n)]
+    p_box, p_pts, p_flag, p_count, p_rows, p_inst = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in hs)
+    size = C.c_size_t(n)
+    for poses_n in (256, 4096):
+        side = int(np.ceil(np.sqrt(poses_n)))      # the world mode's grid of poses, each turned about a random axis
+        poses = np.zeros((poses_n, 3, 4), np.float32)
+        k_ = np.arange(poses_n)
+        for j in range(poses_n):
+            q, r = np.linalg.qr(rng.normal(size=(3, 3)))
+            poses[j, :, :3] = q * np.sign(np.diag(r))
+        poses[:, 0, 3], poses[:, 1, 3] = 2.5 * (k_ % side), 2.5 * (k_ // side)
+        lo = np.array([-1.25, -1.25, -1.25])
+        hi = np.array([2.5 * (side - 1) + 1.25, 2.5 * ((poses_n - 1) // side) + 1.25, 1.25])
+        cell = (hi - lo) / g
+        b = np.zeros((n, 8), np.float32)
+        b[:, 0:3], b[:, 4:7] = lo + idx * cell, lo + (idx + 1) * cell
+        q = np.zeros((n, 4), np.float32)
+        q[:, 0:3], q[:, 3] = lo + (idx + 0.5) * cell, 0.5 * float(np.linalg.norm(cell))
+        ctx.buf_upload(hs[0], b)
+        ctx.buf_upload(hs[1], q)
+        wd = psm.InstanceWorld(ctx, [(th, m) for m in poses])
+        w = wd._w
+
+        def within():
+            ctx.check(lib.psm_world_within_dev(w, p_pts, size, p_flag), "psm_world_within_dev")
+
+        def overlaps():
+            ctx.check(lib.psm_world_box_overlaps_dev(w, p_box, size, p_flag), "psm_world_box_overlaps_dev")
+
+        def count():
+            ctx.check(lib.psm_world_box_count_dev(w, p_box, size, p_count), "psm_world_box_count_dev")
+
+        def triangles(k):
+            return lambda: ctx.check(lib.psm_world_box_triangles_dev(w, p_box, size, C.c_uint32(k), p_rows, p_inst, p_count),
+                                     "psm_world_box_triangles_dev")
+        key = "poses%d_" % poses_n
+        for name, fn in (("overlaps", overlaps), ("count", count), ("triangles_k4", triangles(4)), ("triangles_k16", triangles(16))):
+            out[key + name + "_ms"], out[key + "within_beside_" + name + "_ms"] = abab(ctx, fn, within)
+        within()
+        sphere = float(ctx.buf_download(hs[2], np.uint8, n).mean())
+        overlaps()
+        out[key + "within_fraction"], out[key + "overlaps_fraction"] = round(sphere, 4), round(float(ctx.buf_download(hs[2], np.uint8, n).mean()), 4)
+        count()
+        out[key + "mean_count"] = round(float(ctx.buf_download(hs[3], np.uint32, n).mean()), 2)
+        # one box around half the world (the lower half along x)
+        hb, hc = ctx.buf_alloc(32), ctx.buf_alloc(16)
+        one = np.zeros((1, 8), np.float32)
+        one[0, 0:3], one[0, 4:7] = lo, [0.5 * (lo[0] + hi[0]), hi[1], hi[2]]
+        ctx.buf_upload(hb, one)
+        p_b, p_c = C.c_void_p(ctx.buf_ptr(hb)[0]), C.c_void_p(ctx.buf_ptr(hc)[0])
+        out[key + "half_world_count_ms"] = round(median_ms(ctx, lambda: ctx.check(lib.psm_world_box_count_dev(w, p_b, C.c_size_t(1), p_c),
+                                                                                "psm_world_box_count_dev")), 4)
+        out[key + "half_world_count"] = int(ctx.buf_download(hc, np.uint32, 1)[0])
+        ctx.buf_free(hb)
+        ctx.buf_free(hc)
+        wd.close()
+    for h in hs:
+        ctx.buf_free(h)
+    th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def main():
     sc = scenes.sponza_like()
     ctx = psm.Context(0)
@@ -896,4 +976,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes}.get(" ".join(sys.argv[1:]), main)()
