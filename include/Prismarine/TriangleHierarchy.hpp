@@ -68,6 +68,11 @@ namespace NSM {
         int boxOverlaps(const psm_box_query * d_boxes, size_t n, uint8_t * d_hit);
         int boxCount(const psm_box_query * d_boxes, size_t n, uint32_t * d_count);
         int boxTriangles(const psm_box_query * d_boxes, size_t n, uint32_t k, int32_t * d_tris, uint32_t * d_count);
+        // not in the reference: where a sphere that moves along a line first touches the triangles (t = the distance its centre
+        // travels, 0 when it touches where it starts; a miss is {0, 0, +inf, -1}), and whether it touches any within tmax
+        // (psm_bvh_sweep_sphere_dev / psm_bvh_sweep_occluded_dev), stream-ordered on the context; returns the psm_status
+        int sweepSphere(const psm_sweep_query * d_sweeps, size_t n, psm_hit * d_hits);
+        int sweepOccluded(const psm_sweep_query * d_sweeps, size_t n, uint8_t * d_hit);
         psm_bvh * handle() { return bvh; }
     };
 }

@@ -92,6 +92,16 @@ namespace NSM {
         check(rc, "TriangleHierarchy::boxTriangles");
         return rc;
     }
+    inline int TriangleHierarchy::sweepSphere(const psm_sweep_query * d_sweeps, size_t n, psm_hit * d_hits) {
+        const int rc = psm_bvh_sweep_sphere_dev(bvh, d_sweeps, n, d_hits);
+        check(rc, "TriangleHierarchy::sweepSphere");
+        return rc;
+    }
+    inline int TriangleHierarchy::sweepOccluded(const psm_sweep_query * d_sweeps, size_t n, uint8_t * d_hit) {
+        const int rc = psm_bvh_sweep_occluded_dev(bvh, d_sweeps, n, d_hit);
+        check(rc, "TriangleHierarchy::sweepOccluded");
+        return rc;
+    }
     inline void TriangleHierarchy::setBuildGraph(bool enable) { if (bvh) check(psm_bvh_set_build_graph(bvh, enable ? 1 : 0), "TriangleHierarchy::setBuildGraph"); }
     inline void TriangleHierarchy::configureIntersection(bool clearDepth) { (void)clearDepth; }  // ignored by the reference's shaders too
 

@@ -501,6 +501,60 @@ int psm_bvh_box_overlaps_dev(psm_bvh* bvh, const psm_box_query* d_boxes, size_t 
 int psm_bvh_box_count_dev(psm_bvh* bvh, const psm_box_query* d_boxes, size_t n, uint32_t* d_count);
 int psm_bvh_box_triangles_dev(psm_bvh* bvh, const psm_box_query* d_boxes, size_t n, uint32_t k, int32_t* d_tris, uint32_t* d_count);
 
+/* sweep queries against a built hierarchy (new; no reference counterpart): where a sphere that moves along a
+ * line first touches the hierarchy's triangles, and on which -- the sphere cast of a collision library -- on the same leaves,
+ * stack, context and checks as the queries above. Flat scenes, instanced lists and worlds have none. Semantics:
+ *   - a query {origin, radius, direct, tmax}: direct is normalised with normalize3 exactly as a query ray's, t is the distance
+ *     along that unit direction d, and the sphere of radius `radius` = r has its centre at c(t) = origin + t d for t in [0, tmax]
+ *   - a query is valid iff origin and the normalised direction are finite (a zero direction is not), 0 <= r < +inf and
+ *     tmax >= 0 (NaN fails both); tmax = +inf is no limit. An invalid query is a miss, never an error. r = 0 is valid: a ray
+ *     test with closed edges and none of the ray queries' 1e-5 tolerance, not promised bit-equal to psm_bvh_intersect_dev
+ *   - the candidates are the hierarchy's leaves (PSM_BVH_LEAF_TRI) by load-order triangle id, a triangle read as the build
+ *     stores it: v0, e1 = v1 - v0, e2 = v2 - v0
+ *   - a candidate's first contact is sweep_tri(v0, e1, e2, o, d, r, tmax): the smallest t >= 0 at which the sphere touches the
+ *     triangle, in float32, one fixed operation order, one rounding per operation, nothing fused, division and sqrtf correctly
+ *     rounded (psm_sweep_dev.h; tests/sweep_query_model.py writes it once over a float type and is its canonical statement).
+ *     dot(a, b) = (a0 b0 + a1 b1) + a2 b2; a + s b and a - s b per component, the product first; rr = r r; dd = dot(d, d).
+ *       1. the start: d2 = closest_on_tri(v0, e1, e2, o), the point queries' function bit for bit. If sqrtf(d2) <= r the contact
+ *          is t = 0 with the closest point's (u, v): a triangle psm_bvh_within_dev (o, r) counts has t == 0.
+ *          Otherwise the smallest valid t of the seven features below, in this order, a later one replacing an earlier
+ *          one only when its t is smaller (a tie keeps the earlier: face, v0, v1, v2, edge v0 v1, edge v0 v2, edge v1 v2).
+ *          started(t) = t > 0 ? t : 0: a feature the sphere moves towards and already reaches at the start is a contact at
+ *          t = 0. In real numbers the start test has then fired; in float32 the start test and the features round
+ *          independently, and a sphere that rests on a triangle within rounding of r -- where every sweep leaves it -- and moves
+ *          into it is found by one or the other, never by neither. So t == 0 without psm_bvh_within_dev counting the triangle
+ *          happens only within rounding of dist(o, triangle) = r, for a sphere that is moving in
+ *       2. the face, only under closest_on_tri's sliver rule det = aa bb - ab ab > 2^-16 (aa bb) (aa = dot(e1, e1), ab =
+ *          dot(e1, e2), bb = dot(e2, e2)): n = cross3(e1, e2), w0 = o - v0, s0 = dot(n, w0), sd = dot(n, d), rn = r sqrtf(dot(n,
+ *          n)); needs s0 sd < 0; t = started(((s0 > 0 ? rn : -rn) - s0) / sd); w = w0 + t d, p1 = dot(w, e1), p2 =
+ *          dot(w, e2), u = (bb p1 - ab p2) / det, v = (aa p2 - ab p1) / det; counts iff u >= 0, v >= 0, u + v <= 1 (closed, no
+ *          tolerance)
+ *       3. the vertices q = v0, v0 + e1, v0 + e2 by closest approach: m = o - q, t0 = -dot(m, d) / dd, l = m + t0 d, qq = rr -
+ *          dot(l, l); needs t0 > 0 and qq >= 0; t = started(t0 - sqrtf(qq / dd)); (u, v) = (0, 0), (1, 0), (0, 1)
+ *       4. the edges (q, e) = (v0, e1), (v0, e2), (v0 + e1, e2 - e1), the axial part removed first: ee = dot(e, e) > 0, m = o - q,
+ *          sm = dot(m, e) / ee, sn = dot(d, e) / ee, mp = m - sm e, dp = d - sn e, a = dot(dp, dp); needs a > 0, t0 = -dot(mp, dp)
+ *          / a > 0 and qq = rr - dot(l, l) >= 0 with l = mp + t0 dp; t = started(t0 - sqrtf(qq / a)); counts iff s = sm + t sn lies in
+ *          [0, 1]; (u, v) = (s, 0), (0, s), (1 - s, s)
+ *       The contact counts iff t <= tmax (closed: a sweep that ends exactly at contact hits). The closest-approach form, not
+ *       the textbook quadratic, because the quadratic's constant term cancels in float32 (DESIGN.md 4.17 has the figures).
+ *       Degenerate triangles get a finite, deterministic answer: a zero-length edge is skipped and its vertices decide, a
+ *       sliver has no face and its edges and vertices decide -- near the sliver threshold the face's barycentric noise
+ *       (closest_on_tri) can move a contact by ~2^-7 of the longest edge
+ *   - sweep sphere: d_hits[i] = {u, v, t, tri} of the smallest t over all candidates, on a bit-equal t the lowest triangle id:
+ *     nothing depends on the traversal order. (u, v) is the contact point on the triangle, (v0 + u e1) + v e2; the contact
+ *     normal is (c(t) - contact) / r. A miss is {0, 0, +inf, -1}
+ *   - sweep occluded: d_hit[i] = 1 iff some candidate has a contact within [0, tmax], else 0 (uint8_t, torch.bool-compatible):
+ *     the predicate isfinite(t) of the first call; the walk ends at the first such candidate
+ *   - d_sweeps and d_hits 16-byte aligned; everything else (NULL checks, n = 0, PSM_ERR_STATE before the first build -- "sweep
+ *     query before build" --, PSM_ERR_CAPACITY for a hierarchy deeper than the query stack, stream order, capture, refit, 0 / 1
+ *     leaves) as for the ray queries. A refused call launches nothing and leaves the output buffers untouched */
+typedef struct {
+    float origin[3], radius;
+    float direct[3], tmax;
+} psm_sweep_query; /* 32 B: two 16-byte loads, where a query ray's are */
+int psm_bvh_sweep_sphere_dev(psm_bvh* bvh, const psm_sweep_query* d_sweeps, size_t n, psm_hit* d_hits);
+int psm_bvh_sweep_occluded_dev(psm_bvh* bvh, const psm_sweep_query* d_sweeps, size_t n, uint8_t* d_hit);
+
 /* scene queries: the seven queries above over several hierarchies at once (new; no reference counterpart).
  * A scene is an ordered list of G built hierarchies of ONE context, 1 <= G <= PSM_SCENE_MAX_GEOMETRIES, passed per call (there
  * is no scene handle). The limit is 32 because the per-geometry table then travels with the launch (32 x four pointers = 1 KB

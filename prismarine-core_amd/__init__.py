@@ -29,6 +29,7 @@ EXPORTS = [
     "psm_bvh_closest_point_dev", "psm_bvh_within_dev", "psm_bvh_count_hits_dev", "psm_bvh_inside_dev", "psm_bvh_signed_distance_dev",
     "psm_bvh_first_hits_dev", "psm_bvh_nearest_dev",
     "psm_bvh_box_overlaps_dev", "psm_bvh_box_count_dev", "psm_bvh_box_triangles_dev",
+    "psm_bvh_sweep_sphere_dev", "psm_bvh_sweep_occluded_dev",
     "psm_scene_intersect_dev", "psm_scene_occluded_dev", "psm_scene_count_hits_dev", "psm_scene_closest_point_dev", "psm_scene_within_dev",
     "psm_scene_inside_dev", "psm_scene_signed_distance_dev",
     "psm_instances_intersect_dev", "psm_instances_occluded_dev", "psm_instances_count_hits_dev", "psm_instances_closest_point_dev",
@@ -61,6 +62,7 @@ HIT_DT = np.dtype([("u", "<f4"), ("v", "<f4"), ("t", "<f4"), ("tri", "<i4")])
 QUERY_RAY_DT = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direct", "<f4", 3), ("tmax", "<f4")])   # psm_query_ray
 POINT_QUERY_DT = np.dtype([("p", "<f4", 3), ("rmax", "<f4")])   # psm_point_query
 BOX_QUERY_DT = np.dtype([("lo", "<f4", 3), ("pad0", "<f4"), ("hi", "<f4", 3), ("pad1", "<f4")])   # psm_box_query
+SWEEP_QUERY_DT = np.dtype([("origin", "<f4", 3), ("radius", "<f4"), ("direct", "<f4", 3), ("tmax", "<f4")])   # psm_sweep_query
 QUERY_K_MAX = 16   # psm_hip.h PSM_QUERY_K_MAX
 SCENE_MAX_GEOMETRIES = 32   # psm_hip.h PSM_SCENE_MAX_GEOMETRIES
 WORLD_MAX_INSTANCES = 65536   # psm_hip.h PSM_WORLD_MAX_INSTANCES
@@ -462,6 +464,24 @@ class TriangleHierarchy:
         boxes[:, 0:3], boxes[:, 4:7] = a, b
         return self._launch_np(boxes, out, name, *extra)
 
+    def sweepSphere(self, origins, directions, radius, tmax=np.inf):
+        """Where a sphere of `radius` that moves from each origin along its direction first touches a triangle within the distance
+        tmax (psm_bvh_sweep_sphere_dev; not in the reference): origins, directions [n, 3] (any length; normalised inside, t is
+        the distance along the unit direction), radius and tmax scalars or per-sweep [n]. Returns QueryHits: t = the distance the
+        centre travels to the first contact (0: the sphere touches where it starts -- whenever within(origin, radius) says so,
+        and for a sphere within rounding of its radius of a triangle it is moving into), tri the triangle, and u, v with the contact point = (v0 + u e1) + v e2 (tri = -1, t = +inf: no contact); the
+        contact normal is (origin + t d - contact) / radius. A non-finite origin or direction, a zero direction, a radius that is
+        negative, NaN or infinite and a negative or NaN tmax miss. numpy in: numpy out; torch device tensors in: torch tensors
+        out on the same device, ordered against torch's current stream without synchronising (as intersect()). QueryScene,
+        InstancedScene and InstanceWorld have no sweeps."""
+        return self._query(origins, directions, radius, tmax, "hits", "psm_bvh_sweep_sphere_dev")
+
+    def sweepOccluded(self, origins, directions, radius, tmax=np.inf):
+        """Whether the swept sphere touches any triangle within tmax (psm_bvh_sweep_occluded_dev; not in the reference): the
+        predicate isfinite(sweepSphere().t), the walk ending at the first contact found. A bool array / tensor. Arguments and
+        placement as sweepSphere()."""
+        return self._query(origins, directions, radius, tmax, "bool", "psm_bvh_sweep_occluded_dev")
+
     def _query(self, origins, directions, tmin, tmax, out, name=None, k=None):
         name = name or _RAY_QUERIES[out]
         extra = () if k is None else (C.c_uint32(_k(k, name)),)
@@ -725,7 +745,8 @@ def _query_torch(th, origins, directions, tmin, tmax, out, name, *extra):
     import torch
     dev = origins.device
     if dev.type != "cuda" or directions.device != dev:
-        raise ValueError("intersect / occluded: origins and directions must be tensors on the context's device")
+        raise ValueError("%s: origins and directions must be tensors on the context's device"
+                         % ("sweepSphere / sweepOccluded" if "sweep" in name else "intersect / occluded"))
     o = origins.reshape(-1, 3)
     d = directions.reshape(-1, 3)
     n = o.shape[0]

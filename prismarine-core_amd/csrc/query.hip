@@ -835,7 +835,9 @@ const QueryDesc QUERY_DESC[] = {{"psm_bvh_intersect_dev", "rays", "hits", 16, fa
                                 {"psm_bvh_nearest_dev", "points", "hits", 16, true},
                                 {"psm_bvh_box_overlaps_dev", "boxes", nullptr, 1, false},
                                 {"psm_bvh_box_count_dev", "boxes", "counts", 4, false},
-                                {"psm_bvh_box_triangles_dev", "boxes", "tris", 4, false}};
+                                {"psm_bvh_box_triangles_dev", "boxes", "tris", 4, false},
+                                {"psm_bvh_sweep_sphere_dev", "sweeps", "hits", 16, false},
+                                {"psm_bvh_sweep_occluded_dev", "sweeps", nullptr, 1, false}};
 
 // The data checks every query shares, under the entry point's name: in / out must be non-NULL, in 16-byte aligned, out as its
 // kind asks (a psm_hit 16 bytes, a count 4); samples (the inside kinds only): 1, 3 or 5; the k-best kinds' k travels as
@@ -908,19 +910,22 @@ bool too_deep(const psm_bvh* b) { return depth_bound(b) > QSTACK_MAX; }
 
 // A query of one hierarchy: n == 0 is answered before anything else is looked at; then the data, the state, the depth.
 // The k-best kinds (kbest.hip) come through here too: samples is their k, d_out their [n][k] records, d_count their counts;
-// and the box kinds (box.hip): d_in the boxes, and for the triangles query samples = k, d_out the [n][k] ids, d_count the counts.
+// and the box kinds (box.hip): d_in the boxes, and for the triangles query samples = k, d_out the [n][k] ids, d_count the counts;
+// and the sweep kinds (sweep.hip): d_in the sweeps.
 int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, void* d_out, uint32_t samples = 0, uint32_t* d_count = nullptr) {
     if (!b) return PSM_ERR_INVALID;
     if (n == 0) return PSM_OK;
     psm_ctx* c = b->ctx;
-    const bool points = QUERY_DESC[kind].points, kbest = kind == Q_FIRST_HITS || kind == Q_NEAREST, box = kind >= Q_BOX_ANY;
+    const bool points = QUERY_DESC[kind].points, kbest = kind == Q_FIRST_HITS || kind == Q_NEAREST;
+    const bool box = kind >= Q_BOX_ANY && kind <= Q_BOX_TRIS, sweep = kind == Q_SWEEP || kind == Q_SWEEP_ANY;
     const bool counted = kbest || kind == Q_BOX_TRIS;
     int rc = check_data(c, QUERY_DESC[kind].name, counted ? "counts" : nullptr, kind, d_in, d_out, (const int32_t*)d_count, samples);
     if (rc != PSM_OK) return rc;
     if (!b->built)
-        return set_err(c, PSM_ERR_STATE, box ? "box query before build" : points ? "point query before build" : "ray query before build");
+        return set_err(c, PSM_ERR_STATE, box ? "box query before build" : sweep ? "sweep query before build" : points ? "point query before build" : "ray query before build");
     if (too_deep(b))
         return set_err(c, PSM_ERR_CAPACITY, box      ? "box query: hierarchy deeper than the query stack"
+                                            : sweep  ? "sweep query: hierarchy deeper than the query stack"
                                             : points ? "point query: hierarchy deeper than the query stack"
                                                      : "ray query: hierarchy deeper than the query stack");
     QueryArgs qa = {};
@@ -936,6 +941,7 @@ int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, void* d_out, u
         if (kind == Q_BOX_TRIS) qa.count = d_count;
         return box_launch(c, (int)kind - (int)Q_BOX_ANY, grid, qa);
     }
+    if (sweep) return sweep_launch(c, kind == Q_SWEEP_ANY, grid, qa);   // (sweep.hip)
     return launch(c, BVH_KERNELS, kind, grid, qa);
 }
 
@@ -1100,6 +1106,14 @@ int psm_bvh_box_count_dev(psm_bvh* bvh, const psm_box_query* d_boxes, size_t n, 
 
 int psm_bvh_box_triangles_dev(psm_bvh* bvh, const psm_box_query* d_boxes, size_t n, uint32_t k, int32_t* d_tris, uint32_t* d_count) {
     return psm::query(bvh, psm::Q_BOX_TRIS, d_boxes, n, d_tris, k, d_count);
+}
+
+int psm_bvh_sweep_sphere_dev(psm_bvh* bvh, const psm_sweep_query* d_sweeps, size_t n, psm_hit* d_hits) {
+    return psm::query(bvh, psm::Q_SWEEP, d_sweeps, n, d_hits);
+}
+
+int psm_bvh_sweep_occluded_dev(psm_bvh* bvh, const psm_sweep_query* d_sweeps, size_t n, uint8_t* d_hit) {
+    return psm::query(bvh, psm::Q_SWEEP_ANY, d_sweeps, n, d_hit);
 }
 
 int psm_scene_intersect_dev(psm_bvh* const* geoms, uint32_t count, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits, int32_t* d_geom) {

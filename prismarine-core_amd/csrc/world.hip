@@ -920,7 +920,7 @@ int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* 
     if (n == 0) return PSM_OK;
     psm_ctx* c = w->ctx;
     const char* name = WORLD_NAME[kind];
-    const bool box = kind >= Q_BOX_ANY;
+    const bool box = kind >= Q_BOX_ANY && kind <= Q_BOX_TRIS;   // (a sweep never comes here)
     const bool kbest = kind == Q_FIRST_HITS || kind == Q_NEAREST || kind == Q_BOX_TRIS;   // (the kinds with rows and counts)
     int rc = kbest ? check_data(c, name, "counts", kind, d_in, d_out, (const int32_t*)d_count, samples)
                    : check_data(c, name, "inst", kind, d_in, d_out, d_inst, samples);

@@ -40,6 +40,10 @@ boxCount for ONE box around half the scene (the case an early acceptance of cont
 psm_world_box_triangles_dev) on the world mode's torus at 256 and 4 096 grid poses: the three queries (triangles at k = 4 and 16)
 over the cell boxes of a 64^3 grid of the world's bounds, each alternated A B A B (medians of REPS) with psm_world_within_dev at
 the cell's half-diagonal -- the stand-in a caller had --; and countInBox for ONE box around half the world.
+`query_bench.py sweeps`: the sphere sweeps (psm_bvh_sweep_sphere_dev / psm_bvh_sweep_occluded_dev) on the Sponza-class scene and
+the stress scene (STRESS_TRIS triangles, default 10 M): SWEEP_N (2 M) sweeps along the camera's primary rays with radii of 0.1 %,
+1 % and 5 % of the scene's diagonal, each alternated A B A B (medians of REPS) with psm_bvh_intersect_dev / psm_bvh_occluded_dev
+on the same rays -- the floor a sweep cannot beat --, and the fractions that touch at all and that touch at t = 0.
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -835,6 +839,67 @@ def boxes():
     print(json.dumps(out))
 
 
+def sweeps():
+    lib = psm.lib()
+    out = {"mode": "sweeps", "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+    stress_tris = int(os.environ.get("STRESS_TRIS", "10000000"))
+    want = int(os.environ.get("SWEEP_N", "2000000"))
+    for scene_name, sc in (("sponza", scenes.sponza_like()), ("stress", scenes.stress(stress_tris))):
+        ctx = psm.Context(0)
+        th = psm.TriangleHierarchy(ctx)
+        th.allocate(sc["tris"].shape[0])
+        th.loadTriangles(sc["tris"], sc["normals"], sc["mats"])
+        th.build()
+        rt = psm.Pipeline(ctx, seed=1000)
+        rt.resizeBuffers(W, H)
+        rt.resize(W, H)
+        cam = scenes.camera_matrices(sc["eye"], sc["view"], W, H)
+        rt.camera_matrices(cam[0], cam[1])
+        prim = rt.download_rays()
+        rt.close()
+        n = min(want, prim.shape[0])
+        pick = np.linspace(0, prim.shape[0] - 1, n).astype(np.int64)     # spread over the image, in order
+        v = sc["tris"].reshape(-1, 3)
+        diag = float(np.linalg.norm(v.max(0).astype(np.float64) - v.min(0).astype(np.float64)))
+        out[scene_name + "_tris"], out[scene_name + "_sweeps"], out[scene_name + "_diagonal"] = int(th.info().leaf_count), n, round(diag, 3)
+        q = np.zeros((n, 8), np.float32)
+        q[:, 0:3], q[:, 4:7], q[:, 7] = prim["origin"][pick], prim["direct"][pick], np.inf
+        hs = [ctx.buf_alloc(x) for x in (32 * n, 32 * n, 16 * n, n)]
+        p_rays, p_sweeps, p_hits, p_flag = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in hs)
+        ctx.buf_upload(hs[0], q)                                         # the rays: tmin = 0 where the sweeps' radius is
+        size = C.c_size_t(n)
+
+        def intersect():
+            ctx.check(lib.psm_bvh_intersect_dev(th._h, p_rays, size, p_hits), "psm_bvh_intersect_dev")
+
+        def occluded():
+            ctx.check(lib.psm_bvh_occluded_dev(th._h, p_rays, size, p_flag), "psm_bvh_occluded_dev")
+
+        def sweep():
+            ctx.check(lib.psm_bvh_sweep_sphere_dev(th._h, p_sweeps, size, p_hits), "psm_bvh_sweep_sphere_dev")
+
+        def sweep_any():
+            ctx.check(lib.psm_bvh_sweep_occluded_dev(th._h, p_sweeps, size, p_flag), "psm_bvh_sweep_occluded_dev")
+        intersect()
+        out[scene_name + "_ray_hit_fraction"] = round(float(np.isfinite(ctx.buf_download(hs[2], np.float32, 4 * n).reshape(n, 4)[:, 2]).mean()), 4)
+        for pct in (0.1, 1.0, 5.0):
+            q[:, 3] = 0.01 * pct * diag
+            ctx.buf_upload(hs[1], q)
+            key = "%s_r%g_" % (scene_name, pct)
+            out[key + "sweep_ms"], out[key + "intersect_ms"] = abab(ctx, sweep, intersect)
+            out[key + "sweep_occluded_ms"], out[key + "occluded_ms"] = abab(ctx, sweep_any, occluded)
+            out[key + "sweep_over_intersect"] = round(out[key + "sweep_ms"] / out[key + "intersect_ms"], 2)
+            out[key + "sweep_occluded_over_occluded"] = round(out[key + "sweep_occluded_ms"] / out[key + "occluded_ms"], 2)
+            sweep()
+            t = ctx.buf_download(hs[2], np.float32, 4 * n).reshape(n, 4)[:, 2]
+            out[key + "hit_fraction"], out[key + "t0_fraction"] = round(float(np.isfinite(t).mean()), 4), round(float((t == 0).mean()), 4)
+        for h in hs:
+            ctx.buf_free(h)
+        th.close()
+        ctx.close()
+    print(json.dumps(out))
+
+
 def worldboxes():
     lib = psm.lib()
     ctx = psm.Context(0)
@@ -976,4 +1041,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps}.get(" ".join(sys.argv[1:]), main)()
