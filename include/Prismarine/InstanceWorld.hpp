@@ -48,5 +48,11 @@ namespace NSM {
         int overlapsBox(const psm_box_query * d_boxes, size_t n, uint8_t * d_hit);
         int countInBox(const psm_box_query * d_boxes, size_t n, uint32_t * d_count);
         int trianglesInBox(const psm_box_query * d_boxes, size_t n, uint32_t k, int32_t * d_tri, int32_t * d_inst, uint32_t * d_count);
+        // where a sphere that moves along each of n WORLD lines first touches a triangle of a posed instance (d_hits: the winning
+        // instance's object-space {u, v, t, tri}, d_inst its index, -1 on a miss; the smallest t, on a bit-equal t the lowest
+        // (inst, tri)), and whether it touches one (psm_world_sweep_sphere_dev / psm_world_sweep_occluded_dev): the sweep is
+        // moved into each instance as a ray is and judged by the single hierarchy's sweep test; the flat lists have no such query
+        int sphereCast(const psm_sweep_query * d_sweeps, size_t n, psm_hit * d_hits, int32_t * d_inst);
+        int sphereCastOccluded(const psm_sweep_query * d_sweeps, size_t n, uint8_t * d_hit);
     };
 }

@@ -81,4 +81,14 @@ namespace NSM {
         check(rc, "InstanceWorld::trianglesInBox");
         return rc;
     }
+    inline int InstanceWorld::sphereCast(const psm_sweep_query * d_sweeps, size_t n, psm_hit * d_hits, int32_t * d_inst) {
+        const int rc = psm_world_sweep_sphere_dev(world, d_sweeps, n, d_hits, d_inst);
+        check(rc, "InstanceWorld::sphereCast");
+        return rc;
+    }
+    inline int InstanceWorld::sphereCastOccluded(const psm_sweep_query * d_sweeps, size_t n, uint8_t * d_hit) {
+        const int rc = psm_world_sweep_occluded_dev(world, d_sweeps, n, d_hit);
+        check(rc, "InstanceWorld::sphereCastOccluded");
+        return rc;
+    }
 }

@@ -503,7 +503,8 @@ int psm_bvh_box_triangles_dev(psm_bvh* bvh, const psm_box_query* d_boxes, size_t
 
 /* sweep queries against a built hierarchy (new; no reference counterpart): where a sphere that moves along a
  * line first touches the hierarchy's triangles, and on which -- the sphere cast of a collision library -- on the same leaves,
- * stack, context and checks as the queries above. Flat scenes, instanced lists and worlds have none. Semantics:
+ * stack, context and checks as the queries above. Flat scenes and instanced lists have none; worlds: below
+ * (psm_world_sweep_*_dev: the sweep in world space). Semantics:
  *   - a query {origin, radius, direct, tmax}: direct is normalised with normalize3 exactly as a query ray's, t is the distance
  *     along that unit direction d, and the sphere of radius `radius` = r has its centre at c(t) = origin + t d for t in [0, tmax]
  *   - a query is valid iff origin and the normalised direction are finite (a zero direction is not), 0 <= r < +inf and
@@ -750,6 +751,35 @@ int psm_world_box_overlaps_dev(psm_world* world, const psm_box_query* d_boxes, s
 int psm_world_box_count_dev(psm_world* world, const psm_box_query* d_boxes, size_t n, uint32_t* d_count);
 int psm_world_box_triangles_dev(psm_world* world, const psm_box_query* d_boxes, size_t n, uint32_t k, int32_t* d_tri, int32_t* d_inst,
                                 uint32_t* d_count);
+
+/* sweep queries over a world (new; no reference counterpart): where a sphere that moves along a line given in
+ * WORLD space first touches a triangle of a posed instance, and whether it touches one, over every instance of a world in one
+ * launch. The answer is exactly the brute force over the ordered instance list, whatever the tree looks like. Flat scenes and
+ * instanced lists (psm_scene_*, psm_instances_*) have no sweep. Semantics:
+ *   - a query is a psm_sweep_query {origin, radius, direct, tmax} in world space, valid under the rule of the sweep queries
+ *     against a built hierarchy: origin finite, normalize3(direct) finite (a zero direction is not), 0 <= radius < +inf,
+ *     tmax >= 0. An invalid query is a miss, never an error
+ *   - per instance with m = world_from_object[12] the query moves as a world ray does: o' = inst_point(m, origin), d' =
+ *     normalize3(inst_rotate(m, direct)) -- the origin and the direction as given, not the normalised world direction -- in
+ *     float32, one rounding per operation; radius and tmax are unchanged, because a pose is rigid. An instance in which o' or d'
+ *     is not finite is skipped
+ *   - the candidates are the pairs (inst, tri), tri a leaf of the instance's hierarchy (PSM_BVH_LEAF_TRI); a candidate's first
+ *     contact is sweep_tri(v0, e1, e2, o', d', radius) of the sweep queries above, unchanged, bit for bit, and counts iff
+ *     t <= tmax (closed)
+ *   - sweep sphere: d_hits[i] = the winning instance's object-space {u, v, t, tri} and d_inst[i] its index in the list: the
+ *     smallest t over all candidates, on a bit-equal t the lexicographically lowest (inst, tri), compared unsigned: coincident
+ *     instances tie to the lowest instance. A miss is {0, 0, +inf, -1} with d_inst[i] = -1. t is the distance the centre
+ *     travels along d' in the instance, equal to the world distance to 1.5e-5 (the pose check); the world contact point is the
+ *     pose of (v0 + u e1) + v e2
+ *   - sweep occluded: d_hit[i] = 1 iff some candidate counts, else 0: the predicate isfinite(t) of the first call
+ *   - carried over: the start test of a candidate is closest_on_tri on the moved origin, the function and the moved point of
+ *     psm_world_within_dev bit for bit, so a pair psm_world_within_dev(origin, radius) counts has t == 0
+ *   - nothing depends on the tree, its prune or the order of the walk
+ *   - d_sweeps and d_hits 16-byte, d_inst 4-byte aligned, none NULL; the stale check, the depth budget, n == 0, stream order
+ *     and capture as for the other world queries; an empty world answers misses / 0 without a query kernel. A refused call
+ *     launches nothing and leaves the output buffers untouched */
+int psm_world_sweep_sphere_dev(psm_world* world, const psm_sweep_query* d_sweeps, size_t n, psm_hit* d_hits, int32_t* d_inst);
+int psm_world_sweep_occluded_dev(psm_world* world, const psm_sweep_query* d_sweeps, size_t n, uint8_t* d_hit);
 
 /* ---------------------------------------------------------------------------------------------
  * several frames in flight (new; DESIGN.md "lanes")

@@ -38,6 +38,7 @@ EXPORTS = [
     "psm_world_intersect_dev", "psm_world_occluded_dev", "psm_world_count_hits_dev", "psm_world_closest_point_dev", "psm_world_within_dev",
     "psm_world_inside_dev", "psm_world_signed_distance_dev", "psm_world_first_hits_dev", "psm_world_nearest_dev",
     "psm_world_box_overlaps_dev", "psm_world_box_count_dev", "psm_world_box_triangles_dev",
+    "psm_world_sweep_sphere_dev", "psm_world_sweep_occluded_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -472,8 +473,9 @@ class TriangleHierarchy:
         and for a sphere within rounding of its radius of a triangle it is moving into), tri the triangle, and u, v with the contact point = (v0 + u e1) + v e2 (tri = -1, t = +inf: no contact); the
         contact normal is (origin + t d - contact) / radius. A non-finite origin or direction, a zero direction, a radius that is
         negative, NaN or infinite and a negative or NaN tmax miss. numpy in: numpy out; torch device tensors in: torch tensors
-        out on the same device, ordered against torch's current stream without synchronising (as intersect()). QueryScene,
-        InstancedScene and InstanceWorld have no sweeps."""
+        out on the same device, ordered against torch's current stream without synchronising (as intersect()). QueryScene
+        and InstancedScene have no sweeps; InstanceWorld has its own (sphereCast / sphereCastOccluded: the sweep in world
+        space)."""
         return self._query(origins, directions, radius, tmax, "hits", "psm_bvh_sweep_sphere_dev")
 
     def sweepOccluded(self, origins, directions, radius, tmax=np.inf):
@@ -917,8 +919,9 @@ class InstanceWorld(QueryScene):
     hierarchies as they are when set: after a member was rebuilt, reloaded or reallocated the next query raises PsmError until
     setInstances() is called again; after a member was REFITTED call refresh(). Methods, arguments and numpy / torch placement:
     QueryScene's; QueryHits.geom is the index of the winning instance. A world also has the k-best queries, firstHits() and
-    nearest(), and the box queries overlapsBox(), countInBox() and trianglesInBox() over world-space boxes, which the flat lists
-    (QueryScene, InstancedScene) have not."""
+    nearest(), the box queries overlapsBox(), countInBox() and trianglesInBox() over world-space boxes, and the sphere sweeps
+    sphereCast() and sphereCastOccluded() along world-space lines, which the flat lists (QueryScene, InstancedScene) have
+    not."""
 
     def __init__(self, ctx, entries, capacity=None):
         self.ctx = ctx
@@ -1016,6 +1019,22 @@ class InstanceWorld(QueryScene):
         return self._box_query(lo, hi, "tris", "psm_bvh_box_triangles_dev", k)
 
     _box_query = TriangleHierarchy._box_query
+
+    def sphereCast(self, origins, directions, radius, tmax=np.inf):
+        """Where a sphere of `radius` that moves from each WORLD origin along its world direction first touches a triangle of
+        some instance within the distance tmax (psm_world_sweep_sphere_dev): origins, directions [n, 3] (any length; normalised
+        inside), radius and tmax scalars or per-sweep [n]. The sweep is moved into each instance as a ray is and judged there by
+        TriangleHierarchy.sweepSphere()'s test, so the answer is exactly the brute force over the ordered instance list: the
+        smallest t, on a bit-equal t the lowest (instance, tri). Returns QueryHits with geom: the winning instance's index and
+        its object-space u, v, t, tri (geom = tri = -1, t = +inf: no contact); t = 0 whenever within(origin, radius) holds.
+        Invalid sweeps miss, as sweepSphere()'s. numpy / torch placement as intersect()."""
+        return self._query(origins, directions, radius, tmax, "hits", "psm_bvh_sweep_sphere_dev")
+
+    def sphereCastOccluded(self, origins, directions, radius, tmax=np.inf):
+        """Whether the swept sphere touches any triangle of any instance within tmax (psm_world_sweep_occluded_dev): the
+        predicate isfinite(sphereCast().t), the walk ending at the first contact found. A bool array / tensor. Arguments and
+        placement as sphereCast()."""
+        return self._query(origins, directions, radius, tmax, "bool", "psm_bvh_sweep_occluded_dev")
 
     def _call(self, name, d_in, n, extra, d_out, d_geom):
         name = name.replace("psm_bvh_", "psm_world_")

@@ -1,4 +1,4 @@
-// psm_sweep_dev.h -- the pieces of the sphere sweep a kernel file shares (sweep.hip; a world file later; include/psm_hip.h "sweep
+// psm_sweep_dev.h -- the pieces of the sphere sweep a kernel file shares (sweep.hip, world_sweep.hip; include/psm_hip.h "sweep
 // queries"): the candidate test sweep_tri with its helpers, and sweep_axis, one axis of the swept sphere in the
 // build's normalised space. sweep_tri_from -- sweep_tri given the closest point of the start, which is closest_on_tri's
 // (psm_query_dev.h, device only) -- also compiles for the host: a stand-alone program defines PSM_SWEEP_FN as a host function's

@@ -1,7 +1,8 @@
-// psm_world_dev.h -- the device pieces the kernel files of a world share (world.hip, world_box.hip): the
-// table row, the node of the tree over the instances, the kernel arguments, the padding and the slacks, the two-level walk, and
-// the loads of a row. Moved here from world.hip as they were; every kernel of world.hip compiles to the same instructions as
-// with the pieces in its own file (tools/kernel_diff.py; the digests of tests/test_world_kbest_cpu.py).
+// psm_world_dev.h -- the device pieces the kernel files of a world share (world.hip, world_box.hip, world_sweep.hip; DESIGN.md
+// 4.11, 4.16, 4.18): the table row, the node of the tree over the instances, the kernel arguments, the padding and the slacks,
+// the two-level walk, the loads of a row, the best record of a world (WorldBest) and a ray in a world (WorldRay). Moved here
+// from world.hip as they were; every kernel of world.hip compiles to the same instructions as with the pieces in its own file
+// (tools/kernel_diff.py; the digests of tests/test_world_query_cpu.py and tests/test_world_kbest_cpu.py).
 #pragma once
 #include "psm_common.h"
 #include "psm_internal.h"
@@ -45,6 +46,10 @@ struct WorldArgs {
 // holds the boxes where a ray's two float4 are, a.samples is the triangles query's k, a.hits its [n][k] int32 triangle rows,
 // a.geom its [n][k] instance rows, a.count the counts
 int world_box_launch(psm_ctx* c, int mode, uint32_t grid, const WorldArgs& a);
+
+// world_sweep.hip: the launch of a world's sweep kernel (any: whether there is a contact; else the first contact) for
+// world.hip's host path; a.rays holds the sweeps (psm_sweep_query) where a ray's two float4 are
+int world_sweep_launch(psm_ctx* c, bool any, uint32_t grid, const WorldArgs& a);
 
 namespace {
 
@@ -183,6 +188,107 @@ PSM_D const float4* load_pose(const WorldArgs& w, uint32_t in, float* m) {
     m[8] = u2f(e.x); m[9] = u2f(e.y); m[10] = u2f(e.z); m[11] = u2f(e.w);
     return (const float4*)(((uint64_t)a.w << 32) | a.z);
 }
+
+// The best record of a world (closest hit and closest point; `best` is t or d2). The tree visits the instances in tree order,
+// so SceneBest's one-key trick does not carry over: a candidate (x, inst, tri) wins iff x < best, or x == best and (inst, tri)
+// is lexicographically lower than the record's (no record: binst = btri = -1, the largest as unsigned). Boxes are kept with <=.
+struct WorldBest {
+    float best, bu, bv;
+    int btri, binst;
+    PSM_D void clear(float bound) {
+        best = bound;
+        bu = 0.f;
+        bv = 0.f;
+        btri = -1;
+        binst = -1;
+    }
+    PSM_D bool wins(float x, int inst, int tri) const {
+        return x < best || (x == best && ((uint32_t)inst < (uint32_t)binst || (inst == binst && (uint32_t)tri < (uint32_t)btri)));
+    }
+    PSM_D void take(float x, float u, float v, int inst, int tri) {
+        best = x;
+        bu = u;
+        bv = v;
+        btri = tri;
+        binst = inst;
+    }
+};
+
+// A ray in a world: the object-space ray of the instance the lane is in (query.hip's SceneRay) and the WORLD ray the top level
+// tests: origin, reciprocal of the unit direction (normalize3 of the direction as given: SceneRay::aim's), the query's pad.
+struct WorldRay {
+    const uint4* node32;
+    const float4* tri48;
+    int inst;
+    v3 o, d;
+    float tmin, tmax;
+    Axis X, Y, Z;
+    v3 wo, wiv;
+    float qpad;
+    bool nocull;   // the world direction is no unit vector (zero, non-finite, overflowed): every box is kept
+
+    PSM_D void world_ray(v3 orig, v3 dir) {
+        wo = orig;
+        const v3 dn = normalize3(dir);
+        nocull = !(finite3(dn) && dot3(dn, dn) > 0.5f);
+        wiv = mk3(1.0f / dn.x, 1.0f / dn.y, 1.0f / dn.z);   // (+-inf for an axis-aligned ray)
+        qpad = WORLD_QSLACK * smaxf(smaxf(pabs(orig.x), pabs(orig.y)), pabs(orig.z));
+    }
+    // The slab test of a world box, grown by qpad. minNum / maxNum: on an axis the ray is parallel to, wiv is
+    // +-inf and a plane distance is -inf, +inf or (the origin exactly in the plane: 0 x inf) NaN, which sminf / smaxf ignore.
+    // "Passes a leaf's box => passes every ancestor's": an inner box is the exact min / max union of leaf boxes, float
+    // subtraction and multiplication by one factor are monotone, so on an axis with a finite wiv an ancestor's interval
+    // contains the leaf's. On a parallel axis a leaf passes only with its origin strictly between the grown planes (-inf, +inf:
+    // no constraint) -- a leaf box has lo < hi on every axis (WORLD_FLOOR), so one NaN always comes with an infinity of the
+    // failing sign, and two NaN never -- and strictly between a leaf's planes is strictly between every ancestor's.
+    PSM_D void slab(float lx, float ly, float lz, float hx, float hy, float hz, float& tNear, float& tFar) const {
+        const float ax = ((lx - qpad) - wo.x) * wiv.x, bx = ((hx + qpad) - wo.x) * wiv.x;
+        const float ay = ((ly - qpad) - wo.y) * wiv.y, by = ((hy + qpad) - wo.y) * wiv.y;
+        const float az = ((lz - qpad) - wo.z) * wiv.z, bz = ((hz + qpad) - wo.z) * wiv.z;
+        tNear = smaxf(smaxf(sminf(ax, bx), sminf(ay, by)), sminf(az, bz));
+        tFar = sminf(sminf(smaxf(ax, bx), smaxf(ay, by)), smaxf(az, bz));
+    }
+    // both boxes of a top-level node against [tmin, lim], slackened; written as negations so that a NaN bound keeps the box
+    PSM_D void top_boxes(float4 w0, float4 w1, float4 w2, float lim, bool& okL, bool& okR, float& nL, float& nR) const {
+        float fL, fR;
+        slab(w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, nL, fL);
+        slab(w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, nR, fR);
+        const float hi = lim + WORLD_TSLACK * pabs(lim), lo = tmin - WORLD_TSLACK * pabs(tmin);
+        okL = nocull | (!(nL > fL) & !(nL > hi) & !(fL < lo));
+        okR = nocull | (!(nR > fR) & !(nR > hi) & !(fR < lo));
+    }
+    // enter(): the world ray (orig, dir as given) moved into instance `in` as query.hip's inst_ray moves it, then the axes
+    PSM_D int enter_ray(const WorldArgs& w, int in, v3 orig, v3 dir, const int32_t*& sorted_tri, uint32_t& count) {
+        const RowLoad r = load_row(w, in, *this);
+        o = inst_point(r.m, orig);
+        d = normalize3(inst_rotate(r.m, dir));
+        float M[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) M[k] = u2f(r.sm[SM_M + k]);
+        X = ray_axis(M, 0, o, d);
+        Y = ray_axis(M, 1, o, d);
+        Z = ray_axis(M, 2, o, d);
+        sorted_tri = r.sorted_tri;
+        count = r.sm[SM_COUNT];
+        const int root = (int)r.sm[SM_ROOT];
+        return (finite3(o) && finite3(d)) ? (root >= 0 ? root : -2) : -1;   // -2: valid here, no tree (0 or 1 leaves)
+    }
+    // begin() of the bodies whose query is a ray: the window and the world ray (a dead lane: an empty window)
+    PSM_D void begin_ray(const WorldArgs& w, size_t i, bool al) {
+        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(1.f, 0.f, 0.f, -1.f);
+        if (al) { r0 = w.rays[2 * i]; r1 = w.rays[2 * i + 1]; }
+        tmin = r0.w;
+        tmax = r1.w;
+        world_ray(mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z));
+    }
+    PSM_D void boxes(uint4 n0, uint4 n1, float lim, bool& okL, bool& okR, float& nL, float& nR) const {
+        float fL, fR;
+        psm::slab(X, Y, Z, half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z), nL, fL);
+        psm::slab(X, Y, Z, half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y), nR, fR);
+        okL = (nL <= fL) & (nL <= lim) & (fL >= tmin);
+        okR = (nR <= fR) & (nR <= lim) & (fR >= tmin);
+    }
+};
 
 }  // namespace
 

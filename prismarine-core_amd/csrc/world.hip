@@ -29,114 +29,14 @@
 #include "psm_internal.h"
 #include "psm_query_dev.h"    // the constants, the triangle / box / point tests, inst_point / inst_rotate, INSIDE_DIR
 #include "psm_query_host.h"   // QueryKind, check_data / check_instances, batch_args / launch
-#include "psm_world_dev.h"    // WorldRow / WorldNode / WorldArgs, the WORLD_* constants, world_walk, load_row / load_pose
+#include "psm_world_dev.h"    // WorldRow / WorldNode / WorldArgs, the WORLD_* constants, world_walk, load_row / load_pose,
+                              // WorldBest, WorldRay
 #define PSM_KLIST_FN PSM_D
 #include "psm_world_klist.h"  // WorldKList: the sorted list of the k-best queries (also compiled for the host by a test)
 
 namespace psm {
 
 namespace {
-
-// The best record of a world (closest hit and closest point; `best` is t or d2). The tree visits the instances in tree order,
-// so SceneBest's one-key trick does not carry over: a candidate (x, inst, tri) wins iff x < best, or x == best and (inst, tri)
-// is lexicographically lower than the record's (no record: binst = btri = -1, the largest as unsigned). Boxes are kept with <=.
-struct WorldBest {
-    float best, bu, bv;
-    int btri, binst;
-    PSM_D void clear(float bound) {
-        best = bound;
-        bu = 0.f;
-        bv = 0.f;
-        btri = -1;
-        binst = -1;
-    }
-    PSM_D bool wins(float x, int inst, int tri) const {
-        return x < best || (x == best && ((uint32_t)inst < (uint32_t)binst || (inst == binst && (uint32_t)tri < (uint32_t)btri)));
-    }
-    PSM_D void take(float x, float u, float v, int inst, int tri) {
-        best = x;
-        bu = u;
-        bv = v;
-        btri = tri;
-        binst = inst;
-    }
-};
-
-// A ray in a world: the object-space ray of the instance the lane is in (query.hip's SceneRay) and the WORLD ray the top level
-// tests: origin, reciprocal of the unit direction (normalize3 of the direction as given: SceneRay::aim's), the query's pad.
-struct WorldRay {
-    const uint4* node32;
-    const float4* tri48;
-    int inst;
-    v3 o, d;
-    float tmin, tmax;
-    Axis X, Y, Z;
-    v3 wo, wiv;
-    float qpad;
-    bool nocull;   // the world direction is no unit vector (zero, non-finite, overflowed): every box is kept
-
-    PSM_D void world_ray(v3 orig, v3 dir) {
-        wo = orig;
-        const v3 dn = normalize3(dir);
-        nocull = !(finite3(dn) && dot3(dn, dn) > 0.5f);
-        wiv = mk3(1.0f / dn.x, 1.0f / dn.y, 1.0f / dn.z);   // (+-inf for an axis-aligned ray)
-        qpad = WORLD_QSLACK * smaxf(smaxf(pabs(orig.x), pabs(orig.y)), pabs(orig.z));
-    }
-    // The slab test of a world box, grown by qpad. minNum / maxNum: on an axis the ray is parallel to, wiv is
-    // +-inf and a plane distance is -inf, +inf or (the origin exactly in the plane: 0 x inf) NaN, which sminf / smaxf ignore.
-    // "Passes a leaf's box => passes every ancestor's": an inner box is the exact min / max union of leaf boxes, float
-    // subtraction and multiplication by one factor are monotone, so on an axis with a finite wiv an ancestor's interval
-    // contains the leaf's. On a parallel axis a leaf passes only with its origin strictly between the grown planes (-inf, +inf:
-    // no constraint) -- a leaf box has lo < hi on every axis (WORLD_FLOOR), so one NaN always comes with an infinity of the
-    // failing sign, and two NaN never -- and strictly between a leaf's planes is strictly between every ancestor's.
-    PSM_D void slab(float lx, float ly, float lz, float hx, float hy, float hz, float& tNear, float& tFar) const {
-        const float ax = ((lx - qpad) - wo.x) * wiv.x, bx = ((hx + qpad) - wo.x) * wiv.x;
-        const float ay = ((ly - qpad) - wo.y) * wiv.y, by = ((hy + qpad) - wo.y) * wiv.y;
-        const float az = ((lz - qpad) - wo.z) * wiv.z, bz = ((hz + qpad) - wo.z) * wiv.z;
-        tNear = smaxf(smaxf(sminf(ax, bx), sminf(ay, by)), sminf(az, bz));
-        tFar = sminf(sminf(smaxf(ax, bx), smaxf(ay, by)), smaxf(az, bz));
-    }
-    // both boxes of a top-level node against [tmin, lim], slackened; written as negations so that a NaN bound keeps the box
-    PSM_D void top_boxes(float4 w0, float4 w1, float4 w2, float lim, bool& okL, bool& okR, float& nL, float& nR) const {
-        float fL, fR;
-        slab(w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, nL, fL);
-        slab(w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, nR, fR);
-        const float hi = lim + WORLD_TSLACK * pabs(lim), lo = tmin - WORLD_TSLACK * pabs(tmin);
-        okL = nocull | (!(nL > fL) & !(nL > hi) & !(fL < lo));
-        okR = nocull | (!(nR > fR) & !(nR > hi) & !(fR < lo));
-    }
-    // enter(): the world ray (orig, dir as given) moved into instance `in` as query.hip's inst_ray moves it, then the axes
-    PSM_D int enter_ray(const WorldArgs& w, int in, v3 orig, v3 dir, const int32_t*& sorted_tri, uint32_t& count) {
-        const RowLoad r = load_row(w, in, *this);
-        o = inst_point(r.m, orig);
-        d = normalize3(inst_rotate(r.m, dir));
-        float M[16];
-#pragma unroll
-        for (int k = 0; k < 16; k++) M[k] = u2f(r.sm[SM_M + k]);
-        X = ray_axis(M, 0, o, d);
-        Y = ray_axis(M, 1, o, d);
-        Z = ray_axis(M, 2, o, d);
-        sorted_tri = r.sorted_tri;
-        count = r.sm[SM_COUNT];
-        const int root = (int)r.sm[SM_ROOT];
-        return (finite3(o) && finite3(d)) ? (root >= 0 ? root : -2) : -1;   // -2: valid here, no tree (0 or 1 leaves)
-    }
-    // begin() of the bodies whose query is a ray: the window and the world ray (a dead lane: an empty window)
-    PSM_D void begin_ray(const WorldArgs& w, size_t i, bool al) {
-        float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = make_float4(1.f, 0.f, 0.f, -1.f);
-        if (al) { r0 = w.rays[2 * i]; r1 = w.rays[2 * i + 1]; }
-        tmin = r0.w;
-        tmax = r1.w;
-        world_ray(mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z));
-    }
-    PSM_D void boxes(uint4 n0, uint4 n1, float lim, bool& okL, bool& okR, float& nL, float& nR) const {
-        float fL, fR;
-        psm::slab(X, Y, Z, half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z), nL, fL);
-        psm::slab(X, Y, Z, half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y), nR, fR);
-        okL = (nL <= fL) & (nL <= lim) & (fL >= tmin);
-        okR = (nR <= fR) & (nR <= lim) & (fR >= tmin);
-    }
-};
 
 // closest hit (ANY = false) and any hit (ANY = true)
 template <bool ANY>
@@ -821,10 +721,11 @@ struct psm_world {
 namespace psm {
 namespace {
 
-const char* const WORLD_NAME[12] = {"psm_world_intersect_dev", "psm_world_occluded_dev", "psm_world_closest_point_dev",
+const char* const WORLD_NAME[14] = {"psm_world_intersect_dev", "psm_world_occluded_dev", "psm_world_closest_point_dev",
                                     "psm_world_within_dev", "psm_world_count_hits_dev", "psm_world_inside_dev",
                                     "psm_world_signed_distance_dev", "psm_world_first_hits_dev", "psm_world_nearest_dev",
-                                    "psm_world_box_overlaps_dev", "psm_world_box_count_dev", "psm_world_box_triangles_dev"};
+                                    "psm_world_box_overlaps_dev", "psm_world_box_count_dev", "psm_world_box_triangles_dev",
+                                    "psm_world_sweep_sphere_dev", "psm_world_sweep_occluded_dev"};
 const Kernels<WorldArgs> WORLD_KERNELS = {{world_query_closest, world_query_any, world_query_point, world_query_within,
                                            world_query_count, world_query_inside, world_query_sign}};
 
@@ -913,14 +814,15 @@ int world_upload_and_build(psm_world* w, const char* name) {
 // k-best kinds come through here too: samples is their k, d_out and d_inst their [n][k] rows, d_count their counts (which go
 // through check_data's index slot as "counts", as in query.hip's query(); d_inst is then checked here). And the box kinds
 // (world_box.hip): d_in the world boxes; the triangles query as a k-best kind with int32 rows: d_out the [n][k] triangles,
-// d_inst the [n][k] instances, d_count the counts
+// d_inst the [n][k] instances, d_count the counts. And the sweep kinds (world_sweep.hip): d_in the sweeps, a 16-byte record and
+// d_inst, or a byte, as the closest-hit and the any-hit kinds
 int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_inst, uint32_t samples = 0,
                 uint32_t* d_count = nullptr) {
     if (!w) return PSM_ERR_INVALID;
     if (n == 0) return PSM_OK;
     psm_ctx* c = w->ctx;
     const char* name = WORLD_NAME[kind];
-    const bool box = kind >= Q_BOX_ANY && kind <= Q_BOX_TRIS;   // (a sweep never comes here)
+    const bool box = kind >= Q_BOX_ANY && kind <= Q_BOX_TRIS, sweep = kind == Q_SWEEP || kind == Q_SWEEP_ANY;
     const bool kbest = kind == Q_FIRST_HITS || kind == Q_NEAREST || kind == Q_BOX_TRIS;   // (the kinds with rows and counts)
     int rc = kbest ? check_data(c, name, "counts", kind, d_in, d_out, (const int32_t*)d_count, samples)
                    : check_data(c, name, "inst", kind, d_in, d_out, d_inst, samples);
@@ -956,6 +858,7 @@ int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* 
         if (kind == Q_BOX_TRIS) a.count = d_count;
         return world_box_launch(c, (int)kind - (int)Q_BOX_ANY, grid, a);
     }
+    if (sweep) return world_sweep_launch(c, kind == Q_SWEEP_ANY, grid, a);   // (world_sweep.hip)
     if (kbest) {   // the list: k x 64 x (8 + 4) B of dynamic LDS per wave, beside the stack
         a.count = d_count;
         const size_t lds = (size_t)samples * QUERY_BLOCK * (sizeof(uint2) + sizeof(uint32_t));
@@ -1119,4 +1022,10 @@ int psm_world_box_count_dev(psm_world* w, const psm_box_query* d_boxes, size_t n
 int psm_world_box_triangles_dev(psm_world* w, const psm_box_query* d_boxes, size_t n, uint32_t k, int32_t* d_tri, int32_t* d_inst,
                                 uint32_t* d_count) {
     return psm::world_query(w, psm::Q_BOX_TRIS, d_boxes, n, d_tri, d_inst, k, d_count);
+}
+int psm_world_sweep_sphere_dev(psm_world* w, const psm_sweep_query* d_sweeps, size_t n, psm_hit* d_hits, int32_t* d_inst) {
+    return psm::world_query(w, psm::Q_SWEEP, d_sweeps, n, d_hits, d_inst);
+}
+int psm_world_sweep_occluded_dev(psm_world* w, const psm_sweep_query* d_sweeps, size_t n, uint8_t* d_hit) {
+    return psm::world_query(w, psm::Q_SWEEP_ANY, d_sweeps, n, d_hit, nullptr);
 }

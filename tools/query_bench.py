@@ -40,6 +40,11 @@ boxCount for ONE box around half the scene (the case an early acceptance of cont
 psm_world_box_triangles_dev) on the world mode's torus at 256 and 4 096 grid poses: the three queries (triangles at k = 4 and 16)
 over the cell boxes of a 64^3 grid of the world's bounds, each alternated A B A B (medians of REPS) with psm_world_within_dev at
 the cell's half-diagonal -- the stand-in a caller had --; and countInBox for ONE box around half the world.
+`query_bench.py worldsweeps`: the sphere sweeps of an instance world (psm_world_sweep_sphere_dev / psm_world_sweep_occluded_dev) on
+the worldboxes mode's world, the torus at 256 and 4 096 turned grid poses: WORLD_SWEEP_N (262 144) sweeps along rays through the
+world with radii of 0.1 %, 1 % and 5 % of the world's diagonal, alternated A B A B with the world's intersect / occluded on the same
+rays; the fraction that touches and the fraction that touches at t = 0. No ratio is fixed in advance.
+
 `query_bench.py sweeps`: the sphere sweeps (psm_bvh_sweep_sphere_dev / psm_bvh_sweep_occluded_dev) on the Sponza-class scene and
 the stress scene (STRESS_TRIS triangles, default 10 M): SWEEP_N (2 M) sweeps along the camera's primary rays with radii of 0.1 %,
 1 % and 5 % of the scene's diagonal, each alternated A B A B (medians of REPS) with psm_bvh_intersect_dev / psm_bvh_occluded_dev
@@ -976,6 +981,75 @@ def worldboxes():
     print(json.dumps(out))
 
 
+def worldsweeps():
+    lib = psm.lib()
+    ctx = psm.Context(0)
+    tor = torus(48, 24, 0.7, 0.25)
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(tor.shape[0])
+    th.loadTriangles(tor)
+    th.build()
+    rng = np.random.RandomState(1)
+    n = int(os.environ.get("WORLD_SWEEP_N", "262144"))
+    out = {"mode": "worldsweeps", "queries": n, "torus_triangles": int(tor.shape[0]), "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+    hs = [ctx.buf_alloc(x) for x in (32 * n, 32 * n, 16 * n, 4 * n, n)]
+    p_rays, p_sweeps, p_hits, p_inst, p_flag = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in hs)
+    size = C.c_size_t(n)
+    for poses_n in (256, 4096):
+        side = int(np.ceil(np.sqrt(poses_n)))      # the worldboxes mode's world: a grid of poses, each turned about a random axis
+        poses = np.zeros((poses_n, 3, 4), np.float32)
+        k_ = np.arange(poses_n)
+        for j in range(poses_n):
+            q, r = np.linalg.qr(rng.normal(size=(3, 3)))
+            poses[j, :, :3] = q * np.sign(np.diag(r))
+        poses[:, 0, 3], poses[:, 1, 3] = 2.5 * (k_ % side), 2.5 * (k_ // side)
+        lo = np.array([-1.25, -1.25, -1.25])
+        hi = np.array([2.5 * (side - 1) + 1.25, 2.5 * ((poses_n - 1) // side) + 1.25, 1.25])
+        diag = float(np.linalg.norm(hi - lo))
+        # rays through the world: from a point of its box grown by a fifth towards a point inside it
+        grow = 0.2 * (hi - lo)
+        start = rng.uniform(lo - grow, hi + grow, (n, 3))
+        aim = rng.uniform(lo, hi, (n, 3))
+        q = np.zeros((n, 8), np.float32)
+        q[:, 0:3], q[:, 4:7], q[:, 7] = start, aim - start, np.inf
+        ctx.buf_upload(hs[0], q)                   # the rays: tmin = 0 where the sweeps' radius is
+        wd = psm.InstanceWorld(ctx, [(th, m) for m in poses])
+        w = wd._w
+
+        def intersect():
+            ctx.check(lib.psm_world_intersect_dev(w, p_rays, size, p_hits, p_inst), "psm_world_intersect_dev")
+
+        def occluded():
+            ctx.check(lib.psm_world_occluded_dev(w, p_rays, size, p_flag), "psm_world_occluded_dev")
+
+        def sweep():
+            ctx.check(lib.psm_world_sweep_sphere_dev(w, p_sweeps, size, p_hits, p_inst), "psm_world_sweep_sphere_dev")
+
+        def sweep_any():
+            ctx.check(lib.psm_world_sweep_occluded_dev(w, p_sweeps, size, p_flag), "psm_world_sweep_occluded_dev")
+        key = "poses%d_" % poses_n
+        out[key + "diagonal"] = round(diag, 3)
+        intersect()
+        out[key + "ray_hit_fraction"] = round(float(np.isfinite(ctx.buf_download(hs[2], np.float32, 4 * n).reshape(n, 4)[:, 2]).mean()), 4)
+        for pct in (0.1, 1.0, 5.0):
+            q[:, 3] = 0.01 * pct * diag
+            ctx.buf_upload(hs[1], q)
+            kr = "%sr%g_" % (key, pct)
+            out[kr + "sweep_ms"], out[kr + "intersect_ms"] = abab(ctx, sweep, intersect)
+            out[kr + "sweep_occluded_ms"], out[kr + "occluded_ms"] = abab(ctx, sweep_any, occluded)
+            out[kr + "sweep_over_intersect"] = round(out[kr + "sweep_ms"] / out[kr + "intersect_ms"], 2)
+            out[kr + "sweep_occluded_over_occluded"] = round(out[kr + "sweep_occluded_ms"] / out[kr + "occluded_ms"], 2)
+            sweep()
+            t = ctx.buf_download(hs[2], np.float32, 4 * n).reshape(n, 4)[:, 2]
+            out[kr + "hit_fraction"], out[kr + "t0_fraction"] = round(float(np.isfinite(t).mean()), 4), round(float((t == 0).mean()), 4)
+        wd.close()
+    for h in hs:
+        ctx.buf_free(h)
+    th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def main():
     sc = scenes.sponza_like()
     ctx = psm.Context(0)
@@ -1041,4 +1115,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps}.get(" ".join(sys.argv[1:]), main)()
