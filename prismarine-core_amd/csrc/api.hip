@@ -313,7 +313,7 @@ int psm_bvh_destroy(psm_bvh* b) {
     if (!b) return PSM_ERR_INVALID;
     (void)hipSetDevice(b->ctx->device);
     (void)hipStreamSynchronize(b->ctx->stream);
-    dev_free(b->d_pos); dev_free(b->d_nrm); dev_free(b->d_mats); dev_free(b->d_tri48); dev_free(b->d_tex);
+    dev_free(b->d_pos); dev_free(b->d_nrm); dev_free(b->d_mats); dev_free(b->d_tri48); dev_free(b->d_trishade); dev_free(b->d_tex);
     dev_free(b->d_keys); dev_free(b->d_idx); dev_free(b->d_leafbox); dev_free(b->d_leaftri);
     dev_free(b->d_block); dev_free(b->d_small); dev_free(b->d_opt); dev_free(b->d_seg);
     dev_free(b->d_sorted_tri); dev_free(b->d_pairbox); dev_free(b->d_link); dev_free(b->d_range); dev_free(b->d_node32);
@@ -345,7 +345,7 @@ int psm_bvh_create(psm_ctx* c, size_t max_tris, psm_bvh** out) {
     int rc = PSM_OK;
     auto A = [&](int r) { if (rc == PSM_OK) rc = r; };
     A(dev_alloc(c, &b->d_pos, 9 * n)); A(dev_alloc(c, &b->d_nrm, 9 * n)); A(dev_alloc(c, &b->d_mats, n));
-    A(dev_alloc(c, &b->d_tri48, 3 * n));
+    A(dev_alloc(c, &b->d_tri48, 3 * n)); A(dev_alloc(c, &b->d_trishade, n));
     A(dev_alloc(c, &b->d_tex, 6 * n)); A(dev_alloc(c, &b->d_keys, n)); A(dev_alloc(c, &b->d_idx, n));
     A(dev_alloc(c, &b->d_leafbox, n)); A(dev_alloc(c, &b->d_leaftri, n));
     A(dev_alloc(c, &b->d_block, (n + 255) / 256 + 1)); A(dev_alloc(c, &b->d_small, (size_t)SM_WORDS));
@@ -664,7 +664,7 @@ int psm_rt_destroy(psm_rt* r) {
     (void)hipSetDevice(r->ctx->device);
     (void)hipStreamSynchronize(r->ctx->stream);
     rt_free_grid(r);
-    dev_free(r->presampled); dev_free(r->filtered); dev_free(r->d_lights); dev_free(r->d_mats); dev_free(r->d_cnt); dev_free(r->d_sky); dev_free(r->d_tex_table); dev_free(r->d_geoms);
+    dev_free(r->presampled); dev_free(r->filtered); dev_free(r->d_lights); dev_free(r->d_light_ctr); dev_free(r->d_mats); dev_free(r->d_mat_baked); dev_free(r->d_cnt); dev_free(r->d_sky); dev_free(r->d_tex_table); dev_free(r->d_geoms);
     if (r->d_phase_mem) (void)hipFree(r->d_phase_mem);
     if (r->h_cnt) (void)hipHostFree(r->h_cnt);
     if (r->ev_cnt) (void)hipEventDestroy(r->ev_cnt);
@@ -682,6 +682,7 @@ int psm_rt_create(psm_ctx* c, psm_rt** out) {
     r->ctx = c;
     int rc = dev_alloc(c, &r->d_cnt, (size_t)8);
     if (rc == PSM_OK) rc = dev_alloc(c, &r->d_lights, (size_t)16);
+    if (rc == PSM_OK) rc = dev_alloc(c, &r->d_light_ctr, (size_t)16);
     if (rc == PSM_OK) rc = dev_alloc(c, &r->d_tex_table, (size_t)MAX_TEXTURES);
     if (rc == PSM_OK) rc = dev_alloc(c, &r->d_geoms, (size_t)MAX_TRAV_OBJECTS);
     if (rc == PSM_OK) r->tex_dirty = true;
@@ -698,6 +699,7 @@ int psm_rt_create(psm_ctx* c, psm_rt** out) {
         L[i].lightVector[0] = 0.3f; L[i].lightVector[1] = 1.0f; L[i].lightVector[2] = 0.1f; L[i].lightVector[3] = 400.0f;
     }
     if (hipMemcpyAsync(r->d_lights, L, sizeof(L), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        launch_rt_bake_lights(r) != PSM_OK ||
         hipStreamSynchronize(c->stream) != hipSuccess) { psm_rt_destroy(r); return PSM_ERR_HIP; }
     *out = r;
     return PSM_OK;
@@ -828,6 +830,7 @@ int psm_rt_set_lights(psm_rt* r, const psm_light* lights, uint32_t count) {
     psm_ctx* c = r->ctx;
     (void)hipSetDevice(c->device);
     PSM_HIP(c, hipMemcpyAsync(r->d_lights, lights, count * sizeof(psm_light), hipMemcpyHostToDevice, c->stream));
+    if (int rc = launch_rt_bake_lights(r)) return rc;   // the centres follow the table (shade.hip)
     PSM_HIP(c, hipStreamSynchronize(c->stream));
     r->light_count = count;
     return PSM_OK;
@@ -878,15 +881,19 @@ int psm_rt_set_materials(psm_rt* r, const psm_material* mats, uint32_t count, in
     psm_ctx* c = r->ctx;
     (void)hipSetDevice(c->device);
     PSM_HIP(c, hipStreamSynchronize(c->stream));
-    dev_free(r->d_mats);
+    dev_free(r->d_mats); dev_free(r->d_mat_baked);
+    r->d_mats = nullptr; r->d_mat_baked = nullptr;
+    r->mat_count = 0;
     int rc = dev_alloc(c, &r->d_mats, (size_t)std::max<uint32_t>(count, 1));
+    if (rc == PSM_OK) rc = dev_alloc(c, &r->d_mat_baked, (size_t)3 * std::max<uint32_t>(count, 1));
     if (rc != PSM_OK) return rc;
-    if (count) {
-        PSM_HIP(c, hipMemcpyAsync(r->d_mats, mats, count * sizeof(psm_material), hipMemcpyHostToDevice, c->stream));
-        PSM_HIP(c, hipStreamSynchronize(c->stream));
-    }
     r->mat_count = count;
     r->mat_offset = load_offset;
+    if (count) {
+        PSM_HIP(c, hipMemcpyAsync(r->d_mats, mats, count * sizeof(psm_material), hipMemcpyHostToDevice, c->stream));
+        if (int brc = launch_rt_bake_materials(r)) return brc;   // the untextured hit's constants follow the table (shade.hip)
+        PSM_HIP(c, hipStreamSynchronize(c->stream));
+    }
     // rt_shade builds only the lobe that survives the lobe pick as long as the other one's colour is certain to be 0 (shade.hip);
     // it is NaN instead -- and the reference queues the ray -- where the specular colour is 0 / 0 (a black full-metal material:
     // albedo 0, metallic 1, both after their fp16 round trip) or a colour overflows or is not a number to begin with. Without

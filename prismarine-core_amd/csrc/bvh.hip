@@ -139,7 +139,15 @@ __global__ __launch_bounds__(BOUNDS_BLOCK) void bvh_bounds(const float* __restri
 
 // traversal layout: v0, e1 = v1 - v0, e2 = v2 - v0 (the first three operations of
 // intersectTriangle, include/vertex.glsl:148-156, hoisted; same IEEE results)
-__global__ __launch_bounds__(256) void bvh_prepare_tris(const float* __restrict__ pos, float4* __restrict__ tri48,
+// shading layout: what interpolateMeshData (directTraverse.comp:116-147) derives from the triangle alone, once per triangle
+// instead of once per hit -- normalize(cross(e1, e2)) on the e1, e2 of the traversal record, and the material id's bits
+PSM_D float4 tri_shade_record(float4 e1, float4 e2, int32_t mat) {
+    v3 nor = normalize3(cross3(mk3(e1.x, e1.y, e1.z), mk3(e2.x, e2.y, e2.z)));
+    return make_float4(nor.x, nor.y, nor.z, __int_as_float(mat));
+}
+
+__global__ __launch_bounds__(256) void bvh_prepare_tris(const float* __restrict__ pos, const int32_t* __restrict__ mats,
+                                                        float4* __restrict__ tri48, float4* __restrict__ trishade,
                                                         uint32_t first, uint32_t n) {
     uint32_t t = first + blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= first + n) return;
@@ -150,6 +158,7 @@ __global__ __launch_bounds__(256) void bvh_prepare_tris(const float* __restrict_
     tri48[(size_t)3 * t + 0] = v0;
     tri48[(size_t)3 * t + 1] = e1;
     tri48[(size_t)3 * t + 2] = e2;
+    trishade[t] = tri_shade_record(e1, e2, mats[t]);
 }
 
 // ---- geometry ingestion: vertex/loader.comp:32-152 ----------------------------------
@@ -179,7 +188,7 @@ PSM_D void read_by_accessor(const MeshArgs& a, int accessorID, uint32_t idx, flo
 
 __global__ __launch_bounds__(128) void bvh_load_mesh(MeshArgs a, float* __restrict__ pos, float* __restrict__ nrm,
                                                      int32_t* __restrict__ mats, float4* __restrict__ tri48,
-                                                     float* __restrict__ tex) {
+                                                     float4* __restrict__ trishade, float* __restrict__ tex) {
     int ct = blockIdx.x * 128 + threadIdx.x;
     if (ct >= a.nodeCount) return;
     int trp = a.primitiveType == 1 ? 4 : 3;
@@ -222,9 +231,12 @@ __global__ __launch_bounds__(128) void bvh_load_mesh(MeshArgs a, float* __restri
             tex[(size_t)6 * tidc + 2 * i] = tu[m[i]];
             tex[(size_t)6 * tidc + 2 * i + 1] = tv[m[i]];
         }
+        const float4 e1 = make_float4(vv[1].x - vv[0].x, vv[1].y - vv[0].y, vv[1].z - vv[0].z, 0.0f);
+        const float4 e2 = make_float4(vv[2].x - vv[0].x, vv[2].y - vv[0].y, vv[2].z - vv[0].z, 0.0f);
         tri48[(size_t)3 * tidc + 0] = make_float4(vv[0].x, vv[0].y, vv[0].z, 1.0f);
-        tri48[(size_t)3 * tidc + 1] = make_float4(vv[1].x - vv[0].x, vv[1].y - vv[0].y, vv[1].z - vv[0].z, 0.0f);
-        tri48[(size_t)3 * tidc + 2] = make_float4(vv[2].x - vv[0].x, vv[2].y - vv[0].y, vv[2].z - vv[0].z, 0.0f);
+        tri48[(size_t)3 * tidc + 1] = e1;
+        tri48[(size_t)3 * tidc + 2] = e2;
+        trishade[tidc] = tri_shade_record(e1, e2, a.materialID);
     }
 }
 
@@ -238,7 +250,7 @@ int launch_bvh_load_mesh(psm_bvh* b, const psm_mesh_desc* d, const psm_accessor*
     a.materialID = d->material_id; a.isIndexed = d->is_indexed; a.index16 = d->index16; a.nodeCount = d->node_count;
     a.primitiveType = d->primitive_type; a.loadingOffset = d->loading_offset;
     a.storingOffset = b->tri_count;
-    bvh_load_mesh<<<(d->node_count + 127) / 128, 128, 0, b->ctx->stream>>>(a, b->d_pos, b->d_nrm, b->d_mats, b->d_tri48, b->d_tex);
+    bvh_load_mesh<<<(d->node_count + 127) / 128, 128, 0, b->ctx->stream>>>(a, b->d_pos, b->d_nrm, b->d_mats, b->d_tri48, b->d_trishade, b->d_tex);
     PSM_HIP(b->ctx, hipGetLastError());
     return PSM_OK;
 }
@@ -723,7 +735,7 @@ __global__ __launch_bounds__(256) void bvh_emit(const uint64_t* __restrict__ key
 
 int launch_bvh_prepare_tris(psm_bvh* b, uint32_t first, uint32_t n) {
     if (n == 0) return PSM_OK;
-    bvh_prepare_tris<<<(n + 255) / 256, 256, 0, b->ctx->stream>>>(b->d_pos, b->d_tri48, first, n);
+    bvh_prepare_tris<<<(n + 255) / 256, 256, 0, b->ctx->stream>>>(b->d_pos, b->d_mats, b->d_tri48, b->d_trishade, first, n);
     PSM_HIP(b->ctx, hipGetLastError());
     return PSM_OK;
 }

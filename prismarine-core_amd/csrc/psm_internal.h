@@ -21,7 +21,7 @@ constexpr int OBJ_SHIFT = 27;          // hit.w = triangle | object << 27
 struct ObjGeom {  // what interpolateMeshData reads of one hierarchy (directTraverse.comp:116-147)
     const float4* tri48;
     const float* nrm;
-    const int32_t* tri_mats;
+    const float4* trishade;  // geometric normal | material id, one float4 per triangle (psm_bvh::d_trishade)
     const float* uv;
 };
 
@@ -156,6 +156,7 @@ struct psm_bvh {
     int32_t* d_mats = nullptr;    // material id / triangle
     float* d_tex = nullptr;       // 6 floats / triangle: u,v per vertex
     float4* d_tri48 = nullptr;    // v0, e1, e2 (xyz, w unused) / triangle -- traversal layout
+    float4* d_trishade = nullptr; // normalize(cross(e1, e2)), bits of the material id / triangle -- what rt_shade needs of the triangle itself; written wherever d_tri48 or d_mats is
     uint64_t* d_keys = nullptr;   // Morton codes, slot order then sorted in place
     uint32_t* d_idx = nullptr;    // MortonIndices
     uint4* d_leafbox = nullptr;   // leaf record box, slot order
@@ -211,8 +212,10 @@ struct psm_rt {
     float4* presampled = nullptr;
     float4* filtered = nullptr;
     psm_light* d_lights = nullptr;
+    float4* d_light_ctr = nullptr;   // lightCenter() of the 16 entries of d_lights, refreshed with every upload (shade.hip: rt_bake_lights)
     uint32_t light_count = 1;
     psm_material* d_mats = nullptr;
+    float4* d_mat_baked = nullptr;   // 3 float4 / material: an untextured hit's albedo, emission, mr (shade.hip: rt_bake_materials)
     uint32_t mat_count = 0;
     int32_t mat_offset = 0;
     float sky[4] = {0.5f, 0.7f, 1.0f, 1.0f};
@@ -303,6 +306,8 @@ int launch_rt_camera(psm_rt* r, const float* cam_inv, const float* proj_inv, uin
 int launch_rt_traverse(psm_rt* r, psm_bvh* b);
 int launch_rt_shade(psm_rt* r, psm_bvh* b, uint32_t time);
 int launch_rt_sample(psm_rt* r, psm_rt* src);
+int launch_rt_bake_materials(psm_rt* r);   // d_mats -> d_mat_baked, on the context's stream
+int launch_rt_bake_lights(psm_rt* r);      // d_lights -> d_light_ctr
 // pack / unpack the dense tile of rows [a, b) (bands == NULL) or of rank a in the dealing `bands`
 int launch_rt_pack(psm_rt* r, hipStream_t stream, float* d_buf, int unpack, const BandMap* bands, uint32_t a, uint32_t b);
 int launch_rt_unpack_all(psm_rt* r, hipStream_t stream, const float* d_all, const BandMap& bands, uint32_t skip, size_t stride_floats);

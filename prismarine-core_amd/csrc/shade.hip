@@ -181,9 +181,10 @@ PSM_D void unpack4(uint32_t lo, uint32_t hi, float* o) {
 
 struct SurfSrc {
     const float4* tri48;
+    const float4* trishade;  // per triangle: geometric normal | material id (bvh.hip: tri_shade_record)
     const float* nrm;
-    const int32_t* tri_mats;
     const psm_material* mats;
+    const float4* mat_baked;  // per material: albedo, emission, mr of an untextured hit (rt_bake_materials)
     const float* uv;       // 6 floats / triangle
     const TexDesc* tex;    // MAX_TEXTURES slots
     const ObjGeom* geoms;  // MULTI: per-object geometry, indexed by the tag in hit.w
@@ -219,22 +220,51 @@ PSM_D void fetch_tex(const TexDesc t, float u, float v, int ox, int oy, float* o
     }
 }
 
+// What a hit takes from its material before any texture replaces it (surface.comp:100-161 with validateTexture failing) ...
+PSM_D void mat_constants(const psm_material* m, float* diff, float* emis, float* spc) {
+    diff[0] = pmax(m->diffuse[0], 0.f); diff[1] = pmax(m->diffuse[1], 0.f); diff[2] = pmax(m->diffuse[2], 0.f); diff[3] = 1.0f;
+    emis[0] = emis[1] = emis[2] = emis[3] = 0.f;
+    spc[0] = m->specular[0]; spc[1] = m->specular[1]; spc[2] = m->specular[2]; spc[3] = m->specular[3];
+}
+// ... and the fp16 round trip of the HitRework record they travel in (surface.comp:188-195)
+PSM_D void mat_pack(const float* diff, const float* emis, const float* spc, float* albedo, float* emission, float* mr) {
+    unpack4(pack_half2(diff[0], diff[1]), pack_half2(diff[2], diff[3]), albedo);
+    unpack4(pack_half2(emis[0] * 2.f, emis[1] * 2.f), pack_half2(emis[2] * 2.f, 1.0f), emission);
+    unpack4(pack_half2(spc[1], spc[2]), pack_half2(0.f, 0.f), mr);
+}
+
+// Without textures a hit's albedo, emission and metal / roughness are functions of its material alone: evaluated once per
+// upload of the table (psm_rt_set_materials) by the two functions above -- on the device, so the conversions are the
+// kernel's own -- instead of once per hit. Three float4 per material: albedo | emission | mr.
+__global__ __launch_bounds__(64) void rt_bake_materials(const psm_material* __restrict__ mats, uint32_t count, float4* __restrict__ baked) {
+    uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= count) return;
+    float diff[4], emis[4], spc[4], al[4], em[4], mr[4];
+    mat_constants(mats + i, diff, emis, spc);
+    mat_pack(diff, emis, spc, al, em, mr);
+    baked[(size_t)3 * i + 0] = make_float4(al[0], al[1], al[2], al[3]);
+    baked[(size_t)3 * i + 1] = make_float4(em[0], em[1], em[2], em[3]);
+    baked[(size_t)3 * i + 2] = make_float4(mr[0], mr[1], mr[2], mr[3]);
+}
+
 template <bool TEX, bool MULTI>
 PSM_D Surf surface_eval(float4 hit, const SurfSrc& src) {
     Surf s;
     int tri = __float_as_int(hit.w);
-    ObjGeom g = {src.tri48, src.nrm, src.tri_mats, src.uv};
+    ObjGeom g = {src.tri48, src.nrm, src.trishade, src.uv};
     if (MULTI) {  // the hierarchy whose mosaics were bound when this hit was interpolated
         g = src.geoms[(tri >> OBJ_SHIFT) & (MAX_TRAV_OBJECTS - 1)];
         tri &= (1 << OBJ_SHIFT) - 1;
     }
     float u = hit.x, v = hit.y;
     s.t = hit.z;
-    float4 b = g.tri48[(size_t)3 * tri + 1], c = g.tri48[(size_t)3 * tri + 2];
-    v3 d1 = mk3(b.x, b.y, b.z), d2 = mk3(c.x, c.y, c.z);
+    // the triangle's own terms -- normalize(cross(e1, e2)) and the material id -- come from its shading record, written where
+    // the triangle record is written (bvh.hip) by the same functions on the same e1, e2: one 16-byte load instead of two
+    // record rows, a cross product, a square root, a division and a gather from a third array
+    const float4 ts = g.trishade[tri];
     const float* n = g.nrm + (size_t)9 * tri;   // (cached on purpose, like the triangle records: with the hint 2.40 -> 2.47 ms per frame)
     float vs0 = (1.0f - u) - v, vs1 = u, vs2 = v;
-    v3 nor = normalize3(cross3(d1, d2));
+    v3 nor = mk3(ts.x, ts.y, ts.z);
     v3 nn = mk3((vs0 * n[0] + vs1 * n[3]) + vs2 * n[6], (vs0 * n[1] + vs1 * n[4]) + vs2 * n[7],
                 (vs0 * n[2] + vs1 * n[5]) + vs2 * n[8]);
     nn = normalize3(nn);
@@ -242,16 +272,21 @@ PSM_D Surf surface_eval(float4 hit, const SurfSrc& src) {
     nn = nn * sg;
     s.normal_trav = nn;
     s.normal = normalize3(normalize3(nn));  // surface.comp:176-186 with no normal map
-    int matID = g.tri_mats[tri] - src.mat_offset;
+    int matID = __float_as_int(ts.w) - src.mat_offset;
     s.active = !(matID >= src.mat_count || matID < 0);
 #pragma unroll
     for (int k = 0; k < 4; k++) { s.albedo[k] = 0.f; s.emission[k] = 0.f; s.mr[k] = 0.f; }
-    if (s.active) {
+    if (s.active && !TEX) {  // the sampler table is empty: the material's baked constants
+        const float4 al = src.mat_baked[(size_t)3 * matID], em = src.mat_baked[(size_t)3 * matID + 1], mr = src.mat_baked[(size_t)3 * matID + 2];
+        s.albedo[0] = al.x; s.albedo[1] = al.y; s.albedo[2] = al.z; s.albedo[3] = al.w;
+        s.emission[0] = em.x; s.emission[1] = em.y; s.emission[2] = em.z; s.emission[3] = em.w;
+        s.mr[0] = mr.x; s.mr[1] = mr.y; s.mr[2] = mr.z; s.mr[3] = mr.w;
+    }
+    if (s.active && TEX) {
         const psm_material* m = src.mats + matID;
-        float diff[4] = {pmax(m->diffuse[0], 0.f), pmax(m->diffuse[1], 0.f), pmax(m->diffuse[2], 0.f), 1.0f};
-        float emis[4] = {0.f, 0.f, 0.f, 0.f};
-        float spc[4] = {m->specular[0], m->specular[1], m->specular[2], m->specular[3]};
-        if (TEX) {
+        float diff[4], emis[4], spc[4];
+        mat_constants(m, diff, emis, spc);
+        {
         const float* tc = g.uv + (size_t)6 * tri;
         float tu = (vs0 * tc[0] + vs1 * tc[2]) + vs2 * tc[4], tv = (vs0 * tc[1] + vs1 * tc[3]) + vs2 * tc[5];
         if (valid_tex(src.tex, m->diffusePart)) fetch_tex(src.tex[m->diffusePart], tu, tv, 0, 0, diff);     // :155-161
@@ -259,6 +294,8 @@ PSM_D Surf surface_eval(float4 hit, const SurfSrc& src) {
         if (valid_tex(src.tex, m->specularPart)) fetch_tex(src.tex[m->specularPart], tu, tv, 0, 0, spc);    // :102-108
         if (valid_tex(src.tex, m->bumpPart)) {
             const TexDesc bt = src.tex[m->bumpPart];
+            float4 b = g.tri48[(size_t)3 * tri + 1], c = g.tri48[(size_t)3 * tri + 2];
+            v3 d1 = mk3(b.x, b.y, b.z), d2 = mk3(c.x, c.y, c.z);
             // tangent, directTraverse.comp:190-209
             float du1 = tc[2] - tc[0], du2 = tc[4] - tc[0];
             float dv1 = tc[3] - tc[1], dv2 = tc[5] - tc[1];
@@ -296,9 +333,7 @@ PSM_D Surf surface_eval(float4 hit, const SurfSrc& src) {
                                       (tangent_s.z * w.x + bitangent.z * w.y) + normal_s.z * w.z));
         }
         }  // TEX
-        unpack4(pack_half2(diff[0], diff[1]), pack_half2(diff[2], diff[3]), s.albedo);
-        unpack4(pack_half2(emis[0] * 2.f, emis[1] * 2.f), pack_half2(emis[2] * 2.f, 1.0f), s.emission);
-        unpack4(pack_half2(spc[1], spc[2]), pack_half2(0.f, 0.f), s.mr);
+        mat_pack(diff, emis, spc, s.albedo, s.emission, s.mr);
     }
     return s;
 }
@@ -336,6 +371,15 @@ PSM_D v3 lightCenter(const psm_light& L) {
     float s = (L.lightVector[1] < 0.0f) ? -1.0f : 1.0f;
     return mk3(fmaf(lv.x * s, L.lightVector[3], L.lightOffset[0] + 0.0f), fmaf(lv.y * s, L.lightVector[3], L.lightOffset[1] + 0.0f),
                fmaf(lv.z * s, L.lightVector[3], L.lightOffset[2] + 0.0f));
+}
+// The centre depends on the light alone: evaluated once per upload of the lights (psm_rt_set_lights, the default sun) by the
+// function above, on the device, instead of once per light, per lane and per launch. A zero light vector gives the NaN
+// centre it always gave. One float4 per entry of the light table (w unused).
+__global__ __launch_bounds__(64) void rt_bake_lights(const psm_light* __restrict__ lights, uint32_t count, float4* __restrict__ centres) {
+    uint32_t i = threadIdx.x;
+    if (i >= count) return;
+    const v3 c = lightCenter(lights[i]);
+    centres[i] = make_float4(c.x, c.y, c.z, 0.f);
 }
 // shadinglib.glsl:32-48
 PSM_D float intersectSphere(v3 origin, v3 ray, v3 c, float radius) {
@@ -419,6 +463,28 @@ PSM_D bool create_ray(WRay& r, int texel, uint32_t pkey, OutRay& o, float4* __re
     return true;
 }
 
+// queue_loc (psm_common.h) for the waves of a kernel whose lanes hold consecutive, ascending ray indices: the search runs
+// ONCE, for the index of the wave's first active lane (the smallest one), on wave-uniform values -- queue_loc itself, whose
+// slot gives the segment back: a segment holds at most QUEUE_SEG rays, so slot / QUEUE_SEG is its b. Every other lane's
+// segment is that one or a later one; the wave walks on from there, one uniform step per segment, until no lane's index
+// reaches the next base (0 or 1 steps as a rule: 64 consecutive rays lie in one or two segments). A lane keeps the LAST
+// visited b with bases[b] <= i; the walk ends with i < bases[b + 1] for every lane, and bases never decrease, so that is
+// the one b with bases[b] <= i < bases[b + 1] -- queue_loc's, repeated bases (workgroups that emitted nothing) included.
+// i < total <= bases[nb] for every active lane, so the walk never reads past bases[nb].
+PSM_D uint32_t wave_queue_loc(const uint32_t* __restrict__ bases, uint32_t nb, uint32_t total, uint32_t i) {
+    if (nb <= 1u) return i;
+    const uint32_t i0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)i);
+    uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)(queue_loc(bases, nb, total, i0) / QUEUE_SEG));
+    uint32_t lane_b = b, lane_base = bases[b];
+    uint32_t next = bases[b + 1u];
+    while (__builtin_amdgcn_ballot_w64(i >= next) != 0ull) {
+        b++;
+        if (i >= next) { lane_b = b; lane_base = next; }
+        next = bases[b + 1u];
+    }
+    return lane_b * QUEUE_SEG + (i - lane_base);
+}
+
 struct ShadeArgs {
     RayQueue q;  // the rays to shade
     const float4* hit0;
@@ -426,6 +492,7 @@ struct ShadeArgs {
     const float4* pool;
     SurfSrc src;
     const psm_light* lights;
+    const float4* light_ctr;  // lightCenter() of every entry of `lights` (rt_bake_lights)
     float4 *sA, *sB, *sC;
     uint32_t* blockCounts;
     float4* t_sum;
@@ -451,7 +518,7 @@ __global__ __launch_bounds__(SHADE_BLOCK) void rt_shade(ShadeArgs a) {
     bool have[4] = {false, false, false, false};
     const uint32_t nrays = min(a.nrays, a.q.bases[a.q.nb]);  // never past what the queue holds (psm_rt_set_ray_count)
     if (it < nrays) {
-        const uint32_t loc = queue_loc(a.q.bases, a.q.nb, nrays, it);
+        const uint32_t loc = wave_queue_loc(a.q.bases, a.q.nb, nrays, it);
         float4 A = ld_stream(&a.q.A[loc]), B = ld_stream(&a.q.B[loc]), C = ld_stream(&a.q.C[loc]);
         int in_texel = __float_as_int(A.w);
         uint32_t in_pkey = __float_as_uint(C.w);
@@ -511,7 +578,8 @@ __global__ __launch_bounds__(SHADE_BLOCK) void rt_shade(ShadeArgs a) {
         if (R_DL(ray.bf) > 0 && (type == 1 || type == 2) && !skipping) {
             int nl = a.light_count < 16 ? a.light_count : 16;
             for (int i = 0; i < nl; i++) {
-                v3 ctr = lightCenter(a.lights[i]);
+                const float4 lc4 = a.light_ctr[i];
+                v3 ctr = mk3(lc4.x, lc4.y, lc4.z);
                 float dt = intersectSphere(ray.origin, ray.direct, ctr, a.lights[i].lightColor[3] + GAP);
                 float t = 1.0f * dt;
                 if (lessF(dt, INF) && lessEqualF(t, uvt_t)) lc = i;
@@ -562,6 +630,16 @@ __global__ __launch_bounds__(SHADE_BLOCK) void rt_shade(ShadeArgs a) {
         const v3 hitp = ray.origin;       // the hit point, :155-156
         const v3 incol = ray.color;       // the ray's colour after the light / background tests (unchanged for a `go` ray)
         const int inbf = ray.bf;
+        // A `go` ray with aprom == 0 (an opaque hit: every hit of an untextured scene) leaves nothing behind as the current ray:
+        // its `final` is 0 * 0 = 0 and its colour is color * 0 -- +-0 for an ordinary colour, NaN for a NaN or Inf one -- and the
+        // reclaim's pmax(0.0f, x) returns its FIRST operand, +0, unless 0 < x, which holds for none of those: the colour is
+        // (0, 0, 0), the ray goes inactive (mlength < 0.0001) and is not queued, and `final` = (0, 0, 0) deposits nothing (:244).
+        // Nothing below reads what the two blocks change (ray.origin, ray.color, ray.fin, ray.bf): the secondary rays are built
+        // from hitp, incol, inbf and ray.direct. (A -0 compares equal to 0 and behaves alike: the products change sign at most.)
+        // Rays that are `skipping` keep the reclaim: it deposits their sky or light radiance; so does every aprom that is not a
+        // zero, NaN included.
+        const bool reclaim = !(go && aprom == 0.0f);
+        if (reclaim) {
         if (go) {
             ray.fin = ray.fin * 0.f;
             ray.fin = ray.fin * 0.0f;     // :195 (two products in the reference: the sign of a zero survives them alike)
@@ -589,6 +667,7 @@ __global__ __launch_bounds__(SHADE_BLOCK) void rt_shade(ShadeArgs a) {
                 o.C = make_float4(ray.color.x, ray.color.y, ray.color.z, __uint_as_float(in_pkey));
             }
         }
+        }  // reclaim
         // the secondary rays, :195-210, :219-224, :263-275
         if (go) {
             const float om = 1.0f - aprom;
@@ -631,7 +710,9 @@ __global__ __launch_bounds__(SHADE_BLOCK) void rt_shade(ShadeArgs a) {
                 WRay dr;
                 dr.color = incol * mk3(c_albedo[0], c_albedo[1], c_albedo[2]);
                 dr.color = dr.color * om;                       // :219
-                dr.color = dr.color * (1.0f - coef);            // :268
+                // (the surviving lobe's factor is exactly 1 -- coef is 0 here, 1 - 0 = 1 -- and x * 1 is x for every x, NaN, Inf and
+                // denormals included: the operand is a product itself, so never a signalling NaN, and the kernels keep denormals)
+                if (lobe_refl != refl_lobe) dr.color = dr.color * (1.0f - coef);            // :268
                 dr.direct = sdir;
                 dr.origin = fma3(dr.direct, GAP, hitp);
                 dr.fin = mk3(0.f, 0.f, 0.f);
@@ -648,7 +729,8 @@ __global__ __launch_bounds__(SHADE_BLOCK) void rt_shade(ShadeArgs a) {
                     S_TYPE(sr.bf, 2);
                     S_TARGET(sr.bf, 0);
                     S_BOUNCE(sr.bf, R_BOUNCE(sr.bf) < 1 ? R_BOUNCE(sr.bf) : 1);
-                    v3 ctr = lightCenter(a.lights[0]);
+                    const float4 lc4 = a.light_ctr[0];
+                    v3 ctr = mk3(lc4.x, lc4.y, lc4.z);
                     v3 sd = randomDirectionInSphereU(u10, u11);
                     v3 sl = fma3(sd, a.lights[0].lightColor[3] - 0.0001f, ctr);
                     v3 ldirect = normalize3(sl - sr.origin);
@@ -671,7 +753,7 @@ __global__ __launch_bounds__(SHADE_BLOCK) void rt_shade(ShadeArgs a) {
                 v3 col = mk3(pclamp(sc.x / spca, 0.0f, 1.0f), pclamp(sc.y / spca, 0.0f, 1.0f), pclamp(sc.z / spca, 0.0f, 1.0f));
                 rr.color = incol * col;
                 rr.color = rr.color * om;                   // :220
-                rr.color = rr.color * coef;                 // :267
+                if (lobe_refl != refl_lobe) rr.color = rr.color * coef;                 // :267 (the surviving lobe: coef is exactly 1)
                 rr.origin = fma3(rr.direct, GAP, hitp);
                 rr.fin = mk3(0.f, 0.f, 0.f);
                 rr.bf = inbf;
@@ -685,7 +767,12 @@ __global__ __launch_bounds__(SHADE_BLOCK) void rt_shade(ShadeArgs a) {
             lobe(refl_lobe);              // the surviving lobe
             if (BOTH) lobe(!refl_lobe);   // ... and the other one, whose colour is 0 or NaN
             // ---- emissive: only its deposit (createRay of an inactive ray, rayslib.glsl:162-203)
-            {
+            // Entered only where it can deposit: `ef` is scaled by pclamp(emis, 0, 1), which is +-0 for every emis <= 0 (pmax(x, 0) keeps
+            // a -0, pmin(., 1) passes it on). Each component of `ef` is then x * +-0 with x >= 0, +Inf or NaN (the pmax(., 0) above it
+            // let nothing negative through): +-0 or NaN. mlength3 of such a vector is +-0 or NaN (pmax returns one of its operands),
+            // `>= 0.0001` is false for both, nothing is deposited. So the block runs for emis > 0 and for a NaN emis -- !(emis <= 0) --
+            // and an untextured scene, whose emission is the constant 0, skips it by whole waves.
+            if (!(emis <= 0.0f)) {
                 v3 ef = mk3(pmax(incol.x * c_emission[0], 0.0f), pmax(incol.y * c_emission[1], 0.0f), pmax(incol.z * c_emission[2], 0.0f));
                 if (R_TYPE(inbf) == 1) ef = mk3(0.f, 0.f, 0.f);
                 else ef = mk3(pmax(ef.x, 0.0f), pmax(ef.y, 0.0f), pmax(ef.z, 0.0f));
@@ -739,7 +826,7 @@ __global__ __launch_bounds__(256) void rt_gather_queue(RayQueue q, uint32_t tota
     uint32_t i = blockIdx.x * 256 + threadIdx.x;
     total = min(total, q.bases[q.nb]);
     if (i >= m || i >= total) return;
-    const uint32_t loc = queue_loc(q.bases, q.nb, total, i);
+    const uint32_t loc = wave_queue_loc(q.bases, q.nb, total, i);
     dense[i] = q.A[loc];
     dense[(size_t)m + i] = q.B[loc];
     dense[2 * (size_t)m + i] = q.C[loc];
@@ -899,8 +986,8 @@ int launch_rt_shade(psm_rt* r, psm_bvh* b, uint32_t time) {
     ShadeArgs a;
     a.q = current_queue(r);
     a.hit0 = r->hit0; a.hitN = r->hitN; a.pool = r->pool;
-    a.src.tri48 = b->d_tri48; a.src.nrm = b->d_nrm; a.src.tri_mats = b->d_mats; a.src.uv = b->d_tex;
-    a.src.mats = r->d_mats; a.src.tex = r->d_tex_table; a.lights = r->d_lights;
+    a.src.tri48 = b->d_tri48; a.src.nrm = b->d_nrm; a.src.trishade = b->d_trishade; a.src.uv = b->d_tex;
+    a.src.mats = r->d_mats; a.src.mat_baked = r->d_mat_baked; a.src.tex = r->d_tex_table; a.lights = r->d_lights; a.light_ctr = r->d_light_ctr;
     const int nxt_q = r->cur ^ 1;
     a.sA = r->qA[nxt_q]; a.sB = r->qB[nxt_q]; a.sC = r->qC[nxt_q];  // every workgroup writes its own segment of the next queue
     a.blockCounts = r->d_block;
@@ -917,7 +1004,7 @@ int launch_rt_shade(psm_rt* r, psm_bvh* b, uint32_t time) {
         for (int i = 0; i < r->trav_n; i++)
         {
             const psm_bvh* o = r->trav_objs[i];
-            g[i] = ObjGeom{o->d_tri48, o->d_nrm, o->d_mats, o->d_tex};
+            g[i] = ObjGeom{o->d_tri48, o->d_nrm, o->d_trishade, o->d_tex};
         }
         PSM_HIP(c, hipMemcpyAsync(r->d_geoms, g, sizeof(g), hipMemcpyHostToDevice, c->stream));
         PSM_HIP(c, hipStreamSynchronize(c->stream));
@@ -943,6 +1030,21 @@ int launch_rt_shade(psm_rt* r, psm_bvh* b, uint32_t time) {
     r->cur = nxt;
     r->count_valid = false;
     c->rounds++;
+    return PSM_OK;
+}
+
+int launch_rt_bake_materials(psm_rt* r) {
+    psm_ctx* c = r->ctx;
+    if (r->mat_count == 0) return PSM_OK;
+    rt_bake_materials<<<(r->mat_count + 63) / 64, 64, 0, c->stream>>>(r->d_mats, r->mat_count, r->d_mat_baked);
+    PSM_HIP(c, hipGetLastError());
+    return PSM_OK;
+}
+
+int launch_rt_bake_lights(psm_rt* r) {
+    psm_ctx* c = r->ctx;
+    rt_bake_lights<<<1, 64, 0, c->stream>>>(r->d_lights, 16u, r->d_light_ctr);   // every entry of the table: 16
+    PSM_HIP(c, hipGetLastError());
     return PSM_OK;
 }
 
