@@ -68,6 +68,13 @@ namespace NSM {
         int boxOverlaps(const psm_box_query * d_boxes, size_t n, uint8_t * d_hit);
         int boxCount(const psm_box_query * d_boxes, size_t n, uint32_t * d_count);
         int boxTriangles(const psm_box_query * d_boxes, size_t n, uint32_t k, int32_t * d_tris, uint32_t * d_count);
+        // not in the reference: whether / how many / which triangles meet each of n query triangles (closed: touching counts; a
+        // separating-axis test in float32, psm_hip.h "triangle queries"); triTriangles: 1 <= k <= PSM_QUERY_K_MAX, d_ids [n][k] =
+        // the lowest ids that count, ascending, then -1, d_count [n] = the slots that hold one (psm_bvh_tri_overlaps_dev /
+        // psm_bvh_tri_count_dev / psm_bvh_tri_triangles_dev), stream-ordered on the context; returns the psm_status
+        int triOverlaps(const psm_tri_query * d_tris, size_t n, uint8_t * d_hit);
+        int triCount(const psm_tri_query * d_tris, size_t n, uint32_t * d_count);
+        int triTriangles(const psm_tri_query * d_tris, size_t n, uint32_t k, int32_t * d_ids, uint32_t * d_count);
         // not in the reference: where a sphere that moves along a line first touches the triangles (t = the distance its centre
         // travels, 0 when it touches where it starts; a miss is {0, 0, +inf, -1}), and whether it touches any within tmax
         // (psm_bvh_sweep_sphere_dev / psm_bvh_sweep_occluded_dev), stream-ordered on the context; returns the psm_status

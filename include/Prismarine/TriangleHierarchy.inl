@@ -92,6 +92,21 @@ namespace NSM {
         check(rc, "TriangleHierarchy::boxTriangles");
         return rc;
     }
+    inline int TriangleHierarchy::triOverlaps(const psm_tri_query * d_tris, size_t n, uint8_t * d_hit) {
+        const int rc = psm_bvh_tri_overlaps_dev(bvh, d_tris, n, d_hit);
+        check(rc, "TriangleHierarchy::triOverlaps");
+        return rc;
+    }
+    inline int TriangleHierarchy::triCount(const psm_tri_query * d_tris, size_t n, uint32_t * d_count) {
+        const int rc = psm_bvh_tri_count_dev(bvh, d_tris, n, d_count);
+        check(rc, "TriangleHierarchy::triCount");
+        return rc;
+    }
+    inline int TriangleHierarchy::triTriangles(const psm_tri_query * d_tris, size_t n, uint32_t k, int32_t * d_ids, uint32_t * d_count) {
+        const int rc = psm_bvh_tri_triangles_dev(bvh, d_tris, n, k, d_ids, d_count);
+        check(rc, "TriangleHierarchy::triTriangles");
+        return rc;
+    }
     inline int TriangleHierarchy::sweepSphere(const psm_sweep_query * d_sweeps, size_t n, psm_hit * d_hits) {
         const int rc = psm_bvh_sweep_sphere_dev(bvh, d_sweeps, n, d_hits);
         check(rc, "TriangleHierarchy::sweepSphere");

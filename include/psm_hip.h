@@ -556,6 +556,59 @@ typedef struct {
 int psm_bvh_sweep_sphere_dev(psm_bvh* bvh, const psm_sweep_query* d_sweeps, size_t n, psm_hit* d_hits);
 int psm_bvh_sweep_occluded_dev(psm_bvh* bvh, const psm_sweep_query* d_sweeps, size_t n, uint8_t* d_hit);
 
+/* triangle queries against a built hierarchy (new; no reference counterpart): whether, how many and which of
+ * the hierarchy's triangles meet a given triangle -- the narrow phase of mesh against mesh -- on the same leaves, stack, context
+ * and checks as the queries above. Flat scenes, instanced lists and worlds have none. Semantics:
+ *   - a query {a, b, c} is valid iff its nine numbers are finite; a degenerate query triangle (a segment, a point) is valid. An
+ *     invalid query answers 0, 0, or count 0 with a row of -1: never an error, as for invalid rays, points and boxes. The pads
+ *     are not read
+ *   - the candidates are the hierarchy's leaves (PSM_BVH_LEAF_TRI) by load-order triangle id, a triangle read as the build
+ *     stores it: v0, e1 = v1 - v0, e2 = v2 - v0. A triangle the build dropped stays dropped
+ *   - a candidate counts iff tri_tri(v0, e1, e2, a, b, c): a separating-axis test in float32, one fixed operation order,
+ *     multiplications, additions, subtractions and compares only -- no division, no square root, nothing fused
+ *     (psm_tri_dev.h tri_tri; tests/tri_query_model.py restates it) --, closed: touching counts, as float32 decides it: where
+ *     every operation is exact (coordinates on a lattice) contact counts; elsewhere contact that is exact in real numbers is
+ *     found or missed by the rounding of the sums.
+ *       everything is relative to the stored v0: A = a - v0, B = b - v0, C = c - v0 per component, one rounding each; the stored
+ *       triangle is {0, e1, e2} with the edges e1, e2, e3 = e2 - e1; the query's edges are g1 = B - A, g2 = C - A, g3 = C - B
+ *       dot(x, y) = (x0 y0 + x1 y1) + x2 y2; cross(x, y) = cross3 (psm_math.h): (x1 y2 - y1 x2, x2 y0 - y2 x0, x0 y1 - y0 x1)
+ *       on an axis ax the stored triangle's interval [tmin, tmax] is the min / max of {0, dot(ax, e1), dot(ax, e2)} and the
+ *         query's [qmin, qmax] that of {dot(ax, A), dot(ax, B), dot(ax, C)}; min / max of {x, y, z} are selections:
+ *         m = y < x ? y : x, then z < m ? z : m (max: with >)
+ *       an axis separates iff !(tmax >= qmin && qmax >= tmin): a NaN bound separates
+ *       the pair counts iff none of these 20 axes separates, in this order:
+ *         1. the three unit axes k, no product: {0, e1_k, e2_k} against {A_k, B_k, C_k} -- box_tri's unit axes for the query's
+ *            bounding box [min(a, b, c), max(a, b, c)] (the subtraction is monotonic), which the prune's proof rests on
+ *         2. n = cross(e1, e2), then m = cross(g1, g2)
+ *         3. the nine cross(e_i, g_j), i outer, j inner
+ *         4. cross(n, e_i), i = 1, 2, 3, then cross(m, g_j), j = 1, 2, 3: the in-plane axes that decide coplanar pairs
+ *       (2) and (3) are the complete set for two triangles that are not coplanar, (4) the complete 2-D set for coplanar ones, (1)
+ *       is redundant in real numbers. A zero axis (a degenerate triangle, parallel edges) projects everything to 0 and separates
+ *       nothing: a degenerate triangle on either side gets whatever the remaining axes say, finite and deterministic
+ *     magnitudes: the in-plane axes are products of three coordinate differences and are multiplied by a fourth; with d the
+ *     largest coordinate difference between any two of the pair's six vertices, every intermediate is below 12 d^4, so nothing
+ *     overflows while d < 2^30 (and nothing that decides underflows to 0 while the differences exceed 2^-30). Beyond that an
+ *     overflow gives an infinity or a NaN, an axis that holds one separates and the pair is missed; there is no guard
+ *   - overlaps: d_hit[i] = 1 iff some candidate counts, else 0 (uint8_t, torch.bool-compatible); the walk ends at the first
+ *   - count: d_count[i] = the number c of candidates that count
+ *   - triangles: 1 <= k <= PSM_QUERY_K_MAX; row i of d_ids ([n][k]) holds the min(k, c) LOWEST triangle ids that count,
+ *     ascending, then -1; d_count[i] = min(k, c). With k >= c the row is the complete list; the row for k is the first k slots of
+ *     the row for any larger k
+ *   - nothing depends on the traversal order: a flag, a sum, the lowest ids
+ *   - not covered: the intersection segment itself, a posed query mesh in one call, k > PSM_QUERY_K_MAX
+ *   - k == 0 or k > PSM_QUERY_K_MAX: PSM_ERR_INVALID, nothing is launched. d_tris 16-byte, d_count and d_ids 4-byte aligned;
+ *     everything else (NULL checks, n = 0, PSM_ERR_STATE before the first build -- "triangle query before build" --,
+ *     PSM_ERR_CAPACITY for a hierarchy deeper than the query stack, stream order, capture, refit, 0 / 1 leaves) as for the
+ *     queries above. A refused call launches nothing and leaves the output buffers untouched */
+typedef struct {
+    float a[3], pad0;
+    float b[3], pad1;
+    float c[3], pad2;
+} psm_tri_query; /* 48 B: three 16-byte loads */
+int psm_bvh_tri_overlaps_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t n, uint8_t* d_hit);
+int psm_bvh_tri_count_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t n, uint32_t* d_count);
+int psm_bvh_tri_triangles_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t n, uint32_t k, int32_t* d_ids, uint32_t* d_count);
+
 /* scene queries: the seven queries above over several hierarchies at once (new; no reference counterpart).
  * A scene is an ordered list of G built hierarchies of ONE context, 1 <= G <= PSM_SCENE_MAX_GEOMETRIES, passed per call (there
  * is no scene handle). The limit is 32 because the per-geometry table then travels with the launch (32 x four pointers = 1 KB

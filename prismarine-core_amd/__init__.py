@@ -30,6 +30,7 @@ EXPORTS = [
     "psm_bvh_first_hits_dev", "psm_bvh_nearest_dev",
     "psm_bvh_box_overlaps_dev", "psm_bvh_box_count_dev", "psm_bvh_box_triangles_dev",
     "psm_bvh_sweep_sphere_dev", "psm_bvh_sweep_occluded_dev",
+    "psm_bvh_tri_overlaps_dev", "psm_bvh_tri_count_dev", "psm_bvh_tri_triangles_dev",
     "psm_scene_intersect_dev", "psm_scene_occluded_dev", "psm_scene_count_hits_dev", "psm_scene_closest_point_dev", "psm_scene_within_dev",
     "psm_scene_inside_dev", "psm_scene_signed_distance_dev",
     "psm_instances_intersect_dev", "psm_instances_occluded_dev", "psm_instances_count_hits_dev", "psm_instances_closest_point_dev",
@@ -64,6 +65,7 @@ QUERY_RAY_DT = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direct", "<f4"
 POINT_QUERY_DT = np.dtype([("p", "<f4", 3), ("rmax", "<f4")])   # psm_point_query
 BOX_QUERY_DT = np.dtype([("lo", "<f4", 3), ("pad0", "<f4"), ("hi", "<f4", 3), ("pad1", "<f4")])   # psm_box_query
 SWEEP_QUERY_DT = np.dtype([("origin", "<f4", 3), ("radius", "<f4"), ("direct", "<f4", 3), ("tmax", "<f4")])   # psm_sweep_query
+TRI_QUERY_DT = np.dtype([("a", "<f4", 3), ("pad0", "<f4"), ("b", "<f4", 3), ("pad1", "<f4"), ("c", "<f4", 3), ("pad2", "<f4")])   # psm_tri_query
 QUERY_K_MAX = 16   # psm_hip.h PSM_QUERY_K_MAX
 SCENE_MAX_GEOMETRIES = 32   # psm_hip.h PSM_SCENE_MAX_GEOMETRIES
 WORLD_MAX_INSTANCES = 65536   # psm_hip.h PSM_WORLD_MAX_INSTANCES
@@ -465,6 +467,47 @@ class TriangleHierarchy:
         boxes[:, 0:3], boxes[:, 4:7] = a, b
         return self._launch_np(boxes, out, name, *extra)
 
+    def triOverlaps(self, tris):
+        """Whether some triangle of the hierarchy meets each query triangle (psm_bvh_tri_overlaps_dev; not in the reference): tris
+        [n, 3, 3] or [n, 9], the vertices a, b, c of each. Closed (touching counts); a segment or a point is a valid query
+        triangle, one with a non-finite number meets nothing. The test is a separating-axis test over 20 axes in float32
+        (psm_hip.h "triangle queries"). A bool array / tensor. numpy in: numpy out; torch device tensors in: torch tensors out on
+        the same device, ordered against torch's current stream without synchronising (as intersect()). QueryScene,
+        InstancedScene and InstanceWorld have no triangle queries."""
+        return self._tri_query(tris, "bool", "psm_bvh_tri_overlaps_dev")
+
+    def triCount(self, tris):
+        """The number of triangles that meet each query triangle (psm_bvh_tri_count_dev; not in the reference): what
+        triOverlaps() asks "is there one?" about, counted. A uint32 array, or an int32 tensor for torch tensors. Arguments and
+        placement as triOverlaps()."""
+        return self._tri_query(tris, "count", "psm_bvh_tri_count_dev")
+
+    def triTriangles(self, tris, k):
+        """Which triangles meet each query triangle (psm_bvh_tri_triangles_dev; not in the reference): of the triangles
+        triCount() counts, the min(k, count) lowest ids, ascending. k: 1 .. QUERY_K_MAX. Returns QueryTriLists: tri [n, k] int32
+        (-1 past count) and count [n]; with k >= triCount() the row is the complete list. Arguments and placement as
+        triOverlaps()."""
+        if not 1 <= _k(k, "psm_bvh_tri_triangles_dev") <= QUERY_K_MAX:   # (refused here: no call is made)
+            raise PsmError("psm_bvh_tri_triangles_dev: k must be 1 .. %d" % QUERY_K_MAX)
+        return self._tri_query(tris, "tris", "psm_bvh_tri_triangles_dev", k)
+
+    def _tri_query(self, tris, out, name, k=None):
+        """tris [n, 3, 3] or [n, 9] packed into psm_tri_query records (the pads are 0) on the side the argument lives on"""
+        extra = () if k is None else (C.c_uint32(int(k)),)
+        if type(tris).__module__.split(".")[0] == "torch":
+            import torch
+            dev = tris.device
+            if dev.type != "cuda":
+                raise ValueError("triangle queries: tris must be a tensor on the context's device")
+            t = tris.reshape(-1, 3, 3)
+            packed = torch.zeros((t.shape[0], 3, 4), dtype=torch.float32, device=dev)
+            packed[:, :, 0:3] = t
+            return _launch_torch(self, packed.reshape(-1, 12), out, name, *extra)
+        t = np.ascontiguousarray(tris, np.float32).reshape(-1, 3, 3)
+        packed = np.zeros((t.shape[0], 3, 4), np.float32)
+        packed[:, :, 0:3] = t
+        return self._launch_np(packed.reshape(-1, 12), out, name, *extra)
+
     def sweepSphere(self, origins, directions, radius, tmax=np.inf):
         """Where a sphere of `radius` that moves from each origin along its direction first touches a triangle within the distance
         tmax (psm_bvh_sweep_sphere_dev; not in the reference): origins, directions [n, 3] (any length; normalised inside, t is
@@ -643,8 +686,8 @@ class QueryHitLists:
 
 
 class QueryTriLists:
-    """The rows of TriangleHierarchy.boxTriangles: tri [n, k] int32 (numpy array or torch tensor), the lowest triangle ids that
-    overlap the box, ascending, -1 in the slots past count; count [n] (uint32; an int32 tensor for torch). geom: for the rows of
+    """The rows of TriangleHierarchy.boxTriangles and .triTriangles: tri [n, k] int32 (numpy array or torch tensor), the lowest triangle ids that
+    overlap the box (meet the query triangle), ascending, -1 in the slots past count; count [n] (uint32; an int32 tensor for torch). geom: for the rows of
     InstanceWorld.trianglesInBox the int32 [n, k] array / tensor of each slot's instance (-1 past count; tri is that instance's
     id; the rows ascend in (geom, tri)); None for a single hierarchy's."""
 

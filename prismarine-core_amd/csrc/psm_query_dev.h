@@ -49,6 +49,9 @@ int box_launch(psm_ctx* c, int mode, uint32_t grid, const QueryArgs& a);
 // sweep.hip: the launch of a sweep kernel (any: whether there is a contact, else the first) for query.hip's host path; a.rays holds
 // the sweeps where a ray's two float4 are
 int sweep_launch(psm_ctx* c, bool any, uint32_t grid, const QueryArgs& a);
+// tri.hip: the launch of a triangle-query kernel (mode: 0 overlaps, 1 count, 2 triangles) for query.hip's host path; a.rays holds
+// the query triangles, three float4 each, a.samples is the triangles query's k
+int tri_launch(psm_ctx* c, int mode, uint32_t grid, const QueryArgs& a);
 
 // tri_test (trace.hip) operation for operation, with invDev = 1 / det instead of 1 / (max(|det|, 1e-6) * sign(det)) and without
 // its `t >= -PZERO` rule (the caller's window decides). det == 0 is a miss; u, v, u + v keep the 1e-5 tolerances. Where

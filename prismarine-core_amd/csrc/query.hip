@@ -837,18 +837,21 @@ const QueryDesc QUERY_DESC[] = {{"psm_bvh_intersect_dev", "rays", "hits", 16, fa
                                 {"psm_bvh_box_count_dev", "boxes", "counts", 4, false},
                                 {"psm_bvh_box_triangles_dev", "boxes", "tris", 4, false},
                                 {"psm_bvh_sweep_sphere_dev", "sweeps", "hits", 16, false},
-                                {"psm_bvh_sweep_occluded_dev", "sweeps", nullptr, 1, false}};
+                                {"psm_bvh_sweep_occluded_dev", "sweeps", nullptr, 1, false},
+                                {"psm_bvh_tri_overlaps_dev", "triangles", nullptr, 1, false},
+                                {"psm_bvh_tri_count_dev", "triangles", "counts", 4, false},
+                                {"psm_bvh_tri_triangles_dev", "triangles", "tris", 4, false}};
 
 // The data checks every query shares, under the entry point's name: in / out must be non-NULL, in 16-byte aligned, out as its
 // kind asks (a psm_hit 16 bytes, a count 4); samples (the inside kinds only): 1, 3 or 5; the k-best kinds' k travels as
 // samples: 1 .. PSM_QUERY_K_MAX. index: what the per-query index array (d_geom: the kinds with a psm_hit output only; the
-// k-best kinds' and the box triangles query's d_count) is called in the messages, NULL for a query that has none. A batch that passes makes the context's
+// k-best kinds' and the box and triangle families' triangles queries' d_count) is called in the messages, NULL for a query that has none. A batch that passes makes the context's
 // device the current one.
 int check_data(psm_ctx* c, const char* name, const char* index, QueryKind kind, const void* d_in, const void* d_out, const int32_t* d_geom,
                uint32_t samples) {
     const QueryDesc& k = QUERY_DESC[kind];
     char msg[128];
-    const bool with_geom = index && (k.out_align == 16 || kind == Q_BOX_TRIS);   // (the triangles query: int32 rows and counts)
+    const bool with_geom = index && (k.out_align == 16 || kind == Q_BOX_TRIS || kind == Q_TRI_TRIS);   // (the triangles queries: int32 rows and counts)
     if (!d_in || !d_out || (with_geom && !d_geom)) {
         snprintf(msg, sizeof msg, "%s: NULL pointer", name);
         return set_err(c, PSM_ERR_INVALID, msg);
@@ -868,7 +871,7 @@ int check_data(psm_ctx* c, const char* name, const char* index, QueryKind kind, 
         snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", name);
         return set_err(c, PSM_ERR_INVALID, msg);
     }
-    if ((kind == Q_FIRST_HITS || kind == Q_NEAREST || kind == Q_BOX_TRIS) && (samples == 0 || samples > PSM_QUERY_K_MAX)) {
+    if ((kind == Q_FIRST_HITS || kind == Q_NEAREST || kind == Q_BOX_TRIS || kind == Q_TRI_TRIS) && (samples == 0 || samples > PSM_QUERY_K_MAX)) {
         snprintf(msg, sizeof msg, "%s: k must be 1 .. %d", name, PSM_QUERY_K_MAX);
         return set_err(c, PSM_ERR_INVALID, msg);
     }
@@ -911,20 +914,23 @@ bool too_deep(const psm_bvh* b) { return depth_bound(b) > QSTACK_MAX; }
 // A query of one hierarchy: n == 0 is answered before anything else is looked at; then the data, the state, the depth.
 // The k-best kinds (kbest.hip) come through here too: samples is their k, d_out their [n][k] records, d_count their counts;
 // and the box kinds (box.hip): d_in the boxes, and for the triangles query samples = k, d_out the [n][k] ids, d_count the counts;
-// and the sweep kinds (sweep.hip): d_in the sweeps.
+// and the sweep kinds (sweep.hip): d_in the sweeps; and the triangle kinds (tri.hip): d_in the query triangles, the rest as the box
+// kinds.
 int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, void* d_out, uint32_t samples = 0, uint32_t* d_count = nullptr) {
     if (!b) return PSM_ERR_INVALID;
     if (n == 0) return PSM_OK;
     psm_ctx* c = b->ctx;
     const bool points = QUERY_DESC[kind].points, kbest = kind == Q_FIRST_HITS || kind == Q_NEAREST;
     const bool box = kind >= Q_BOX_ANY && kind <= Q_BOX_TRIS, sweep = kind == Q_SWEEP || kind == Q_SWEEP_ANY;
-    const bool counted = kbest || kind == Q_BOX_TRIS;
+    const bool tri = kind >= Q_TRI_ANY && kind <= Q_TRI_TRIS;
+    const bool counted = kbest || kind == Q_BOX_TRIS || kind == Q_TRI_TRIS;
     int rc = check_data(c, QUERY_DESC[kind].name, counted ? "counts" : nullptr, kind, d_in, d_out, (const int32_t*)d_count, samples);
     if (rc != PSM_OK) return rc;
     if (!b->built)
-        return set_err(c, PSM_ERR_STATE, box ? "box query before build" : sweep ? "sweep query before build" : points ? "point query before build" : "ray query before build");
+        return set_err(c, PSM_ERR_STATE, box ? "box query before build" : tri ? "triangle query before build" : sweep ? "sweep query before build" : points ? "point query before build" : "ray query before build");
     if (too_deep(b))
         return set_err(c, PSM_ERR_CAPACITY, box      ? "box query: hierarchy deeper than the query stack"
+                                            : tri    ? "triangle query: hierarchy deeper than the query stack"
                                             : sweep  ? "sweep query: hierarchy deeper than the query stack"
                                             : points ? "point query: hierarchy deeper than the query stack"
                                                      : "ray query: hierarchy deeper than the query stack");
@@ -942,6 +948,10 @@ int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, void* d_out, u
         return box_launch(c, (int)kind - (int)Q_BOX_ANY, grid, qa);
     }
     if (sweep) return sweep_launch(c, kind == Q_SWEEP_ANY, grid, qa);   // (sweep.hip)
+    if (tri) {   // (tri.hip; the triangles query's rows are d_out, its counts d_count)
+        if (kind == Q_TRI_TRIS) qa.count = d_count;
+        return tri_launch(c, (int)kind - (int)Q_TRI_ANY, grid, qa);
+    }
     return launch(c, BVH_KERNELS, kind, grid, qa);
 }
 
@@ -1106,6 +1116,18 @@ int psm_bvh_box_count_dev(psm_bvh* bvh, const psm_box_query* d_boxes, size_t n, 
 
 int psm_bvh_box_triangles_dev(psm_bvh* bvh, const psm_box_query* d_boxes, size_t n, uint32_t k, int32_t* d_tris, uint32_t* d_count) {
     return psm::query(bvh, psm::Q_BOX_TRIS, d_boxes, n, d_tris, k, d_count);
+}
+
+int psm_bvh_tri_overlaps_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t n, uint8_t* d_hit) {
+    return psm::query(bvh, psm::Q_TRI_ANY, d_tris, n, d_hit);
+}
+
+int psm_bvh_tri_count_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t n, uint32_t* d_count) {
+    return psm::query(bvh, psm::Q_TRI_COUNT, d_tris, n, d_count);
+}
+
+int psm_bvh_tri_triangles_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t n, uint32_t k, int32_t* d_ids, uint32_t* d_count) {
+    return psm::query(bvh, psm::Q_TRI_TRIS, d_tris, n, d_ids, k, d_count);
 }
 
 int psm_bvh_sweep_sphere_dev(psm_bvh* bvh, const psm_sweep_query* d_sweeps, size_t n, psm_hit* d_hits) {

@@ -49,6 +49,12 @@ rays; the fraction that touches and the fraction that touches at t = 0. No ratio
 the stress scene (STRESS_TRIS triangles, default 10 M): SWEEP_N (2 M) sweeps along the camera's primary rays with radii of 0.1 %,
 1 % and 5 % of the scene's diagonal, each alternated A B A B (medians of REPS) with psm_bvh_intersect_dev / psm_bvh_occluded_dev
 on the same rays -- the floor a sweep cannot beat --, and the fractions that touch at all and that touch at t = 0.
+`query_bench.py triangles`: the triangle queries (psm_bvh_tri_overlaps_dev / psm_bvh_tri_count_dev / psm_bvh_tri_triangles_dev) on the
+Sponza-class scene and the stress scene (STRESS_TRIS triangles, default 10 M), the three queries (triangles at k = 4 and 16), each
+alternated A B A B (medians of REPS) with boxCount / boxTriangles over the same triangles' bounding boxes -- the stand-in a caller
+had, a superset -- on two query sets: a second mesh of small triangles, a torus (TRI_TORUS_NU x TRI_TORUS_NV quads) placed to cut
+through the scene, and TRI_SLANTED (4 096) scene-sized slanted triangles, where the bounding box is a poor proxy; for each the
+fraction of queries that report and the ratio of box count to triangle count. No ratio is fixed in advance.
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -844,6 +850,81 @@ def boxes():
     print(json.dumps(out))
 
 
+def triangles():
+    lib = psm.lib()
+    out = {"mode": "triangles", "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+    stress_tris = int(os.environ.get("STRESS_TRIS", "10000000"))
+    nu, nv = int(os.environ.get("TRI_TORUS_NU", "512")), int(os.environ.get("TRI_TORUS_NV", "256"))
+    slanted = int(os.environ.get("TRI_SLANTED", "4096"))
+    for scene_name, sc in (("sponza", scenes.sponza_like()), ("stress", scenes.stress(stress_tris))):
+        ctx = psm.Context(0)
+        th = psm.TriangleHierarchy(ctx)
+        th.allocate(sc["tris"].shape[0])
+        th.loadTriangles(sc["tris"], sc["normals"], sc["mats"])
+        th.build()
+        v = sc["tris"].reshape(-1, 3)
+        lo, hi = v.min(0).astype(np.float64), v.max(0).astype(np.float64)
+        centre, ext = 0.5 * (lo + hi), hi - lo
+        out[scene_name + "_tris"] = int(th.info().leaf_count)
+        rng = np.random.RandomState(11)
+        # a second mesh cutting through the scene: a torus around the vertical axis through the centre, tilted
+        R = 0.25 * float(ext.max())
+        t = torus(nu, nv, R, 0.4 * R).reshape(-1, 3).astype(np.float64)
+        tilt = np.array([[1, 0, 0], [0, np.cos(0.5), -np.sin(0.5)], [0, np.sin(0.5), np.cos(0.5)]])
+        mesh = (t @ tilt.T + centre).reshape(-1, 3, 3)
+        # scene-sized slanted triangles: the vertices anywhere within a fifth of the extent of a point of the scene
+        big = rng.uniform(lo, hi, (slanted, 1, 3)) + rng.uniform(-0.2, 0.2, (slanted, 3, 3)) * ext
+        for set_name, q in (("torus", mesh), ("slanted", big)):
+            q = q.astype(np.float32)
+            n = q.shape[0]
+            rec = np.zeros((n, 3, 4), np.float32)
+            rec[:, :, 0:3] = q
+            b = np.zeros((n, 8), np.float32)
+            b[:, 0:3], b[:, 4:7] = q.min(axis=1), q.max(axis=1)
+            hs = [ctx.buf_alloc(x) for x in (48 * n, 32 * n, n, 4 * n, 4 * 16 * n)]
+            p_tri, p_box, p_flag, p_count, p_rows = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in hs)
+            ctx.buf_upload(hs[0], rec.reshape(n, 12))
+            ctx.buf_upload(hs[1], b)
+            size = C.c_size_t(n)
+
+            def overlaps():
+                ctx.check(lib.psm_bvh_tri_overlaps_dev(th._h, p_tri, size, p_flag), "psm_bvh_tri_overlaps_dev")
+
+            def count():
+                ctx.check(lib.psm_bvh_tri_count_dev(th._h, p_tri, size, p_count), "psm_bvh_tri_count_dev")
+
+            def tri_rows(k):
+                return lambda: ctx.check(lib.psm_bvh_tri_triangles_dev(th._h, p_tri, size, C.c_uint32(k), p_rows, p_count),
+                                         "psm_bvh_tri_triangles_dev")
+
+            def box_count():
+                ctx.check(lib.psm_bvh_box_count_dev(th._h, p_box, size, p_count), "psm_bvh_box_count_dev")
+
+            def box_rows(k):
+                return lambda: ctx.check(lib.psm_bvh_box_triangles_dev(th._h, p_box, size, C.c_uint32(k), p_rows, p_count),
+                                         "psm_bvh_box_triangles_dev")
+            key = "%s_%s_" % (scene_name, set_name)
+            out[key + "queries"] = n
+            for name, fn, beside, other in (("overlaps", overlaps, "box_count", box_count), ("count", count, "box_count", box_count),
+                                            ("triangles_k4", tri_rows(4), "box_triangles_k4", box_rows(4)),
+                                            ("triangles_k16", tri_rows(16), "box_triangles_k16", box_rows(16))):
+                out[key + name + "_ms"], out[key + beside + "_beside_" + name + "_ms"] = abab(ctx, fn, other)
+            overlaps()
+            out[key + "overlaps_fraction"] = round(float(ctx.buf_download(hs[2], np.uint8, n).mean()), 4)
+            count()
+            tri_total = float(ctx.buf_download(hs[3], np.uint32, n).astype(np.float64).sum())
+            box_count()
+            box_counts = ctx.buf_download(hs[3], np.uint32, n)
+            out[key + "box_reports_fraction"] = round(float((box_counts > 0).mean()), 4)
+            out[key + "mean_count"], out[key + "box_mean_count"] = round(tri_total / n, 3), round(float(box_counts.mean()), 3)
+            out[key + "box_count_over_count"] = round(float(box_counts.astype(np.float64).sum()) / max(tri_total, 1.0), 2)
+            for h in hs:
+                ctx.buf_free(h)
+        th.close()
+        ctx.close()
+    print(json.dumps(out))
+
+
 def sweeps():
     lib = psm.lib()
     out = {"mode": "sweeps", "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
@@ -1115,4 +1196,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles}.get(" ".join(sys.argv[1:]), main)()
