@@ -54,5 +54,13 @@ namespace NSM {
         // moved into each instance as a ray is and judged by the single hierarchy's sweep test; the flat lists have no such query
         int sphereCast(const psm_sweep_query * d_sweeps, size_t n, psm_hit * d_hits, int32_t * d_inst);
         int sphereCastOccluded(const psm_sweep_query * d_sweeps, size_t n, uint8_t * d_hit);
+        // whether / how many / which (instance, triangle) pairs meet each of n WORLD triangles (closed: touching counts): the query
+        // triangle is never moved, each candidate triangle is posed forward and judged by the single hierarchy's triangle test;
+        // trianglesOnTriangle: 1 <= k <= PSM_QUERY_K_MAX, d_tri and d_inst [n][k] = the lowest (inst, tri) that count, ascending,
+        // then -1 in both, d_count [n] = the slots filled (psm_world_tri_overlaps_dev / psm_world_tri_count_dev /
+        // psm_world_tri_triangles_dev); the flat lists have no such query
+        int overlapsTriangle(const psm_tri_query * d_tris, size_t n, uint8_t * d_hit);
+        int countOnTriangle(const psm_tri_query * d_tris, size_t n, uint32_t * d_count);
+        int trianglesOnTriangle(const psm_tri_query * d_tris, size_t n, uint32_t k, int32_t * d_tri, int32_t * d_inst, uint32_t * d_count);
     };
 }

@@ -91,4 +91,19 @@ namespace NSM {
         check(rc, "InstanceWorld::sphereCastOccluded");
         return rc;
     }
+    inline int InstanceWorld::overlapsTriangle(const psm_tri_query * d_tris, size_t n, uint8_t * d_hit) {
+        const int rc = psm_world_tri_overlaps_dev(world, d_tris, n, d_hit);
+        check(rc, "InstanceWorld::overlapsTriangle");
+        return rc;
+    }
+    inline int InstanceWorld::countOnTriangle(const psm_tri_query * d_tris, size_t n, uint32_t * d_count) {
+        const int rc = psm_world_tri_count_dev(world, d_tris, n, d_count);
+        check(rc, "InstanceWorld::countOnTriangle");
+        return rc;
+    }
+    inline int InstanceWorld::trianglesOnTriangle(const psm_tri_query * d_tris, size_t n, uint32_t k, int32_t * d_tri, int32_t * d_inst, uint32_t * d_count) {
+        const int rc = psm_world_tri_triangles_dev(world, d_tris, n, k, d_tri, d_inst, d_count);
+        check(rc, "InstanceWorld::trianglesOnTriangle");
+        return rc;
+    }
 }

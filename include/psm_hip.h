@@ -558,7 +558,7 @@ int psm_bvh_sweep_occluded_dev(psm_bvh* bvh, const psm_sweep_query* d_sweeps, si
 
 /* triangle queries against a built hierarchy (new; no reference counterpart): whether, how many and which of
  * the hierarchy's triangles meet a given triangle -- the narrow phase of mesh against mesh -- on the same leaves, stack, context
- * and checks as the queries above. Flat scenes, instanced lists and worlds have none. Semantics:
+ * and checks as the queries above. A world has them over its posed instances (psm_world_tri_*_dev below); flat scenes and instanced lists have none. Semantics:
  *   - a query {a, b, c} is valid iff its nine numbers are finite; a degenerate query triangle (a segment, a point) is valid. An
  *     invalid query answers 0, 0, or count 0 with a row of -1: never an error, as for invalid rays, points and boxes. The pads
  *     are not read
@@ -595,7 +595,8 @@ int psm_bvh_sweep_occluded_dev(psm_bvh* bvh, const psm_sweep_query* d_sweeps, si
  *     ascending, then -1; d_count[i] = min(k, c). With k >= c the row is the complete list; the row for k is the first k slots of
  *     the row for any larger k
  *   - nothing depends on the traversal order: a flag, a sum, the lowest ids
- *   - not covered: the intersection segment itself, a posed query mesh in one call, k > PSM_QUERY_K_MAX
+ *   - not covered: the intersection segment itself, a posed query mesh in one call, k > PSM_QUERY_K_MAX, flat scenes and
+ *     instanced lists
  *   - k == 0 or k > PSM_QUERY_K_MAX: PSM_ERR_INVALID, nothing is launched. d_tris 16-byte, d_count and d_ids 4-byte aligned;
  *     everything else (NULL checks, n = 0, PSM_ERR_STATE before the first build -- "triangle query before build" --,
  *     PSM_ERR_CAPACITY for a hierarchy deeper than the query stack, stream order, capture, refit, 0 / 1 leaves) as for the
@@ -833,6 +834,38 @@ int psm_world_box_triangles_dev(psm_world* world, const psm_box_query* d_boxes, 
  *     launches nothing and leaves the output buffers untouched */
 int psm_world_sweep_sphere_dev(psm_world* world, const psm_sweep_query* d_sweeps, size_t n, psm_hit* d_hits, int32_t* d_inst);
 int psm_world_sweep_occluded_dev(psm_world* world, const psm_sweep_query* d_sweeps, size_t n, uint8_t* d_hit);
+
+/* triangle queries over a world (new; no reference counterpart): whether, how many and which (instance,
+ * triangle) pairs of a world meet a triangle given in WORLD space, in one launch: the narrow phase of a mesh against the posed
+ * bodies of a world. The contract is the box queries' over a world with the candidate test of the triangle queries against a
+ * built hierarchy. Flat scenes and instanced lists (psm_scene_*, psm_instances_*) have no triangle query. Semantics:
+ *   - a query is a psm_tri_query {a, b, c} in world space and is never moved. It is valid iff its nine numbers are finite; a
+ *     segment or a point is a valid query; an invalid query answers 0, 0, or count 0 with rows of -1. The query is not moved,
+ *     so there is no per-instance validity
+ *   - the candidates are the pairs (inst, tri): inst an index of the world's ordered list, tri a leaf of that instance's
+ *     hierarchy (PSM_BVH_LEAF_TRI), stored as v0, e1, e2
+ *   - with m = world_from_object[12] of the instance the candidate counts iff
+ *       tri_tri(fwd_point(m, v0), fwd_vec(m, e1), fwd_vec(m, e2), a, b, c)
+ *     fwd_point and fwd_vec the functions of the box queries over a world, tri_tri the function of the triangle queries above,
+ *     all unchanged, bit for bit, in float32, one rounding per operation, nothing fused. The edges are R e1 and R e2 -- not
+ *     differences of posed vertices
+ *   - the flat answer, which a world reproduces exactly, is taken over the ordered instance list and all leaves of every member:
+ *       overlaps: d_hit[i] = 1 iff some candidate counts, else 0
+ *       count: d_count[i] = the number c of candidates that count, summed over the instances (uint32)
+ *       triangles: 1 <= k <= PSM_QUERY_K_MAX; rows i of d_tri and d_inst ([n][k] int32 each) hold the min(k, c) LOWEST pairs
+ *         (inst, tri) that count in lexicographic order, ascending (inst and tri compared unsigned); the slots past
+ *         d_count[i] = min(k, c) hold -1 in both. The row for k is a prefix of the row for any larger k; coincident instances
+ *         list every shared triangle once per instance, the lowest instance first
+ *   - nothing depends on the tree, its prune or the order of the walk: a flag, a sum, the lowest pairs
+ *   - an identity world of one answers as psm_bvh_tri_overlaps_dev / _count_dev / _triangles_dev of its hierarchy, bit for bit
+ *   - k == 0 or k > PSM_QUERY_K_MAX: PSM_ERR_INVALID, nothing is launched, as for the k-best queries. d_tris 16-byte, d_count,
+ *     d_tri and d_inst 4-byte aligned, none NULL; the stale check, the depth budget, n == 0, stream order and capture as for the
+ *     other world queries; an empty world answers 0 / 0 / count 0 and rows of -1 without a query kernel. A refused call
+ *     launches nothing and leaves the output buffers untouched */
+int psm_world_tri_overlaps_dev(psm_world* world, const psm_tri_query* d_tris, size_t n, uint8_t* d_hit);
+int psm_world_tri_count_dev(psm_world* world, const psm_tri_query* d_tris, size_t n, uint32_t* d_count);
+int psm_world_tri_triangles_dev(psm_world* world, const psm_tri_query* d_tris, size_t n, uint32_t k, int32_t* d_tri, int32_t* d_inst,
+                                uint32_t* d_count);
 
 /* ---------------------------------------------------------------------------------------------
  * several frames in flight (new; DESIGN.md "lanes")

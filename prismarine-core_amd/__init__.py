@@ -40,6 +40,7 @@ EXPORTS = [
     "psm_world_inside_dev", "psm_world_signed_distance_dev", "psm_world_first_hits_dev", "psm_world_nearest_dev",
     "psm_world_box_overlaps_dev", "psm_world_box_count_dev", "psm_world_box_triangles_dev",
     "psm_world_sweep_sphere_dev", "psm_world_sweep_occluded_dev",
+    "psm_world_tri_overlaps_dev", "psm_world_tri_count_dev", "psm_world_tri_triangles_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -472,8 +473,9 @@ class TriangleHierarchy:
         [n, 3, 3] or [n, 9], the vertices a, b, c of each. Closed (touching counts); a segment or a point is a valid query
         triangle, one with a non-finite number meets nothing. The test is a separating-axis test over 20 axes in float32
         (psm_hip.h "triangle queries"). A bool array / tensor. numpy in: numpy out; torch device tensors in: torch tensors out on
-        the same device, ordered against torch's current stream without synchronising (as intersect()). QueryScene,
-        InstancedScene and InstanceWorld have no triangle queries."""
+        the same device, ordered against torch's current stream without synchronising (as intersect()). QueryScene and
+        InstancedScene have no triangle queries; InstanceWorld has its own (overlapsTriangle / countOnTriangle /
+        trianglesOnTriangle: the query triangle in world space)."""
         return self._tri_query(tris, "bool", "psm_bvh_tri_overlaps_dev")
 
     def triCount(self, tris):
@@ -962,9 +964,10 @@ class InstanceWorld(QueryScene):
     hierarchies as they are when set: after a member was rebuilt, reloaded or reallocated the next query raises PsmError until
     setInstances() is called again; after a member was REFITTED call refresh(). Methods, arguments and numpy / torch placement:
     QueryScene's; QueryHits.geom is the index of the winning instance. A world also has the k-best queries, firstHits() and
-    nearest(), the box queries overlapsBox(), countInBox() and trianglesInBox() over world-space boxes, and the sphere sweeps
-    sphereCast() and sphereCastOccluded() along world-space lines, which the flat lists (QueryScene, InstancedScene) have
-    not."""
+    nearest(), the box queries overlapsBox(), countInBox() and trianglesInBox() over world-space boxes, the sphere sweeps
+    sphereCast() and sphereCastOccluded() along world-space lines, and the triangle queries overlapsTriangle(),
+    countOnTriangle() and trianglesOnTriangle() on world-space triangles, which the flat lists (QueryScene, InstancedScene)
+    have not."""
 
     def __init__(self, ctx, entries, capacity=None):
         self.ctx = ctx
@@ -1078,6 +1081,30 @@ class InstanceWorld(QueryScene):
         predicate isfinite(sphereCast().t), the walk ending at the first contact found. A bool array / tensor. Arguments and
         placement as sphereCast()."""
         return self._query(origins, directions, radius, tmax, "bool", "psm_bvh_sweep_occluded_dev")
+
+    def overlapsTriangle(self, tris):
+        """Whether some triangle of some instance meets each WORLD triangle (psm_world_tri_overlaps_dev): tris [n, 3, 3] or
+        [n, 9], the vertices a, b, c of each. The query stays in world space; each candidate triangle is posed forward in float32
+        (v0' = R v0 + T, e1' = R e1, e2' = R e2) and judged by triOverlaps()'s test (psm_hip.h "triangle queries over a world").
+        Closed; a segment or a point is a valid query; one with a non-finite number meets nothing. A bool array / tensor; numpy /
+        torch placement as intersect()."""
+        return self._tri_query(tris, "bool", "psm_bvh_tri_overlaps_dev")
+
+    def countOnTriangle(self, tris):
+        """The number of (instance, triangle) pairs that meet each world triangle, summed over the instances
+        (psm_world_tri_count_dev). A uint32 array, or an int32 tensor for torch tensors. Arguments as overlapsTriangle()."""
+        return self._tri_query(tris, "count", "psm_bvh_tri_count_dev")
+
+    def trianglesOnTriangle(self, tris, k):
+        """Which triangles of which instances meet each world triangle (psm_world_tri_triangles_dev): of the pairs
+        countOnTriangle() counts, the min(k, count) lowest in (instance, tri), ascending -- coincident instances list a shared
+        triangle once per instance, the lowest instance first. k: 1 .. QUERY_K_MAX. Returns QueryTriLists: tri and geom (the
+        slot's instance) [n, k] int32, -1 in both past count, and count [n]. Arguments as overlapsTriangle()."""
+        if not 1 <= _k(k, "psm_world_tri_triangles_dev") <= QUERY_K_MAX:   # (refused here: no call is made)
+            raise PsmError("psm_world_tri_triangles_dev: k must be 1 .. %d" % QUERY_K_MAX)
+        return self._tri_query(tris, "tris", "psm_bvh_tri_triangles_dev", k)
+
+    _tri_query = TriangleHierarchy._tri_query
 
     def _call(self, name, d_in, n, extra, d_out, d_geom):
         name = name.replace("psm_bvh_", "psm_world_")

@@ -721,11 +721,12 @@ struct psm_world {
 namespace psm {
 namespace {
 
-const char* const WORLD_NAME[14] = {"psm_world_intersect_dev", "psm_world_occluded_dev", "psm_world_closest_point_dev",
+const char* const WORLD_NAME[17] = {"psm_world_intersect_dev", "psm_world_occluded_dev", "psm_world_closest_point_dev",
                                     "psm_world_within_dev", "psm_world_count_hits_dev", "psm_world_inside_dev",
                                     "psm_world_signed_distance_dev", "psm_world_first_hits_dev", "psm_world_nearest_dev",
                                     "psm_world_box_overlaps_dev", "psm_world_box_count_dev", "psm_world_box_triangles_dev",
-                                    "psm_world_sweep_sphere_dev", "psm_world_sweep_occluded_dev"};
+                                    "psm_world_sweep_sphere_dev", "psm_world_sweep_occluded_dev",
+                                    "psm_world_tri_overlaps_dev", "psm_world_tri_count_dev", "psm_world_tri_triangles_dev"};
 const Kernels<WorldArgs> WORLD_KERNELS = {{world_query_closest, world_query_any, world_query_point, world_query_within,
                                            world_query_count, world_query_inside, world_query_sign}};
 
@@ -815,7 +816,8 @@ int world_upload_and_build(psm_world* w, const char* name) {
 // through check_data's index slot as "counts", as in query.hip's query(); d_inst is then checked here). And the box kinds
 // (world_box.hip): d_in the world boxes; the triangles query as a k-best kind with int32 rows: d_out the [n][k] triangles,
 // d_inst the [n][k] instances, d_count the counts. And the sweep kinds (world_sweep.hip): d_in the sweeps, a 16-byte record and
-// d_inst, or a byte, as the closest-hit and the any-hit kinds
+// d_inst, or a byte, as the closest-hit and the any-hit kinds. And the triangle kinds (world_tri.hip): d_in the world triangles
+// (psm_tri_query), everything else as the box kinds
 int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_inst, uint32_t samples = 0,
                 uint32_t* d_count = nullptr) {
     if (!w) return PSM_ERR_INVALID;
@@ -823,7 +825,8 @@ int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* 
     psm_ctx* c = w->ctx;
     const char* name = WORLD_NAME[kind];
     const bool box = kind >= Q_BOX_ANY && kind <= Q_BOX_TRIS, sweep = kind == Q_SWEEP || kind == Q_SWEEP_ANY;
-    const bool kbest = kind == Q_FIRST_HITS || kind == Q_NEAREST || kind == Q_BOX_TRIS;   // (the kinds with rows and counts)
+    const bool tri = kind >= Q_TRI_ANY && kind <= Q_TRI_TRIS;
+    const bool kbest = kind == Q_FIRST_HITS || kind == Q_NEAREST || kind == Q_BOX_TRIS || kind == Q_TRI_TRIS;   // (the kinds with rows and counts)
     int rc = kbest ? check_data(c, name, "counts", kind, d_in, d_out, (const int32_t*)d_count, samples)
                    : check_data(c, name, "inst", kind, d_in, d_out, d_inst, samples);
     if (rc != PSM_OK) return rc;
@@ -835,7 +838,7 @@ int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* 
     const size_t rows = kbest ? n * samples : n;   // (samples <= PSM_QUERY_K_MAX here)
     if (w->count == 0) {   // an empty world: every query misses, no query kernel runs
         const unsigned per = QUERY_DESC[kind].out_align;
-        if (kind == Q_BOX_TRIS) {   // rows of -1 in both arrays
+        if (kind == Q_BOX_TRIS || kind == Q_TRI_TRIS) {   // rows of -1 in both arrays
             PSM_HIP(c, hipMemsetAsync(d_out, 0xFF, rows * sizeof(int32_t), c->stream));
             PSM_HIP(c, hipMemsetAsync(d_inst, 0xFF, rows * sizeof(int32_t), c->stream));
         } else if (per == 16) world_fill_miss<<<(unsigned)((rows + 255) / 256), 256, 0, c->stream>>>((float4*)d_out, d_inst, rows);
@@ -859,6 +862,10 @@ int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* 
         return world_box_launch(c, (int)kind - (int)Q_BOX_ANY, grid, a);
     }
     if (sweep) return world_sweep_launch(c, kind == Q_SWEEP_ANY, grid, a);   // (world_sweep.hip)
+    if (tri) {   // (world_tri.hip; rows, counts and the list's LDS as the box kinds')
+        if (kind == Q_TRI_TRIS) a.count = d_count;
+        return world_tri_launch(c, (int)kind - (int)Q_TRI_ANY, grid, a);
+    }
     if (kbest) {   // the list: k x 64 x (8 + 4) B of dynamic LDS per wave, beside the stack
         a.count = d_count;
         const size_t lds = (size_t)samples * QUERY_BLOCK * (sizeof(uint2) + sizeof(uint32_t));
@@ -1022,6 +1029,16 @@ int psm_world_box_count_dev(psm_world* w, const psm_box_query* d_boxes, size_t n
 int psm_world_box_triangles_dev(psm_world* w, const psm_box_query* d_boxes, size_t n, uint32_t k, int32_t* d_tri, int32_t* d_inst,
                                 uint32_t* d_count) {
     return psm::world_query(w, psm::Q_BOX_TRIS, d_boxes, n, d_tri, d_inst, k, d_count);
+}
+int psm_world_tri_overlaps_dev(psm_world* w, const psm_tri_query* d_tris, size_t n, uint8_t* d_hit) {
+    return psm::world_query(w, psm::Q_TRI_ANY, d_tris, n, d_hit, nullptr);
+}
+int psm_world_tri_count_dev(psm_world* w, const psm_tri_query* d_tris, size_t n, uint32_t* d_count) {
+    return psm::world_query(w, psm::Q_TRI_COUNT, d_tris, n, d_count, nullptr);
+}
+int psm_world_tri_triangles_dev(psm_world* w, const psm_tri_query* d_tris, size_t n, uint32_t k, int32_t* d_tri, int32_t* d_inst,
+                                uint32_t* d_count) {
+    return psm::world_query(w, psm::Q_TRI_TRIS, d_tris, n, d_tri, d_inst, k, d_count);
 }
 int psm_world_sweep_sphere_dev(psm_world* w, const psm_sweep_query* d_sweeps, size_t n, psm_hit* d_hits, int32_t* d_inst) {
     return psm::world_query(w, psm::Q_SWEEP, d_sweeps, n, d_hits, d_inst);

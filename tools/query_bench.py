@@ -55,6 +55,12 @@ alternated A B A B (medians of REPS) with boxCount / boxTriangles over the same 
 had, a superset -- on two query sets: a second mesh of small triangles, a torus (TRI_TORUS_NU x TRI_TORUS_NV quads) placed to cut
 through the scene, and TRI_SLANTED (4 096) scene-sized slanted triangles, where the bounding box is a poor proxy; for each the
 fraction of queries that report and the ratio of box count to triangle count. No ratio is fixed in advance.
+`query_bench.py worldtriangles`: the triangle queries of an instance world (psm_world_tri_overlaps_dev / psm_world_tri_count_dev /
+psm_world_tri_triangles_dev) on the worldboxes mode's world, the torus at 256 and 4 096 turned grid poses, the three queries
+(triangles at k = 4 and 16), each alternated A B A B (medians of REPS) with countInBox / trianglesInBox over the same triangles'
+bounding boxes -- the one-launch stand-in a caller had, a superset: context, not a bar -- on two query sets: a second torus posed
+WTRI_BODIES (64) times beside bodies of the world, so that the meshes cut, and WTRI_SLANTED (4 096) body-sized slanted triangles;
+for each the fraction of queries that report and the ratio of box-reported to triangle-reported pairs. No ratio is fixed in advance.
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -1062,6 +1068,92 @@ def worldboxes():
     print(json.dumps(out))
 
 
+def worldtriangles():
+    lib = psm.lib()
+    ctx = psm.Context(0)
+    tor = torus(48, 24, 0.7, 0.25)
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(tor.shape[0])
+    th.loadTriangles(tor)
+    th.build()
+    rng = np.random.RandomState(1)
+    bodies, slanted = int(os.environ.get("WTRI_BODIES", "64")), int(os.environ.get("WTRI_SLANTED", "4096"))
+    out = {"mode": "worldtriangles", "torus_triangles": int(tor.shape[0]), "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+
+    def turn():
+        q, r = np.linalg.qr(rng.normal(size=(3, 3)))
+        return q * np.sign(np.diag(r))
+    for poses_n in (256, 4096):
+        side = int(np.ceil(np.sqrt(poses_n)))      # the worldboxes mode's world: a grid of poses, each turned about a random axis
+        poses = np.zeros((poses_n, 3, 4), np.float32)
+        k_ = np.arange(poses_n)
+        for j in range(poses_n):
+            poses[j, :, :3] = turn()
+        poses[:, 0, 3], poses[:, 1, 3] = 2.5 * (k_ % side), 2.5 * (k_ // side)
+        lo = np.array([-1.25, -1.25, -1.25])
+        hi = np.array([2.5 * (side - 1) + 1.25, 2.5 * ((poses_n - 1) // side) + 1.25, 1.25])
+        wd = psm.InstanceWorld(ctx, [(th, m) for m in poses])
+        w = wd._w
+        # a second torus posed `bodies` times: turned, and set half a radius beside a body of the world, so the two meshes cut
+        mesh = []
+        for j in rng.choice(poses_n, bodies, replace=False):
+            at = poses[j, :, 3].astype(np.float64) + rng.uniform(-0.5, 0.5, 3)
+            mesh.append(tor.reshape(-1, 3).astype(np.float64) @ turn().T + at)
+        mesh = np.concatenate(mesh).reshape(-1, 3, 3)
+        # body-sized slanted triangles: the vertices anywhere within a body's radius of a point of the world
+        big = rng.uniform(lo, hi, (slanted, 1, 3)) + rng.uniform(-1.0, 1.0, (slanted, 3, 3))
+        for set_name, q in (("torus", mesh), ("slanted", big)):
+            q = q.astype(np.float32)
+            n = q.shape[0]
+            rec = np.zeros((n, 3, 4), np.float32)
+            rec[:, :, 0:3] = q
+            b = np.zeros((n, 8), np.float32)
+            b[:, 0:3], b[:, 4:7] = q.min(axis=1), q.max(axis=1)
+            hs = [ctx.buf_alloc(x) for x in (48 * n, 32 * n, n, 4 * n, 4 * 16 * n, 4 * 16 * n)]
+            p_tri, p_box, p_flag, p_count, p_rows, p_inst = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in hs)
+            ctx.buf_upload(hs[0], rec.reshape(n, 12))
+            ctx.buf_upload(hs[1], b)
+            size = C.c_size_t(n)
+
+            def overlaps():
+                ctx.check(lib.psm_world_tri_overlaps_dev(w, p_tri, size, p_flag), "psm_world_tri_overlaps_dev")
+
+            def count():
+                ctx.check(lib.psm_world_tri_count_dev(w, p_tri, size, p_count), "psm_world_tri_count_dev")
+
+            def tri_rows(k):
+                return lambda: ctx.check(lib.psm_world_tri_triangles_dev(w, p_tri, size, C.c_uint32(k), p_rows, p_inst, p_count),
+                                         "psm_world_tri_triangles_dev")
+
+            def box_count():
+                ctx.check(lib.psm_world_box_count_dev(w, p_box, size, p_count), "psm_world_box_count_dev")
+
+            def box_rows(k):
+                return lambda: ctx.check(lib.psm_world_box_triangles_dev(w, p_box, size, C.c_uint32(k), p_rows, p_inst, p_count),
+                                         "psm_world_box_triangles_dev")
+            key = "poses%d_%s_" % (poses_n, set_name)
+            out[key + "queries"] = n
+            for name, fn, beside, other in (("overlaps", overlaps, "box_count", box_count), ("count", count, "box_count", box_count),
+                                            ("triangles_k4", tri_rows(4), "box_triangles_k4", box_rows(4)),
+                                            ("triangles_k16", tri_rows(16), "box_triangles_k16", box_rows(16))):
+                out[key + name + "_ms"], out[key + beside + "_beside_" + name + "_ms"] = abab(ctx, fn, other)
+            overlaps()
+            out[key + "overlaps_fraction"] = round(float(ctx.buf_download(hs[2], np.uint8, n).mean()), 4)
+            count()
+            tri_total = float(ctx.buf_download(hs[3], np.uint32, n).astype(np.float64).sum())
+            box_count()
+            box_counts = ctx.buf_download(hs[3], np.uint32, n)
+            out[key + "box_reports_fraction"] = round(float((box_counts > 0).mean()), 4)
+            out[key + "mean_count"], out[key + "box_mean_count"] = round(tri_total / n, 3), round(float(box_counts.mean()), 3)
+            out[key + "box_count_over_count"] = round(float(box_counts.astype(np.float64).sum()) / max(tri_total, 1.0), 2)
+            for h in hs:
+                ctx.buf_free(h)
+        wd.close()
+    th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def worldsweeps():
     lib = psm.lib()
     ctx = psm.Context(0)
@@ -1196,4 +1288,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "worldtriangles": worldtriangles}.get(" ".join(sys.argv[1:]), main)()
