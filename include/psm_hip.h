@@ -360,6 +360,13 @@ int psm_rt_download_texels(psm_rt* rt, float* sum_rgba, float* coord_xy, int32_t
  *   - a hierarchy of 0 leaves misses everything; one of 1 leaf tests that leaf
  *   - after psm_bvh_refit the refitted boxes are used; as for every refit this is right only for triangles that moved within
  *     the build's bounds (the fit transform and the fp16 box padding are the build's)
+ *   - what is promised against a brute force over the leaves: exact on WELL-POSED hits. A hit (ray, triangle, t) is well-posed
+ *     iff the point origin + t direct, mapped by the build's transform (psm_bvh_info.transform), lies at most 2.5e-4 (half the
+ *     boxes' padding) outside the triangle's normalised bounding box on every axis. Every hit is, except those of a ray almost
+ *     in a triangle's plane, where det is rounding noise and t with it. A ray all of whose accepted hits are well-posed gets the
+ *     brute force's answer bit for bit. An ill-posed hit of a grazing ray may be reported or not, but is never invented (a
+ *     reported hit is a candidate of the brute force, with its u, v, t), and the closest and the any-hit answer never miss a
+ *     well-posed hit: the closest is no later in (t, tri) than the best well-posed one
  * Stream-ordered on the hierarchy's context, no host synchronisation (a query can be captured into a graph, except the first one
  * of a context, which allocates its stack area). The stack is sized to the builder's height bound (63 Morton bits + log2 of the
  * largest run of equal codes): no subtree is ever dropped. Any n; d_rays and d_hits 16-byte aligned (PSM_ERR_INVALID otherwise);
@@ -403,7 +410,10 @@ int psm_bvh_within_dev(psm_bvh* bvh, const psm_point_query* d_points, size_t n, 
  *   - count: d_count[i] = the number of candidates (the hierarchy's leaves, PSM_BVH_LEAF_TRI) that ray i hits inside its window:
  *     the triangle test and tmin <= t <= tmax of psm_bvh_occluded_dev, which asks "is there one?" of the same predicate. A ray
  *     that is invalid by the ray queries' rules (NaN, non-finite origin or direction, zero direction, tmin > tmax) counts 0; 0
- *     leaves: 0; 1 leaf: that leaf is tested. A sum of integers: it does not depend on the traversal order
+ *     leaves: 0; 1 leaf: that leaf is tested. A sum of integers: it does not depend on the traversal order. Exact on a ray all of
+ *     whose accepted hits are well-posed (the ray queries' rule above); otherwise between the number of well-posed hits and the
+ *     number of accepted ones -- an ill-posed hit of a grazing ray may be counted or not, and is never invented. The vote and
+ *     the sign below are exact for a point all of whose rays are such rays
  *   - inside: for point p the rays {p, tmin = 0, PSM_INSIDE_DIRECTIONS[k], tmax = +inf}, k = 0 .. samples - 1, are counted as
  *     above (each row normalised with normalize3 like every query ray's direction); a ray votes "inside" iff its count is odd,
  *     and d_inside[i] = 1 iff more than half of the rays vote so, else 0 (uint8_t, torch.bool-compatible). samples must be 1, 3

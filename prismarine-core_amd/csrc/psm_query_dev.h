@@ -97,15 +97,27 @@ PSM_D Row affine_row(const float* M, int k, v3 x) {
 // One axis of the ray in the build's normalised space, set up so that a box plane b gives its (inflated) distance in ONE fmaf:
 //   P = (M (o, 1)).k, D = (M (d, 0)).k      -- the affine map aabbmaker applied to the vertices (mat_vec with w = 1; the w row is
 //                                             never read), applied to the line o + t d: the slab distances are WORLD t
-//   lo plane: fmaf(b, inv, nlo) = (b - (P + h)) / D,  hi plane: fmaf(b, inv, nhi) = (b - (P - h)) / D
-// i.e. the box grown by h on both sides (for either sign of D). h covers the rounding of P, D and the slab arithmetic: each is a
+//   lo plane: fmaf(b, inv, nlo) = (b - (P + h)) / D,  hi plane: fmaf(b, inv, nhi) = (b - (P - h')) / D,  h' = h + 2^-12
+// i.e. the box grown by h below and h' above (for either sign of D; the constant: further down). h covers the rounding of P, D and the slab arithmetic: each is a
 // few ulps of |b| + S (S = |m0 ox| + |m1 oy| + |m2 oz| + |m3| bounds |P| and the rounding of its sum), and the error of D moves the
 // plane distance by t |dD| <= 3 eps t sum_j |M_kj d_j|, which for the fit transform (M's 3 x 3 part is diagonal unless the build's
 // optimisation matrix rotates) is 3 eps |b - P| <= 3 eps (1 + S). All of it is < 8 eps (2 + S); h = 2^-16 (2 + S) ~ 128 eps (2 + S)
-// -- with a 16x margin left for an optimisation matrix whose 3 x 3 part has a condition number up to ~16. A box is then dropped
-// only when its exact slab interval misses [tmin, limit]. The hit itself lies in its leaf's exact box: an accepted hit point is
-// within ~1e-5 edge lengths of its triangle (the u, v tolerances), and the leaf box is the triangle's padded by PZERO = 5e-4
-// before the fp16 rounding (<= 2.44e-4 in [0, 1]), >= 2.5e-4 normalised units of headroom.
+// -- with a 16x margin left for an optimisation matrix whose 3 x 3 part has a condition number up to ~16 (tests/test_ray_prune_cpu.py
+// holds the margin to a brute force under rotating, shearing and anisotropic matrices). A box is then dropped only when its exact
+// slab interval misses [tmin, limit].
+// Which hits lie in their leaf's box: the WELL-POSED ones -- a hit whose point o + t d, mapped by M, is at most 2.5e-4 (PZERO / 2)
+// outside its triangle's exact normalised bounding box on every axis (tests/ray_prune_model.py). Where |det| is
+// well above its rounding an accepted hit point is within ~1e-5 edge lengths of its triangle (the u, v tolerances) and is
+// well-posed; that holds for well-posed hits ONLY: for a ray almost in the triangle's plane det is noise, t with it, and the point
+// can be anywhere. Such a hit may be reported or not (it is never invented); only well-posed hits are promised.
+// The leaf box is the triangle's padded by PZERO = 5e-4 before the fp16 rounding. In [0.5, 1) that rounding takes at most
+// 2^-12 = 2.44e-4 of the padding: >= 2.5e-4 of headroom. But a leaf at the top of the scene has its padded corner in
+// [1, 1 + PZERO), where fp16's half-ulp is 2^-11 = 4.88e-4 and the corner can round down to 1.0: as little as 1.2e-5 of the
+// padding is left. Only a box's UPPER planes can lie there (a lower corner is a vertex less PZERO: below 1, and fp16 is finer
+// toward 0), so the hi plane's margin carries the constant 2^-12 on top of h (1.2e-5 + 2^-12 > 2.5e-4) and the lo plane's is h
+// alone: the box grown so holds every well-posed hit of its triangle wherever the box lies. (Without the constant a window
+// tmin = tmax = t lost such a hit on the deep fixture under a build matrix: DESIGN.md 4.5.) The points' gaps keep h alone: they
+// measure distances to the triangles themselves, which the boxes hold exactly.
 // A direction component under 1e-20 in magnitude is taken as +-1e-20 (no infinite reciprocal): the line moves by t * 1e-20,
 // below h for every t < 1e15.
 struct Axis {
@@ -119,7 +131,7 @@ PSM_D Axis ray_axis(const float* M, int k, v3 o, v3 d) {
     Axis a;
     a.inv = 1.0f / D;
     a.nlo = -(r.P + r.h) * a.inv;
-    a.nhi = (r.h - r.P) * a.inv;
+    a.nhi = ((r.h + 0x1p-12f) - r.P) * a.inv;
     return a;
 }
 

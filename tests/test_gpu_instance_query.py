@@ -11,9 +11,12 @@ import pytest
 import inside_query_model as IQ
 import instance_query_model as NQ
 import query_model as Q
+import ray_prune_model as RP
 import scene_query_model as SQ
 from test_gpu_fuzz import fuzz_case
 from test_gpu_inside_query import _scene_points
+from test_gpu_point_query import ROT_SCALE, SHEAR
+from test_gpu_point_query import _hier as _hier_opt
 from test_gpu_query import _camera_rays, _hier, _leaves, _nonfinite, _random_rays, _windows
 from test_gpu_scene_query import _same, _sizes
 from test_instance_query_cpu import BAKED_CASES
@@ -32,9 +35,9 @@ U = np.uint32
 class _Inst:
     """hierarchies over meshes, an InstancedScene of (hierarchy index, pose) entries, and the model's instances"""
 
-    def __init__(self, psm, ctx, meshes, entries):
+    def __init__(self, psm, ctx, meshes, entries, opts=None):
         self.psm, self.meshes = psm, [np.ascontiguousarray(t, F).reshape(-1, 3, 3) for t in meshes]
-        self.ths = [_hier(psm, ctx, t) for t in self.meshes]
+        self.ths = [_hier(psm, ctx, t) for t in self.meshes] if opts is None else [_hier_opt(psm, ctx, t, m) for t, m in zip(self.meshes, opts)]
         self.which = [k for k, _ in entries]
         self.scene = psm.InstancedScene(ctx, [(self.ths[k], m) for k, m in entries])
 
@@ -145,6 +148,37 @@ def test_instances_fuzz_soups(psm, ctx, seed, parts):
         tris = np.concatenate([tris] * parts)
     with _cut_and_posed(psm, ctx, tris, parts, 500 + seed) as sc:
         _all_cases(sc, tris, o[:192], d[:192], 300 + seed)
+
+
+@pytest.mark.parametrize("opt", [ROT_SCALE, SHEAR], ids=["rotate_scale", "shear"])
+def test_a_member_built_with_an_optimisation_matrix(psm, ctx, oracle, scenes, opt):
+    """One of three posed members built with a matrix: the file's yardsticks, bit for bit, on the rays that are fully well-posed
+    in every member's object space and on the points whose vote rays all are (tests/ray_prune_model.py; the other rays' contract
+    is the single hierarchy's, tests/test_gpu_ray_matrix.py); at most 1 % of the rays and of the points are left out"""
+    sm = scenes.sponza_like(3001)
+    tris = sm["tris"].reshape(-1, 3, 3)
+    pieces, _ = SQ.split(tris, _sizes(tris.shape[0], 3))
+    diag = float(np.linalg.norm(tris.reshape(-1, 3).max(0) - tris.reshape(-1, 3).min(0)))
+    with _Inst(psm, ctx, pieces, list(enumerate(_poses(73, 3, 0.05 * diag))), [None, opt, None]) as sc:
+        t = np.array(sc.ths[1].info().transform).reshape(4, 4)[:3, :3]
+        assert np.abs(t - np.diag(np.diag(t))).max() > 0.01
+        members = [(tr, lv, np.array(sc.ths[k].info().transform, F), m) for k, (tr, lv, m) in zip(sc.which, sc.insts())]
+        world = np.concatenate([NQ.posed(tr, m) for tr, _, _, m in members])     # (the grazing rays graze the POSED triangles)
+        rng = np.random.RandomState(62)
+        oo, od = _camera_rays(oracle, scenes, sm, 32, 16)
+        rays = RP.ray_classes(rng, world, oo, od, 512)
+        o, d = (np.concatenate([rays[c][k] for c in ("own", "random", "outside", "tilt1e-3", "tilt1e-5")]) for k in (0, 1))
+        keep = RP.fully_well_posed(members, o, d)
+        assert (~keep).sum() <= 0.01 * keep.size, int((~keep).sum())
+        o, d = o[keep], d[keep]
+        got = _check_rays(sc, o, d)
+        assert (got.geom == 1).sum() > 50 and (got.geom == 2).sum() > 50   # (the member with the matrix is hit, and another)
+        _check_rays(sc, o, d, *_windows(rng, got.t.copy(), o.shape[0]))
+        p = _scene_points(rng, world, 512)
+        sure = RP.vote_rays_well_posed(members, p, IQ.INSIDE_DIRECTIONS)
+        assert (~sure).sum() <= 0.01 * sure.size, int((~sure).sum())
+        _check_points(sc, p[sure])
+        _check_points(sc, p[sure], rng.uniform(0, 2.0, int(sure.sum())).astype(F), samples=(3,))
 
 
 @functools.lru_cache(maxsize=None)

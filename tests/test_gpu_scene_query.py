@@ -10,9 +10,12 @@ import pytest
 
 import inside_query_model as IQ
 import query_model as Q
+import ray_prune_model as RP
 import scene_query_model as SQ
 from test_gpu_fuzz import fuzz_case
 from test_gpu_inside_query import _scene_points
+from test_gpu_point_query import ROT_SCALE, SHEAR
+from test_gpu_point_query import _hier as _hier_opt
 from test_gpu_query import _camera_rays, _hier, _leaves, _nonfinite, _random_rays, _windows
 
 try:   # (imported before the library loads its HIP runtime, as tests/test_gpu_query.py)
@@ -31,9 +34,9 @@ U = np.uint32
 class _Scene:
     """hierarchies over the parts of a mesh, the scene over them, and the model's geometries (tris, leaves)"""
 
-    def __init__(self, psm, ctx, parts):
+    def __init__(self, psm, ctx, parts, opts=None):
         self.psm, self.parts = psm, [np.ascontiguousarray(t, F).reshape(-1, 3, 3) for t in parts]
-        self.ths = [_hier(psm, ctx, t) for t in self.parts]
+        self.ths = [_hier(psm, ctx, t) for t in self.parts] if opts is None else [_hier_opt(psm, ctx, t, m) for t, m in zip(self.parts, opts)]
         self.scene = psm.QueryScene(ctx, self.ths)
 
     def geoms(self):
@@ -161,6 +164,36 @@ def test_scene_sponza_like(psm, ctx, oracle, scenes, parts):
     with _Scene(psm, ctx, pieces) as sc:
         got = _all_cases(sc, tris, o, d, 40 + parts)
         assert len(set(got.geom[got.geom >= 0])) >= 2
+
+
+@pytest.mark.parametrize("opt", [ROT_SCALE, SHEAR], ids=["rotate_scale", "shear"])
+def test_a_member_built_with_an_optimisation_matrix(psm, ctx, oracle, scenes, opt):
+    """One of three members built with a matrix: the file's yardsticks, bit for bit, on the rays that are fully well-posed in
+    every member and on the points whose vote rays all are (tests/ray_prune_model.py: the contract of the other rays is the
+    single hierarchy's, tests/test_gpu_ray_matrix.py); at most 1 % of the rays and of the points are left out"""
+    sm = scenes.sponza_like(3001)
+    tris = sm["tris"].reshape(-1, 3, 3)
+    pieces, _ = SQ.split(tris, _sizes(tris.shape[0], 3))
+    with _Scene(psm, ctx, pieces, [None, opt, None]) as sc:
+        t = np.array(sc.ths[1].info().transform).reshape(4, 4)[:3, :3]
+        assert np.abs(t - np.diag(np.diag(t))).max() > 0.01
+
+        members = [(tr, _leaves(psm, th), np.array(th.info().transform, F), None) for tr, th in zip(sc.parts, sc.ths)]
+        rng = np.random.RandomState(61)
+        oo, od = _camera_rays(oracle, scenes, sm, 32, 16)
+        rays = RP.ray_classes(rng, tris, oo, od, 512)
+        o, d = (np.concatenate([rays[c][k] for c in ("own", "random", "outside", "tilt1e-3", "tilt1e-5")]) for k in (0, 1))
+        keep = RP.fully_well_posed(members, o, d)
+        assert (~keep).sum() <= 0.01 * keep.size, int((~keep).sum())
+        o, d = o[keep], d[keep]
+        got = _check_rays(sc, o, d)
+        assert (got.geom == 1).sum() > 50 and (got.geom == 2).sum() > 50   # (the member with the matrix is hit, and another)
+        _check_rays(sc, o, d, *_windows(rng, got.t.copy(), o.shape[0]))
+        p = _scene_points(rng, tris, 512)
+        sure = RP.vote_rays_well_posed(members, p, IQ.INSIDE_DIRECTIONS)
+        assert (~sure).sum() <= 0.01 * sure.size, int((~sure).sum())
+        _check_points(sc, p[sure])
+        _check_points(sc, p[sure], rng.uniform(0, 2.0, int(sure.sum())).astype(F), samples=(3,))
 
 
 @pytest.mark.parametrize("seed,parts", [(0, 2), (1, 3), (2, 8), (3, 3), (4, 2), (5, 8), (6, 3), (7, 2)])

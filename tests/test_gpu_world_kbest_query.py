@@ -12,7 +12,8 @@ import instance_query_model as NQ
 import query_model as Q
 import world_kbest_query_model as WK
 from test_gpu_kbest_query import GRID_CAP, _quad
-from test_gpu_world_query import _World, _meshes, _posed_entries, _queries
+from test_gpu_point_query import ROT_SCALE, SHEAR
+from test_gpu_world_query import _World, _meshes, _posed_entries, _queries, matrix_world_queries
 from test_world_query_cpu import _same, _shift
 
 try:   # (imported before the library loads its HIP runtime, as tests/test_gpu_query.py)
@@ -95,6 +96,25 @@ def test_world_kbest_parity_with_the_model(psm, ctx, n):
             assert _spread_rows(einst, ecount).sum() >= 100 and _spread_rows(pinst, pcount).sum() >= 100
         if n > 1:
             assert (ecount > 2).any() and (pcount > 2).any()
+
+
+@pytest.mark.parametrize("opt", [ROT_SCALE, SHEAR], ids=["rotate_scale", "shear"])
+def test_a_member_built_with_an_optimisation_matrix(psm, ctx, opt):
+    """the torus of a two-mesh world built with a matrix: firstHits on the rays that are fully well-posed in every instance
+    (tests/ray_prune_model.py; at most 1 % are left out) and nearest on every point, bit for bit against the model and the
+    world's own older answers"""
+    ico, tor = _meshes()
+    entries, _ = _posed_entries(7, 107)
+    with _World(psm, ctx, [ico, tor], entries, [None, opt]) as sc:
+        t = np.array(sc.ths[1].info().transform).reshape(4, 4)[:3, :3]
+        assert np.abs(t - np.diag(np.diag(t))).max() > 0.01
+        (o, d, tmin, tmax), _ = matrix_world_queries(sc, 64)
+        _, (p, rmax) = _queries(np.random.RandomState(65), 2.0, 1024)
+        insts = sc.insts()
+        _, einst, ecount = check_rays(sc, o, d, KS, tmin, tmax, insts)
+        check_rays(sc, o, d, (4, 16), insts=insts)
+        _, pinst, pcount = check_points(sc, p, KS, rmax, insts)
+        assert (ecount > 2).any() and (pcount > 2).any() and (einst[:, 0] % 2 == 1).any() and (pinst[:, 0] % 2 == 1).any()
 
 
 def test_world_kbest_stacked_sheets(psm, ctx):

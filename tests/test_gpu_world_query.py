@@ -9,7 +9,10 @@ import pytest
 import inside_query_model as IQ
 import instance_query_model as NQ
 import query_model as Q
+import ray_prune_model as RP
 import world_query_model as WQ
+from test_gpu_point_query import ROT_SCALE, SHEAR
+from test_gpu_point_query import _hier as _hier_opt
 from test_gpu_query import _hier, _leaves
 from test_world_query_cpu import _same, _shift, soup_case, soup_entries, unit_box
 
@@ -27,16 +30,21 @@ U = np.uint32
 class _World:
     """hierarchies over meshes, an InstanceWorld of (mesh index, pose) entries, and the model's instances"""
 
-    def __init__(self, psm, ctx, meshes, entries):
+    def __init__(self, psm, ctx, meshes, entries, opts=None):
         self.psm, self.ctx = psm, ctx
         self.meshes = [np.ascontiguousarray(t, F).reshape(-1, 3, 3) for t in meshes]
-        self.ths = [_hier(psm, ctx, t) for t in self.meshes]
+        self.ths = [_hier(psm, ctx, t) for t in self.meshes] if opts is None else [_hier_opt(psm, ctx, t, m) for t, m in zip(self.meshes, opts)]
         self.which = [k for k, _ in entries]
         self.world = psm.InstanceWorld(ctx, [(self.ths[k], m) for k, m in entries])
 
     def insts(self):
         leaves = [_leaves(self.psm, th) for th in self.ths]
         return [(self.meshes[k], leaves[k], m) for k, m in zip(self.which, self.world.transforms())]
+
+    def members(self):
+        """the instances as tests/ray_prune_model.py judges rays against them: (tris, leaves, the hierarchy's transform, pose)"""
+        ms = [np.array(th.info().transform, F) for th in self.ths]
+        return [(tr, lv, ms[k], m) for k, (tr, lv, m) in zip(self.which, self.insts())]
 
     def __enter__(self):
         return self
@@ -119,6 +127,37 @@ def test_world_parity_with_the_flat_list(psm, ctx, n):
         rays, points = _queries(np.random.RandomState(n), spread)
         got, gp = _check(sc, rays, points, samples=(3, 5))
         assert (got.geom >= 0).sum() > 50 and (gp.geom >= 0).sum() > 50
+
+
+def matrix_world_queries(sc, seed, n=1024):
+    """rays and points for a world one of whose members was built with a matrix: the files' random queries plus rays that graze
+    the posed triangles, cut down to the rays that are fully well-posed in every instance and the points whose vote rays all are
+    (tests/ray_prune_model.py); at most 1 % of either is left out. Returns (o, d, tmin, tmax), (p, rmax)."""
+    members = sc.members()
+    rng = np.random.RandomState(seed)
+    (o, d, tmin, tmax), (p, rmax) = _queries(rng, 2.0, n)
+    posed = np.concatenate([NQ.posed(tr, m) for tr, _, _, m in members])
+    graze = [RP.grazing_rays(rng, posed, n // 4, tilt) for tilt in (1e-3, 1e-5)]
+    o, d = np.concatenate([o] + [g[0] for g in graze]), np.concatenate([d] + [g[1] for g in graze])
+    tmin, tmax = np.concatenate([tmin, np.zeros(n // 2, F)]), np.concatenate([tmax, np.full(n // 2, np.inf, F)])
+    keep = RP.fully_well_posed(members, o, d)
+    sure = RP.vote_rays_well_posed(members, p, IQ.INSIDE_DIRECTIONS)
+    assert (~keep).sum() <= 0.01 * keep.size and (~sure).sum() <= 0.01 * sure.size, (int((~keep).sum()), int((~sure).sum()))
+    return (o[keep], d[keep], tmin[keep], tmax[keep]), (p[sure], rmax[sure])
+
+
+@pytest.mark.parametrize("opt", [ROT_SCALE, SHEAR], ids=["rotate_scale", "shear"])
+def test_a_member_built_with_an_optimisation_matrix(psm, ctx, opt):
+    """the torus of a two-mesh world built with a matrix: the seven kinds bit for bit against the flat answer on the fully
+    well-posed rays and points (the other rays' contract is the single hierarchy's, tests/test_gpu_ray_matrix.py)"""
+    ico, tor = _meshes()
+    entries, _ = _posed_entries(7, 107)
+    with _World(psm, ctx, [ico, tor], entries, [None, opt]) as sc:
+        t = np.array(sc.ths[1].info().transform).reshape(4, 4)[:3, :3]
+        assert np.abs(t - np.diag(np.diag(t))).max() > 0.01
+        rays, points = matrix_world_queries(sc, 63)
+        got, gp = _check(sc, rays, points)
+        assert (got.geom >= 0).sum() > 50 and (got.geom[got.geom >= 0] % 2 == 1).any() and (gp.geom >= 0).sum() > 50
 
 
 def test_world_adversarial_soup(psm, ctx, scenes):

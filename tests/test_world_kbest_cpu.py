@@ -219,7 +219,9 @@ def test_world_kbest_kernels_codegen():
 
 def test_the_16_kernels_of_kbest_hip_and_world_hip_are_unchanged(tmp_path):
     """the instruction streams and sizes of kbest.hip's 2 and world.hip's 14 kernels are those recorded from the commit before the
-    world's k-best queries (tests/golden/world_kbest_kernels_before.json: tools/kernel_diff.py's normal form, hashed)"""
+    world's k-best queries (tests/golden/world_kbest_kernels_before.json: tools/kernel_diff.py's normal form, hashed). The digests
+    of the 6 ray kernels among them (bvh_query_first_hits and the world's five) were recorded anew when ray_axis's margin grew by
+    2^-12 (psm_query_dev.h, DESIGN.md 4.5: the one change of their code since); the 10 others' are the first recording's."""
     now = {}
     for src in ("kbest.hip", "world.hip"):
         out = tmp_path / src.replace(".hip", ".s")

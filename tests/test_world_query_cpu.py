@@ -288,7 +288,9 @@ def _kernel_digests(asm_path):
 def test_the_21_kernels_of_query_hip_are_unchanged(tmp_path):
     """query.hip's 21 kernels' instruction streams and sizes are those recorded from the commit before the worlds
     (tests/golden/query_kernels_before_worlds.json: tools/kernel_diff.py's normal form, hashed), whatever has moved between the
-    file and the headers it shares with kbest.hip and world.hip since"""
+    file and the headers it shares with kbest.hip and world.hip since. The 15 ray kernels' digests were recorded anew when
+    ray_axis's margin grew by 2^-12 (psm_query_dev.h, DESIGN.md 4.5: the one change of their code since); the 6 point kernels'
+    are the first recording's."""
     import json
     out = tmp_path / "query.s"
     out.write_text(csrc_asm("query.hip"))
