@@ -75,6 +75,16 @@ namespace NSM {
         int triOverlaps(const psm_tri_query * d_tris, size_t n, uint8_t * d_hit);
         int triCount(const psm_tri_query * d_tris, size_t n, uint32_t * d_count);
         int triTriangles(const psm_tri_query * d_tris, size_t n, uint32_t k, int32_t * d_ids, uint32_t * d_count);
+        // not in the reference: whether / how many / which triangles meet each stored triangle of another built hierarchy `other`
+        // (of the same context) at each of p rigid poses (glm's convention, as InstancedScene's: a point of other's object space
+        // goes to m * x in this hierarchy's), posed in float32 on the device and answered as triOverlaps / triCount / triTriangles
+        // answer it (psm_hip.h "mesh queries"). With T = other->triangleCount: d_hit [p], d_count [p][T], d_ids [p][T][k],
+        // 1 <= k <= PSM_QUERY_K_MAX, indexed by other's load-order triangle id (psm_bvh_mesh_overlaps_dev / psm_bvh_mesh_count_dev
+        // / psm_bvh_mesh_triangles_dev). The poses are host memory read at the call, which waits once for their upload; the
+        // kernel is stream-ordered on the context; returns the psm_status
+        int meshOverlaps(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, uint8_t * d_hit);
+        int meshCount(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, uint32_t * d_count);
+        int meshTriangles(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, uint32_t k, int32_t * d_ids, uint32_t * d_count);
         // not in the reference: where a sphere that moves along a line first touches the triangles (t = the distance its centre
         // travels, 0 when it touches where it starts; a miss is {0, 0, +inf, -1}), and whether it touches any within tmax
         // (psm_bvh_sweep_sphere_dev / psm_bvh_sweep_occluded_dev), stream-ordered on the context; returns the psm_status

@@ -107,6 +107,34 @@ namespace NSM {
         check(rc, "TriangleHierarchy::triTriangles");
         return rc;
     }
+    namespace detail {
+    // psm_hip.h wants row-major 3 x 4 [R | T] matrices: m12[4 * row + col] = m[col][row], glm's last row dropped
+    inline std::vector<float> meshPoses(const glm::mat4 * m, size_t p) {
+        std::vector<float> m12(12 * p);
+        for (size_t q = 0; q < p; q++)
+            for (int row = 0; row < 3; row++)
+                for (int col = 0; col < 4; col++) m12[12 * q + 4 * row + col] = m[q][col][row];
+        return m12;
+    }
+    }
+    inline int TriangleHierarchy::meshOverlaps(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, uint8_t * d_hit) {
+        const std::vector<float> m12 = detail::meshPoses(poses, p);
+        const int rc = psm_bvh_mesh_overlaps_dev(bvh, other ? other->bvh : nullptr, m12.data(), p, d_hit);
+        check(rc, "TriangleHierarchy::meshOverlaps");
+        return rc;
+    }
+    inline int TriangleHierarchy::meshCount(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, uint32_t * d_count) {
+        const std::vector<float> m12 = detail::meshPoses(poses, p);
+        const int rc = psm_bvh_mesh_count_dev(bvh, other ? other->bvh : nullptr, m12.data(), p, d_count);
+        check(rc, "TriangleHierarchy::meshCount");
+        return rc;
+    }
+    inline int TriangleHierarchy::meshTriangles(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, uint32_t k, int32_t * d_ids, uint32_t * d_count) {
+        const std::vector<float> m12 = detail::meshPoses(poses, p);
+        const int rc = psm_bvh_mesh_triangles_dev(bvh, other ? other->bvh : nullptr, m12.data(), p, k, d_ids, d_count);
+        check(rc, "TriangleHierarchy::meshTriangles");
+        return rc;
+    }
     inline int TriangleHierarchy::sweepSphere(const psm_sweep_query * d_sweeps, size_t n, psm_hit * d_hits) {
         const int rc = psm_bvh_sweep_sphere_dev(bvh, d_sweeps, n, d_hits);
         check(rc, "TriangleHierarchy::sweepSphere");

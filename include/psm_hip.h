@@ -620,6 +620,56 @@ int psm_bvh_tri_overlaps_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t n
 int psm_bvh_tri_count_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t n, uint32_t* d_count);
 int psm_bvh_tri_triangles_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t n, uint32_t k, int32_t* d_ids, uint32_t* d_count);
 
+/* mesh queries against a built hierarchy (new; no reference counterpart): the triangle queries above with the
+ * query triangles taken from ANOTHER built hierarchy `other` of the same context, at each of p rigid poses, in one call: does
+ * part B at this pose cut part A, where, and with which triangles. `bvh` is the hierarchy being queried. Nothing is downloaded,
+ * posed on the host or packed: no psm_tri_query record exists anywhere. Flat scenes, instanced lists and worlds have none.
+ * Semantics:
+ *   - poses: HOST memory, p x 12 floats, each a row-major 3 x 4 [R | T] that takes a point of other's object space into bvh's
+ *     (x' = R x + T), read at the call as psm_instance is and checked as its matrix is (finite; R^T R within 1e-5 of the
+ *     identity in every entry, in double: rotations and reflections)
+ *   - T = other's loaded triangle count (psm_bvh_info.triangle_count). Outputs are indexed by pose q and by other's load-order
+ *     triangle id t, like everything else in this header: d_hit [p], d_count [p][T], d_ids [p][T][k]
+ *   - the query of (pose m, triangle t of other) comes from other's STORED record (v0, e1 = v1 - v0, e2 = v2 - v0), in float32,
+ *     one rounding per operation, nothing fused, with fwd_point / fwd_vec of the world box queries (below):
+ *       a = fwd_point(m, v0),  b = a + fwd_vec(m, e1),  c = a + fwd_vec(m, e2)
+ *     At the identity pose the query is the stored triangle, not the loaded one: a = v0 and b = fl(v0 + e1) =
+ *     fl(v0 + fl(v1 - v0)), which can differ from the loaded vertex v1 by an ulp (and c from v2)
+ *   - the answer for (m, t) is BIT FOR BIT what psm_bvh_tri_overlaps_dev / psm_bvh_tri_count_dev / psm_bvh_tri_triangles_dev
+ *     answer for psm_tri_query {a, b, c} on bvh: the same tri_tri, the same prune on the same bounding box, the same k rule
+ *     (1 <= k <= PSM_QUERY_K_MAX), the same rows (the min(k, c) lowest ids of bvh that count, ascending, then -1; d_count =
+ *     min(k, c)). A query whose posed image holds a non-finite number (an overflow) answers as an invalid psm_tri_query: 0, or
+ *     count 0 with a row of -1
+ *   - a triangle of other that its build dropped (not in PSM_BVH_LEAF_TRI) answers count 0 with a row of -1 at every pose
+ *   - overlaps: d_hit[q] = 1 iff some leaf of other at pose q meets some leaf of bvh -- the OR over the pose's queries --, else 0
+ *   - other == bvh is allowed: a self-intersection check at the identity. Every leaf then meets at least ITSELF (the query is
+ *     the stored triangle: A = 0), and its neighbours that share a vertex or an edge; the caller discounts these
+ *   - nothing depends on the traversal order, on either hierarchy's tree or on timing: a flag, sums, the lowest ids. Query i
+ *     of the launch is pose i / L and other's leaf i % L by ascending triangle id (L its leaf count): the queries, and their
+ *     order, of the triangle queries over the same posed triangles packed in load order (DESIGN.md 4.21 has what other's
+ *     Morton order measured: slower)
+ *   - refusals, all before any launch and with the outputs untouched: NULL bvh or other (PSM_ERR_INVALID, no message: there is
+ *     no context to keep one); then, with a message on bvh's context, NULL poses or outputs, d_count / d_ids not 4-byte aligned,
+ *     k == 0 or k > PSM_QUERY_K_MAX (PSM_ERR_INVALID); either hierarchy not built (PSM_ERR_STATE, "mesh query before build");
+ *     bvh deeper than the query stack (PSM_ERR_CAPACITY); hierarchies of different contexts (PSM_ERR_INVALID); a pose that is
+ *     not finite or not rigid, named by its index (PSM_ERR_INVALID); p x T >= 2^32 (PSM_ERR_CAPACITY)
+ *   - p == 0 returns PSM_OK and touches nothing (it is answered before everything but the NULL handles). Otherwise the outputs
+ *     are cleared in stream order (0, rows of -1) before the one kernel: other without leaves launches none; bvh without leaves
+ *     answers 0 / -1 everywhere
+ *   - the poses go to the device as a world's do: copied on the context's stream into a buffer the context owns, and the call
+ *     waits for that copy (and, in the same wait, reads other's leaf count). The call therefore synchronises the context's
+ *     stream once before its launch and cannot be captured into a graph; the kernel itself is stream-ordered like every query.
+ *     That upload, the wait and the clears are what a call costs beside the triangle queries on records that are already
+ *     packed and resident (measured: 0.03 to 0.05 ms at 2 304 answers; DESIGN.md 4.21 times them apart from the kernel)
+ *   - study knob, no part of the contract: the overlaps kernel lets a lane skip its walk when its pose's flag already reads 1,
+ *     by itself only in launches of more than PSM_QUERY_GRID_CAP waves; the environment variable PSM_MESH_SKIP = 0 / 1, read
+ *     at each call, forces that off / on (tools/query_bench.py meshes, tests/test_gpu_mesh_query.py). The answer is the same
+ *   - not covered: a mesh against a world, a flat scene or an instanced list; a dual-tree walk that prunes whole subtrees of
+ *     other; the intersection segments; k > PSM_QUERY_K_MAX */
+int psm_bvh_mesh_overlaps_dev(psm_bvh* bvh, psm_bvh* other, const float* poses, size_t p, uint8_t* d_hit);
+int psm_bvh_mesh_count_dev(psm_bvh* bvh, psm_bvh* other, const float* poses, size_t p, uint32_t* d_count);
+int psm_bvh_mesh_triangles_dev(psm_bvh* bvh, psm_bvh* other, const float* poses, size_t p, uint32_t k, int32_t* d_ids, uint32_t* d_count);
+
 /* scene queries: the seven queries above over several hierarchies at once (new; no reference counterpart).
  * A scene is an ordered list of G built hierarchies of ONE context, 1 <= G <= PSM_SCENE_MAX_GEOMETRIES, passed per call (there
  * is no scene handle). The limit is 32 because the per-geometry table then travels with the launch (32 x four pointers = 1 KB

@@ -31,6 +31,7 @@ EXPORTS = [
     "psm_bvh_box_overlaps_dev", "psm_bvh_box_count_dev", "psm_bvh_box_triangles_dev",
     "psm_bvh_sweep_sphere_dev", "psm_bvh_sweep_occluded_dev",
     "psm_bvh_tri_overlaps_dev", "psm_bvh_tri_count_dev", "psm_bvh_tri_triangles_dev",
+    "psm_bvh_mesh_overlaps_dev", "psm_bvh_mesh_count_dev", "psm_bvh_mesh_triangles_dev",
     "psm_scene_intersect_dev", "psm_scene_occluded_dev", "psm_scene_count_hits_dev", "psm_scene_closest_point_dev", "psm_scene_within_dev",
     "psm_scene_inside_dev", "psm_scene_signed_distance_dev",
     "psm_instances_intersect_dev", "psm_instances_occluded_dev", "psm_instances_count_hits_dev", "psm_instances_closest_point_dev",
@@ -510,6 +511,77 @@ class TriangleHierarchy:
         packed[:, :, 0:3] = t
         return self._launch_np(packed.reshape(-1, 12), out, name, *extra)
 
+    def meshOverlaps(self, other, poses, as_torch=False):
+        """Whether `other`, another built TriangleHierarchy of this context, meets this one anywhere at each pose
+        (psm_bvh_mesh_overlaps_dev; not in the reference). poses: one matrix or [p, 3, 4] / [p, 4, 4], each a rigid [R | T] that
+        takes a point of other's object space into this hierarchy's (x' = R x + T), checked as an instance's pose is: a
+        non-rigid one raises before any call. The query triangles are other's stored leaves posed in float32 on the device
+        (psm_hip.h "mesh queries"); each is answered bit for bit as triOverlaps() answers it. A numpy bool [p]; with
+        as_torch=True a torch bool tensor on the context's device, the launch ordered against torch's current stream by events
+        (the call itself waits once for its pose upload, as InstanceWorld.setTransforms does). QueryScene, InstancedScene and
+        InstanceWorld have no mesh queries."""
+        return self._mesh_query(other, poses, "bool", "psm_bvh_mesh_overlaps_dev", None, as_torch)
+
+    def meshCount(self, other, poses, as_torch=False):
+        """How many triangles of this hierarchy meet each triangle of `other` at each pose (psm_bvh_mesh_count_dev; not in the
+        reference): uint32 [p, T], T = other.triangleCount, indexed by other's load-order triangle id (an int32 tensor with
+        as_torch=True); a triangle other's build dropped counts 0. With other = self at the identity every leaf counts at
+        least itself. Arguments and placement as meshOverlaps()."""
+        return self._mesh_query(other, poses, "count", "psm_bvh_mesh_count_dev", None, as_torch)
+
+    def meshTriangles(self, other, poses, k, as_torch=False):
+        """Which triangles of this hierarchy meet each triangle of `other` at each pose (psm_bvh_mesh_triangles_dev; not in the
+        reference): of the triangles meshCount() counts, the min(k, count) lowest ids, ascending. k: 1 .. QUERY_K_MAX. Returns
+        QueryTriLists: tri [p, T, k] int32 (-1 past count) and count [p, T]. Arguments and placement as meshOverlaps()."""
+        if not 1 <= _k(k, "psm_bvh_mesh_triangles_dev") <= QUERY_K_MAX:   # (refused here: no call is made)
+            raise PsmError("psm_bvh_mesh_triangles_dev: k must be 1 .. %d" % QUERY_K_MAX)
+        return self._mesh_query(other, poses, "tris", "psm_bvh_mesh_triangles_dev", int(k), as_torch)
+
+    def _mesh_query(self, other, poses, out, name, k, as_torch):
+        """one mesh query: the poses checked and packed [p, 12] on the host, the outputs [p] / [p, T] / [p, T, k] and [p, T]"""
+        if not isinstance(other, TriangleHierarchy):
+            raise TypeError("%s: other must be a TriangleHierarchy" % name)
+        m = np.asarray(poses)
+        if m.ndim == 2:
+            m = m[None]
+        if m.ndim != 3:
+            raise ValueError("%s: poses must be one matrix or [p, 3, 4] / [p, 4, 4]" % name)
+        p, t = m.shape[0], int(other.triangleCount)
+        m12 = np.ascontiguousarray(np.stack([_pose(x, name) for x in m]).reshape(p, 12) if p else np.zeros((0, 12)), np.float32)
+        extra = () if k is None else (C.c_uint32(k),)
+        cells, kk = p * t, 1 if k is None else k
+        fn = getattr(lib(), name)
+
+        def call(d_out, d_count):
+            tail = () if d_count is None else (C.c_void_p(d_count),)
+            self.ctx.check(fn(self._h, other._h, _p(m12), C.c_size_t(p), *extra, C.c_void_p(d_out), *tail), name)
+
+        if as_torch:
+            import torch
+            dev = torch.device("cuda", self.ctx.device)
+            shape, dtype = {"bool": ((p,), torch.uint8), "count": ((p, t), torch.int32), "tris": ((p, t, kk), torch.int32)}[out]
+            res = torch.empty(shape, dtype=dtype, device=dev)
+            cnt = torch.empty((p, t), dtype=torch.int32, device=dev) if out == "tris" else None
+            _torch_ordered(self.ctx, dev, lambda: call(res.data_ptr(), None if cnt is None else cnt.data_ptr()))
+            return QueryTriLists(res, cnt) if out == "tris" else (res.view(torch.bool) if out == "bool" else res)
+        ctx = self.ctx
+        per = {"bool": p, "count": 4 * cells, "tris": 4 * cells * kk}[out]
+        ho = ctx.buf_alloc(max(per, 16))
+        hc = ctx.buf_alloc(max(4 * cells, 16)) if out == "tris" else None
+        try:
+            call(ctx.buf_ptr(ho)[0], None if hc is None else ctx.buf_ptr(hc)[0])
+            if out == "bool":
+                return ctx.buf_download(ho, np.uint8, p).view(np.bool_) if p else np.zeros(0, np.bool_)
+            if out == "count":
+                return (ctx.buf_download(ho, np.uint32, cells) if cells else np.zeros(0, np.uint32)).reshape(p, t)
+            ids = ctx.buf_download(ho, np.int32, cells * kk) if cells else np.zeros(0, np.int32)
+            cnt = ctx.buf_download(hc, np.uint32, cells) if cells else np.zeros(0, np.uint32)
+            return QueryTriLists(ids.reshape(p, t, kk), cnt.reshape(p, t))
+        finally:
+            ctx.buf_free(ho)
+            if hc is not None:
+                ctx.buf_free(hc)
+
     def sweepSphere(self, origins, directions, radius, tmax=np.inf):
         """Where a sphere of `radius` that moves from each origin along its direction first touches a triangle within the distance
         tmax (psm_bvh_sweep_sphere_dev; not in the reference): origins, directions [n, 3] (any length; normalised inside, t is
@@ -807,6 +879,26 @@ def _query_torch(th, origins, directions, tmin, tmax, out, name, *extra):
     return _launch_torch(th, rays, out, name, *extra)
 
 
+def _torch_ordered(ctx, dev, call):
+    """call() -- launches on the context's stream -- between what torch's current stream of `dev` has queued and what it queues
+    next: the two streams ordered by events when they differ, no host synchronisation."""
+    import torch
+    cur = torch.cuda.current_stream(dev)
+    mine = ctx.stream or 0   # (NULL: the device's null stream, torch's default stream)
+    other = mine != cur.cuda_stream
+    if other:   # the context's stream waits for the packing (torch's event, HIP's wait: no host synchronisation)
+        ev_in = torch.cuda.Event()
+        ev_in.record(cur)
+        _hip_check(_hip().hipStreamWaitEvent(C.c_void_p(mine), C.c_void_p(ev_in.cuda_event), C.c_uint(0)), "hipStreamWaitEvent")
+    call()
+    if other:   # ... and torch's stream for the kernel: every later use of the outputs, and of the inputs' memory, comes after it
+        hip, ev = _hip(), C.c_void_p()
+        _hip_check(hip.hipEventCreateWithFlags(C.byref(ev), C.c_uint(2)), "hipEventCreateWithFlags")   # hipEventDisableTiming
+        _hip_check(hip.hipEventRecord(ev, C.c_void_p(mine)), "hipEventRecord")
+        _hip_check(hip.hipStreamWaitEvent(C.c_void_p(cur.cuda_stream), ev, C.c_uint(0)), "hipStreamWaitEvent")
+        _hip_check(hip.hipEventDestroy(ev), "hipEventDestroy")
+
+
 def _launch_torch(th, packed, kind, name, *extra):
     """One query launch over device records `packed` (made on torch's current stream) on the context's stream: the two streams
     ordered by events when they differ -- no host synchronisation. kind: the result's (_QUERY_OUT): QueryHits, a bool or an int32
@@ -821,21 +913,9 @@ def _launch_torch(th, packed, kind, name, *extra):
     out = torch.empty(shape, dtype=dtype, device=dev)
     geom = torch.empty((n,), dtype=torch.int32, device=dev) if (th._scene and kind == "hits") or lists or tris else None
     inst = torch.empty(shape[:2], dtype=torch.int32, device=dev) if (lists or tris) and th._scene else None   # (a world's rows)
-    cur = torch.cuda.current_stream(dev)
-    mine = th.ctx.stream or 0   # (NULL: the device's null stream, torch's default stream)
-    other = mine != cur.cuda_stream
-    if other:   # the context's stream waits for the packing (torch's event, HIP's wait: no host synchronisation)
-        ev_in = torch.cuda.Event()
-        ev_in.record(cur)
-        _hip_check(_hip().hipStreamWaitEvent(C.c_void_p(mine), C.c_void_p(ev_in.cuda_event), C.c_uint(0)), "hipStreamWaitEvent")
     d_geom = None if geom is None else geom.data_ptr()
-    th._call(name, packed.data_ptr(), n, extra, out.data_ptr(), d_geom if inst is None else (inst.data_ptr(), d_geom))
-    if other:   # ... and torch's stream for the kernel: every later use of `out`, and of the memory of `packed`, comes after it
-        hip, ev = _hip(), C.c_void_p()
-        _hip_check(hip.hipEventCreateWithFlags(C.byref(ev), C.c_uint(2)), "hipEventCreateWithFlags")   # hipEventDisableTiming
-        _hip_check(hip.hipEventRecord(ev, C.c_void_p(mine)), "hipEventRecord")
-        _hip_check(hip.hipStreamWaitEvent(C.c_void_p(cur.cuda_stream), ev, C.c_uint(0)), "hipStreamWaitEvent")
-        _hip_check(hip.hipEventDestroy(ev), "hipEventDestroy")
+    _torch_ordered(th.ctx, dev, lambda: th._call(name, packed.data_ptr(), n, extra, out.data_ptr(),
+                                                 d_geom if inst is None else (inst.data_ptr(), d_geom)))
     if lists:
         return QueryHitLists(out, geom, inst)
     if tris:

@@ -178,6 +178,7 @@ int psm_ctx_destroy(psm_ctx* c) {
     if (c->sort_overflow) (void)hipHostFree(c->sort_overflow);
     dev_free(c->d_counters);
     psm::query_release(c);   // query.hip: the ray queries' stack area
+    psm::mesh_release(c);    // mesh.hip: the mesh queries' pose area
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return PSM_OK;

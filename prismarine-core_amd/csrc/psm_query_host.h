@@ -8,6 +8,7 @@
 namespace psm {
 
 void query_release(psm_ctx* c);               // query.hip, for psm_ctx_destroy: the context's stack area goes with it
+void mesh_release(psm_ctx* c);                // mesh.hip, for psm_ctx_destroy: the device copy of the mesh queries' poses goes with it
 uint64_t bvh_generation(const psm_bvh* b);    // api.hip: bumped by every build of the hierarchy
 
 // (Q_FIRST_HITS, Q_NEAREST: the k-best queries of kbest.hip and of world.hip's worlds: no entry in the kernel tables; Q_BOX_ANY,

@@ -61,6 +61,15 @@ psm_world_tri_triangles_dev) on the worldboxes mode's world, the torus at 256 an
 bounding boxes -- the one-launch stand-in a caller had, a superset: context, not a bar -- on two query sets: a second torus posed
 WTRI_BODIES (64) times beside bodies of the world, so that the meshes cut, and WTRI_SLANTED (4 096) body-sized slanted triangles;
 for each the fraction of queries that report and the ratio of box-reported to triangle-reported pairs. No ratio is fixed in advance.
+`query_bench.py meshes`: the mesh queries (psm_bvh_mesh_overlaps_dev / psm_bvh_mesh_count_dev / psm_bvh_mesh_triangles_dev) on the
+Sponza-class scene, cut by the worldboxes mode's torus (2 304 triangles) scaled to a quarter of its extent, and on that torus cut by
+itself, at 1, 64 and 1 024 poses placed so that the meshes cut (the build of the other mesh excluded), the torus loaded as it is
+made (in strips) and with its triangles shuffled. Per case, each pair alternated
+A B A B (host-timed medians of REPS): (a) the mesh query, against (b) triCount / triTriangles (k = 16) over the same posed triangles
+already resident on the device as psm_tri_query records in load order -- kernel for kernel --, the two B series of count giving
+the spread between runs, and the call's own overhead (upload, wait, clears: a mesh query of a mesh without leaves) timed apart; (c) the path the call replaces: download of the other mesh's triangles, posing in numpy,
+packing, upload, triCount (timed as a whole, alternated with (a)); and the flag query with its early-out skip forced on and off
+(PSM_MESH_SKIP = 1 / 0; by itself a launch skips when it takes the grid-stride loop). No ratio is fixed in advance.
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -931,6 +940,137 @@ def triangles():
     print(json.dumps(out))
 
 
+def meshes():
+    lib = psm.lib()
+
+    def posed(src, poses):
+        """the query triangles [p, t, 3, 3] of the stored (v0, e1, e2) of src [t, 3, 3] at poses [p, 3, 4], in float32 in the
+        library's operation order (psm_hip.h "mesh queries"): (b) and (c) then ask exactly what (a) asks"""
+        m = poses[:, None]
+        v0, e1, e2 = src[None, :, 0], (src[:, 1] - src[:, 0])[None], (src[:, 2] - src[:, 0])[None]
+
+        def vec(d):
+            return np.stack([(m[..., k, 0] * d[..., 0] + m[..., k, 1] * d[..., 1]) + m[..., k, 2] * d[..., 2] for k in range(3)], axis=-1)
+        a = vec(v0) + m[..., 3]
+        return np.stack([a, a + vec(e1), a + vec(e2)], axis=2)
+    out = {"mode": "meshes", "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+    tor = torus(48, 24, 0.7, 0.25).reshape(-1, 3, 3)
+    sp = scenes.sponza_like()
+    rng = np.random.RandomState(13)
+
+    def hier(ctx, tris):
+        th = psm.TriangleHierarchy(ctx)
+        th.allocate(tris.shape[0])
+        th.loadTriangles(np.ascontiguousarray(tris, np.float32).reshape(-1, 9))
+        th.build()
+        return th
+
+    def rotation():
+        q = rng.normal(size=4)
+        w, x, y, z = q / np.linalg.norm(q)
+        return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                         [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                         [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+    for scene_name, tris in (("sponza", sp["tris"].reshape(-1, 3, 3)), ("torus", tor)):
+        ctx = psm.Context(0)
+        v = tris.reshape(-1, 3)
+        lo, hi = v.min(0).astype(np.float64), v.max(0).astype(np.float64)
+        ext = hi - lo
+        # the other mesh: the torus, a quarter of the scene's extent across (the torus against itself: as it is)
+        scale = 1.0 if scene_name == "torus" else 0.25 * float(ext.max()) / 1.9
+        otris = (tor.astype(np.float64) * scale).astype(np.float32)
+        th = hier(ctx, tris)
+        out[scene_name + "_tris"] = int(th.info().leaf_count)
+        # the other mesh as the torus is made (strips: a load order that is already coherent), and with its triangles shuffled (a
+        # load order that says nothing about place: what the Morton order of the lane mapping is there for)
+        for order, otris in (("", otris), ("shuffled_", otris[np.random.RandomState(14).permutation(otris.shape[0])])):
+            other = hier(ctx, otris)
+            t = otris.shape[0]
+            # as many triangles, none a leaf: a mesh query of it uploads, waits and clears as the real one does and launches no
+            # kernel -- what a call costs beside the triangle queries on records that are already packed and resident
+            hollow = hier(ctx, np.repeat(otris[:, :1], 3, axis=1))
+            out[scene_name + "_other_tris"] = int(other.info().leaf_count)
+            for p in (1, 64, 1024):
+                # poses at which the meshes cut: the other mesh turned at random, its centre on a vertex of the queried mesh
+                # (the same poses for either load order of the other mesh)
+                rng.seed(1000 + p)
+                at = v[rng.choice(v.shape[0], p)].astype(np.float64)
+                poses = np.stack([np.concatenate([rotation(), c.reshape(3, 1)], axis=1) for c in at]).astype(np.float32)
+                m12 = np.ascontiguousarray(poses.reshape(p, 12))
+                n = p * t
+                hs = [ctx.buf_alloc(x) for x in (48 * n, max(p, 16), 4 * n, 4 * 16 * n, 4 * n)]
+                p_tri, p_flag, p_count, p_rows, p_count2 = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in hs)
+                size, np_, pm = C.c_size_t(n), C.c_size_t(p), m12.ctypes.data_as(C.c_void_p)
+
+                def pack():
+                    src = other.download(psm.BVH_POSITIONS, np.float32, 9 * t).reshape(t, 3, 3)   # the other mesh, from the device
+                    rec = np.zeros((p, t, 3, 4), np.float32)
+                    rec[:, :, :, 0:3] = posed(src, poses)
+                    return rec.reshape(n, 12)
+                ctx.buf_upload(hs[0], pack())
+
+                def mesh_overlaps():
+                    ctx.check(lib.psm_bvh_mesh_overlaps_dev(th._h, other._h, pm, np_, p_flag), "psm_bvh_mesh_overlaps_dev")
+
+                def forced(skip):
+                    def run():
+                        os.environ["PSM_MESH_SKIP"] = skip
+                        try:
+                            mesh_overlaps()
+                        finally:
+                            del os.environ["PSM_MESH_SKIP"]
+                    return run
+
+                def mesh_count():
+                    ctx.check(lib.psm_bvh_mesh_count_dev(th._h, other._h, pm, np_, p_count), "psm_bvh_mesh_count_dev")
+
+                def mesh_rows():
+                    ctx.check(lib.psm_bvh_mesh_triangles_dev(th._h, other._h, pm, np_, C.c_uint32(16), p_rows, p_count), "psm_bvh_mesh_triangles_dev")
+
+                def count_overhead():
+                    ctx.check(lib.psm_bvh_mesh_count_dev(th._h, hollow._h, pm, np_, p_count), "psm_bvh_mesh_count_dev")
+
+                def tri_overlaps():
+                    ctx.check(lib.psm_bvh_tri_overlaps_dev(th._h, p_tri, size, p_count2), "psm_bvh_tri_overlaps_dev")
+
+                def tri_count():
+                    ctx.check(lib.psm_bvh_tri_count_dev(th._h, p_tri, size, p_count2), "psm_bvh_tri_count_dev")
+
+                def tri_rows():
+                    ctx.check(lib.psm_bvh_tri_triangles_dev(th._h, p_tri, size, C.c_uint32(16), p_rows, p_count2), "psm_bvh_tri_triangles_dev")
+
+                def full_path():
+                    ctx.buf_upload(hs[0], pack())
+                    tri_count()
+                key = "%s_%sp%d_" % (scene_name, order, p)
+                out[key + "queries"] = n
+                # (overlaps: the per-triangle flags of (b) are n bytes, the per-pose flags of (a) p bytes: (b) answers more)
+                for name, fa, beside, fb in (("mesh_count", mesh_count, "tri_count", tri_count), ("mesh_overlaps", mesh_overlaps, "tri_overlaps", tri_overlaps),
+                                             ("mesh_triangles_k16", mesh_rows, "tri_triangles_k16", tri_rows),
+                                             ("mesh_count_again", mesh_count, "tri_count_again", tri_count),
+                                             ("mesh_overlaps_skip", forced("1"), "mesh_overlaps_no_skip", forced("0"))):
+                    out[key + name + "_ms"], out[key + beside + "_ms"] = abab(ctx, fa, fb)
+                out[key + "mesh_count_overhead_ms"] = round(median_ms(ctx, count_overhead), 4)
+                if n <= 64 * 2304 and not order:   # (the numpy posing of 2.4 M triangles takes seconds: the point is made at 1 and 64 poses)
+                    out[key + "mesh_count_beside_full_path_ms"], out[key + "full_path_ms"] = abab(ctx, mesh_count, full_path)
+                mesh_count()
+                mine = ctx.buf_download(hs[2], np.uint32, n)
+                tri_count()
+                theirs = ctx.buf_download(hs[4], np.uint32, n)
+                out[key + "equal"] = bool(np.array_equal(mine, theirs))
+                mesh_overlaps()
+                out[key + "poses_that_cut"] = round(float(ctx.buf_download(hs[1], np.uint8, p).mean()), 4)
+                out[key + "triangles_that_meet"], out[key + "mean_count"] = round(float((mine > 0).mean()), 4), round(float(mine.mean()), 3)
+                for h in hs:
+                    ctx.buf_free(h)
+            other.close()
+            hollow.close()
+        th.close()
+        ctx.close()
+    print(json.dumps(out))
+
+
 def sweeps():
     lib = psm.lib()
     out = {"mode": "sweeps", "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
@@ -1288,4 +1428,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "worldtriangles": worldtriangles}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "meshes": meshes, "worldtriangles": worldtriangles}.get(" ".join(sys.argv[1:]), main)()
