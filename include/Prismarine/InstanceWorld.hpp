@@ -62,5 +62,15 @@ namespace NSM {
         int overlapsTriangle(const psm_tri_query * d_tris, size_t n, uint8_t * d_hit);
         int countOnTriangle(const psm_tri_query * d_tris, size_t n, uint32_t * d_count);
         int trianglesOnTriangle(const psm_tri_query * d_tris, size_t n, uint32_t k, int32_t * d_tri, int32_t * d_inst, uint32_t * d_count);
+        // whether / how many / which (instance, triangle) pairs meet each stored triangle of ANOTHER built hierarchy at each of p
+        // rigid poses that take its object space into WORLD space (glm::mat4, last row 0 0 0 1), in one call: each query triangle
+        // is posed on the device and answered bit for bit as the three queries above answer it. skip: an instance that is left
+        // out (the other indices kept), -1 for none. d_hit [p]; d_count [p][T], T other's loaded triangle count; trianglesOnMesh:
+        // d_tri and d_inst [p][T][k], d_count [p][T]. The poses are host memory read at the call, which waits once for their
+        // upload and cannot be captured into a graph (psm_world_mesh_overlaps_dev / psm_world_mesh_count_dev /
+        // psm_world_mesh_triangles_dev); the flat lists have no such query
+        int overlapsMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, uint8_t * d_hit);
+        int countOnMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, uint32_t * d_count);
+        int trianglesOnMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, uint32_t k, int32_t * d_tri, int32_t * d_inst, uint32_t * d_count);
     };
 }

@@ -106,4 +106,22 @@ namespace NSM {
         check(rc, "InstanceWorld::trianglesOnTriangle");
         return rc;
     }
+    inline int InstanceWorld::overlapsMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, uint8_t * d_hit) {
+        const std::vector<float> m12 = detail::meshPoses(poses, p);   // (TriangleHierarchy.inl)
+        const int rc = psm_world_mesh_overlaps_dev(world, other ? other->handle() : nullptr, m12.data(), p, int32_t(skip), d_hit);
+        check(rc, "InstanceWorld::overlapsMesh");
+        return rc;
+    }
+    inline int InstanceWorld::countOnMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, uint32_t * d_count) {
+        const std::vector<float> m12 = detail::meshPoses(poses, p);
+        const int rc = psm_world_mesh_count_dev(world, other ? other->handle() : nullptr, m12.data(), p, int32_t(skip), d_count);
+        check(rc, "InstanceWorld::countOnMesh");
+        return rc;
+    }
+    inline int InstanceWorld::trianglesOnMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, uint32_t k, int32_t * d_tri, int32_t * d_inst, uint32_t * d_count) {
+        const std::vector<float> m12 = detail::meshPoses(poses, p);
+        const int rc = psm_world_mesh_triangles_dev(world, other ? other->handle() : nullptr, m12.data(), p, int32_t(skip), k, d_tri, d_inst, d_count);
+        check(rc, "InstanceWorld::trianglesOnMesh");
+        return rc;
+    }
 }

@@ -665,7 +665,8 @@ int psm_bvh_tri_triangles_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t 
  *     by itself only in launches of more than PSM_QUERY_GRID_CAP waves; the environment variable PSM_MESH_SKIP = 0 / 1, read
  *     at each call, forces that off / on (tools/query_bench.py meshes, tests/test_gpu_mesh_query.py). The answer is the same
  *   - not covered: a mesh against a world, a flat scene or an instanced list; a dual-tree walk that prunes whole subtrees of
- *     other; the intersection segments; k > PSM_QUERY_K_MAX */
+ *     other; the intersection segments; k > PSM_QUERY_K_MAX
+ *     (since added: a mesh against a world -- "mesh queries over a world" below, psm_world_mesh_*_dev) */
 int psm_bvh_mesh_overlaps_dev(psm_bvh* bvh, psm_bvh* other, const float* poses, size_t p, uint8_t* d_hit);
 int psm_bvh_mesh_count_dev(psm_bvh* bvh, psm_bvh* other, const float* poses, size_t p, uint32_t* d_count);
 int psm_bvh_mesh_triangles_dev(psm_bvh* bvh, psm_bvh* other, const float* poses, size_t p, uint32_t k, int32_t* d_ids, uint32_t* d_count);
@@ -926,6 +927,55 @@ int psm_world_tri_overlaps_dev(psm_world* world, const psm_tri_query* d_tris, si
 int psm_world_tri_count_dev(psm_world* world, const psm_tri_query* d_tris, size_t n, uint32_t* d_count);
 int psm_world_tri_triangles_dev(psm_world* world, const psm_tri_query* d_tris, size_t n, uint32_t k, int32_t* d_tri, int32_t* d_inst,
                                 uint32_t* d_count);
+
+/* mesh queries over a world (new; no reference counterpart): the triangle queries over a world above with the
+ * query triangles taken from a built hierarchy `other` of the world's context, at each of p rigid poses, in one call: does body
+ * B, at each of these candidate poses, cut any of the bodies of the scene, which ones, and where. The mesh queries against a
+ * built hierarchy with a world where `bvh` was. Nothing is downloaded, posed on the host or packed. Semantics:
+ *   - other: a built hierarchy of the world's context; it may be one of the world's own members
+ *   - poses: HOST memory, p x 12 floats, each a row-major 3 x 4 [R | T] that takes a point of other's object space into WORLD
+ *     space (x' = R x + T), read at the call and checked as psm_instance's matrix is (finite; R^T R within 1e-5 of the identity
+ *     in every entry, in double: rotations and reflections)
+ *   - T = other's loaded triangle count. Outputs are indexed by pose q and by other's load-order triangle id t: d_hit [p],
+ *     d_count [p][T], d_tri and d_inst [p][T][k]
+ *   - the query of (pose m, triangle t of other) is that of the mesh queries, from other's STORED record, unchanged:
+ *       a = fwd_point(m, v0),  b = a + fwd_vec(m, e1),  c = a + fwd_vec(m, e2)
+ *     in float32, one rounding per operation, nothing fused
+ *   - with skip = -1 the answer for (m, t) is BIT FOR BIT what psm_world_tri_overlaps_dev / psm_world_tri_count_dev /
+ *     psm_world_tri_triangles_dev answer for psm_tri_query {a, b, c} on the same world: the candidate (inst, tri) is posed forward
+ *     (R v0 + T, R e1, R e2) and judged by tri_tri; the same k rule (1 <= k <= PSM_QUERY_K_MAX), the same rows (the min(k, c)
+ *     lowest (inst, tri) that count, ascending, then -1 in both arrays; d_count = min(k, c)). A query whose posed image holds a
+ *     non-finite number (an overflow) meets nothing: 0, or count 0 with rows of -1
+ *   - a triangle of other that its build dropped (not in PSM_BVH_LEAF_TRI) answers count 0 with rows of -1 at every pose
+ *   - overlaps: d_hit[q] = 1 iff some leaf of other at pose q meets some candidate -- the OR over the pose's queries --, else 0
+ *   - skip = s >= 0 leaves instance s out: the answer is that of the ordered instance list with entry s removed and the other
+ *     indices KEPT ("body s at a new pose against all the others" is one call with other = its hierarchy). It is decided where
+ *     an instance is entered (the lone leaf of a one-leaf member and a world of one included), never by a filter after the
+ *     test: a skipped instance costs nothing. skip must be -1 or below psm_world_count()
+ *   - with other a member of the world at its own pose and skip = -1, every leaf meets at least itself in that instance
+ *   - nothing depends on the top-level tree, a member's tree, other's tree, the order of the walk or timing. Query i of the
+ *     launch is pose i / L and other's leaf i % L by ascending triangle id (L its leaf count): the queries, in the order, of the
+ *     triangle queries over a world for the same posed triangles packed in load order
+ *   - refusals, all on the host before any launch and with the outputs untouched: NULL world (PSM_ERR_INVALID, no message, as
+ *     every world query); then, with a message on the world's context: NULL other, poses or outputs, d_count / d_tri / d_inst
+ *     not 4-byte aligned, k == 0 or k > PSM_QUERY_K_MAX (PSM_ERR_INVALID); other not built (PSM_ERR_STATE,
+ *     "mesh query before build"); other of another context (PSM_ERR_INVALID); a stale world (PSM_ERR_STATE: the check and the
+ *     message of every world query); a pose that is not finite or not rigid, named by its index (PSM_ERR_INVALID); skip out of
+ *     range (PSM_ERR_INVALID); p x T >= 2^32 (PSM_ERR_CAPACITY)
+ *   - p == 0 returns PSM_OK and touches nothing (it is answered before everything but the NULL world). Otherwise the outputs are
+ *     cleared in stream order (0, rows of -1) before the one kernel; an empty world and an other without leaves launch no query
+ *     kernel
+ *   - the poses go to the device as the mesh queries' do: copied on the context's stream into a buffer the context owns, and the
+ *     call waits for that copy (and, in the same wait, reads other's leaf count). The call therefore synchronises the context's
+ *     stream ONCE before its launch and CANNOT be captured into a graph; the kernel itself is stream-ordered like every query
+ *   - study knob, no part of the contract: PSM_MESH_SKIP = 0 / 1 as for the mesh queries (the overlaps kernel lets a lane skip
+ *     its walk when its pose's flag already reads 1, by itself only in launches of more than PSM_QUERY_GRID_CAP waves)
+ *   - not covered: mesh queries over flat scenes and instanced lists (psm_scene_*, psm_instances_*); a dual-tree walk; the
+ *     intersection segments; more than one skipped instance; k > PSM_QUERY_K_MAX; graph capture of the call */
+int psm_world_mesh_overlaps_dev(psm_world* world, psm_bvh* other, const float* poses, size_t p, int32_t skip, uint8_t* d_hit);
+int psm_world_mesh_count_dev(psm_world* world, psm_bvh* other, const float* poses, size_t p, int32_t skip, uint32_t* d_count);
+int psm_world_mesh_triangles_dev(psm_world* world, psm_bvh* other, const float* poses, size_t p, int32_t skip, uint32_t k,
+                                 int32_t* d_tri, int32_t* d_inst, uint32_t* d_count);
 
 /* ---------------------------------------------------------------------------------------------
  * several frames in flight (new; DESIGN.md "lanes")

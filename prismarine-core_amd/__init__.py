@@ -42,6 +42,7 @@ EXPORTS = [
     "psm_world_box_overlaps_dev", "psm_world_box_count_dev", "psm_world_box_triangles_dev",
     "psm_world_sweep_sphere_dev", "psm_world_sweep_occluded_dev",
     "psm_world_tri_overlaps_dev", "psm_world_tri_count_dev", "psm_world_tri_triangles_dev",
+    "psm_world_mesh_overlaps_dev", "psm_world_mesh_count_dev", "psm_world_mesh_triangles_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -518,8 +519,8 @@ class TriangleHierarchy:
         non-rigid one raises before any call. The query triangles are other's stored leaves posed in float32 on the device
         (psm_hip.h "mesh queries"); each is answered bit for bit as triOverlaps() answers it. A numpy bool [p]; with
         as_torch=True a torch bool tensor on the context's device, the launch ordered against torch's current stream by events
-        (the call itself waits once for its pose upload, as InstanceWorld.setTransforms does). QueryScene, InstancedScene and
-        InstanceWorld have no mesh queries."""
+        (the call itself waits once for its pose upload, as InstanceWorld.setTransforms does). QueryScene and InstancedScene
+        have no mesh queries; an InstanceWorld has overlapsMesh() / countOnMesh() / trianglesOnMesh()."""
         return self._mesh_query(other, poses, "bool", "psm_bvh_mesh_overlaps_dev", None, as_torch)
 
     def meshCount(self, other, poses, as_torch=False):
@@ -1046,8 +1047,8 @@ class InstanceWorld(QueryScene):
     QueryScene's; QueryHits.geom is the index of the winning instance. A world also has the k-best queries, firstHits() and
     nearest(), the box queries overlapsBox(), countInBox() and trianglesInBox() over world-space boxes, the sphere sweeps
     sphereCast() and sphereCastOccluded() along world-space lines, and the triangle queries overlapsTriangle(),
-    countOnTriangle() and trianglesOnTriangle() on world-space triangles, which the flat lists (QueryScene, InstancedScene)
-    have not."""
+    countOnTriangle() and trianglesOnTriangle() on world-space triangles, and the mesh queries overlapsMesh(), countOnMesh()
+    and trianglesOnMesh() of another hierarchy at world poses, which the flat lists (QueryScene, InstancedScene) have not."""
 
     def __init__(self, ctx, entries, capacity=None):
         self.ctx = ctx
@@ -1185,6 +1186,91 @@ class InstanceWorld(QueryScene):
         return self._tri_query(tris, "tris", "psm_bvh_tri_triangles_dev", k)
 
     _tri_query = TriangleHierarchy._tri_query
+
+    def overlapsMesh(self, other, poses, skip=None, as_torch=False):
+        """Whether `other`, a built TriangleHierarchy of this context (it may be a member of the world), meets some triangle of
+        some instance at each pose (psm_world_mesh_overlaps_dev; not in the reference). poses: one matrix or [p, 3, 4] /
+        [p, 4, 4], each a rigid [R | T] that takes a point of other's object space into WORLD space, checked as an instance's
+        pose is: a non-rigid one raises before any call. The query triangles are other's stored leaves posed in float32 on the
+        device (psm_hip.h "mesh queries over a world"); each is answered bit for bit as overlapsTriangle() answers it. skip: an
+        instance index that is left out (the answer is that of the list without it, the other indices kept: "body i at a new
+        pose against all the others" is skip=i with other = its hierarchy), None for none. A numpy bool [p]; with as_torch=True a
+        torch bool tensor on the context's device, the launch ordered against torch's current stream by events (the call itself
+        waits once for its pose upload, as setTransforms() does, and cannot be captured into a graph)."""
+        return self._mesh_query(other, poses, skip, "bool", "psm_world_mesh_overlaps_dev", None, as_torch)
+
+    def countOnMesh(self, other, poses, skip=None, as_torch=False):
+        """How many (instance, triangle) pairs of the world meet each triangle of `other` at each pose
+        (psm_world_mesh_count_dev; not in the reference): uint32 [p, T], T = other.triangleCount, indexed by other's load-order
+        triangle id (an int32 tensor with as_torch=True); a triangle other's build dropped counts 0. Arguments and placement
+        as overlapsMesh()."""
+        return self._mesh_query(other, poses, skip, "count", "psm_world_mesh_count_dev", None, as_torch)
+
+    def trianglesOnMesh(self, other, poses, k, skip=None, as_torch=False):
+        """Which triangles of which instances meet each triangle of `other` at each pose (psm_world_mesh_triangles_dev; not in
+        the reference): of the pairs countOnMesh() counts, the min(k, count) lowest in (instance, tri), ascending. k: 1 ..
+        QUERY_K_MAX. Returns QueryTriLists: tri and geom (the slot's instance) [p, T, k] int32, -1 in both past count, and count
+        [p, T]. Arguments and placement as overlapsMesh()."""
+        if not 1 <= _k(k, "psm_world_mesh_triangles_dev") <= QUERY_K_MAX:   # (refused here: no call is made)
+            raise PsmError("psm_world_mesh_triangles_dev: k must be 1 .. %d" % QUERY_K_MAX)
+        return self._mesh_query(other, poses, skip, "tris", "psm_world_mesh_triangles_dev", int(k), as_torch)
+
+    def _mesh_query(self, other, poses, skip, out, name, k, as_torch):
+        """one mesh query of the world (TriangleHierarchy._mesh_query's shape): the poses and skip checked on the host, the
+        poses packed [p, 12], the outputs [p] / [p, T] / [p, T, k] twice and [p, T]"""
+        if not isinstance(other, TriangleHierarchy):
+            raise TypeError("%s: other must be a TriangleHierarchy" % name)
+        m = np.asarray(poses)
+        if m.ndim == 2:
+            m = m[None]
+        if m.ndim != 3:
+            raise ValueError("%s: poses must be one matrix or [p, 3, 4] / [p, 4, 4]" % name)
+        p, t = m.shape[0], int(other.triangleCount)
+        m12 = np.ascontiguousarray(np.stack([_pose(x, name) for x in m]).reshape(p, 12) if p else np.zeros((0, 12)), np.float32)
+        if skip is None:
+            s = -1
+        else:
+            s = int(skip)
+            if s != skip or isinstance(skip, bool) or not 0 <= s < len(self.hierarchies):   # (refused here: no call is made)
+                raise PsmError("%s: skip must be None or an instance index 0 .. %d" % (name, len(self.hierarchies) - 1))
+        self._fresh(name)
+        extra = () if k is None else (C.c_uint32(k),)
+        cells, kk = p * t, 1 if k is None else k
+        fn = getattr(lib(), name)
+
+        def call(d_out, d_inst, d_count):
+            tail = () if d_count is None else (C.c_void_p(d_inst), C.c_void_p(d_count))
+            self.ctx.check(fn(self._w, other._h, _p(m12), C.c_size_t(p), C.c_int32(s), *extra, C.c_void_p(d_out), *tail), name)
+
+        if as_torch:
+            import torch
+            dev = torch.device("cuda", self.ctx.device)
+            shape, dtype = {"bool": ((p,), torch.uint8), "count": ((p, t), torch.int32), "tris": ((p, t, kk), torch.int32)}[out]
+            res = torch.empty(shape, dtype=dtype, device=dev)
+            inst = torch.empty(shape, dtype=dtype, device=dev) if out == "tris" else None
+            cnt = torch.empty((p, t), dtype=torch.int32, device=dev) if out == "tris" else None
+            _torch_ordered(self.ctx, dev, lambda: call(res.data_ptr(), None if inst is None else inst.data_ptr(),
+                                                       None if cnt is None else cnt.data_ptr()))
+            return QueryTriLists(res, cnt, inst) if out == "tris" else (res.view(torch.bool) if out == "bool" else res)
+        ctx = self.ctx
+        per = {"bool": p, "count": 4 * cells, "tris": 4 * cells * kk}[out]
+        ho = ctx.buf_alloc(max(per, 16))
+        hi = ctx.buf_alloc(max(per, 16)) if out == "tris" else None
+        hc = ctx.buf_alloc(max(4 * cells, 16)) if out == "tris" else None
+        try:
+            call(ctx.buf_ptr(ho)[0], None if hi is None else ctx.buf_ptr(hi)[0], None if hc is None else ctx.buf_ptr(hc)[0])
+            if out == "bool":
+                return ctx.buf_download(ho, np.uint8, p).view(np.bool_) if p else np.zeros(0, np.bool_)
+            if out == "count":
+                return (ctx.buf_download(ho, np.uint32, cells) if cells else np.zeros(0, np.uint32)).reshape(p, t)
+            ids = ctx.buf_download(ho, np.int32, cells * kk) if cells else np.zeros(0, np.int32)
+            ins = ctx.buf_download(hi, np.int32, cells * kk) if cells else np.zeros(0, np.int32)
+            cnt = ctx.buf_download(hc, np.uint32, cells) if cells else np.zeros(0, np.uint32)
+            return QueryTriLists(ids.reshape(p, t, kk), cnt.reshape(p, t), ins.reshape(p, t, kk))
+        finally:
+            for h in (ho, hi, hc):
+                if h is not None:
+                    ctx.buf_free(h)
 
     def _call(self, name, d_in, n, extra, d_out, d_geom):
         name = name.replace("psm_bvh_", "psm_world_")

@@ -161,6 +161,9 @@ struct PoseArea {
 std::mutex pose_mu;
 std::unordered_map<const psm_ctx*, PoseArea> pose_area;
 
+}  // namespace
+
+// (psm_query_host.h: the mesh queries over a world, world.hip's world_mesh_query(), upload their poses here too)
 int poses_for(psm_ctx* c, size_t bytes, void** out) {
     std::lock_guard<std::mutex> lk(pose_mu);
     PoseArea& a = pose_area[c];
@@ -178,6 +181,8 @@ int poses_for(psm_ctx* c, size_t bytes, void** out) {
     *out = a.ptr;
     return PSM_OK;
 }
+
+namespace {
 
 const char* const MESH_NAME[] = {"psm_bvh_mesh_overlaps_dev", "psm_bvh_mesh_count_dev", "psm_bvh_mesh_triangles_dev"};
 

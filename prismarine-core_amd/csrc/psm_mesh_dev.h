@@ -1,4 +1,4 @@
-// psm_mesh_dev.h -- what a mesh query (mesh.hip; include/psm_hip.h "mesh queries") adds in front of the triangle
+// psm_mesh_dev.h -- what a mesh query (mesh.hip, and world_mesh.hip over a world; include/psm_hip.h "mesh queries") adds in front of the triangle
 // queries' candidate test: which (pose, leaf) a launch's query i is, and the query triangle of a stored leaf at a pose. Both also
 // compile for the host: a stand-alone program defines PSM_MESH_FN (and PSM_TRI_FN, PSM_WORLD_BOX_FN) as a host function's
 // decoration before it includes this file (tests/cpp/mesh_pose_host.cpp), and the CPU test holds what they compute against

@@ -1,5 +1,5 @@
 // psm_world_dev.h -- the device pieces the kernel files of a world share (world.hip, world_box.hip, world_sweep.hip,
-// world_tri.hip): the table row, the node of the tree over the instances, the kernel arguments, the padding and the slacks,
+// world_tri.hip, world_mesh.hip): the table row, the node of the tree over the instances, the kernel arguments, the padding and the slacks,
 // the two-level walk, the loads of a row, the best record of a world (WorldBest) and a ray in a world (WorldRay). Moved here
 // from world.hip as they were; every kernel of world.hip compiles to the same instructions as with the pieces in its own file
 // (tools/kernel_diff.py; the digests of tests/test_world_query_cpu.py and tests/test_world_kbest_cpu.py).
@@ -54,6 +54,27 @@ int world_tri_launch(psm_ctx* c, int mode, uint32_t grid, const WorldArgs& a);
 // world_sweep.hip: the launch of a world's sweep kernel (any: whether there is a contact; else the first contact) for
 // world.hip's host path; a.rays holds the sweeps (psm_sweep_query) where a ray's two float4 are
 int world_sweep_launch(psm_ctx* c, bool any, uint32_t grid, const WorldArgs& a);
+
+// WorldArgs keeps its layout; what a mesh query over a world (world_mesh.hip) adds travels beside it. w: the
+// world, spill and outputs (occluded: the flag per pose; count: [p][T]; hits / geom: the int32 [p][T][k] rows), samples = k,
+// n = p x L; rays is not read
+struct WorldMeshArgs {
+    WorldArgs w;
+    const float4* tri48;        // the other hierarchy's v0, e1, e2 per triangle
+    const int32_t* leaf_tri;    // ... and its leaves in slot order: leaf j is triangle leaf_tri[j], ascending
+    const float4* poses;        // [p] x three float4: the rows of [R | T], other's object space into world space
+    uint64_t magic;             // mesh_magic(L)
+    uint32_t L, T;              // the other's leaf count and loaded triangle count
+    uint32_t flags;             // WORLD_MESH_FLAG_*
+    int32_t skip;               // the instance that is never entered, -1: none
+};
+constexpr uint32_t WORLD_MESH_FLAG_SKIP = 1u;   // the flag kernel: a lane whose pose's flag already reads 1 does not walk
+// the most answers (poses x triangles) of one call: the kernels index them with 32 bits (psm_mesh_dev.h's MESH_QUERIES_MAX)
+constexpr uint64_t WORLD_MESH_ANSWERS_MAX = (uint64_t)1 << 32;
+
+// world_mesh.hip: the launch of a world's mesh kernel (mode: 0 overlaps, 1 count, 2 triangles) for world.hip's host path
+// (world_mesh_query()); a.w.samples is the triangles query's k; magic is set there from a.L (mesh_magic, psm_mesh_dev.h)
+int world_mesh_launch(psm_ctx* c, int mode, uint32_t grid, WorldMeshArgs a);
 
 namespace {
 

@@ -20,6 +20,7 @@
 // one). Lanes of a wave may be at different levels: the loop body holds the three steps under one branch each.
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <unordered_map>
@@ -877,6 +878,100 @@ int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* 
     return launch(c, WORLD_KERNELS, kind, grid, a);
 }
 
+const char* const WORLD_MESH_NAME[] = {"psm_world_mesh_overlaps_dev", "psm_world_mesh_count_dev", "psm_world_mesh_triangles_dev"};
+
+// A mesh query of a world (world_mesh.hip): mesh.hip's mesh_query() with a world where the queried hierarchy was.
+// The NULL world and p == 0 are answered before anything else is looked at; then the data, k, the other hierarchy's state and
+// context, the stale check (every world query's), the poses, skip, the number of answers -- all on the host, before any launch,
+// the outputs untouched. Then the poses go to the device (mesh.hip's pose area: a copy on the context's stream and one
+// synchronisation, the other hierarchy's leaf count coming back in the same wait), the outputs are cleared in stream order, and
+// one kernel runs unless the world is empty or the other hierarchy has no leaf. mode: 0 overlaps, 1 count, 2 triangles
+int world_mesh_query(psm_world* w, psm_bvh* o, const float* poses, size_t p, int32_t skip, int mode, uint32_t k, void* d_out,
+                     int32_t* d_inst, uint32_t* d_count) {
+    if (!w) return PSM_ERR_INVALID;
+    if (p == 0) return PSM_OK;
+    psm_ctx* c = w->ctx;
+    const char* name = WORLD_MESH_NAME[mode];
+    char msg[192];
+    const bool rows = mode == 2;
+    if (!o || !poses || !d_out || (rows && (!d_inst || !d_count))) {
+        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (mode != 0 && ((uintptr_t)d_out & 3u) != 0) {
+        snprintf(msg, sizeof msg, "%s: %s not 4-byte aligned", name, rows ? "tris" : "counts");
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (rows && (((uintptr_t)d_inst & 3u) != 0 || ((uintptr_t)d_count & 3u) != 0)) {
+        snprintf(msg, sizeof msg, "%s: %s not 4-byte aligned", name, ((uintptr_t)d_inst & 3u) != 0 ? "inst" : "counts");
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (rows && (k == 0 || k > PSM_QUERY_K_MAX)) {
+        snprintf(msg, sizeof msg, "%s: k must be 1 .. %d", name, PSM_QUERY_K_MAX);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (!o->built) return set_err(c, PSM_ERR_STATE, "mesh query before build");
+    if (o->ctx != c) {
+        snprintf(msg, sizeof msg, "%s: the world and the other hierarchy are of different contexts", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    const int stale = first_stale(w);
+    if (stale >= 0) return refuse_stale(w, name, stale);
+    for (size_t q = 0; q < p; q++)
+        if (const char* why = pose_fault(poses + 12 * q)) {
+            snprintf(msg, sizeof msg, "%s: pose %zu %s", name, q, why);
+            return set_err(c, PSM_ERR_INVALID, msg);
+        }
+    if (skip < -1 || (skip >= 0 && (uint32_t)skip >= w->count)) {
+        snprintf(msg, sizeof msg, "%s: skip %d of a world of %u (-1: no instance is left out)", name, (int)skip, w->count);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    const uint32_t T = o->tri_count;
+    if ((uint64_t)p * T >= WORLD_MESH_ANSWERS_MAX) {
+        snprintf(msg, sizeof msg, "%s: %zu poses of %u triangles are more than 2^32 answers", name, p, T);
+        return set_err(c, PSM_ERR_CAPACITY, msg);
+    }
+    (void)hipSetDevice(c->device);
+    uint32_t L = 0;
+    void* d_poses = nullptr;
+    WorldMeshArgs m = {};
+    uint32_t grid = 0;
+    if (w->count != 0) {   // (an empty world: no query kernel, nothing to upload; the clears alone)
+        int rc = poses_for(c, p * 12 * sizeof(float), &d_poses);
+        if (rc != PSM_OK) return rc;
+        PSM_HIP(c, hipMemcpyAsync(d_poses, poses, p * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        PSM_HIP(c, hipMemcpyAsync(&L, o->d_small + SM_COUNT, sizeof L, hipMemcpyDeviceToHost, c->stream));
+        PSM_HIP(c, hipStreamSynchronize(c->stream));
+        if (L > T) return set_err(c, PSM_ERR_STATE, "mesh query: the other hierarchy's leaf count exceeds its triangle count");
+        // (the context's stack area is allocated here, on its first query: the last thing that can fail before the outputs change)
+        rc = batch_args(c, nullptr, p * (size_t)L, d_out, k, m.w, grid);
+        if (rc != PSM_OK) return rc;
+    }
+    // the outputs, cleared in stream order: a dropped triangle's entries and an unset flag read 0 / -1
+    const size_t cells = p * (size_t)T;
+    if (mode == 0) PSM_HIP(c, hipMemsetAsync(d_out, 0, p, c->stream));
+    if (mode == 1) PSM_HIP(c, hipMemsetAsync(d_out, 0, cells * sizeof(uint32_t), c->stream));
+    if (rows) {
+        PSM_HIP(c, hipMemsetAsync(d_out, 0xff, cells * k * sizeof(int32_t), c->stream));
+        PSM_HIP(c, hipMemsetAsync(d_inst, 0xff, cells * k * sizeof(int32_t), c->stream));
+        PSM_HIP(c, hipMemsetAsync(d_count, 0, cells * sizeof(uint32_t), c->stream));
+    }
+    if (w->count == 0 || L == 0) return PSM_OK;
+    m.w.geom = d_inst;
+    if (rows) m.w.count = d_count;
+    m.w.root = w->count == 1 ? ~0 : 0;
+    m.w.rows = w->d_rows;
+    m.w.nodes = w->d_nodes;
+    m.tri48 = o->d_tri48; m.leaf_tri = o->d_leaftri; m.poses = (const float4*)d_poses;
+    m.L = L; m.T = T; m.skip = skip;
+    // The flag kernel's skip of lanes whose pose is already flagged: mesh.hip's rule (on by itself where the launch takes the
+    // grid-stride loop) and mesh.hip's study knob, PSM_MESH_SKIP = 0 / 1 (psm_hip.h)
+    const char* knob = getenv("PSM_MESH_SKIP");
+    const bool strided = (p * (size_t)L + QUERY_BLOCK - 1) / QUERY_BLOCK > QUERY_GRID_CAP;
+    m.flags = (knob ? knob[0] != '0' : strided) ? WORLD_MESH_FLAG_SKIP : 0u;
+    return world_mesh_launch(c, mode, grid, m);
+}
+
 template <class T>
 int world_alloc(psm_ctx* c, T** p, size_t n) {
     PSM_HIP(c, hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
@@ -1045,4 +1140,14 @@ int psm_world_sweep_sphere_dev(psm_world* w, const psm_sweep_query* d_sweeps, si
 }
 int psm_world_sweep_occluded_dev(psm_world* w, const psm_sweep_query* d_sweeps, size_t n, uint8_t* d_hit) {
     return psm::world_query(w, psm::Q_SWEEP_ANY, d_sweeps, n, d_hit, nullptr);
+}
+int psm_world_mesh_overlaps_dev(psm_world* w, psm_bvh* other, const float* poses, size_t p, int32_t skip, uint8_t* d_hit) {
+    return psm::world_mesh_query(w, other, poses, p, skip, 0, 0, d_hit, nullptr, nullptr);
+}
+int psm_world_mesh_count_dev(psm_world* w, psm_bvh* other, const float* poses, size_t p, int32_t skip, uint32_t* d_count) {
+    return psm::world_mesh_query(w, other, poses, p, skip, 1, 0, d_count, nullptr, nullptr);
+}
+int psm_world_mesh_triangles_dev(psm_world* w, psm_bvh* other, const float* poses, size_t p, int32_t skip, uint32_t k, int32_t* d_tri,
+                                 int32_t* d_inst, uint32_t* d_count) {
+    return psm::world_mesh_query(w, other, poses, p, skip, 2, k, d_tri, d_inst, d_count);
 }

@@ -70,6 +70,13 @@ already resident on the device as psm_tri_query records in load order -- kernel 
 the spread between runs, and the call's own overhead (upload, wait, clears: a mesh query of a mesh without leaves) timed apart; (c) the path the call replaces: download of the other mesh's triangles, posing in numpy,
 packing, upload, triCount (timed as a whole, alternated with (a)); and the flag query with its early-out skip forced on and off
 (PSM_MESH_SKIP = 1 / 0; by itself a launch skips when it takes the grid-stride loop). No ratio is fixed in advance.
+`query_bench.py worldmeshes`: the mesh queries of an instance world (psm_world_mesh_overlaps_dev / psm_world_mesh_count_dev /
+psm_world_mesh_triangles_dev) on the worldtriangles mode's world of 4 096 torus poses and on the Sponza-class scene as a world of one,
+the other mesh the torus (2 304 triangles; a quarter of the scene's extent across against the scene) at 1, 64 and 1 024 poses placed
+so that the meshes cut. Per case and query, alternated A B A B (host-timed medians of REPS), twice: (a) the world mesh query, the
+whole call, against (b) countOnTriangle / overlapsTriangle / trianglesOnTriangle (k = 16) over the same posed triangles already
+resident on the device as psm_tri_query records in load order; the two (b) medians give the spread between runs; and the call's
+own overhead (checks, upload, wait, clears: the same call on a mesh without leaves) timed apart. No ratio is fixed in advance.
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -940,19 +947,20 @@ def triangles():
     print(json.dumps(out))
 
 
+def posed(src, poses):
+    """the query triangles [p, t, 3, 3] of the stored (v0, e1, e2) of src [t, 3, 3] at poses [p, 3, 4], in float32 in the
+    library's operation order (psm_hip.h "mesh queries"): (b) and (c) then ask exactly what (a) asks"""
+    m = poses[:, None]
+    v0, e1, e2 = src[None, :, 0], (src[:, 1] - src[:, 0])[None], (src[:, 2] - src[:, 0])[None]
+
+    def vec(d):
+        return np.stack([(m[..., k, 0] * d[..., 0] + m[..., k, 1] * d[..., 1]) + m[..., k, 2] * d[..., 2] for k in range(3)], axis=-1)
+    a = vec(v0) + m[..., 3]
+    return np.stack([a, a + vec(e1), a + vec(e2)], axis=2)
+
+
 def meshes():
     lib = psm.lib()
-
-    def posed(src, poses):
-        """the query triangles [p, t, 3, 3] of the stored (v0, e1, e2) of src [t, 3, 3] at poses [p, 3, 4], in float32 in the
-        library's operation order (psm_hip.h "mesh queries"): (b) and (c) then ask exactly what (a) asks"""
-        m = poses[:, None]
-        v0, e1, e2 = src[None, :, 0], (src[:, 1] - src[:, 0])[None], (src[:, 2] - src[:, 0])[None]
-
-        def vec(d):
-            return np.stack([(m[..., k, 0] * d[..., 0] + m[..., k, 1] * d[..., 1]) + m[..., k, 2] * d[..., 2] for k in range(3)], axis=-1)
-        a = vec(v0) + m[..., 3]
-        return np.stack([a, a + vec(e1), a + vec(e2)], axis=2)
     out = {"mode": "meshes", "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
     tor = torus(48, 24, 0.7, 0.25).reshape(-1, 3, 3)
     sp = scenes.sponza_like()
@@ -1294,6 +1302,114 @@ def worldtriangles():
     print(json.dumps(out))
 
 
+def worldmeshes():
+    lib = psm.lib()
+    ctx = psm.Context(0)
+    tor = torus(48, 24, 0.7, 0.25).reshape(-1, 3, 3)
+    rng = np.random.RandomState(17)
+    out = {"mode": "worldmeshes", "torus_triangles": int(tor.shape[0]), "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+
+    def hier(tris):
+        th = psm.TriangleHierarchy(ctx)
+        th.allocate(tris.shape[0])
+        th.loadTriangles(np.ascontiguousarray(tris, np.float32).reshape(-1, 9))
+        th.build()
+        return th
+
+    def turn():
+        q, r = np.linalg.qr(rng.normal(size=(3, 3)))
+        return q * np.sign(np.diag(r))
+    # the worldtriangles mode's world (4 096 turned grid poses of the torus), and the Sponza-class scene as a world of one
+    poses_n = 4096
+    side = int(np.ceil(np.sqrt(poses_n)))
+    grid = np.zeros((poses_n, 3, 4), np.float32)
+    k_ = np.arange(poses_n)
+    for j in range(poses_n):
+        grid[j, :, :3] = turn()
+    grid[:, 0, 3], grid[:, 1, 3] = 2.5 * (k_ % side), 2.5 * (k_ // side)
+    sp = scenes.sponza_like()["tris"].reshape(-1, 3, 3)
+    identity = np.eye(3, 4, dtype=np.float32)
+    for world_name, tris, world_poses in (("torus4096", tor, grid), ("sponza", sp, identity[None])):
+        member = hier(tris)
+        wd = psm.InstanceWorld(ctx, [(member, m) for m in world_poses])
+        w = wd._w
+        v = tris.reshape(-1, 3)
+        # the other mesh: the torus as it is against the world of tori, a quarter of the scene's extent across against the scene
+        scale = 1.0 if world_name != "sponza" else 0.25 * float((v.max(0) - v.min(0)).max()) / 1.9
+        otris = (tor.astype(np.float64) * scale).astype(np.float32)
+        other = hier(otris)
+        t = otris.shape[0]
+        # as many triangles, none a leaf: a call on it checks, uploads, waits and clears as the real one does and launches no kernel
+        hollow = hier(np.repeat(otris[:, :1], 3, axis=1))
+        out[world_name + "_instances"], out[world_name + "_member_tris"] = len(wd), int(member.info().leaf_count)
+        out[world_name + "_other_tris"] = int(other.info().leaf_count)
+        src = other.download(psm.BVH_POSITIONS, np.float32, 9 * t).reshape(t, 3, 3)
+        for p in (1, 64, 1024):
+            # poses at which the meshes cut: the other mesh turned at random, its centre half a radius beside a body of the world
+            # (the scene: on one of its vertices)
+            rng.seed(2000 + p)
+            if world_name == "sponza":
+                at = v[rng.choice(v.shape[0], p)].astype(np.float64)
+            else:
+                at = world_poses[rng.choice(poses_n, p, replace=False), :, 3].astype(np.float64) + rng.uniform(-0.5, 0.5, (p, 3))
+            poses = np.stack([np.concatenate([turn(), c.reshape(3, 1)], axis=1) for c in at]).astype(np.float32)
+            m12 = np.ascontiguousarray(poses.reshape(p, 12))
+            n = p * t
+            hs = [ctx.buf_alloc(x) for x in (48 * n, max(p, 16), max(n, 16), 4 * n, 4 * 16 * n, 4 * 16 * n, 4 * n)]
+            p_tri, p_flag, p_flags, p_count, p_rows, p_inst, p_count2 = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in hs)
+            size, np_, pm, none = C.c_size_t(n), C.c_size_t(p), m12.ctypes.data_as(C.c_void_p), C.c_int32(-1)
+            rec = np.zeros((p, t, 3, 4), np.float32)
+            rec[:, :, :, 0:3] = posed(src, poses)
+            ctx.buf_upload(hs[0], rec.reshape(n, 12))
+
+            def mesh_overlaps():
+                ctx.check(lib.psm_world_mesh_overlaps_dev(w, other._h, pm, np_, none, p_flag), "psm_world_mesh_overlaps_dev")
+
+            def mesh_count():
+                ctx.check(lib.psm_world_mesh_count_dev(w, other._h, pm, np_, none, p_count), "psm_world_mesh_count_dev")
+
+            def mesh_rows():
+                ctx.check(lib.psm_world_mesh_triangles_dev(w, other._h, pm, np_, none, C.c_uint32(16), p_rows, p_inst, p_count), "psm_world_mesh_triangles_dev")
+
+            def overhead(fn_name, *outs):
+                fn = getattr(lib, fn_name)
+                return lambda: ctx.check(fn(w, hollow._h, pm, np_, none, *outs), fn_name)
+
+            def tri_overlaps():
+                ctx.check(lib.psm_world_tri_overlaps_dev(w, p_tri, size, p_flags), "psm_world_tri_overlaps_dev")
+
+            def tri_count():
+                ctx.check(lib.psm_world_tri_count_dev(w, p_tri, size, p_count2), "psm_world_tri_count_dev")
+
+            def tri_rows():
+                ctx.check(lib.psm_world_tri_triangles_dev(w, p_tri, size, C.c_uint32(16), p_rows, p_inst, p_count2), "psm_world_tri_triangles_dev")
+            key = "%s_p%d_" % (world_name, p)
+            out[key + "queries"] = n
+            # (a) and (b) alternated A B A B, (b) twice per case: its two medians give the spread between runs
+            for name, fa, fb, fo in (("count", mesh_count, tri_count, overhead("psm_world_mesh_count_dev", p_count)),
+                                     ("overlaps", mesh_overlaps, tri_overlaps, overhead("psm_world_mesh_overlaps_dev", p_flag)),
+                                     ("triangles_k16", mesh_rows, tri_rows, overhead("psm_world_mesh_triangles_dev", C.c_uint32(16), p_rows, p_inst, p_count))):
+                a1, b1 = abab(ctx, fa, fb)
+                a2, b2 = abab(ctx, fa, fb)
+                out[key + name + "_a_ms"], out[key + name + "_b_ms"] = [a1, a2], [b1, b2]
+                out[key + name + "_overhead_ms"] = round(median_ms(ctx, fo), 4)
+            mesh_count()
+            mine = ctx.buf_download(hs[3], np.uint32, n)
+            tri_count()
+            theirs = ctx.buf_download(hs[6], np.uint32, n)
+            out[key + "equal"] = bool(np.array_equal(mine, theirs))
+            mesh_overlaps()
+            out[key + "poses_that_cut"] = round(float(ctx.buf_download(hs[1], np.uint8, p).mean()), 4)
+            out[key + "triangles_that_meet"], out[key + "mean_count"] = round(float((mine > 0).mean()), 4), round(float(mine.mean()), 3)
+            for h in hs:
+                ctx.buf_free(h)
+        wd.close()
+        for th in (other, hollow, member):
+            th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def worldsweeps():
     lib = psm.lib()
     ctx = psm.Context(0)
@@ -1428,4 +1544,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "meshes": meshes, "worldtriangles": worldtriangles}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "meshes": meshes, "worldtriangles": worldtriangles, "worldmeshes": worldmeshes}.get(" ".join(sys.argv[1:]), main)()
