@@ -75,6 +75,13 @@ namespace NSM {
         int triOverlaps(const psm_tri_query * d_tris, size_t n, uint8_t * d_hit);
         int triCount(const psm_tri_query * d_tris, size_t n, uint32_t * d_count);
         int triTriangles(const psm_tri_query * d_tris, size_t n, uint32_t k, int32_t * d_ids, uint32_t * d_count);
+        // not in the reference: the nearest triangle to each of n query triangles within its rmax -- d_hits [n] = {u, v, dist, tri,
+        // s, t, 0, 0}, (u, v) on the stored triangle and (s, t) on the query's, a miss {0, 0, +inf, -1, 0, 0, 0, 0} -- and whether
+        // any is within it, d_flag [n] (fifteen vertex-face and edge-edge features in float32, 0 where the triangles meet; psm_hip.h
+        // "clearance queries"; psm_bvh_tri_closest_dev / psm_bvh_tri_within_dev), stream-ordered on the context; returns the
+        // psm_status
+        int triClosest(const psm_tri_dist_query * d_queries, size_t n, psm_tri_hit * d_hits);
+        int triWithin(const psm_tri_dist_query * d_queries, size_t n, uint8_t * d_flag);
         // not in the reference: whether / how many / which triangles meet each stored triangle of another built hierarchy `other`
         // (of the same context) at each of p rigid poses (glm's convention, as InstancedScene's: a point of other's object space
         // goes to m * x in this hierarchy's), posed in float32 on the device and answered as triOverlaps / triCount / triTriangles

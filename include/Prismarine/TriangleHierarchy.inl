@@ -107,6 +107,16 @@ namespace NSM {
         check(rc, "TriangleHierarchy::triTriangles");
         return rc;
     }
+    inline int TriangleHierarchy::triClosest(const psm_tri_dist_query * d_queries, size_t n, psm_tri_hit * d_hits) {
+        const int rc = psm_bvh_tri_closest_dev(bvh, d_queries, n, d_hits);
+        check(rc, "TriangleHierarchy::triClosest");
+        return rc;
+    }
+    inline int TriangleHierarchy::triWithin(const psm_tri_dist_query * d_queries, size_t n, uint8_t * d_flag) {
+        const int rc = psm_bvh_tri_within_dev(bvh, d_queries, n, d_flag);
+        check(rc, "TriangleHierarchy::triWithin");
+        return rc;
+    }
     namespace detail {
     // psm_hip.h wants row-major 3 x 4 [R | T] matrices: m12[4 * row + col] = m[col][row], glm's last row dropped
     inline std::vector<float> meshPoses(const glm::mat4 * m, size_t p) {

@@ -620,6 +620,73 @@ int psm_bvh_tri_overlaps_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t n
 int psm_bvh_tri_count_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t n, uint32_t* d_count);
 int psm_bvh_tri_triangles_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t n, uint32_t k, int32_t* d_ids, uint32_t* d_count);
 
+/* clearance queries against a built hierarchy (new; no reference counterpart): how far a given triangle is
+ * from the hierarchy's triangles -- which one is nearest, at what distance and at which two points, and whether any is within
+ * a radius -- on the same leaves, stack, context and checks as the queries above. The triangle family's counterpart of
+ * psm_bvh_closest_point_dev / psm_bvh_within_dev. Flat scenes, instanced lists, worlds and posed meshes have none. Semantics:
+ *   - a query {a, rmax, b, c} is valid iff its nine coordinates are finite and rmax is neither NaN nor negative; -0 is 0 and
+ *     +inf is no limit (the point queries' rules). A degenerate query triangle (a segment, a point) is valid. An invalid query
+ *     is a miss, never an error. The pads are not read
+ *   - the candidates are the hierarchy's leaves (PSM_BVH_LEAF_TRI) by load-order triangle id, a triangle read as the build
+ *     stores it: v0, e1 = v1 - v0, e2 = v2 - v0
+ *   - a candidate's distance is tri_dist(v0, e1, e2, a, b, c) in float32, one fixed operation order, one rounding per
+ *     operation, nothing fused, division and sqrtf correctly rounded (psm_tri_dist_dev.h; tests/tri_dist_query_model.py writes
+ *     it once over a float type and is its canonical statement).
+ *       everything is relative to the stored v0, as tri_tri has it: A = a - v0, B = b - v0, C = c - v0, g1 = B - A, g2 = C - A,
+ *       g3 = C - B, e3 = e2 - e1: the overlap test and the distances see the same rounded coordinates
+ *       1. fifteen features, in this order, each giving four weights (u, v) of e1, e2 and (s, t) of g1, g2:
+ *            F0 - F2   the query's vertices a, b, c against the stored triangle: (u, v) of closest_on_tri(v0, e1, e2, a | b | c),
+ *                      the point queries' function bit for bit; (s, t) = (0, 0), (1, 0), (0, 1)
+ *            F3 - F5   the stored vertices 0, e1, e2 against the query triangle: (s, t) of closest_on_tri(A, g1, g2, 0 | e1 | e2);
+ *                      (u, v) = (0, 0), (1, 0), (0, 1)
+ *            F6 - F14  the nine edge pairs e_i, g_j, i outer, j inner (tri_tri's order), by seg_seg(p1, d1, p2, d2) with
+ *                      (p1, d1) = (0, e1), (0, e2), (e1, e3) and (p2, d2) = (A, g1), (A, g2), (B, g3); a weight x along
+ *                      e1 / e2 / e3 is (u, v) = (x, 0) / (0, x) / (1 - x, x), a weight y along g1 / g2 / g3 likewise for (s, t)
+ *          seg_seg: the clamped closest points of two segments (Ericson 5.1.9): r = p1 - p2, a = dot(d1, d1), e = dot(d2, d2),
+ *          b = dot(d1, d2), c = dot(d1, r), f = dot(d2, r), den = a e - b b; skew = den > 2^-16 (a e);
+ *          x0 = clamp01(skew ? (b f - c e) / den : 0); y = e > 0 ? clamp01((b x0 + f) / e) : 0; x = a > 0 ? clamp01((b y - c) / a) : 0
+ *          (a zero-length segment is its point; a pair whose den is within its own rounding -- sin^2 of the angle at most
+ *          2^-16, closest_on_tri's sliver threshold -- is parallel; clamp01 takes a NaN to 0: finite weights in [0, 1] for
+ *          every finite input)
+ *       2. every feature's d2 is computed the same way from its weights: Q = (A + s g1) + t g2, P = u e1 + v e2 per component,
+ *          d2 = dot(Q - P, Q - P): (tri, u, v, s, t) reproduce the value exactly. The smallest d2 wins; on a bit-equal d2 the
+ *          first in the order (F0 is taken first; a later feature replaces the winner iff its d2 is smaller)
+ *       3. if tri_tri(v0, e1, e2, a, b, c) holds (the triangle queries' test above) the pair's d2 is 0: two triangles that meet
+ *          have clearance 0, and an edge that pierces a face leaves all fifteen features positive. The weights reported are
+ *          STILL step 2's winner: where the two boundaries come closest, not a point of the intersection. tri_tri's 20 axes are
+ *          complete for two triangles with an area; where neither has one (a segment against a segment or a point), and for a
+ *          segment lying in a triangle's plane, it lacks axes and may hold for a pair that is apart (its block above: "whatever
+ *          the remaining axes say"): such a pair is at 0 too -- the side a clearance check errs on, and what
+ *          psm_bvh_tri_overlaps_dev answers for it
+ *       4. dist = sqrtf(d2); the candidate counts iff dist <= rmax (closed)
+ *     accuracy: on well-shaped triangles dist is within 2^-19 L of the real distance, L the largest coordinate difference of the
+ *     pair's six vertices relative to v0 (DESIGN.md 4.23 has the measured figure); a sliver on either side keeps
+ *     closest_on_tri's per-triangle bound. Coordinate differences beyond 2^30 overflow tri_tri (above), beyond
+ *     2^63 the squares: d2 is then +inf or NaN and the candidate does not count
+ *   - closest: d_hits[i] = {u, v, dist, tri, s, t, 0, 0} of the smallest d2 over all candidates that count, on a bit-equal d2
+ *     the lowest triangle id: nothing depends on the traversal order. The first 16 bytes are a psm_hit. The nearest point of the
+ *     stored triangle is (v0 + u e1) + v e2, that of the query triangle (a + s (b - a)) + t (c - a). A miss, or an invalid
+ *     query, is {0, 0, +inf, -1, 0, 0, 0, 0}
+ *   - within: d_flag[i] = 1 iff some candidate counts, else 0 (uint8_t, torch.bool-compatible): the predicate tri >= 0 of the
+ *     first call; the walk ends at the first such candidate
+ *   - not covered: a posed mesh in one call and per-pose clearance, worlds, flat scenes and instanced lists, the k nearest
+ *     triangles, penetration depth, an intersection point at dist = 0
+ *   - d_queries and d_hits 16-byte aligned; everything else (NULL checks, n = 0, PSM_ERR_STATE before the first build --
+ *     "clearance query before build" --, PSM_ERR_CAPACITY for a hierarchy deeper than the query stack, stream order, capture,
+ *     refit, 0 / 1 leaves) as for the queries above. A refused call launches nothing and leaves the output buffers untouched */
+typedef struct {
+    float a[3], rmax;
+    float b[3], pad0;
+    float c[3], pad1;
+} psm_tri_dist_query; /* 48 B: three 16-byte loads; psm_tri_query's layout with rmax where its first pad is */
+typedef struct {
+    float u, v, dist; /* the first 16 bytes: a psm_hit */
+    int32_t tri;
+    float s, t, zero0, zero1;
+} psm_tri_hit; /* 32 B: two 16-byte stores */
+int psm_bvh_tri_closest_dev(psm_bvh* bvh, const psm_tri_dist_query* d_queries, size_t n, psm_tri_hit* d_hits);
+int psm_bvh_tri_within_dev(psm_bvh* bvh, const psm_tri_dist_query* d_queries, size_t n, uint8_t* d_flag);
+
 /* mesh queries against a built hierarchy (new; no reference counterpart): the triangle queries above with the
  * query triangles taken from ANOTHER built hierarchy `other` of the same context, at each of p rigid poses, in one call: does
  * part B at this pose cut part A, where, and with which triangles. `bvh` is the hierarchy being queried. Nothing is downloaded,

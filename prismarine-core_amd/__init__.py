@@ -31,6 +31,7 @@ EXPORTS = [
     "psm_bvh_box_overlaps_dev", "psm_bvh_box_count_dev", "psm_bvh_box_triangles_dev",
     "psm_bvh_sweep_sphere_dev", "psm_bvh_sweep_occluded_dev",
     "psm_bvh_tri_overlaps_dev", "psm_bvh_tri_count_dev", "psm_bvh_tri_triangles_dev",
+    "psm_bvh_tri_closest_dev", "psm_bvh_tri_within_dev",
     "psm_bvh_mesh_overlaps_dev", "psm_bvh_mesh_count_dev", "psm_bvh_mesh_triangles_dev",
     "psm_scene_intersect_dev", "psm_scene_occluded_dev", "psm_scene_count_hits_dev", "psm_scene_closest_point_dev", "psm_scene_within_dev",
     "psm_scene_inside_dev", "psm_scene_signed_distance_dev",
@@ -69,6 +70,8 @@ POINT_QUERY_DT = np.dtype([("p", "<f4", 3), ("rmax", "<f4")])   # psm_point_quer
 BOX_QUERY_DT = np.dtype([("lo", "<f4", 3), ("pad0", "<f4"), ("hi", "<f4", 3), ("pad1", "<f4")])   # psm_box_query
 SWEEP_QUERY_DT = np.dtype([("origin", "<f4", 3), ("radius", "<f4"), ("direct", "<f4", 3), ("tmax", "<f4")])   # psm_sweep_query
 TRI_QUERY_DT = np.dtype([("a", "<f4", 3), ("pad0", "<f4"), ("b", "<f4", 3), ("pad1", "<f4"), ("c", "<f4", 3), ("pad2", "<f4")])   # psm_tri_query
+TRI_DIST_QUERY_DT = np.dtype([("a", "<f4", 3), ("rmax", "<f4"), ("b", "<f4", 3), ("pad0", "<f4"), ("c", "<f4", 3), ("pad1", "<f4")])   # psm_tri_dist_query
+TRI_HIT_DT = np.dtype([("u", "<f4"), ("v", "<f4"), ("dist", "<f4"), ("tri", "<i4"), ("s", "<f4"), ("t", "<f4"), ("zero0", "<f4"), ("zero1", "<f4")])   # psm_tri_hit
 QUERY_K_MAX = 16   # psm_hip.h PSM_QUERY_K_MAX
 SCENE_MAX_GEOMETRIES = 32   # psm_hip.h PSM_SCENE_MAX_GEOMETRIES
 WORLD_MAX_INSTANCES = 65536   # psm_hip.h PSM_WORLD_MAX_INSTANCES
@@ -512,6 +515,41 @@ class TriangleHierarchy:
         packed[:, :, 0:3] = t
         return self._launch_np(packed.reshape(-1, 12), out, name, *extra)
 
+    def triClosest(self, tris, rmax=np.inf):
+        """The nearest triangle of the hierarchy to each query triangle within rmax, its distance and the two nearest points
+        (psm_bvh_tri_closest_dev; not in the reference): tris [n, 3, 3] or [n, 9], rmax a scalar or [n] (+inf: no limit; NaN
+        or negative: a miss). Triangles that meet have distance 0; a segment or a point is a valid query triangle. The distance
+        is the smallest of fifteen vertex-face and edge-edge features in float32 (psm_hip.h "clearance queries"); on a bit-equal
+        squared distance the lowest id wins. Returns QueryTriHits: u, v, dist, tri, s, t (tri = -1, dist = +inf on a miss).
+        numpy in: numpy out; torch device tensors in: torch tensors out on the same device, ordered against torch's current
+        stream without synchronising (as intersect()). QueryScene, InstancedScene and InstanceWorld have no clearance
+        queries."""
+        return self._tri_dist_query(tris, rmax, "trihits", "psm_bvh_tri_closest_dev")
+
+    def triWithin(self, tris, r):
+        """Whether some triangle of the hierarchy is within r of each query triangle (psm_bvh_tri_within_dev; not in the
+        reference): triClosest(tris, r).tri >= 0, with the walk ended at the first such triangle. A bool array / tensor.
+        Arguments and placement as triClosest()."""
+        return self._tri_dist_query(tris, r, "bool", "psm_bvh_tri_within_dev")
+
+    def _tri_dist_query(self, tris, rmax, out, name):
+        """tris [n, 3, 3] or [n, 9] and rmax packed into psm_tri_dist_query records (the pads are 0) on the side tris lives on"""
+        if type(tris).__module__.split(".")[0] == "torch":
+            import torch
+            dev = tris.device
+            if dev.type != "cuda":
+                raise ValueError("clearance queries: tris must be a tensor on the context's device")
+            t = tris.reshape(-1, 3, 3)
+            packed = torch.zeros((t.shape[0], 3, 4), dtype=torch.float32, device=dev)
+            packed[:, :, 0:3] = t
+            packed[:, 0, 3] = torch.as_tensor(rmax, dtype=torch.float32, device=dev)
+            return _launch_torch(self, packed.reshape(-1, 12), out, name)
+        t = np.ascontiguousarray(tris, np.float32).reshape(-1, 3, 3)
+        packed = np.zeros((t.shape[0], 3, 4), np.float32)
+        packed[:, :, 0:3] = t
+        packed[:, 0, 3] = rmax
+        return self._launch_np(packed.reshape(-1, 12), out, name)
+
     def meshOverlaps(self, other, poses, as_torch=False):
         """Whether `other`, another built TriangleHierarchy of this context, meets this one anywhere at each pose
         (psm_bvh_mesh_overlaps_dev; not in the reference). poses: one matrix or [p, 3, 4] / [p, 4, 4], each a rigid [R | T] that
@@ -718,7 +756,8 @@ class TriangleHierarchy:
 # a query's result by kind: bytes per query and the numpy type of the array returned ("hits": QueryHits over float32 [n, 4];
 # "lists": QueryHitLists over float32 [n, k, 4] -- 16 bytes per slot, k the launch's extra argument -- and a count per query;
 # "tris": QueryTriLists over int32 [n, k] -- 4 bytes per slot -- and a count per query)
-_QUERY_OUT = {"hits": (16, np.float32), "bool": (1, np.bool_), "count": (4, np.uint32), "lists": (16, np.float32), "tris": (4, np.int32)}
+# "trihits": QueryTriHits over float32 [n, 8] -- psm_tri_hit, 32 bytes per query
+_QUERY_OUT = {"trihits": (32, np.float32), "hits": (16, np.float32), "bool": (1, np.bool_), "count": (4, np.uint32), "lists": (16, np.float32), "tris": (4, np.int32)}
 _RAY_QUERIES = {"hits": "psm_bvh_intersect_dev", "bool": "psm_bvh_occluded_dev", "count": "psm_bvh_count_hits_dev"}
 
 
@@ -775,6 +814,45 @@ class QueryTriLists:
         return self.tri.shape[0]
 
 
+class QueryTriHits:
+    """The records of TriangleHierarchy.triClosest: `buffer` [n, 8] float32 (numpy array or torch tensor) holds psm_tri_hit
+    records (u, v, dist, tri, s, t, 0, 0); u, v, dist, tri (int32), s and t are views of it. (u, v) weigh e1, e2 of the stored
+    triangle `tri`, (s, t) weigh b - a, c - a of the query triangle; a miss is tri = -1, dist = +inf."""
+
+    def __init__(self, buffer):
+        self.buffer = buffer
+        self.u, self.v, self.dist = buffer[:, 0], buffer[:, 1], buffer[:, 2]
+        self.s, self.t = buffer[:, 4], buffer[:, 5]
+        if isinstance(buffer, np.ndarray):
+            self.tri = buffer.view(np.int32)[:, 3]
+        else:
+            import torch
+            self.tri = buffer.view(torch.int32)[:, 3]
+
+    def __len__(self):
+        return self.buffer.shape[0]
+
+    def points(self, mesh_tris, query_tris):
+        """the two nearest points in world space, [n, 3] each: (v0 + u e1) + v e2 on the mesh's triangle `tri` (mesh_tris
+        [T, 3, 3], the triangles as loaded) and (a + s (b - a)) + t (c - a) on the query triangle; a miss gives NaN rows"""
+        u, v, s, t = self.u[:, None], self.v[:, None], self.s[:, None], self.t[:, None]
+        ids = self.tri.clip(0) if isinstance(self.buffer, np.ndarray) else self.tri.clip(0).long()
+        m = mesh_tris.reshape(-1, 3, 3)[ids]
+        q = query_tris.reshape(-1, 3, 3)
+        on_mesh = (m[:, 0] + u * (m[:, 1] - m[:, 0])) + v * (m[:, 2] - m[:, 0])
+        on_query = (q[:, 0] + s * (q[:, 1] - q[:, 0])) + t * (q[:, 2] - q[:, 0])
+        miss = (self.tri < 0)[:, None]
+        return on_mesh + _nan_where(miss, on_mesh), on_query + _nan_where(miss, on_query)
+
+
+def _nan_where(mask, like):
+    """an array / tensor shaped as `like`: NaN where mask, else 0"""
+    if isinstance(like, np.ndarray):
+        return np.where(mask, np.float32(np.nan), np.float32(0)) * np.ones_like(like)
+    import torch
+    return torch.where(mask, torch.full_like(like, float("nan")), torch.zeros_like(like))
+
+
 class QueryHits:
     """Closest hits of TriangleHierarchy.intersect (closest points of .closestPoint and .signedDistance: t is the distance): `buffer` [n, 4] float32 (numpy array or torch tensor) holds psm_hit records
     (u, v, t, tri); t, u, v and tri (int32) are views of it. geom: for a QueryScene's results the int32 array / tensor of the
@@ -820,11 +898,15 @@ def _launch_np(th, packed, out, name, *extra):
                 return QueryTriLists(np.zeros((0, k), np.int32), np.zeros(0, np.uint32), None if hi is None else np.zeros((0, k), np.int32))
             if out == "hits":
                 return QueryHits(np.zeros((0, 4), np.float32), np.zeros(0, np.int32) if geom else None)
+            if out == "trihits":
+                return QueryTriHits(np.zeros((0, 8), np.float32))
             return np.zeros(0, dtype)
         if out == "bool":
             return ctx.buf_download(ho, np.uint8, n).view(np.bool_)
         if out == "count":
             return ctx.buf_download(ho, np.uint32, n)
+        if out == "trihits":
+            return QueryTriHits(ctx.buf_download(ho, np.float32, 8 * n).reshape(n, 8))
         if tris:
             return QueryTriLists(ctx.buf_download(ho, np.int32, k * n).reshape(n, k), ctx.buf_download(hg, np.uint32, n),
                                  None if hi is None else ctx.buf_download(hi, np.int32, k * n).reshape(n, k))
@@ -908,7 +990,7 @@ def _launch_torch(th, packed, kind, name, *extra):
     dev = packed.device
     n = packed.shape[0]
     lists, tris = kind == "lists", kind == "tris"
-    shape, dtype = {"hits": ((n, 4), torch.float32), "bool": ((n,), torch.uint8), "count": ((n,), torch.int32),
+    shape, dtype = {"trihits": ((n, 8), torch.float32), "hits": ((n, 4), torch.float32), "bool": ((n,), torch.uint8), "count": ((n,), torch.int32),
                     "lists": ((n, extra[0].value if lists else 1, 4), torch.float32),
                     "tris": ((n, extra[0].value if tris else 1), torch.int32)}[kind]
     out = torch.empty(shape, dtype=dtype, device=dev)
@@ -921,6 +1003,8 @@ def _launch_torch(th, packed, kind, name, *extra):
         return QueryHitLists(out, geom, inst)
     if tris:
         return QueryTriLists(out, geom, inst)
+    if kind == "trihits":
+        return QueryTriHits(out)
     return QueryHits(out, geom) if kind == "hits" else (out.view(torch.bool) if kind == "bool" else out)
 
 

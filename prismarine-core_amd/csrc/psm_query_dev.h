@@ -52,6 +52,9 @@ int sweep_launch(psm_ctx* c, bool any, uint32_t grid, const QueryArgs& a);
 // tri.hip: the launch of a triangle-query kernel (mode: 0 overlaps, 1 count, 2 triangles) for query.hip's host path; a.rays holds
 // the query triangles, three float4 each, a.samples is the triangles query's k
 int tri_launch(psm_ctx* c, int mode, uint32_t grid, const QueryArgs& a);
+// tri_dist.hip: the launch of a clearance kernel (within: whether a triangle is within rmax, else the nearest) for query.hip's
+// host path; a.rays holds the query triangles (psm_tri_dist_query), three float4 each; a.hits two float4 per query
+int tri_dist_launch(psm_ctx* c, bool within, uint32_t grid, const QueryArgs& a);
 
 // tri_test (trace.hip) operation for operation, with invDev = 1 / det instead of 1 / (max(|det|, 1e-6) * sign(det)) and without
 // its `t >= -PZERO` rule (the caller's window decides). det == 0 is a miss; u, v, u + v keep the 1e-5 tolerances. Where
@@ -227,7 +230,13 @@ PSM_D void query_walk(const QueryArgs& a, Body& q) {
 
 // ---- point queries: closest point and within radius (psm_point_query; include/psm_hip.h) ---------------------
 
-PSM_D float clamp01(float x) {   // (x > 0 ? x : 0) then (x < 1 ? x : 1): NaN and -0 give +0 (tests/point_query_model.py _clamp01)
+// clamp01 and closest_on_tri also compile for the host: a stand-alone program defines PSM_POINT_FN as a host function's
+// decoration before it includes this file (tests/cpp/tri_dist_host.cpp, through psm_tri_dist_dev.h)
+#ifndef PSM_POINT_FN
+#define PSM_POINT_FN PSM_D
+#endif
+
+PSM_POINT_FN float clamp01(float x) {   // (x > 0 ? x : 0) then (x < 1 ? x : 1): NaN and -0 give +0 (tests/point_query_model.py _clamp01)
     x = x > 0.f ? x : 0.f;
     return x < 1.f ? x : 1.f;
 }
@@ -245,7 +254,7 @@ PSM_D float clamp01(float x) {   // (x > 0 ? x : 0) then (x < 1 ? x : 1): NaN an
 //     s = 2^-8 a distance can be off by ~2^-7 L either way.
 //     The face's u, v are clamped into the triangle (u in [0, 1], v in [0, 1 - u]): c never leaves the triangle by more than
 //     rounding, which the pruning bound relies on.
-PSM_D float closest_on_tri(v3 v0, v3 e1, v3 e2, v3 p, float& U, float& V) {
+PSM_POINT_FN float closest_on_tri(v3 v0, v3 e1, v3 e2, v3 p, float& U, float& V) {
     const v3 ap = p - v0;
     const float aa = dot3(e1, e1), ab = dot3(e1, e2), bb = dot3(e2, e2);
     const float d1 = dot3(e1, ap), d2 = dot3(e2, ap);
@@ -316,6 +325,22 @@ PSM_D float closest_on_tri(v3 v0, v3 e1, v3 e2, v3 p, float& U, float& V) {
 // rmax: a candidate counts iff sqrtf(d2) <= rmax; sqrtf is correctly rounded, so such a d2 is <= rmax^2 (1 + 2^-22), and the
 // bound starts at fl(rmax^2) (1 + 2^-20) + 2^-126 (above it for every rmax; +inf for rmax = +inf). Non-finite or overflowing
 // arithmetic only makes h infinite or a gap NaN, which fmaxf takes as 0: the box is kept.
+// The clearance queries (tri_dist.hip) use the same bound with the query triangle's bounding box in place of
+// the point. [gl_k, gh_k] is box_row's interval of the box's image on axis k, grown by its h = 2^-16 (2 + S); the gap of a child
+// box is g_k = max(mn_k - gh_k, gl_k - mx_k, 0). A pair's d2 is tri_dist_d2's dot3(Q - P, Q - P) with P = u e1 + v e2 and
+// Q = (A + s g1) + t g2 for weights in [0, 1] (u + v and s + t at most 1 up to one rounding). Let x = v0 + P and y = v0 + Q for
+// the COMPUTED P and Q. P differs from the point of the stored triangle with those weights by the two products' and the sum's
+// roundings, < 3 u (|e1| + |e2|) per component: far inside the leaf box's PZERO padding, so M3 x + m lies in the box. Q differs
+// from the point of the real query triangle with those weights by the roundings of A = a - v0, of g1, g2 and of its three sums,
+// < 8 u (max(|a_j|, |b_j|, |c_j|) + |v0_j|) on component j (u = 2^-24, one rounding); on normalised axis k that moves the image
+// by < 8 u (S + T), S as box_row has it and T = sum_j |m_kj v0_j|. For a diagonal M3 (the plain fit) T <= 1 + |m_k3| <= 1 + S,
+// because v0's image lies in the unit cube: the move is < 16 u (2 + S), a sixteenth of h = 256 u (2 + S); the 16x is left for a
+// full M3, where T exceeds the image by up to the matrix's condition number (16: the rays' allowance, above). So the image of y
+// lies in [gl_k, gh_k], |(M3 (x - y)).k| >= g_k, both forms of the bound hold for |x - y|, and the computed
+// d2 >= (1 - 6 u) |Q - P|^2 = (1 - 6 u) |x - y|^2 (one subtraction, three squares and two sums: each (1 + u)), inside the
+// 1 - 2^-18 scale. A pair that tri_tri holds has d2 = 0: its unit axes did not separate, so the query's box meets the stored
+// triangle's on every axis, every g_k is 0 and LB^2 = 0 (tri.hip's argument). tests/test_tri_dist_query_cpu.py
+// holds LB^2 <= d2 for every pair under plain, rotating, rotate-and-scale and shearing matrices.
 struct PointBound {
     float il0, il1, il2;   // (1 / lambda_k), 0 for a zero row
     float wf;              // (1 - 2^-18), divided by (1 + 2 c_max) for the orthogonal form

@@ -16,8 +16,8 @@ uint64_t bvh_generation(const psm_bvh* b);    // api.hip: bumped by every build 
 // (Q_FIRST_HITS, Q_NEAREST: the k-best queries of kbest.hip and of world.hip's worlds: no entry in the kernel tables; Q_BOX_ANY,
 // Q_BOX_COUNT, Q_BOX_TRIS: the box queries of box.hip and world_box.hip: no entry there either; Q_SWEEP, Q_SWEEP_ANY: the sphere
 // sweeps of sweep.hip and world_sweep.hip: no entry there either; Q_TRI_ANY, Q_TRI_COUNT, Q_TRI_TRIS: the triangle queries of tri.hip and world_tri.hip: no entry
-// there either)
-enum QueryKind { Q_CLOSEST, Q_ANY, Q_POINT, Q_WITHIN, Q_COUNT, Q_INSIDE, Q_SIGNED, Q_FIRST_HITS, Q_NEAREST, Q_BOX_ANY, Q_BOX_COUNT, Q_BOX_TRIS, Q_SWEEP, Q_SWEEP_ANY, Q_TRI_ANY, Q_TRI_COUNT, Q_TRI_TRIS };
+// there either; Q_TRI_CLOSEST, Q_TRI_WITHIN: the clearance queries of tri_dist.hip: no entry there either)
+enum QueryKind { Q_CLOSEST, Q_ANY, Q_POINT, Q_WITHIN, Q_COUNT, Q_INSIDE, Q_SIGNED, Q_FIRST_HITS, Q_NEAREST, Q_BOX_ANY, Q_BOX_COUNT, Q_BOX_TRIS, Q_SWEEP, Q_SWEEP_ANY, Q_TRI_ANY, Q_TRI_COUNT, Q_TRI_TRIS, Q_TRI_CLOSEST, Q_TRI_WITHIN };
 // per kind: the single-hierarchy entry point, what the input and the output are called in its messages (out: NULL when its
 // alignment is not checked: a byte per query), the output's alignment, the family in the state / capacity texts
 struct QueryDesc {

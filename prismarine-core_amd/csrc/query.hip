@@ -840,7 +840,9 @@ const QueryDesc QUERY_DESC[] = {{"psm_bvh_intersect_dev", "rays", "hits", 16, fa
                                 {"psm_bvh_sweep_occluded_dev", "sweeps", nullptr, 1, false},
                                 {"psm_bvh_tri_overlaps_dev", "triangles", nullptr, 1, false},
                                 {"psm_bvh_tri_count_dev", "triangles", "counts", 4, false},
-                                {"psm_bvh_tri_triangles_dev", "triangles", "tris", 4, false}};
+                                {"psm_bvh_tri_triangles_dev", "triangles", "tris", 4, false},
+                                {"psm_bvh_tri_closest_dev", "triangles", "hits", 16, false},
+                                {"psm_bvh_tri_within_dev", "triangles", nullptr, 1, false}};
 
 // The data checks every query shares, under the entry point's name: in / out must be non-NULL, in 16-byte aligned, out as its
 // kind asks (a psm_hit 16 bytes, a count 4); samples (the inside kinds only): 1, 3 or 5; the k-best kinds' k travels as
@@ -915,7 +917,7 @@ bool too_deep(const psm_bvh* b) { return depth_bound(b) > QSTACK_MAX; }
 // The k-best kinds (kbest.hip) come through here too: samples is their k, d_out their [n][k] records, d_count their counts;
 // and the box kinds (box.hip): d_in the boxes, and for the triangles query samples = k, d_out the [n][k] ids, d_count the counts;
 // and the sweep kinds (sweep.hip): d_in the sweeps; and the triangle kinds (tri.hip): d_in the query triangles, the rest as the box
-// kinds.
+// kinds; and the clearance kinds (tri_dist.hip): d_in the query triangles with their rmax, d_out two float4 per query or a byte.
 int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, void* d_out, uint32_t samples = 0, uint32_t* d_count = nullptr) {
     if (!b) return PSM_ERR_INVALID;
     if (n == 0) return PSM_OK;
@@ -923,13 +925,15 @@ int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, void* d_out, u
     const bool points = QUERY_DESC[kind].points, kbest = kind == Q_FIRST_HITS || kind == Q_NEAREST;
     const bool box = kind >= Q_BOX_ANY && kind <= Q_BOX_TRIS, sweep = kind == Q_SWEEP || kind == Q_SWEEP_ANY;
     const bool tri = kind >= Q_TRI_ANY && kind <= Q_TRI_TRIS;
+    const bool clear = kind == Q_TRI_CLOSEST || kind == Q_TRI_WITHIN;
     const bool counted = kbest || kind == Q_BOX_TRIS || kind == Q_TRI_TRIS;
     int rc = check_data(c, QUERY_DESC[kind].name, counted ? "counts" : nullptr, kind, d_in, d_out, (const int32_t*)d_count, samples);
     if (rc != PSM_OK) return rc;
     if (!b->built)
-        return set_err(c, PSM_ERR_STATE, box ? "box query before build" : tri ? "triangle query before build" : sweep ? "sweep query before build" : points ? "point query before build" : "ray query before build");
+        return set_err(c, PSM_ERR_STATE, box ? "box query before build" : clear ? "clearance query before build" : tri ? "triangle query before build" : sweep ? "sweep query before build" : points ? "point query before build" : "ray query before build");
     if (too_deep(b))
         return set_err(c, PSM_ERR_CAPACITY, box      ? "box query: hierarchy deeper than the query stack"
+                                            : clear  ? "clearance query: hierarchy deeper than the query stack"
                                             : tri    ? "triangle query: hierarchy deeper than the query stack"
                                             : sweep  ? "sweep query: hierarchy deeper than the query stack"
                                             : points ? "point query: hierarchy deeper than the query stack"
@@ -952,6 +956,7 @@ int query(psm_bvh* b, QueryKind kind, const void* d_in, size_t n, void* d_out, u
         if (kind == Q_TRI_TRIS) qa.count = d_count;
         return tri_launch(c, (int)kind - (int)Q_TRI_ANY, grid, qa);
     }
+    if (clear) return tri_dist_launch(c, kind == Q_TRI_WITHIN, grid, qa);   // (tri_dist.hip)
     return launch(c, BVH_KERNELS, kind, grid, qa);
 }
 
@@ -1128,6 +1133,14 @@ int psm_bvh_tri_count_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t n, u
 
 int psm_bvh_tri_triangles_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t n, uint32_t k, int32_t* d_ids, uint32_t* d_count) {
     return psm::query(bvh, psm::Q_TRI_TRIS, d_tris, n, d_ids, k, d_count);
+}
+
+int psm_bvh_tri_closest_dev(psm_bvh* bvh, const psm_tri_dist_query* d_queries, size_t n, psm_tri_hit* d_hits) {
+    return psm::query(bvh, psm::Q_TRI_CLOSEST, d_queries, n, d_hits);
+}
+
+int psm_bvh_tri_within_dev(psm_bvh* bvh, const psm_tri_dist_query* d_queries, size_t n, uint8_t* d_flag) {
+    return psm::query(bvh, psm::Q_TRI_WITHIN, d_queries, n, d_flag);
 }
 
 int psm_bvh_sweep_sphere_dev(psm_bvh* bvh, const psm_sweep_query* d_sweeps, size_t n, psm_hit* d_hits) {

@@ -55,6 +55,11 @@ alternated A B A B (medians of REPS) with boxCount / boxTriangles over the same 
 had, a superset -- on two query sets: a second mesh of small triangles, a torus (TRI_TORUS_NU x TRI_TORUS_NV quads) placed to cut
 through the scene, and TRI_SLANTED (4 096) scene-sized slanted triangles, where the bounding box is a poor proxy; for each the
 fraction of queries that report and the ratio of box count to triangle count. No ratio is fixed in advance.
+`query_bench.py clearance`: the clearance queries (psm_bvh_tri_closest_dev / psm_bvh_tri_within_dev) on the Sponza-class scene and the
+stress scene, on the triangles mode's two query sets (the torus of small triangles, the scene-sized slanted ones), at rmax = +inf and
+at a small finite rmax (CLEAR_RMAX, default 1 % of the scene's diagonal): triClosest alternated A B A B (host-timed medians of REPS)
+with triCount on the same triangles, triWithin with closestPoint on the queries' centroids at the same rmax -- context columns, not
+bars: neither answers the clearance question --, and the fractions that find a triangle and that are at distance 0.
 `query_bench.py worldtriangles`: the triangle queries of an instance world (psm_world_tri_overlaps_dev / psm_world_tri_count_dev /
 psm_world_tri_triangles_dev) on the worldboxes mode's world, the torus at 256 and 4 096 turned grid poses, the three queries
 (triangles at k = 4 and 16), each alternated A B A B (medians of REPS) with countInBox / trianglesInBox over the same triangles'
@@ -947,6 +952,76 @@ def triangles():
     print(json.dumps(out))
 
 
+def clearance():
+    lib = psm.lib()
+    out = {"mode": "clearance", "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+    stress_tris = int(os.environ.get("STRESS_TRIS", "10000000"))
+    nu, nv = int(os.environ.get("TRI_TORUS_NU", "512")), int(os.environ.get("TRI_TORUS_NV", "256"))
+    slanted = int(os.environ.get("TRI_SLANTED", "4096"))
+    small = float(os.environ.get("CLEAR_RMAX", "0.01"))
+    names = os.environ.get("CLEAR_SCENES", "sponza,stress").split(",")
+    for scene_name in names:
+        sc = scenes.sponza_like() if scene_name == "sponza" else scenes.stress(stress_tris)
+        ctx = psm.Context(0)
+        th = psm.TriangleHierarchy(ctx)
+        th.allocate(sc["tris"].shape[0])
+        th.loadTriangles(sc["tris"], sc["normals"], sc["mats"])
+        th.build()
+        v = sc["tris"].reshape(-1, 3)
+        lo, hi = v.min(0).astype(np.float64), v.max(0).astype(np.float64)
+        centre, ext = 0.5 * (lo + hi), hi - lo
+        out[scene_name + "_tris"] = int(th.info().leaf_count)
+        rng = np.random.RandomState(11)
+        R = 0.25 * float(ext.max())                                   # the triangles mode's two query sets
+        t = torus(nu, nv, R, 0.4 * R).reshape(-1, 3).astype(np.float64)
+        tilt = np.array([[1, 0, 0], [0, np.cos(0.5), -np.sin(0.5)], [0, np.sin(0.5), np.cos(0.5)]])
+        mesh = (t @ tilt.T + centre).reshape(-1, 3, 3)
+        big = rng.uniform(lo, hi, (slanted, 1, 3)) + rng.uniform(-0.2, 0.2, (slanted, 3, 3)) * ext
+        for set_name, q in (("torus", mesh), ("slanted", big)):
+            q = q.astype(np.float32)
+            n = q.shape[0]
+            hs = [ctx.buf_alloc(x) for x in (48 * n, 16 * n, 32 * n, n, 4 * n)]
+            p_tri, p_pts, p_hits, p_flag, p_count = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in hs)
+            size = C.c_size_t(n)
+
+            def closest():
+                ctx.check(lib.psm_bvh_tri_closest_dev(th._h, p_tri, size, p_hits), "psm_bvh_tri_closest_dev")
+
+            def within():
+                ctx.check(lib.psm_bvh_tri_within_dev(th._h, p_tri, size, p_flag), "psm_bvh_tri_within_dev")
+
+            def count():   # (reads the same records: rmax lies where psm_tri_query has a pad)
+                ctx.check(lib.psm_bvh_tri_count_dev(th._h, p_tri, size, p_count), "psm_bvh_tri_count_dev")
+
+            def point():
+                ctx.check(lib.psm_bvh_closest_point_dev(th._h, p_pts, size, p_hits), "psm_bvh_closest_point_dev")
+            for r_name, rmax in (("inf", np.inf), ("small", small * float(np.linalg.norm(ext)))):
+                rec = np.zeros((n, 3, 4), np.float32)
+                rec[:, :, 0:3] = q
+                rec[:, 0, 3] = rmax
+                pts = np.empty((n, 4), np.float32)
+                pts[:, 0:3], pts[:, 3] = q.mean(axis=1), rmax
+                ctx.buf_upload(hs[0], rec.reshape(n, 12))
+                ctx.buf_upload(hs[1], pts)
+                key = "%s_%s_rmax_%s_" % (scene_name, set_name, r_name)
+                out[key + "queries"], out[key + "rmax"] = n, (None if np.isinf(rmax) else round(float(rmax), 5))
+                out[key + "closest_ms"], out[key + "tri_count_beside_closest_ms"] = abab(ctx, closest, count)
+                out[key + "within_ms"], out[key + "closest_point_beside_within_ms"] = abab(ctx, within, point)
+                closest()
+                hits = ctx.buf_download(hs[2], np.float32, 8 * n).reshape(n, 8)
+                found = hits.view(np.int32)[:, 3] >= 0
+                out[key + "found_fraction"] = round(float(found.mean()), 4)
+                out[key + "at_distance_0_fraction"] = round(float((hits[:, 2] == 0).mean()), 4)
+                out[key + "mean_dist_over_diagonal"] = round(float(hits[found, 2].mean() / np.linalg.norm(ext)), 5) if found.any() else None
+                within()
+                assert np.array_equal(ctx.buf_download(hs[3], np.uint8, n).astype(bool), found)
+            for h in hs:
+                ctx.buf_free(h)
+        th.close()
+        ctx.close()
+    print(json.dumps(out))
+
+
 def posed(src, poses):
     """the query triangles [p, t, 3, 3] of the stored (v0, e1, e2) of src [t, 3, 3] at poses [p, 3, 4], in float32 in the
     library's operation order (psm_hip.h "mesh queries"): (b) and (c) then ask exactly what (a) asks"""
@@ -1544,4 +1619,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "meshes": meshes, "worldtriangles": worldtriangles, "worldmeshes": worldmeshes}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "worldtriangles": worldtriangles, "worldmeshes": worldmeshes}.get(" ".join(sys.argv[1:]), main)()
