@@ -1,12 +1,13 @@
 """An independent second opinion on the camera pass and the sampler (test infrastructure).
 
-Written from the reference's GLSL alone -- raytracing/camera.comp:22-101 (the perspective branch), include/rayslib.glsl
+Written from the reference's GLSL alone -- raytracing/camera.comp:14-101 (the perspective branch and, with enable360, the
+equirect branch :48-59 with its two quaternion helpers :14-20), include/rayslib.glsl
 :129-156,205-222 (how the ray is stored), include/random.glsl:11-46, include/mathlib.glsl:27,73-81 (divW, mult4) and raytracing/sampler.comp:37-97 -- in plain numpy float32, NOT
 from oracle/psm_oracle*.c. Canonical rules it shares with the oracle by construction: `time` is an
 explicit seed, the two jitter draws are taken x first, a frame's texel value is the sum of its deposits (what
 collectSamples adds up over the chain), a texel "has samples" when the camera pass has visited it.
 
-camera_rays(cam_inv, proj_inv, w, h, time) -> origin (n,3), direct (n,3), coord (n,2), bitfield (n,)
+camera_rays(cam_inv, proj_inv, w, h, time, enable360=False) -> origin (n,3), direct (n,3), coord (n,2), bitfield (n,)
 sample(coord, tsum, flag, presampled, w, h, dw, dh, samples_lock) -> presampled'
 """
 import numpy as np
@@ -49,7 +50,23 @@ def clamp(x, lo, hi):
     return F(min(max(F(x), F(lo)), F(hi)))
 
 
-def camera_rays(cam_inv, proj_inv, w, h, time):
+PI = F(3.1415926535897932384626422832795028841971)   # constants.glsl:83
+
+
+def cross(a, b):
+    return np.array([F(F(a[1] * b[2]) - F(b[1] * a[2])), F(F(a[2] * b[0]) - F(b[2] * a[0])), F(F(a[0] * b[1]) - F(b[0] * a[1]))], np.float32)
+
+
+def rotation_quat(axis, half_angle):  # camera.comp:18-20
+    return np.append(np.asarray(axis, np.float32) * F(np.sin(half_angle)), F(np.cos(half_angle))).astype(np.float32)
+
+
+def rotate_vector(quat, vec):  # camera.comp:14-16
+    inner = (cross(vec, quat[:3]) + quat[3] * vec).astype(np.float32)
+    return (vec + F(2.0) * cross(inner, quat[:3])).astype(np.float32)
+
+
+def camera_rays(cam_inv, proj_inv, w, h, time, enable360=False):
     n = w * h
     origin = np.zeros((n, 3), np.float32)
     direct = np.zeros((n, 3), np.float32)
@@ -65,6 +82,15 @@ def camera_rays(cam_inv, proj_inv, w, h, time):
         cy = F(F(F(y) + ry) * res_inv[1])
         coord[idx] = (cx, cy)
         ndc = (F(F(cx * F(2.0)) - F(1.0)), F(F(cy * F(2.0)) - F(1.0)))
+        if enable360:                                   # :48-59: no divW, no normalize -- the direction is camInv's image of a unit vector
+            px, py = F(F(ndc[0] * F(-1.0)) * PI), F(F(ndc[1] * F(0.5)) * PI)
+            vctr = np.array([F(F(np.cos(py)) * F(np.cos(px))), F(F(np.cos(py)) * F(np.sin(px))), F(np.sin(py))], np.float32)
+            vctr = rotate_vector(rotation_quat((0.0, 0.0, -1.0), F(PI / F(4.0))), vctr)
+            vctr = rotate_vector(rotation_quat((1.0, 0.0, 0.0), F(PI / F(4.0))), vctr)
+            origin[idx] = mult4(cam_inv, (F(0.0), F(0.0), F(0.0), F(1.0)))[:3]
+            direct[idx] = mult4(cam_inv, (vctr[0], vctr[1], vctr[2], F(0.0)))[:3]
+            bitfield[idx] = 1 | (0 << 1) | (0 << 3) | ((4 - 1) << 8) | (1 << 12)
+            continue
         co = div_w(mult4(cam_inv, mult4(proj_inv, (ndc[0], ndc[1], F(0.999), F(1.0)))))   # :61
         og = div_w(mult4(cam_inv, mult4(proj_inv, (ndc[0], ndc[1], F(0.0), F(1.0)))))     # :62
         d = (co[:3] - og[:3]).astype(np.float32)

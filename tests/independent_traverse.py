@@ -1,7 +1,7 @@
 """An independent second opinion on the BVH traversal (test infrastructure).
 
 Written from the reference's GLSL alone -- raytracing/directTraverse.comp:49-112 (stack, reorderTriangles), :261-309
-(testIntersectionPacked), :333-484 (traverse), include/mathlib.glsl:10-14,107-126,129-193 (tolerant compares,
+(testIntersectionPacked), :333-484 (traverse), :219-258,335-346,503-507 (a chain that arrives from an earlier hierarchy), include/mathlib.glsl:10-14,107-126,129-193 (tolerant compares,
 intersectCubeSingle, intersectCubeDual: the fp32 branch, no AMD_F16_BVH, no ENABLE_AMD_INSTRUCTION_SET),
 include/vertex.glsl:140-189 (intersectTriangle) -- as a plain Python state machine on numpy float32 scalars, NOT from
 oracle/psm_oracle.c. It walks the oracle's canonical node array (whose construction has its own second opinion,
@@ -9,7 +9,18 @@ independent_build.py). Canonical rules it shares with the oracle by construction
 ignore a NaN operand, fma is fused, M v is summed as ((m0 x + m1 y) + m2 z) + m3 w, a 16-entry stack whose overflowing
 pushes are dropped, an equal-distance list of 8 entries whose overflowing writes are dropped.
 
-traverse(nodes, tris, M, origin, direct) -> (chain [(tri, t, u, v), ...] in list order, node visits, triangle tests)
+A ray that arrives with a chain (multi-BVH: ray.hit != -1, :503) starts its search at the distance of that chain's head
+(:335-336) with an empty baked list (:345); what it bakes is then written over the chain's entries from the head on, one
+includeChain call per baked entry (:219-250): an old entry is reused while there is one (its `next` is kept, :226,236), a new one
+is linked behind the last when they run out (:229-231,244-248). So a chain of m entries that meets k baked hits leaves
+[the k new ones] + [the old ones from position k on] -- also when the new hits are NEARER, where the old tail stays linked
+behind them although it lies farther -- and a ray that bakes nothing keeps its chain (chainID = nextHt, :344). Triangle ids are
+the hierarchy's own plus `tri_base`, its first triangle's place in the scene's arrays (the leaves hold local ids; the id that
+testIntersectionPacked avoids, res.triangleID, starts at LONGEST in every hierarchy, :337). Not modelled: `hid > 0` (:225,229),
+which takes hit-buffer slot 0 for "no chain" -- a chain here is a list, not a slot.
+
+traverse(nodes, tris, M, origin, direct, chain_in=None, tri_base=0)
+    -> (chain [(tri, t, u, v), ...] in list order, node visits, triangle tests)
 """
 import numpy as np
 
@@ -131,10 +142,11 @@ def intersect_triangle(tris, orig, dr, tri):  # vertex.glsl:140-189; returns (T,
     return INF, F(0), F(0)
 
 
-def traverse(nodes, tris, M, origin, direct):
+def traverse(nodes, tris, M, origin, direct, chain_in=None, tri_base=0):
     pdata, boxes = nodes["pdata"], nodes["box"]
     M = np.asarray(M, np.float32).reshape(4, 4)
-    st = {"predist": INF, "tri": LONGEST, "baked": [None] * BAKED, "count": 0, "tests": 0}
+    chain_in = list(chain_in) if chain_in is not None else []
+    st = {"predist": F(chain_in[0][1]) if chain_in else INF, "tri": LONGEST, "baked": [None] * BAKED, "count": 0, "tests": 0}   # :335-337,345
     direct = normalize(tuple(F(x) for x in direct))                                                   # :350
     origin = tuple(F(x) for x in origin)
     torig = tuple(F(F(F(F(M[i][0] * origin[0]) + F(M[i][1] * origin[1])) + F(M[i][2] * origin[2])) + M[i][3]) for i in range(3))   # :353
@@ -263,4 +275,5 @@ def traverse(nodes, tris, M, origin, direct):
             clean.append(bk[iround])
     if n > 0 and len(clean) <= BAKED:
         clean.append(bk[n - 1])
-    return [(c[3], c[2], c[0], c[1]) for c in clean], visits, st["tests"]
+    new = [(c[3] + tri_base, c[2], c[0], c[1]) for c in clean]
+    return new + chain_in[len(new):], visits, st["tests"]                                             # includeChain, :219-250
