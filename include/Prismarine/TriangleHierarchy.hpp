@@ -92,6 +92,15 @@ namespace NSM {
         int meshOverlaps(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, uint8_t * d_hit);
         int meshCount(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, uint32_t * d_count);
         int meshTriangles(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, uint32_t k, int32_t * d_ids, uint32_t * d_count);
+        // not in the reference: how close `other` comes at each of p poses (poses, T and indexing as meshCount) -- meshClosest:
+        // d_hits [p][T], the record triClosest writes for each posed triangle of other under the one rmax; meshClearance: d_hits
+        // [p], the one nearest pair of each pose {u, v, dist, tri, s, t, other, 0}: the smallest dist, on an equal dist the
+        // lowest triangle of other, a miss {0, 0, +inf, -1, 0, 0, -1, 0}; meshWithin: d_flag [p], whether any pair is within r
+        // (psm_hip.h "mesh clearance"; psm_bvh_mesh_closest_dev / psm_bvh_mesh_within_dev / psm_bvh_mesh_clearance_dev). The
+        // call waits once for its pose upload; the kernels are stream-ordered on the context; returns the psm_status
+        int meshClosest(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, float rmax, psm_tri_hit * d_hits);
+        int meshWithin(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, float r, uint8_t * d_flag);
+        int meshClearance(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, float rmax, psm_mesh_hit * d_hits);
         // not in the reference: where a sphere that moves along a line first touches the triangles (t = the distance its centre
         // travels, 0 when it touches where it starts; a miss is {0, 0, +inf, -1}), and whether it touches any within tmax
         // (psm_bvh_sweep_sphere_dev / psm_bvh_sweep_occluded_dev), stream-ordered on the context; returns the psm_status

@@ -145,6 +145,24 @@ namespace NSM {
         check(rc, "TriangleHierarchy::meshTriangles");
         return rc;
     }
+    inline int TriangleHierarchy::meshClosest(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, float rmax, psm_tri_hit * d_hits) {
+        const std::vector<float> m12 = detail::meshPoses(poses, p);
+        const int rc = psm_bvh_mesh_closest_dev(bvh, other ? other->bvh : nullptr, m12.data(), p, rmax, d_hits);
+        check(rc, "TriangleHierarchy::meshClosest");
+        return rc;
+    }
+    inline int TriangleHierarchy::meshWithin(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, float r, uint8_t * d_flag) {
+        const std::vector<float> m12 = detail::meshPoses(poses, p);
+        const int rc = psm_bvh_mesh_within_dev(bvh, other ? other->bvh : nullptr, m12.data(), p, r, d_flag);
+        check(rc, "TriangleHierarchy::meshWithin");
+        return rc;
+    }
+    inline int TriangleHierarchy::meshClearance(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, float rmax, psm_mesh_hit * d_hits) {
+        const std::vector<float> m12 = detail::meshPoses(poses, p);
+        const int rc = psm_bvh_mesh_clearance_dev(bvh, other ? other->bvh : nullptr, m12.data(), p, rmax, d_hits);
+        check(rc, "TriangleHierarchy::meshClearance");
+        return rc;
+    }
     inline int TriangleHierarchy::sweepSphere(const psm_sweep_query * d_sweeps, size_t n, psm_hit * d_hits) {
         const int rc = psm_bvh_sweep_sphere_dev(bvh, d_sweeps, n, d_hits);
         check(rc, "TriangleHierarchy::sweepSphere");

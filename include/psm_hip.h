@@ -738,6 +738,54 @@ int psm_bvh_mesh_overlaps_dev(psm_bvh* bvh, psm_bvh* other, const float* poses, 
 int psm_bvh_mesh_count_dev(psm_bvh* bvh, psm_bvh* other, const float* poses, size_t p, uint32_t* d_count);
 int psm_bvh_mesh_triangles_dev(psm_bvh* bvh, psm_bvh* other, const float* poses, size_t p, uint32_t k, int32_t* d_ids, uint32_t* d_count);
 
+/* mesh clearance against a built hierarchy (new; no reference counterpart): the clearance queries above with
+ * the query triangles taken from ANOTHER built hierarchy `other` of the same context, at each of p rigid poses, in one call,
+ * and the ONE nearest pair of each pose: how close part B comes to part A at this pose, and where -- what a placement search, a
+ * tolerance check ("at least 2 mm between A and B at each of these 1 000 poses") and a collision margin ask. Unless said
+ * otherwise below, everything is as psm_bvh_mesh_count_dev has it: bvh, other, poses, p, T = other's loaded triangle count,
+ * indexing by other's load-order triangle id, how the poses are checked and uploaded, the one synchronisation, no graph
+ * capture. Semantics:
+ *   - rmax / r: one scalar per call. NaN or negative is not a refusal: it answers as psm_bvh_tri_closest_dev does for such a
+ *     query, a miss everywhere. -0 is 0, +inf is no limit
+ *   - mesh_closest: d_hits [p][T]. The record of (pose q, triangle t of other) is BIT FOR BIT what psm_bvh_tri_closest_dev
+ *     writes for psm_tri_dist_query {a, rmax, b, c}, with a, b, c the posed triangle of the mesh queries
+ *     (a = fwd_point(m, v0), b = a + fwd_vec(m, e1), c = a + fwd_vec(m, e2)). A triangle that other's build dropped reads
+ *     the miss record {0, 0, +inf, -1, 0, 0, 0, 0} at every pose, as does one whose posed image is not finite
+ *   - mesh_clearance: d_hits [p], one psm_mesh_hit per pose. Let t* be the lowest t among the triangles of other whose
+ *     mesh_closest record has the smallest dist, comparing the float32 dist as stored. The record is that triangle's
+ *     mesh_closest record, bit for bit, with other = t*. A pose where no pair counts reads {0, 0, +inf, -1, 0, 0, -1, 0}.
+ *     The rule is stated on dist, not on d2, so that it can be checked from the public outputs alone. (u, v) weigh e1, e2 of
+ *     bvh's triangle tri; (s, t) weigh b - a, c - a of the posed triangle `other`: the two witness points, both in bvh's space
+ *   - mesh_within: d_flag [p]; d_flag[q] = 1 iff mesh_clearance at rmax = r finds a pair at pose q, else 0. The walk of a
+ *     triangle ends at its first pair that counts
+ *   - nothing depends on the traversal order, on either hierarchy's tree or on timing. Inside the clearance launch the lanes
+ *     of a pose share one 64-bit word, (bits(dist) << 32) | t, lowered by atomic minimum and read back as a smaller rmax;
+ *     nobody waits on it; every value it takes is the dist of a real pair that counts, so the final word is (the smallest
+ *     dist, t*) under every schedule (mesh_dist.hip and DESIGN.md 4.24 have the argument). The weights do not travel through
+ *     the word: a second, tiny launch walks triangle t* of each pose again and writes the record
+ *   - refusals: the mesh queries' own, with the same texts under these names, all before any launch and with the outputs
+ *     untouched: NULL bvh or other (PSM_ERR_INVALID, no message); NULL poses or output; d_hits not 16-byte aligned
+ *     (PSM_ERR_INVALID); either hierarchy not built (PSM_ERR_STATE, "mesh query before build"); bvh deeper than the query stack
+ *     (PSM_ERR_CAPACITY); hierarchies of different contexts; a pose that is not finite or not rigid, named by its index
+ *     (PSM_ERR_INVALID); p x T >= 2^32 (PSM_ERR_CAPACITY). p == 0 returns PSM_OK and touches nothing
+ *   - other without leaves launches no walk and answers a miss everywhere; bvh without leaves answers a miss everywhere
+ *   - study knobs, no part of the contract, read at each call: PSM_MESH_BOUND = 0 / 1 decides whether the clearance kernel's
+ *     lanes read the shared word (0: every lane walks with rmax alone; the answer is the same; the default is 1; 2 and 3 are
+ *     the variants DESIGN.md 4.24 compares); PSM_MESH_SKIP = 0 / 1 is the within kernel's skip of a pose whose flag already
+ *     reads 1, as psm_bvh_mesh_overlaps_dev has it
+ *   - not covered: clearance over an InstanceWorld, a QueryScene or an InstancedScene; a per-pose rmax; the k closest pairs; a
+ *     dual-tree walk that prunes whole subtrees of other; penetration depth; graph capture of the call */
+typedef struct {
+    float u, v, dist; /* the first 24 bytes: a psm_tri_hit */
+    int32_t tri;
+    float s, t;
+    int32_t other; /* t*: the triangle of other, -1 on a miss */
+    float zero;
+} psm_mesh_hit; /* 32 B: two 16-byte stores */
+int psm_bvh_mesh_closest_dev(psm_bvh* bvh, psm_bvh* other, const float* poses, size_t p, float rmax, psm_tri_hit* d_hits);
+int psm_bvh_mesh_within_dev(psm_bvh* bvh, psm_bvh* other, const float* poses, size_t p, float r, uint8_t* d_flag);
+int psm_bvh_mesh_clearance_dev(psm_bvh* bvh, psm_bvh* other, const float* poses, size_t p, float rmax, psm_mesh_hit* d_hits);
+
 /* scene queries: the seven queries above over several hierarchies at once (new; no reference counterpart).
  * A scene is an ordered list of G built hierarchies of ONE context, 1 <= G <= PSM_SCENE_MAX_GEOMETRIES, passed per call (there
  * is no scene handle). The limit is 32 because the per-geometry table then travels with the launch (32 x four pointers = 1 KB

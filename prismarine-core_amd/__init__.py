@@ -33,6 +33,7 @@ EXPORTS = [
     "psm_bvh_tri_overlaps_dev", "psm_bvh_tri_count_dev", "psm_bvh_tri_triangles_dev",
     "psm_bvh_tri_closest_dev", "psm_bvh_tri_within_dev",
     "psm_bvh_mesh_overlaps_dev", "psm_bvh_mesh_count_dev", "psm_bvh_mesh_triangles_dev",
+    "psm_bvh_mesh_closest_dev", "psm_bvh_mesh_within_dev", "psm_bvh_mesh_clearance_dev",
     "psm_scene_intersect_dev", "psm_scene_occluded_dev", "psm_scene_count_hits_dev", "psm_scene_closest_point_dev", "psm_scene_within_dev",
     "psm_scene_inside_dev", "psm_scene_signed_distance_dev",
     "psm_instances_intersect_dev", "psm_instances_occluded_dev", "psm_instances_count_hits_dev", "psm_instances_closest_point_dev",
@@ -72,6 +73,7 @@ SWEEP_QUERY_DT = np.dtype([("origin", "<f4", 3), ("radius", "<f4"), ("direct", "
 TRI_QUERY_DT = np.dtype([("a", "<f4", 3), ("pad0", "<f4"), ("b", "<f4", 3), ("pad1", "<f4"), ("c", "<f4", 3), ("pad2", "<f4")])   # psm_tri_query
 TRI_DIST_QUERY_DT = np.dtype([("a", "<f4", 3), ("rmax", "<f4"), ("b", "<f4", 3), ("pad0", "<f4"), ("c", "<f4", 3), ("pad1", "<f4")])   # psm_tri_dist_query
 TRI_HIT_DT = np.dtype([("u", "<f4"), ("v", "<f4"), ("dist", "<f4"), ("tri", "<i4"), ("s", "<f4"), ("t", "<f4"), ("zero0", "<f4"), ("zero1", "<f4")])   # psm_tri_hit
+MESH_HIT_DT = np.dtype([("u", "<f4"), ("v", "<f4"), ("dist", "<f4"), ("tri", "<i4"), ("s", "<f4"), ("t", "<f4"), ("other", "<i4"), ("zero", "<f4")])   # psm_mesh_hit
 QUERY_K_MAX = 16   # psm_hip.h PSM_QUERY_K_MAX
 SCENE_MAX_GEOMETRIES = 32   # psm_hip.h PSM_SCENE_MAX_GEOMETRIES
 WORLD_MAX_INSTANCES = 65536   # psm_hip.h PSM_WORLD_MAX_INSTANCES
@@ -578,15 +580,7 @@ class TriangleHierarchy:
 
     def _mesh_query(self, other, poses, out, name, k, as_torch):
         """one mesh query: the poses checked and packed [p, 12] on the host, the outputs [p] / [p, T] / [p, T, k] and [p, T]"""
-        if not isinstance(other, TriangleHierarchy):
-            raise TypeError("%s: other must be a TriangleHierarchy" % name)
-        m = np.asarray(poses)
-        if m.ndim == 2:
-            m = m[None]
-        if m.ndim != 3:
-            raise ValueError("%s: poses must be one matrix or [p, 3, 4] / [p, 4, 4]" % name)
-        p, t = m.shape[0], int(other.triangleCount)
-        m12 = np.ascontiguousarray(np.stack([_pose(x, name) for x in m]).reshape(p, 12) if p else np.zeros((0, 12)), np.float32)
+        m12, p, t = _mesh_poses(other, poses, name)
         extra = () if k is None else (C.c_uint32(k),)
         cells, kk = p * t, 1 if k is None else k
         fn = getattr(lib(), name)
@@ -620,6 +614,57 @@ class TriangleHierarchy:
             ctx.buf_free(ho)
             if hc is not None:
                 ctx.buf_free(hc)
+
+    def meshClosest(self, other, poses, rmax=np.inf, as_torch=False):
+        """The nearest triangle of this hierarchy to each triangle of `other` at each pose within rmax, its distance and the two
+        nearest points (psm_bvh_mesh_closest_dev; not in the reference): each stored triangle of other is posed in float32 on
+        the device, as meshCount() poses it, and answered bit for bit as triClosest() answers it. rmax: one scalar (+inf: no
+        limit; NaN or negative: a miss everywhere). Returns QueryMeshHits over a [p, T, 8] buffer, T = other.triangleCount,
+        indexed by other's load-order triangle id: u, v, dist, tri, s, t ([p, T] views; tri = -1, dist = +inf on a miss and for
+        a triangle other's build dropped); .other is None. Arguments and placement as meshOverlaps()."""
+        return self._mesh_dist_query(other, poses, rmax, "closest", "psm_bvh_mesh_closest_dev", as_torch)
+
+    def meshWithin(self, other, poses, r, as_torch=False):
+        """Whether some triangle of `other` comes within r of some triangle of this hierarchy at each pose
+        (psm_bvh_mesh_within_dev; not in the reference): meshClearance(other, poses, r).tri >= 0, with every walk ended at its
+        first such pair. A bool [p]. Arguments and placement as meshOverlaps()."""
+        return self._mesh_dist_query(other, poses, r, "bool", "psm_bvh_mesh_within_dev", as_torch)
+
+    def meshClearance(self, other, poses, rmax=np.inf, as_torch=False):
+        """The one nearest pair of each pose (psm_bvh_mesh_clearance_dev; not in the reference): of meshClosest()'s records of
+        a pose the one with the smallest dist, on an equal float32 dist the lowest triangle of other -- found inside the launch,
+        the triangles of a pose sharing the best distance so far as their bound. Returns QueryMeshHits over a [p, 8] buffer:
+        u, v, dist, tri, s, t and .other, the int32 id of other's triangle (tri = other = -1, dist = +inf where no pair is
+        within rmax); .points() gives the two witness points. Arguments and placement as meshOverlaps()."""
+        return self._mesh_dist_query(other, poses, rmax, "clearance", "psm_bvh_mesh_clearance_dev", as_torch)
+
+    def _mesh_dist_query(self, other, poses, rmax, out, name, as_torch):
+        """one mesh clearance query: the poses as _mesh_query packs them, rmax one float, the output [p, T, 8] / [p] / [p, 8]"""
+        m12, p, t = _mesh_poses(other, poses, name)
+        if np.ndim(rmax) != 0:
+            raise ValueError("%s: rmax must be one scalar" % name)
+        shape = {"closest": (p, t, 8), "bool": (p,), "clearance": (p, 8)}[out]
+        fn = getattr(lib(), name)
+
+        def call(d_out):
+            self.ctx.check(fn(self._h, other._h, _p(m12), C.c_size_t(p), C.c_float(rmax), C.c_void_p(d_out)), name)
+
+        if as_torch:
+            import torch
+            dev = torch.device("cuda", self.ctx.device)
+            res = torch.empty(shape, dtype=torch.uint8 if out == "bool" else torch.float32, device=dev)
+            _torch_ordered(self.ctx, dev, lambda: call(res.data_ptr()))
+            return res.view(torch.bool) if out == "bool" else QueryMeshHits(res, out == "clearance")
+        ctx = self.ctx
+        n = int(np.prod(shape))
+        ho = ctx.buf_alloc(max(n if out == "bool" else 4 * n, 16))
+        try:
+            call(ctx.buf_ptr(ho)[0])
+            if out == "bool":
+                return ctx.buf_download(ho, np.uint8, p).view(np.bool_) if p else np.zeros(0, np.bool_)
+            return QueryMeshHits((ctx.buf_download(ho, np.float32, n) if n else np.zeros(0, np.float32)).reshape(shape), out == "clearance")
+        finally:
+            ctx.buf_free(ho)
 
     def sweepSphere(self, origins, directions, radius, tmax=np.inf):
         """Where a sphere of `radius` that moves from each origin along its direction first touches a triangle within the distance
@@ -843,6 +888,65 @@ class QueryTriHits:
         on_query = (q[:, 0] + s * (q[:, 1] - q[:, 0])) + t * (q[:, 2] - q[:, 0])
         miss = (self.tri < 0)[:, None]
         return on_mesh + _nan_where(miss, on_mesh), on_query + _nan_where(miss, on_query)
+
+
+class QueryMeshHits:
+    """The records of TriangleHierarchy.meshClosest ([p, T, 8]) and .meshClearance ([p, 8]): `buffer`, float32 (numpy array or
+    torch tensor), holds psm_tri_hit / psm_mesh_hit records; u, v, dist, tri (int32), s and t are views on its last axis.
+    (u, v) weigh e1, e2 of this hierarchy's triangle `tri`, (s, t) weigh b - a, c - a of the posed triangle of the other mesh.
+    other: for meshClearance the int32 view of slot 6, the other mesh's triangle (-1 on a miss); None for meshClosest, whose
+    second index is that triangle. QueryTriHits stays what triClosest returns."""
+
+    def __init__(self, buffer, per_pose=False):
+        self.buffer = buffer
+        self.u, self.v, self.dist = buffer[..., 0], buffer[..., 1], buffer[..., 2]
+        self.s, self.t = buffer[..., 4], buffer[..., 5]
+        if isinstance(buffer, np.ndarray):
+            ints = buffer.view(np.int32)
+        else:
+            import torch
+            ints = buffer.view(torch.int32)
+        self.tri = ints[..., 3]
+        self.other = ints[..., 6] if per_pose else None
+
+    def __len__(self):
+        return self.buffer.shape[0]
+
+    def points(self, mesh_tris, other_tris, poses):
+        """meshClearance's two witness points in this hierarchy's space, [p, 3] each: (v0 + u e1) + v e2 on this hierarchy's
+        triangle `tri` (mesh_tris [T', 3, 3], the triangles as loaded) and (a + s (b - a)) + t (c - a) on the other mesh's
+        triangle `other` (other_tris [T, 3, 3], as loaded) moved by its pose (poses [p, 3, 4] / [p, 4, 4]; float64 here, not
+        the device's float32 image); a miss gives NaN rows. numpy arrays."""
+        if self.other is None:
+            raise ValueError("points(): the records of meshClearance have them; meshClosest's are per (pose, triangle)")
+        rec = self.buffer if isinstance(self.buffer, np.ndarray) else self.buffer.cpu().numpy()
+        ids = rec.view(np.int32)
+        miss = ids[:, 3] < 0
+        m = np.asarray(mesh_tris, np.float64).reshape(-1, 3, 3)[ids[:, 3].clip(0)] if len(rec) else np.zeros((0, 3, 3))
+        o = np.asarray(other_tris, np.float64).reshape(-1, 3, 3)[ids[:, 6].clip(0)] if len(rec) else np.zeros((0, 3, 3))
+        pm = np.asarray(poses, np.float64)
+        pm = (pm[None] if pm.ndim == 2 else pm)[:, :3, :]
+        o = np.einsum("pij,pkj->pki", pm[:, :, :3], o) + pm[:, None, :, 3]
+        u, v, s, t = (rec[:, k:k + 1].astype(np.float64) for k in (0, 1, 4, 5))
+        on_mesh = (m[:, 0] + u * (m[:, 1] - m[:, 0])) + v * (m[:, 2] - m[:, 0])
+        on_other = (o[:, 0] + s * (o[:, 1] - o[:, 0])) + t * (o[:, 2] - o[:, 0])
+        on_mesh[miss] = np.nan
+        on_other[miss] = np.nan
+        return on_mesh, on_other
+
+
+def _mesh_poses(other, poses, name):
+    """the poses of a mesh query checked and packed [p, 12] float32 on the host; with them p and other's triangle count"""
+    if not isinstance(other, TriangleHierarchy):
+        raise TypeError("%s: other must be a TriangleHierarchy" % name)
+    m = np.asarray(poses)
+    if m.ndim == 2:
+        m = m[None]
+    if m.ndim != 3:
+        raise ValueError("%s: poses must be one matrix or [p, 3, 4] / [p, 4, 4]" % name)
+    p = m.shape[0]
+    m12 = np.ascontiguousarray(np.stack([_pose(x, name) for x in m]).reshape(p, 12) if p else np.zeros((0, 12)), np.float32)
+    return m12, p, int(other.triangleCount)
 
 
 def _nan_where(mask, like):

@@ -153,20 +153,19 @@ __global__ __launch_bounds__(QUERY_BLOCK, MESH_LIST_WAVES) void bvh_query_mesh_t
 
 namespace {
 
-// the device copy of a call's poses, per context (grown on demand; every call runs on the context's stream, never two at once)
+// the device copy of a call's poses, per context (grown on demand; every call runs on the context's stream, never two at once),
+// and beside it the words the poses of a mesh clearance call share (mesh_dist.hip)
 struct PoseArea {
     void* ptr = nullptr;
     size_t bytes = 0;
 };
+struct PoseAreas {
+    PoseArea poses, keys;
+};
 std::mutex pose_mu;
-std::unordered_map<const psm_ctx*, PoseArea> pose_area;
+std::unordered_map<const psm_ctx*, PoseAreas> pose_area;
 
-}  // namespace
-
-// (psm_query_host.h: the mesh queries over a world, world.hip's world_mesh_query(), upload their poses here too)
-int poses_for(psm_ctx* c, size_t bytes, void** out) {
-    std::lock_guard<std::mutex> lk(pose_mu);
-    PoseArea& a = pose_area[c];
+int area_for(psm_ctx* c, PoseArea& a, size_t bytes, void** out) {
     if (a.bytes < bytes) {
         // (the stream is idle wherever this is reached after a call: every call ends its upload with a synchronisation, and a
         // kernel that read the old area is in stream order before the free)
@@ -180,6 +179,20 @@ int poses_for(psm_ctx* c, size_t bytes, void** out) {
     }
     *out = a.ptr;
     return PSM_OK;
+}
+
+}  // namespace
+
+// (psm_query_host.h: the mesh queries over a world, world.hip's world_mesh_query(), upload their poses here too)
+int poses_for(psm_ctx* c, size_t bytes, void** out) {
+    std::lock_guard<std::mutex> lk(pose_mu);
+    return area_for(c, pose_area[c].poses, bytes, out);
+}
+
+// (psm_query_host.h: mesh_dist.hip's key words, one uint64 per pose of a clearance call)
+int mesh_keys_for(psm_ctx* c, size_t bytes, void** out) {
+    std::lock_guard<std::mutex> lk(pose_mu);
+    return area_for(c, pose_area[c].keys, bytes, out);
 }
 
 namespace {
@@ -271,12 +284,13 @@ int mesh_query(psm_bvh* b, psm_bvh* o, const float* poses, size_t p, int mode, u
 
 }  // namespace
 
-// for psm_ctx_destroy: the context's pose area goes with it
+// for psm_ctx_destroy: the context's pose area and its key words go with it
 void mesh_release(psm_ctx* c) {
     std::lock_guard<std::mutex> lk(pose_mu);
     auto it = pose_area.find(c);
     if (it == pose_area.end()) return;
-    if (it->second.ptr) (void)hipFree(it->second.ptr);
+    if (it->second.poses.ptr) (void)hipFree(it->second.poses.ptr);
+    if (it->second.keys.ptr) (void)hipFree(it->second.keys.ptr);
     pose_area.erase(it);
 }
 

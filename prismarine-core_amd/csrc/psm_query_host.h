@@ -11,6 +11,8 @@ void query_release(psm_ctx* c);               // query.hip, for psm_ctx_destroy:
 void mesh_release(psm_ctx* c);                // mesh.hip, for psm_ctx_destroy: the device copy of the mesh queries' poses goes with it
 // mesh.hip: the device copy of a call's poses, per context (grown on demand; every call runs on the context's stream)
 int poses_for(psm_ctx* c, size_t bytes, void** out);
+// mesh.hip: beside them, the 64-bit words the poses of a mesh clearance call share (mesh_dist.hip), grown and released alike
+int mesh_keys_for(psm_ctx* c, size_t bytes, void** out);
 uint64_t bvh_generation(const psm_bvh* b);    // api.hip: bumped by every build of the hierarchy
 
 // (Q_FIRST_HITS, Q_NEAREST: the k-best queries of kbest.hip and of world.hip's worlds: no entry in the kernel tables; Q_BOX_ANY,

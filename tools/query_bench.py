@@ -82,6 +82,14 @@ so that the meshes cut. Per case and query, alternated A B A B (host-timed media
 whole call, against (b) countOnTriangle / overlapsTriangle / trianglesOnTriangle (k = 16) over the same posed triangles already
 resident on the device as psm_tri_query records in load order; the two (b) medians give the spread between runs; and the call's
 own overhead (checks, upload, wait, clears: the same call on a mesh without leaves) timed apart. No ratio is fixed in advance.
+`query_bench.py meshclearance`: mesh clearance (psm_bvh_mesh_closest_dev / psm_bvh_mesh_within_dev / psm_bvh_mesh_clearance_dev) on
+the Sponza-class scene and the stress scene (CLEAR_SCENES), the other mesh the meshes mode's torus (2 304 triangles, a quarter of the
+scene's extent across) and its hollow twin (as many triangles, none a leaf: the call's own overhead), at 1 and 1 024 poses whose
+centres lie up to two torus radii off a vertex of the scene (some cut, most come near). Alternated A B A B (host-timed medians of
+REPS, the whole call): meshClearance with the shared bound off and on (PSM_MESH_BOUND = 0 / 1), then on against its two variants
+(2: the word read in begin() alone and published at finish() alone; 3: re-read before every leaf, published at finish() alone),
+meshClearance against meshClosest plus a torch min over the device buffer (what a caller had), meshWithin at 1 % of the diagonal
+against meshOverlaps (context: it answers less) and with its skip forced on and off (PSM_MESH_SKIP = 1 / 0). No ratio is fixed in advance.
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -1022,6 +1030,115 @@ def clearance():
     print(json.dumps(out))
 
 
+def meshclearance():
+    import torch
+    lib = psm.lib()
+    out = {"mode": "meshclearance", "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+    stress_tris = int(os.environ.get("STRESS_TRIS", "10000000"))
+    tor = torus(48, 24, 0.7, 0.25).reshape(-1, 3, 3)
+    rng = np.random.RandomState(17)
+
+    def hier(ctx, tris):
+        th = psm.TriangleHierarchy(ctx)
+        th.allocate(tris.shape[0])
+        th.loadTriangles(np.ascontiguousarray(tris, np.float32).reshape(-1, 9))
+        th.build()
+        return th
+
+    def rotation():
+        q = rng.normal(size=4)
+        w, x, y, z = q / np.linalg.norm(q)
+        return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                         [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                         [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+    for scene_name in os.environ.get("CLEAR_SCENES", "sponza,stress").split(","):
+        sc = scenes.sponza_like() if scene_name == "sponza" else scenes.stress(stress_tris)
+        tris = sc["tris"].reshape(-1, 3, 3)
+        ctx = psm.Context(0)
+        v = tris.reshape(-1, 3)
+        lo, hi = v.min(0).astype(np.float64), v.max(0).astype(np.float64)
+        ext = hi - lo
+        scale = 0.25 * float(ext.max()) / 1.9
+        otris = (tor.astype(np.float64) * scale).astype(np.float32)
+        th = hier(ctx, tris)
+        out[scene_name + "_tris"] = int(th.info().leaf_count)
+        r_small = 0.01 * float(np.linalg.norm(ext))
+        t = otris.shape[0]
+        for other_name, other in (("torus", hier(ctx, otris)), ("hollow", hier(ctx, np.repeat(otris[:, :1], 3, axis=1)))):
+            for p in (1, 1024):
+                rng.seed(2000 + p)
+                at = v[rng.choice(v.shape[0], p)].astype(np.float64)
+                off = rng.normal(size=(p, 3))
+                off *= (rng.uniform(0, 2 * 0.95 * scale, p) / np.linalg.norm(off, axis=1))[:, None]
+                poses = np.stack([np.concatenate([rotation(), c.reshape(3, 1)], axis=1) for c in at + off]).astype(np.float32)
+                m12 = np.ascontiguousarray(poses.reshape(p, 12))
+                hs = [ctx.buf_alloc(x) for x in (32 * p, max(p, 16), max(p, 16))]
+                p_pair, p_flag, p_cut = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in hs)
+                all_hits = torch.empty((p, t, 8), dtype=torch.float32, device=torch.device("cuda", ctx.device))
+                np_, pm, inf = C.c_size_t(p), m12.ctypes.data_as(C.c_void_p), C.c_float(np.inf)
+
+                def clearance(bound=None):
+                    def run():
+                        if bound is not None:
+                            os.environ["PSM_MESH_BOUND"] = bound
+                        try:
+                            ctx.check(lib.psm_bvh_mesh_clearance_dev(th._h, other._h, pm, np_, inf, p_pair), "psm_bvh_mesh_clearance_dev")
+                        finally:
+                            if bound is not None:
+                                del os.environ["PSM_MESH_BOUND"]
+                    return run
+
+                def closest_min():
+                    ctx.check(lib.psm_bvh_mesh_closest_dev(th._h, other._h, pm, np_, inf, C.c_void_p(all_hits.data_ptr())), "psm_bvh_mesh_closest_dev")
+                    ctx.sync()
+                    least = all_hits[:, :, 2].min(dim=1)
+                    torch.cuda.synchronize()
+                    return least
+
+                def within():
+                    ctx.check(lib.psm_bvh_mesh_within_dev(th._h, other._h, pm, np_, C.c_float(r_small), p_flag), "psm_bvh_mesh_within_dev")
+
+                def overlaps():
+                    ctx.check(lib.psm_bvh_mesh_overlaps_dev(th._h, other._h, pm, np_, p_cut), "psm_bvh_mesh_overlaps_dev")
+
+                def within_forced(skip):
+                    def run():
+                        os.environ["PSM_MESH_SKIP"] = skip
+                        try:
+                            within()
+                        finally:
+                            del os.environ["PSM_MESH_SKIP"]
+                    return run
+                key = "%s_%s_p%d_" % (scene_name, other_name, p)
+                out[key + "queries"] = p * int(other.info().leaf_count)
+                out[key + "clearance_bound_off_ms"], out[key + "clearance_bound_on_ms"] = abab(ctx, clearance("0"), clearance("1"))
+                if other_name == "torus":
+                    out[key + "clearance_on_again_ms"], out[key + "clearance_begin_only_ms"] = abab(ctx, clearance("1"), clearance("2"))
+                    out[key + "clearance_on_third_ms"], out[key + "clearance_publish_late_ms"] = abab(ctx, clearance("1"), clearance("3"))
+                out[key + "clearance_ms"], out[key + "closest_plus_torch_min_ms"] = abab(ctx, clearance(), closest_min)
+                out[key + "within_1pct_ms"], out[key + "overlaps_ms"] = abab(ctx, within, overlaps)
+                if other_name == "torus":
+                    out[key + "within_skip_ms"], out[key + "within_no_skip_ms"] = abab(ctx, within_forced("1"), within_forced("0"))
+                clearance()()
+                ctx.sync()
+                pair = ctx.buf_download(hs[0], np.float32, 8 * p).reshape(p, 8)
+                least = closest_min()
+                out[key + "equal"] = bool(np.array_equal(pair[:, 2], least.values.cpu().numpy()))   # (the tests hold the whole record)
+                out[key + "at_distance_0_fraction"] = round(float((pair[:, 2] == 0).mean()), 4)
+                out[key + "mean_dist_over_diagonal"] = round(float(pair[:, 2].mean() / np.linalg.norm(ext)), 5) if np.isfinite(pair[:, 2]).all() else None
+                within()
+                ctx.sync()
+                out[key + "within_fraction"] = round(float(ctx.buf_download(hs[1], np.uint8, p).mean()), 4)
+                del all_hits
+                for h in hs:
+                    ctx.buf_free(h)
+            other.close()
+        th.close()
+        ctx.close()
+    print(json.dumps(out))
+
+
 def posed(src, poses):
     """the query triangles [p, t, 3, 3] of the stored (v0, e1, e2) of src [t, 3, 3] at poses [p, 3, 4], in float32 in the
     library's operation order (psm_hip.h "mesh queries"): (b) and (c) then ask exactly what (a) asks"""
@@ -1619,4 +1736,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "worldtriangles": worldtriangles, "worldmeshes": worldmeshes}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "worldmeshes": worldmeshes}.get(" ".join(sys.argv[1:]), main)()
