@@ -62,6 +62,14 @@ namespace NSM {
         int overlapsTriangle(const psm_tri_query * d_tris, size_t n, uint8_t * d_hit);
         int countOnTriangle(const psm_tri_query * d_tris, size_t n, uint32_t * d_count);
         int trianglesOnTriangle(const psm_tri_query * d_tris, size_t n, uint32_t k, int32_t * d_tri, int32_t * d_inst, uint32_t * d_count);
+        // which (instance, triangle) pair is nearest to each of n WORLD triangles within its rmax, how far and at which two points
+        // (d_hits: {u, v, dist, tri, s, t, 0, 0}, (u, v) weights of the stored = the posed triangle's edges, (s, t) of the
+        // query's; d_inst the instance, -1 on a miss; the smallest float32 d2, on a bit-equal d2 the lowest (inst, tri)), and
+        // whether any pair is within it: the query triangle is never moved, each candidate triangle is posed forward and judged
+        // by the single hierarchy's clearance test, so dist == 0 exactly where overlapsTriangle counts the pair
+        // (psm_world_tri_closest_dev / psm_world_tri_within_dev); the flat lists have no such query
+        int closestToTriangle(const psm_tri_dist_query * d_tris, size_t n, psm_tri_hit * d_hits, int32_t * d_inst);
+        int withinOfTriangle(const psm_tri_dist_query * d_tris, size_t n, uint8_t * d_hit);
         // whether / how many / which (instance, triangle) pairs meet each stored triangle of ANOTHER built hierarchy at each of p
         // rigid poses that take its object space into WORLD space (glm::mat4, last row 0 0 0 1), in one call: each query triangle
         // is posed on the device and answered bit for bit as the three queries above answer it. skip: an instance that is left

@@ -106,6 +106,16 @@ namespace NSM {
         check(rc, "InstanceWorld::trianglesOnTriangle");
         return rc;
     }
+    inline int InstanceWorld::closestToTriangle(const psm_tri_dist_query * d_tris, size_t n, psm_tri_hit * d_hits, int32_t * d_inst) {
+        const int rc = psm_world_tri_closest_dev(world, d_tris, n, d_hits, d_inst);
+        check(rc, "InstanceWorld::closestToTriangle");
+        return rc;
+    }
+    inline int InstanceWorld::withinOfTriangle(const psm_tri_dist_query * d_tris, size_t n, uint8_t * d_hit) {
+        const int rc = psm_world_tri_within_dev(world, d_tris, n, d_hit);
+        check(rc, "InstanceWorld::withinOfTriangle");
+        return rc;
+    }
     inline int InstanceWorld::overlapsMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, uint8_t * d_hit) {
         const std::vector<float> m12 = detail::meshPoses(poses, p);   // (TriangleHierarchy.inl)
         const int rc = psm_world_mesh_overlaps_dev(world, other ? other->handle() : nullptr, m12.data(), p, int32_t(skip), d_hit);

@@ -669,8 +669,8 @@ int psm_bvh_tri_triangles_dev(psm_bvh* bvh, const psm_tri_query* d_tris, size_t 
  *     query, is {0, 0, +inf, -1, 0, 0, 0, 0}
  *   - within: d_flag[i] = 1 iff some candidate counts, else 0 (uint8_t, torch.bool-compatible): the predicate tri >= 0 of the
  *     first call; the walk ends at the first such candidate
- *   - not covered: a posed mesh in one call and per-pose clearance, worlds, flat scenes and instanced lists, the k nearest
- *     triangles, penetration depth, an intersection point at dist = 0
+ *   - not covered: a posed mesh in one call and per-pose clearance, flat scenes and instanced lists (a world has them:
+ *     "clearance queries over a world" below), the k nearest triangles, penetration depth, an intersection point at dist = 0
  *   - d_queries and d_hits 16-byte aligned; everything else (NULL checks, n = 0, PSM_ERR_STATE before the first build --
  *     "clearance query before build" --, PSM_ERR_CAPACITY for a hierarchy deeper than the query stack, stream order, capture,
  *     refit, 0 / 1 leaves) as for the queries above. A refused call launches nothing and leaves the output buffers untouched */
@@ -1042,6 +1042,33 @@ int psm_world_tri_overlaps_dev(psm_world* world, const psm_tri_query* d_tris, si
 int psm_world_tri_count_dev(psm_world* world, const psm_tri_query* d_tris, size_t n, uint32_t* d_count);
 int psm_world_tri_triangles_dev(psm_world* world, const psm_tri_query* d_tris, size_t n, uint32_t k, int32_t* d_tri, int32_t* d_inst,
                                 uint32_t* d_count);
+
+/* clearance queries over a world (new; no reference counterpart): which (instance, triangle) pair of a world is
+ * nearest to a triangle given in WORLD space, how far and at which two points, and whether any pair is within a radius, in one
+ * launch: how much room a triangle has among the posed bodies of a world. The clearance queries against a built hierarchy with
+ * the candidates of the triangle queries over a world. Flat scenes and instanced lists have no clearance query. Semantics:
+ *   - a query is a psm_tri_dist_query {a, rmax, b, c} in world space and is never moved. It is valid iff its nine coordinates
+ *     are finite and rmax >= 0 (NaN or negative: a miss; +inf: no limit), as for psm_bvh_tri_closest_dev; a segment or a point
+ *     is a valid query. The query is not moved, so there is no per-instance validity
+ *   - the candidates are the pairs (inst, tri) of the triangle queries over a world. With m = world_from_object[12] of the
+ *     instance the pair's distance is
+ *       tri_dist(fwd_point(m, v0), fwd_vec(m, e1), fwd_vec(m, e2), a, b, c)
+ *     tri_dist the function of the clearance queries above, fwd_point and fwd_vec those of the box queries over a world, all
+ *     unchanged, bit for bit, in float32. So dist == 0 exactly for the pairs psm_world_tri_overlaps_dev counts: the same tri_tri
+ *     on the same eighteen numbers
+ *   - the flat answer, which a world reproduces exactly: of all pairs with sqrtf(d2) <= rmax the smallest float32 d2 wins, on a
+ *     bit-equal d2 the lexicographically lowest (inst, tri), both compared unsigned. closest writes psm_tri_hit {u, v, dist =
+ *     sqrtf(d2), tri, s, t, 0, 0} and d_inst[i] = inst; a miss is {0, 0, +inf, -1, 0, 0, 0, 0} and -1. (u, v) weigh the STORED
+ *     triangle's e1, e2 -- weights are the same for the object-space and the posed triangle: the point on the instance is
+ *     (v0' + u e1') + v e2' with the posed v0', e1', e2' -- and (s, t) weigh the query's b - a, c - a
+ *   - within: d_hit[i] = 1 iff closest with rmax = r finds a pair, else 0
+ *   - nothing depends on the tree, its prune or the order of the walk
+ *   - an identity world of one answers as psm_bvh_tri_closest_dev / psm_bvh_tri_within_dev of its hierarchy, bit for bit
+ *   - d_tris and d_hits 16-byte, d_inst 4-byte aligned, none NULL; the stale check, the depth budget, n == 0, stream order and
+ *     capture as for the other world queries; an empty world answers misses / 0 without a query kernel. A refused call launches
+ *     nothing and leaves the output buffers untouched */
+int psm_world_tri_closest_dev(psm_world* world, const psm_tri_dist_query* d_tris, size_t n, psm_tri_hit* d_hits, int32_t* d_inst);
+int psm_world_tri_within_dev(psm_world* world, const psm_tri_dist_query* d_tris, size_t n, uint8_t* d_hit);
 
 /* mesh queries over a world (new; no reference counterpart): the triangle queries over a world above with the
  * query triangles taken from a built hierarchy `other` of the world's context, at each of p rigid poses, in one call: does body

@@ -44,6 +44,7 @@ EXPORTS = [
     "psm_world_box_overlaps_dev", "psm_world_box_count_dev", "psm_world_box_triangles_dev",
     "psm_world_sweep_sphere_dev", "psm_world_sweep_occluded_dev",
     "psm_world_tri_overlaps_dev", "psm_world_tri_count_dev", "psm_world_tri_triangles_dev",
+    "psm_world_tri_closest_dev", "psm_world_tri_within_dev",
     "psm_world_mesh_overlaps_dev", "psm_world_mesh_count_dev", "psm_world_mesh_triangles_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
@@ -524,8 +525,8 @@ class TriangleHierarchy:
         is the smallest of fifteen vertex-face and edge-edge features in float32 (psm_hip.h "clearance queries"); on a bit-equal
         squared distance the lowest id wins. Returns QueryTriHits: u, v, dist, tri, s, t (tri = -1, dist = +inf on a miss).
         numpy in: numpy out; torch device tensors in: torch tensors out on the same device, ordered against torch's current
-        stream without synchronising (as intersect()). QueryScene, InstancedScene and InstanceWorld have no clearance
-        queries."""
+        stream without synchronising (as intersect()). QueryScene and InstancedScene have no clearance queries; an
+        InstanceWorld has closestToTriangle() / withinOfTriangle()."""
         return self._tri_dist_query(tris, rmax, "trihits", "psm_bvh_tri_closest_dev")
 
     def triWithin(self, tris, r):
@@ -860,12 +861,15 @@ class QueryTriLists:
 
 
 class QueryTriHits:
-    """The records of TriangleHierarchy.triClosest: `buffer` [n, 8] float32 (numpy array or torch tensor) holds psm_tri_hit
-    records (u, v, dist, tri, s, t, 0, 0); u, v, dist, tri (int32), s and t are views of it. (u, v) weigh e1, e2 of the stored
-    triangle `tri`, (s, t) weigh b - a, c - a of the query triangle; a miss is tri = -1, dist = +inf."""
+    """The records of TriangleHierarchy.triClosest and InstanceWorld.closestToTriangle: `buffer` [n, 8] float32 (numpy array or
+    torch tensor) holds psm_tri_hit records (u, v, dist, tri, s, t, 0, 0); u, v, dist, tri (int32), s and t are views of it.
+    (u, v) weigh e1, e2 of the stored triangle `tri`, (s, t) weigh b - a, c - a of the query triangle; a miss is tri = -1,
+    dist = +inf. geom: for an InstanceWorld's records the int32 array / tensor of the winning instance's index (-1 on a miss, tri
+    is that instance's id); None for a single hierarchy's."""
 
-    def __init__(self, buffer):
+    def __init__(self, buffer, geom=None):
         self.buffer = buffer
+        self.geom = geom
         self.u, self.v, self.dist = buffer[:, 0], buffer[:, 1], buffer[:, 2]
         self.s, self.t = buffer[:, 4], buffer[:, 5]
         if isinstance(buffer, np.ndarray):
@@ -888,6 +892,26 @@ class QueryTriHits:
         on_query = (q[:, 0] + s * (q[:, 1] - q[:, 0])) + t * (q[:, 2] - q[:, 0])
         miss = (self.tri < 0)[:, None]
         return on_mesh + _nan_where(miss, on_mesh), on_query + _nan_where(miss, on_query)
+
+    def points_world(self, world_tris_of_instances, query_tris):
+        """points() for the records of InstanceWorld.closestToTriangle: world_tris_of_instances[j] holds instance j's triangles
+        AS POSED, [T_j, 3, 3] in world space (its loaded triangles moved by its pose: R x + T per vertex); the point on the
+        world is (v0' + u e1') + v e2' on triangle `tri` of instance `geom`. numpy arrays, [n, 3] each; a miss gives NaN rows"""
+        if self.geom is None:
+            raise ValueError("points_world(): the records of InstanceWorld.closestToTriangle have an instance; use points()")
+        rec = self.buffer if isinstance(self.buffer, np.ndarray) else self.buffer.cpu().numpy()
+        geom = self.geom if isinstance(self.geom, np.ndarray) else self.geom.cpu().numpy()
+        tri = rec.view(np.int32)[:, 3]
+        q = np.asarray(query_tris, np.float32).reshape(-1, 3, 3)
+        m = np.full((rec.shape[0], 3, 3), np.nan, np.float32)
+        for j in np.unique(geom[geom >= 0]):
+            rows = geom == j
+            m[rows] = np.asarray(world_tris_of_instances[j], np.float32).reshape(-1, 3, 3)[tri[rows]]
+        u, v, s, t = (rec[:, k:k + 1] for k in (0, 1, 4, 5))
+        on_world = (m[:, 0] + u * (m[:, 1] - m[:, 0])) + v * (m[:, 2] - m[:, 0])
+        on_query = (q[:, 0] + s * (q[:, 1] - q[:, 0])) + t * (q[:, 2] - q[:, 0])
+        on_query[tri < 0] = np.nan
+        return on_world, on_query
 
 
 class QueryMeshHits:
@@ -985,7 +1009,7 @@ def _launch_np(th, packed, out, name, *extra):
     tris = out == "tris"     # (a box query's id rows: k slots per query and the counts, as the lists')
     lists = out == "lists"   # (k rows per query, and the counts travel where a scene's geometry indices do)
     k = extra[0].value if lists or tris else 1
-    geom = (th._scene and out == "hits") or lists or tris
+    geom = (th._scene and out in ("hits", "trihits")) or lists or tris   # (a world's clearance records carry the instance too)
     hr, ho = ctx.buf_alloc(max(packed.nbytes, 32)), ctx.buf_alloc(max(per * k * n, 16))
     hg = ctx.buf_alloc(max(4 * n, 16)) if geom else None
     hi = ctx.buf_alloc(max(4 * k * n, 16)) if (lists or tris) and th._scene else None   # (a world's rows: the instance of every slot)
@@ -1003,14 +1027,14 @@ def _launch_np(th, packed, out, name, *extra):
             if out == "hits":
                 return QueryHits(np.zeros((0, 4), np.float32), np.zeros(0, np.int32) if geom else None)
             if out == "trihits":
-                return QueryTriHits(np.zeros((0, 8), np.float32))
+                return QueryTriHits(np.zeros((0, 8), np.float32), np.zeros(0, np.int32) if geom else None)
             return np.zeros(0, dtype)
         if out == "bool":
             return ctx.buf_download(ho, np.uint8, n).view(np.bool_)
         if out == "count":
             return ctx.buf_download(ho, np.uint32, n)
         if out == "trihits":
-            return QueryTriHits(ctx.buf_download(ho, np.float32, 8 * n).reshape(n, 8))
+            return QueryTriHits(ctx.buf_download(ho, np.float32, 8 * n).reshape(n, 8), ctx.buf_download(hg, np.int32, n) if geom else None)
         if tris:
             return QueryTriLists(ctx.buf_download(ho, np.int32, k * n).reshape(n, k), ctx.buf_download(hg, np.uint32, n),
                                  None if hi is None else ctx.buf_download(hi, np.int32, k * n).reshape(n, k))
@@ -1098,7 +1122,7 @@ def _launch_torch(th, packed, kind, name, *extra):
                     "lists": ((n, extra[0].value if lists else 1, 4), torch.float32),
                     "tris": ((n, extra[0].value if tris else 1), torch.int32)}[kind]
     out = torch.empty(shape, dtype=dtype, device=dev)
-    geom = torch.empty((n,), dtype=torch.int32, device=dev) if (th._scene and kind == "hits") or lists or tris else None
+    geom = torch.empty((n,), dtype=torch.int32, device=dev) if (th._scene and kind in ("hits", "trihits")) or lists or tris else None
     inst = torch.empty(shape[:2], dtype=torch.int32, device=dev) if (lists or tris) and th._scene else None   # (a world's rows)
     d_geom = None if geom is None else geom.data_ptr()
     _torch_ordered(th.ctx, dev, lambda: th._call(name, packed.data_ptr(), n, extra, out.data_ptr(),
@@ -1108,7 +1132,7 @@ def _launch_torch(th, packed, kind, name, *extra):
     if tris:
         return QueryTriLists(out, geom, inst)
     if kind == "trihits":
-        return QueryTriHits(out)
+        return QueryTriHits(out, geom)
     return QueryHits(out, geom) if kind == "hits" else (out.view(torch.bool) if kind == "bool" else out)
 
 
@@ -1236,7 +1260,8 @@ class InstanceWorld(QueryScene):
     nearest(), the box queries overlapsBox(), countInBox() and trianglesInBox() over world-space boxes, the sphere sweeps
     sphereCast() and sphereCastOccluded() along world-space lines, and the triangle queries overlapsTriangle(),
     countOnTriangle() and trianglesOnTriangle() on world-space triangles, and the mesh queries overlapsMesh(), countOnMesh()
-    and trianglesOnMesh() of another hierarchy at world poses, which the flat lists (QueryScene, InstancedScene) have not."""
+    and trianglesOnMesh() of another hierarchy at world poses, and the clearance queries closestToTriangle() and
+    withinOfTriangle() on world-space triangles, which the flat lists (QueryScene, InstancedScene) have not."""
 
     def __init__(self, ctx, entries, capacity=None):
         self.ctx = ctx
@@ -1374,6 +1399,25 @@ class InstanceWorld(QueryScene):
         return self._tri_query(tris, "tris", "psm_bvh_tri_triangles_dev", k)
 
     _tri_query = TriangleHierarchy._tri_query
+
+    def closestToTriangle(self, tris, rmax=np.inf):
+        """The nearest (instance, triangle) pair of the world to each WORLD triangle within rmax, its distance and the two
+        nearest points (psm_world_tri_closest_dev): tris [n, 3, 3] or [n, 9], rmax a scalar or [n] (+inf: no limit; NaN or
+        negative: a miss). The query stays in world space; each candidate triangle is posed forward in float32 (v0' = R v0 + T,
+        e1' = R e1, e2' = R e2) and judged by triClosest()'s test (psm_hip.h "clearance queries over a world"), so dist == 0
+        exactly where overlapsTriangle() counts the pair. The smallest float32 squared distance wins, on a bit-equal one the
+        lowest (instance, tri). Returns QueryTriHits with geom, the winning instance (geom = tri = -1, dist = +inf on a miss);
+        (u, v) weigh the stored triangle's edges, which are weights of the posed triangle as well: the point on the world is
+        (v0' + u e1') + v e2' (QueryTriHits.points_world). numpy / torch placement as triClosest()."""
+        return self._tri_dist_query(tris, rmax, "trihits", "psm_bvh_tri_closest_dev")
+
+    def withinOfTriangle(self, tris, r):
+        """Whether some triangle of some instance is within r of each world triangle (psm_world_tri_within_dev): the predicate
+        closestToTriangle(tris, r).tri >= 0, with the walk ended at the first such pair. A bool array / tensor. Arguments and
+        placement as closestToTriangle()."""
+        return self._tri_dist_query(tris, r, "bool", "psm_bvh_tri_within_dev")
+
+    _tri_dist_query = TriangleHierarchy._tri_dist_query
 
     def overlapsMesh(self, other, poses, skip=None, as_torch=False):
         """Whether `other`, a built TriangleHierarchy of this context (it may be a member of the world), meets some triangle of

@@ -111,6 +111,18 @@ PSM_TRI_FN TriDist tri_dist(v3 v0, v3 e1, v3 e2, v3 a, v3 b, v3 c) {
     return w;
 }
 
+// LB^2 of one child box (mn / mx: its fp16 corners) against the grown image interval [gl, gh] of the query's bounding box per
+// normalised axis: PointImage::lb2 with the gap to an interval (a NaN gap is 0: kept). tri_dist.hip's prune and, with a world's
+// intervals, world_tri_dist.hip's (psm_query_dev.h has the bound's derivation)
+PSM_D float tri_dist_lb2(const PointBound& B, float glx, float gly, float glz, float ghx, float ghy, float ghz, float mnx, float mny,
+                         float mnz, float mxx, float mxy, float mxz) {
+    const float tx = smaxf(smaxf(mnx - ghx, glx - mxx), 0.f) * B.il0;
+    const float ty = smaxf(smaxf(mny - ghy, gly - mxy), 0.f) * B.il1;
+    const float tz = smaxf(smaxf(mnz - ghz, glz - mxz), 0.f) * B.il2;
+    const float m = smaxf(smaxf(tx, ty), tz);
+    return (B.orth ? ((tx * tx + ty * ty) + tz * tz) : m * m) * B.wf;
+}
+
 }  // namespace
 
 }  // namespace psm

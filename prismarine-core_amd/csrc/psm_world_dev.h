@@ -1,5 +1,5 @@
 // psm_world_dev.h -- the device pieces the kernel files of a world share (world.hip, world_box.hip, world_sweep.hip,
-// world_tri.hip, world_mesh.hip): the table row, the node of the tree over the instances, the kernel arguments, the padding and the slacks,
+// world_tri.hip, world_tri_dist.hip, world_mesh.hip): the table row, the node of the tree over the instances, the kernel arguments, the padding and the slacks,
 // the two-level walk, the loads of a row, the best record of a world (WorldBest) and a ray in a world (WorldRay). Moved here
 // from world.hip as they were; every kernel of world.hip compiles to the same instructions as with the pieces in its own file
 // (tools/kernel_diff.py; the digests of tests/test_world_query_cpu.py and tests/test_world_kbest_cpu.py).
@@ -50,6 +50,12 @@ int world_box_launch(psm_ctx* c, int mode, uint32_t grid, const WorldArgs& a);
 // world_tri.hip: the launch of a world's triangle kernel (mode: 0 overlaps, 1 count, 2 triangles) for world.hip's host path;
 // a.rays holds the query triangles (psm_tri_query: three float4 each), the rest as world_box_launch
 int world_tri_launch(psm_ctx* c, int mode, uint32_t grid, const WorldArgs& a);
+
+// world_tri_dist.hip: the launch of a world's clearance kernel (within: whether a pair is within rmax; else the nearest pair) for
+// world.hip's host path; a.rays holds the query triangles (psm_tri_dist_query: three float4 each, rmax in the first's w), a.hits
+// the psm_tri_hit records (two float4 each) and a.geom the instances, or a.occluded the flags. a.rows == NULL (a world without
+// instances): the closest query's miss records are written and nothing walks
+int world_tri_dist_launch(psm_ctx* c, bool within, uint32_t grid, const WorldArgs& a);
 
 // world_sweep.hip: the launch of a world's sweep kernel (any: whether there is a contact; else the first contact) for
 // world.hip's host path; a.rays holds the sweeps (psm_sweep_query) where a ray's two float4 are

@@ -59,13 +59,9 @@ struct TriDistBody {
         box_row(M, 2, lo, hi, glz, ghz);
         return valid;
     }
-    // LB^2 of one child box (mn / mx: its fp16 corners): PointImage::lb2 with the gap to an interval (a NaN gap is 0: kept)
+    // LB^2 of one child box (mn / mx: its fp16 corners): tri_dist_lb2 (psm_tri_dist_dev.h) on this query's intervals
     PSM_D float lb2(float mnx, float mny, float mnz, float mxx, float mxy, float mxz) const {
-        const float tx = smaxf(smaxf(mnx - ghx, glx - mxx), 0.f) * B.il0;
-        const float ty = smaxf(smaxf(mny - ghy, gly - mxy), 0.f) * B.il1;
-        const float tz = smaxf(smaxf(mnz - ghz, glz - mxz), 0.f) * B.il2;
-        const float m = smaxf(smaxf(tx, ty), tz);
-        return (B.orth ? ((tx * tx + ty * ty) + tz * tz) : m * m) * B.wf;
+        return tri_dist_lb2(B, glx, gly, glz, ghx, ghy, ghz, mnx, mny, mnz, mxx, mxy, mxz);
     }
     // kept iff LB^2 <= best (<=: a triangle as near as the best and of a lower id still counts); the order key is LB^2
     PSM_D void children(uint4 n0, uint4 n1, bool& okL, bool& okR, float& kL, float& kR) const {

@@ -722,12 +722,13 @@ struct psm_world {
 namespace psm {
 namespace {
 
-const char* const WORLD_NAME[17] = {"psm_world_intersect_dev", "psm_world_occluded_dev", "psm_world_closest_point_dev",
+const char* const WORLD_NAME[19] = {"psm_world_intersect_dev", "psm_world_occluded_dev", "psm_world_closest_point_dev",
                                     "psm_world_within_dev", "psm_world_count_hits_dev", "psm_world_inside_dev",
                                     "psm_world_signed_distance_dev", "psm_world_first_hits_dev", "psm_world_nearest_dev",
                                     "psm_world_box_overlaps_dev", "psm_world_box_count_dev", "psm_world_box_triangles_dev",
                                     "psm_world_sweep_sphere_dev", "psm_world_sweep_occluded_dev",
-                                    "psm_world_tri_overlaps_dev", "psm_world_tri_count_dev", "psm_world_tri_triangles_dev"};
+                                    "psm_world_tri_overlaps_dev", "psm_world_tri_count_dev", "psm_world_tri_triangles_dev",
+                                    "psm_world_tri_closest_dev", "psm_world_tri_within_dev"};
 const Kernels<WorldArgs> WORLD_KERNELS = {{world_query_closest, world_query_any, world_query_point, world_query_within,
                                            world_query_count, world_query_inside, world_query_sign}};
 
@@ -818,7 +819,8 @@ int world_upload_and_build(psm_world* w, const char* name) {
 // (world_box.hip): d_in the world boxes; the triangles query as a k-best kind with int32 rows: d_out the [n][k] triangles,
 // d_inst the [n][k] instances, d_count the counts. And the sweep kinds (world_sweep.hip): d_in the sweeps, a 16-byte record and
 // d_inst, or a byte, as the closest-hit and the any-hit kinds. And the triangle kinds (world_tri.hip): d_in the world triangles
-// (psm_tri_query), everything else as the box kinds
+// (psm_tri_query), everything else as the box kinds. And the clearance kinds (world_tri_dist.hip): d_in the world triangles with
+// their rmax (psm_tri_dist_query), d_out two float4 per query and d_inst, or a byte
 int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* d_out, int32_t* d_inst, uint32_t samples = 0,
                 uint32_t* d_count = nullptr) {
     if (!w) return PSM_ERR_INVALID;
@@ -827,6 +829,7 @@ int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* 
     const char* name = WORLD_NAME[kind];
     const bool box = kind >= Q_BOX_ANY && kind <= Q_BOX_TRIS, sweep = kind == Q_SWEEP || kind == Q_SWEEP_ANY;
     const bool tri = kind >= Q_TRI_ANY && kind <= Q_TRI_TRIS;
+    const bool clear = kind == Q_TRI_CLOSEST || kind == Q_TRI_WITHIN;
     const bool kbest = kind == Q_FIRST_HITS || kind == Q_NEAREST || kind == Q_BOX_TRIS || kind == Q_TRI_TRIS;   // (the kinds with rows and counts)
     int rc = kbest ? check_data(c, name, "counts", kind, d_in, d_out, (const int32_t*)d_count, samples)
                    : check_data(c, name, "inst", kind, d_in, d_out, d_inst, samples);
@@ -842,6 +845,12 @@ int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* 
         if (kind == Q_BOX_TRIS || kind == Q_TRI_TRIS) {   // rows of -1 in both arrays
             PSM_HIP(c, hipMemsetAsync(d_out, 0xFF, rows * sizeof(int32_t), c->stream));
             PSM_HIP(c, hipMemsetAsync(d_inst, 0xFF, rows * sizeof(int32_t), c->stream));
+        } else if (kind == Q_TRI_CLOSEST) {   // (a psm_tri_hit is two float4: world_tri_dist.hip writes the miss records)
+            WorldArgs e = {};
+            e.n = n;
+            e.hits = (float4*)d_out;
+            e.geom = d_inst;
+            return world_tri_dist_launch(c, false, 0, e);
         } else if (per == 16) world_fill_miss<<<(unsigned)((rows + 255) / 256), 256, 0, c->stream>>>((float4*)d_out, d_inst, rows);
         else PSM_HIP(c, hipMemsetAsync(d_out, 0, n * per, c->stream));
         PSM_HIP(c, hipGetLastError());
@@ -867,6 +876,7 @@ int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* 
         if (kind == Q_TRI_TRIS) a.count = d_count;
         return world_tri_launch(c, (int)kind - (int)Q_TRI_ANY, grid, a);
     }
+    if (clear) return world_tri_dist_launch(c, kind == Q_TRI_WITHIN, grid, a);   // (world_tri_dist.hip)
     if (kbest) {   // the list: k x 64 x (8 + 4) B of dynamic LDS per wave, beside the stack
         a.count = d_count;
         const size_t lds = (size_t)samples * QUERY_BLOCK * (sizeof(uint2) + sizeof(uint32_t));
@@ -1134,6 +1144,12 @@ int psm_world_tri_count_dev(psm_world* w, const psm_tri_query* d_tris, size_t n,
 int psm_world_tri_triangles_dev(psm_world* w, const psm_tri_query* d_tris, size_t n, uint32_t k, int32_t* d_tri, int32_t* d_inst,
                                 uint32_t* d_count) {
     return psm::world_query(w, psm::Q_TRI_TRIS, d_tris, n, d_tri, d_inst, k, d_count);
+}
+int psm_world_tri_closest_dev(psm_world* w, const psm_tri_dist_query* d_tris, size_t n, psm_tri_hit* d_hits, int32_t* d_inst) {
+    return psm::world_query(w, psm::Q_TRI_CLOSEST, d_tris, n, d_hits, d_inst);
+}
+int psm_world_tri_within_dev(psm_world* w, const psm_tri_dist_query* d_tris, size_t n, uint8_t* d_hit) {
+    return psm::world_query(w, psm::Q_TRI_WITHIN, d_tris, n, d_hit, nullptr);
 }
 int psm_world_sweep_sphere_dev(psm_world* w, const psm_sweep_query* d_sweeps, size_t n, psm_hit* d_hits, int32_t* d_inst) {
     return psm::world_query(w, psm::Q_SWEEP, d_sweeps, n, d_hits, d_inst);

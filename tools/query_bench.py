@@ -82,6 +82,14 @@ so that the meshes cut. Per case and query, alternated A B A B (host-timed media
 whole call, against (b) countOnTriangle / overlapsTriangle / trianglesOnTriangle (k = 16) over the same posed triangles already
 resident on the device as psm_tri_query records in load order; the two (b) medians give the spread between runs; and the call's
 own overhead (checks, upload, wait, clears: the same call on a mesh without leaves) timed apart. No ratio is fixed in advance.
+`query_bench.py world-clearance`: the clearance queries of an instance world (psm_world_tri_closest_dev / psm_world_tri_within_dev) on
+worlds of 1, 64 and 1 024 turned grid poses (WCLEAR_POSES) of the Sponza-class scene and of the worldboxes mode's torus
+(WCLEAR_SCENES), WCLEAR_QUERIES (2^16) world triangles of a twentieth of a body's extent anywhere in the world's box, at rmax = +inf
+and at a small one (WCLEAR_RMAX, default 1 % of a body's diagonal). closestToTriangle and withinOfTriangle (the whole numpy call:
+upload, one launch, download), each alternated A B A B (host-timed medians of REPS; one timed call from 1 024 instances on) with what a caller
+could do before: the queries moved into every instance on the host, TriangleHierarchy.triClosest once per instance, the minimum on
+the host. Both times, the ratio, the fraction that finds a pair, and the largest difference between the two distances (they differ
+by the rounding of the host's move). No ratio is fixed in advance.
 `query_bench.py meshclearance`: mesh clearance (psm_bvh_mesh_closest_dev / psm_bvh_mesh_within_dev / psm_bvh_mesh_clearance_dev) on
 the Sponza-class scene and the stress scene (CLEAR_SCENES), the other mesh the meshes mode's torus (2 304 triangles, a quarter of the
 scene's extent across) and its hollow twin (as many triangles, none a leaf: the call's own overhead), at 1 and 1 024 poses whose
@@ -1494,6 +1502,81 @@ def worldtriangles():
     print(json.dumps(out))
 
 
+def worldclearance():
+    out = {"mode": "world-clearance", "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+    n = int(os.environ.get("WCLEAR_QUERIES", str(1 << 16)))
+    small = float(os.environ.get("WCLEAR_RMAX", "0.01"))
+    counts = [int(x) for x in os.environ.get("WCLEAR_POSES", "1,64,1024").split(",")]
+    for scene_name in os.environ.get("WCLEAR_SCENES", "sponza,torus").split(","):
+        tris = (scenes.sponza_like()["tris"] if scene_name == "sponza" else torus(48, 24, 0.7, 0.25)).reshape(-1, 3, 3).astype(np.float32)
+        ctx = psm.Context(0)
+        th = psm.TriangleHierarchy(ctx)
+        th.allocate(tris.shape[0])
+        th.loadTriangles(np.ascontiguousarray(tris.reshape(-1, 9)))
+        th.build()
+        out[scene_name + "_tris"] = int(th.info().leaf_count)
+        v = tris.reshape(-1, 3).astype(np.float64)
+        centre, radius = 0.5 * (v.min(0) + v.max(0)), 0.5 * float(np.linalg.norm(v.max(0) - v.min(0)))
+        rng = np.random.RandomState(23)
+        for poses_n in counts:
+            side = int(np.ceil(np.sqrt(poses_n)))       # a grid of poses a body's diameter apart, each turned about a random axis
+            poses = np.zeros((poses_n, 3, 4))
+            for j in range(poses_n):
+                q_, r_ = np.linalg.qr(rng.normal(size=(3, 3)))
+                rot = q_ * np.sign(np.diag(r_))
+                poses[j, :, :3] = rot
+                poses[j, :, 3] = np.array([2.0 * radius * (j % side), 2.0 * radius * (j // side), 0.0]) - rot @ centre
+            poses = poses.astype(np.float32)
+            lo = np.array([-radius, -radius, -radius])
+            hi = np.array([2.0 * radius * (side - 1) + radius, 2.0 * radius * ((poses_n - 1) // side) + radius, radius])
+            q = (rng.uniform(lo, hi, (n, 1, 3)) + rng.uniform(-0.05, 0.05, (n, 3, 3)) * radius).astype(np.float32)
+            wd = psm.InstanceWorld(ctx, [(th, m) for m in poses])
+            reps = REPS if poses_n < 1024 else 1
+            p64 = poses.astype(np.float64)
+
+            def loop(rmax, flag):
+                """what a caller had: per instance, the queries moved by R^T (x - T) on the host, triClosest, the host minimum"""
+                best, who = np.full(n, np.inf, np.float32), np.full(n, -1, np.int32)
+                for j in range(poses_n):
+                    moved = ((q.astype(np.float64) - p64[j, :, 3]) @ p64[j, :, :3]).astype(np.float32)
+                    d = th.triClosest(moved, rmax).dist
+                    nearer = d < best
+                    best, who = np.where(nearer, d, best), np.where(nearer, j, who).astype(np.int32)
+                return (who >= 0) if flag else (best, who)
+
+            def abab_n(fa, fb):
+                """medians (ms) of the two whole calls, alternated A B A B after a warm-up call of each, and their last results"""
+                ra, rb = fa(), fb()
+                ta, tb = [], []
+                for _ in range(reps):
+                    t0 = time.perf_counter()
+                    ra = fa()
+                    t1 = time.perf_counter()
+                    rb = fb()
+                    t2 = time.perf_counter()
+                    ta.append((t1 - t0) * 1e3)
+                    tb.append((t2 - t1) * 1e3)
+                return round(float(np.median(ta)), 3), round(float(np.median(tb)), 3), ra, rb
+            for rname, rmax in (("inf", np.inf), ("small", small * 2.0 * radius)):
+                key = "%s_poses%d_rmax_%s_" % (scene_name, poses_n, rname)
+                print("world-clearance: " + key[:-1], file=sys.stderr, flush=True)   # (a case of the loop takes minutes)
+                a, b, got, (best, who) = abab_n(lambda: wd.closestToTriangle(q, rmax), lambda: loop(rmax, False))
+                out[key + "closest_ms"], out[key + "loop_ms"], out[key + "loop_over_closest"] = a, b, round(b / a, 2)
+                a, b, flags, loop_flags = abab_n(lambda: wd.withinOfTriangle(q, rmax), lambda: loop(rmax, True))
+                out[key + "within_ms"], out[key + "within_loop_ms"], out[key + "loop_over_within"] = a, b, round(b / a, 2)
+                both = (got.tri >= 0) & (who >= 0)
+                out[key + "found_fraction"] = round(float((got.tri >= 0).mean()), 4)
+                out[key + "found_by_one_alone"] = int(((got.tri >= 0) != (who >= 0)).sum())
+                out[key + "within_differs"] = int((flags != loop_flags).sum())
+                out[key + "largest_dist_difference"] = float(np.abs(got.dist[both] - best[both]).max()) if both.any() else 0.0
+                out[key + "same_instance_fraction"] = round(float((got.geom[both] == who[both]).mean()), 4) if both.any() else 1.0
+            out["%s_poses%d_reps" % (scene_name, poses_n)] = reps
+            wd.close()
+        th.close()
+        ctx.close()
+    print(json.dumps(out))
+
+
 def worldmeshes():
     lib = psm.lib()
     ctx = psm.Context(0)
@@ -1736,4 +1819,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "worldmeshes": worldmeshes}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "world-clearance": worldclearance, "worldmeshes": worldmeshes}.get(" ".join(sys.argv[1:]), main)()
