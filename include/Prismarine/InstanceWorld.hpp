@@ -80,5 +80,14 @@ namespace NSM {
         int overlapsMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, uint8_t * d_hit);
         int countOnMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, uint32_t * d_count);
         int trianglesOnMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, uint32_t k, int32_t * d_tri, int32_t * d_inst, uint32_t * d_count);
+        // how close each stored triangle of ANOTHER built hierarchy comes to the world's (instance, triangle) pairs at each of p
+        // rigid poses within rmax (closestToMesh: d_hits [p][T] psm_tri_hit, d_inst [p][T], each bit for bit closestToTriangle's
+        // answer for the posed triangle), whether any comes within r (withinOfMesh: d_flag [p]) and the ONE nearest pair of each
+        // pose (clearanceToMesh: d_hits [p] psm_mesh_hit, d_inst [p]: the smallest dist, then the lowest triangle of other, then
+        // closestToTriangle's (inst, tri)). poses, skip, the one wait and no graph capture as overlapsMesh
+        // (psm_world_mesh_closest_dev / psm_world_mesh_within_dev / psm_world_mesh_clearance_dev)
+        int closestToMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, float rmax, psm_tri_hit * d_hits, int32_t * d_inst);
+        int withinOfMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, float r, uint8_t * d_flag);
+        int clearanceToMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, float rmax, psm_mesh_hit * d_hits, int32_t * d_inst);
     };
 }

@@ -134,4 +134,22 @@ namespace NSM {
         check(rc, "InstanceWorld::trianglesOnMesh");
         return rc;
     }
+    inline int InstanceWorld::closestToMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, float rmax, psm_tri_hit * d_hits, int32_t * d_inst) {
+        const std::vector<float> m12 = detail::meshPoses(poses, p);
+        const int rc = psm_world_mesh_closest_dev(world, other ? other->handle() : nullptr, m12.data(), p, int32_t(skip), rmax, d_hits, d_inst);
+        check(rc, "InstanceWorld::closestToMesh");
+        return rc;
+    }
+    inline int InstanceWorld::withinOfMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, float r, uint8_t * d_flag) {
+        const std::vector<float> m12 = detail::meshPoses(poses, p);
+        const int rc = psm_world_mesh_within_dev(world, other ? other->handle() : nullptr, m12.data(), p, int32_t(skip), r, d_flag);
+        check(rc, "InstanceWorld::withinOfMesh");
+        return rc;
+    }
+    inline int InstanceWorld::clearanceToMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, float rmax, psm_mesh_hit * d_hits, int32_t * d_inst) {
+        const std::vector<float> m12 = detail::meshPoses(poses, p);
+        const int rc = psm_world_mesh_clearance_dev(world, other ? other->handle() : nullptr, m12.data(), p, int32_t(skip), rmax, d_hits, d_inst);
+        check(rc, "InstanceWorld::clearanceToMesh");
+        return rc;
+    }
 }

@@ -774,7 +774,9 @@ int psm_bvh_mesh_triangles_dev(psm_bvh* bvh, psm_bvh* other, const float* poses,
  *     the variants DESIGN.md 4.24 compares); PSM_MESH_SKIP = 0 / 1 is the within kernel's skip of a pose whose flag already
  *     reads 1, as psm_bvh_mesh_overlaps_dev has it
  *   - not covered: clearance over an InstanceWorld, a QueryScene or an InstancedScene; a per-pose rmax; the k closest pairs; a
- *     dual-tree walk that prunes whole subtrees of other; penetration depth; graph capture of the call */
+ *     dual-tree walk that prunes whole subtrees of other; penetration depth; graph capture of the call
+ *     (since added: clearance over an InstanceWorld -- "mesh clearance over a world" below, psm_world_mesh_closest_dev /
+ *     _within_dev / _clearance_dev) */
 typedef struct {
     float u, v, dist; /* the first 24 bytes: a psm_tri_hit */
     int32_t tri;
@@ -1118,6 +1120,51 @@ int psm_world_mesh_overlaps_dev(psm_world* world, psm_bvh* other, const float* p
 int psm_world_mesh_count_dev(psm_world* world, psm_bvh* other, const float* poses, size_t p, int32_t skip, uint32_t* d_count);
 int psm_world_mesh_triangles_dev(psm_world* world, psm_bvh* other, const float* poses, size_t p, int32_t skip, uint32_t k,
                                  int32_t* d_tri, int32_t* d_inst, uint32_t* d_count);
+
+/* mesh clearance over a world (new; no reference counterpart): "mesh clearance" above with a world where `bvh`
+ * was -- how close body B comes to the other bodies of a scene at each of p candidate poses, and where. The clearance queries
+ * over a world with the query triangles taken from a built hierarchy `other` of the world's context, posed on the device, and
+ * the ONE nearest pair of each pose. world, other, poses, p, skip, T = other's loaded triangle count and the indexing by other's
+ * load-order triangle id are those of "mesh queries over a world". Semantics:
+ *   - mesh_closest: d_hits [p][T], d_inst [p][T]. The record and the instance of (pose q, triangle t of other) are BIT FOR BIT
+ *     what psm_world_tri_closest_dev writes for psm_tri_dist_query {a, rmax, b, c}, with a, b, c the posed triangle exactly as
+ *     the mesh queries make it (a = fwd_point(m, v0), b = a + fwd_vec(m, e1), c = a + fwd_vec(m, e2)): of all pairs (inst, tri)
+ *     of the world with sqrtf(d2) <= rmax the smallest float32 d2, on a bit-equal d2 the lexicographically lowest (inst, tri).
+ *     With skip = i >= 0 instance i is left out and the other indices are KEPT, decided where an instance is entered. The miss
+ *     record {0, 0, +inf, -1, 0, 0, 0, 0} and instance -1 are written for a triangle that other's build dropped, for one whose
+ *     posed image is not finite, and for every triangle when the world is empty
+ *   - mesh_clearance: d_hits [p], one psm_mesh_hit per pose, d_inst [p]. Let t* be the lowest t among the triangles of other
+ *     whose mesh_closest record has the smallest dist, comparing the float32 dist as stored. The record is that triangle's
+ *     mesh_closest record, bit for bit, with other = t*, and d_inst its instance. A pose where no pair counts reads
+ *     {0, 0, +inf, -1, 0, 0, -1, 0} and instance -1. (u, v) weigh e1, e2 of the instance's stored triangle tri -- the same
+ *     weights on its posed image --, (s, t) weigh b - a, c - a of the posed triangle `other`: both witness points in world space
+ *   - mesh_within: d_flag [p]; d_flag[q] = 1 iff mesh_clearance at rmax = r finds a pair at pose q, else 0. The walk of a
+ *     triangle ends at its first pair that counts
+ *   - rmax / r: one scalar per call. NaN or negative is not a refusal: it answers a miss everywhere. -0 is 0, +inf is no limit
+ *   - nothing depends on the top-level tree, a member's tree, other's tree, the order of the walk or timing. Inside the
+ *     clearance launch the lanes of a pose share the 64-bit word of "mesh clearance", (bits(dist) << 32) | t, t the triangle of
+ *     OTHER: the word never holds the world's side of the pair, so it needs no instance. Every value it takes is the dist of a
+ *     real pair that counts (never one of the skipped instance), so the final word is (the smallest dist, t*) under every
+ *     schedule; a second, tiny launch of one lane per pose walks posed triangle t* again with that dist for rmax, as
+ *     mesh_closest would with the same skip, and writes the record and the instance
+ *   - refusals: those of the mesh queries over a world, in the same order and with the same texts under these names, all on the
+ *     host before any launch and with the outputs untouched: NULL world (PSM_ERR_INVALID, no message); p == 0 returns PSM_OK and
+ *     touches nothing; NULL other, poses, d_hits / d_flag or d_inst; d_hits not 16-byte aligned, d_inst not 4-byte aligned
+ *     (PSM_ERR_INVALID); other not built (PSM_ERR_STATE, "mesh query before build"); other of another context
+ *     (PSM_ERR_INVALID); a stale world (PSM_ERR_STATE); a pose that is not finite or not rigid, named by its index
+ *     (PSM_ERR_INVALID); skip out of range (PSM_ERR_INVALID); p x T >= 2^32 (PSM_ERR_CAPACITY)
+ *   - the poses go to the device as the mesh queries' do: one copy on the context's stream and ONE synchronisation before the
+ *     launch (other's leaf count comes back in the same wait). The call CANNOT be captured into a graph. An empty world and an
+ *     other without leaves launch no walk: the miss records (flags of 0) are written in stream order
+ *   - study knobs, no part of the contract, read at each call: PSM_MESH_BOUND = 0 / 1 / 2 / 3 and PSM_MESH_SKIP = 0 / 1, with the
+ *     meanings "mesh clearance" gives them; the answer is the same under each
+ *   - not covered: clearance over a QueryScene or an InstancedScene; a per-pose rmax; more than one skipped instance; the k
+ *     closest pairs; a dual-tree walk; penetration depth; graph capture of the call */
+int psm_world_mesh_closest_dev(psm_world* world, psm_bvh* other, const float* poses, size_t p, int32_t skip, float rmax,
+                               psm_tri_hit* d_hits /*[p][T]*/, int32_t* d_inst /*[p][T]*/);
+int psm_world_mesh_within_dev(psm_world* world, psm_bvh* other, const float* poses, size_t p, int32_t skip, float r, uint8_t* d_flag /*[p]*/);
+int psm_world_mesh_clearance_dev(psm_world* world, psm_bvh* other, const float* poses, size_t p, int32_t skip, float rmax,
+                                 psm_mesh_hit* d_hits /*[p]*/, int32_t* d_inst /*[p]*/);
 
 /* ---------------------------------------------------------------------------------------------
  * several frames in flight (new; DESIGN.md "lanes")

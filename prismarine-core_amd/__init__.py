@@ -46,6 +46,7 @@ EXPORTS = [
     "psm_world_tri_overlaps_dev", "psm_world_tri_count_dev", "psm_world_tri_triangles_dev",
     "psm_world_tri_closest_dev", "psm_world_tri_within_dev",
     "psm_world_mesh_overlaps_dev", "psm_world_mesh_count_dev", "psm_world_mesh_triangles_dev",
+    "psm_world_mesh_closest_dev", "psm_world_mesh_within_dev", "psm_world_mesh_clearance_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -865,18 +866,19 @@ class QueryTriHits:
     torch tensor) holds psm_tri_hit records (u, v, dist, tri, s, t, 0, 0); u, v, dist, tri (int32), s and t are views of it.
     (u, v) weigh e1, e2 of the stored triangle `tri`, (s, t) weigh b - a, c - a of the query triangle; a miss is tri = -1,
     dist = +inf. geom: for an InstanceWorld's records the int32 array / tensor of the winning instance's index (-1 on a miss, tri
-    is that instance's id); None for a single hierarchy's."""
+    is that instance's id); None for a single hierarchy's. InstanceWorld.closestToMesh's records are [p, T, 8] with geom [p, T]:
+    the views are on the last axis (points() and points_world() take the flat [n, 8] records)."""
 
     def __init__(self, buffer, geom=None):
         self.buffer = buffer
         self.geom = geom
-        self.u, self.v, self.dist = buffer[:, 0], buffer[:, 1], buffer[:, 2]
-        self.s, self.t = buffer[:, 4], buffer[:, 5]
+        self.u, self.v, self.dist = buffer[..., 0], buffer[..., 1], buffer[..., 2]
+        self.s, self.t = buffer[..., 4], buffer[..., 5]
         if isinstance(buffer, np.ndarray):
-            self.tri = buffer.view(np.int32)[:, 3]
+            self.tri = buffer.view(np.int32)[..., 3]
         else:
             import torch
-            self.tri = buffer.view(torch.int32)[:, 3]
+            self.tri = buffer.view(torch.int32)[..., 3]
 
     def __len__(self):
         return self.buffer.shape[0]
@@ -919,10 +921,12 @@ class QueryMeshHits:
     torch tensor), holds psm_tri_hit / psm_mesh_hit records; u, v, dist, tri (int32), s and t are views on its last axis.
     (u, v) weigh e1, e2 of this hierarchy's triangle `tri`, (s, t) weigh b - a, c - a of the posed triangle of the other mesh.
     other: for meshClearance the int32 view of slot 6, the other mesh's triangle (-1 on a miss); None for meshClosest, whose
-    second index is that triangle. QueryTriHits stays what triClosest returns."""
+    second index is that triangle. QueryTriHits stays what triClosest returns. geom: for InstanceWorld.clearanceToMesh's records
+    the int32 array / tensor [p] of the winning instance (-1 on a miss; tri is that instance's id); None for a hierarchy's."""
 
-    def __init__(self, buffer, per_pose=False):
+    def __init__(self, buffer, per_pose=False, geom=None):
         self.buffer = buffer
+        self.geom = geom
         self.u, self.v, self.dist = buffer[..., 0], buffer[..., 1], buffer[..., 2]
         self.s, self.t = buffer[..., 4], buffer[..., 5]
         if isinstance(buffer, np.ndarray):
@@ -957,6 +961,20 @@ class QueryMeshHits:
         on_mesh[miss] = np.nan
         on_other[miss] = np.nan
         return on_mesh, on_other
+
+
+    def points_world(self, world_tris_of_instances, other_tris, poses):
+        """points() for the records of InstanceWorld.clearanceToMesh, in world space, [p, 3] each: the point on triangle `tri` of
+        instance `geom` (world_tris_of_instances[j]: instance j's triangles AS POSED, as QueryTriHits.points_world takes them)
+        and the point on the other mesh's triangle `other` moved by its pose (float32 here); a miss gives NaN rows"""
+        if self.other is None or self.geom is None:
+            raise ValueError("points_world(): the records of InstanceWorld.clearanceToMesh have an instance and a triangle of other")
+        rec = self.buffer if isinstance(self.buffer, np.ndarray) else self.buffer.cpu().numpy()
+        o = np.asarray(other_tris, np.float32).reshape(-1, 3, 3)[rec.view(np.int32)[:, 6].clip(0)] if len(rec) else np.zeros((0, 3, 3), np.float32)
+        pm = np.asarray(poses, np.float32)
+        pm = (pm[None] if pm.ndim == 2 else pm)[:, :3, :]
+        posed = np.einsum("pij,pkj->pki", pm[:, :, :3], o) + pm[:, None, :, 3]
+        return QueryTriHits(rec, self.geom).points_world(world_tris_of_instances, posed)
 
 
 def _mesh_poses(other, poses, name):
@@ -1261,7 +1279,8 @@ class InstanceWorld(QueryScene):
     sphereCast() and sphereCastOccluded() along world-space lines, and the triangle queries overlapsTriangle(),
     countOnTriangle() and trianglesOnTriangle() on world-space triangles, and the mesh queries overlapsMesh(), countOnMesh()
     and trianglesOnMesh() of another hierarchy at world poses, and the clearance queries closestToTriangle() and
-    withinOfTriangle() on world-space triangles, which the flat lists (QueryScene, InstancedScene) have not."""
+    withinOfTriangle() on world-space triangles, and mesh clearance closestToMesh(), withinOfMesh() and clearanceToMesh() of
+    another hierarchy at world poses, which the flat lists (QueryScene, InstancedScene) have not."""
 
     def __init__(self, ctx, entries, capacity=None):
         self.ctx = ctx
@@ -1503,6 +1522,75 @@ class InstanceWorld(QueryScene):
             for h in (ho, hi, hc):
                 if h is not None:
                     ctx.buf_free(h)
+
+    def closestToMesh(self, other, poses, rmax=np.inf, skip=None, as_torch=False):
+        """The nearest (instance, triangle) pair of the world to each triangle of `other` at each pose within rmax
+        (psm_world_mesh_closest_dev; not in the reference): each stored triangle of other is posed in float32 on the device, as
+        countOnMesh() poses it, and answered bit for bit as closestToTriangle() answers it. rmax: one scalar (+inf: no limit; NaN
+        or negative: a miss everywhere). Returns QueryTriHits over a [p, T, 8] buffer with geom [p, T], T = other.triangleCount,
+        indexed by other's load-order triangle id (tri = geom = -1, dist = +inf on a miss and for a triangle other's build
+        dropped). skip, the poses and the placement as overlapsMesh()."""
+        return self._mesh_dist_query(other, poses, rmax, skip, "closest", "psm_world_mesh_closest_dev", as_torch)
+
+    def withinOfMesh(self, other, poses, r, skip=None, as_torch=False):
+        """Whether some triangle of `other` comes within r of some triangle of some instance at each pose
+        (psm_world_mesh_within_dev; not in the reference): clearanceToMesh(other, poses, r, skip).tri >= 0, with every walk ended
+        at its first such pair. A bool [p]. Arguments and placement as closestToMesh()."""
+        return self._mesh_dist_query(other, poses, r, skip, "bool", "psm_world_mesh_within_dev", as_torch)
+
+    def clearanceToMesh(self, other, poses, rmax=np.inf, skip=None, as_torch=False):
+        """The one nearest pair of each pose (psm_world_mesh_clearance_dev; not in the reference): of closestToMesh()'s records
+        of a pose the one with the smallest dist, on an equal float32 dist the lowest triangle of other -- found inside the
+        launch, the triangles of a pose sharing the best distance so far as their bound. Returns QueryMeshHits over a [p, 8]
+        buffer with geom [p]: u, v, dist, tri, s, t, .other (other's triangle) and .geom (the instance; tri = other = geom = -1,
+        dist = +inf where no pair is within rmax); .points_world() gives the two witness points. Arguments and placement as
+        closestToMesh()."""
+        return self._mesh_dist_query(other, poses, rmax, skip, "clearance", "psm_world_mesh_clearance_dev", as_torch)
+
+    def _mesh_dist_query(self, other, poses, rmax, skip, out, name, as_torch):
+        """one mesh clearance query of the world: poses and skip as _mesh_query checks and packs them, rmax one float, the
+        outputs [p, T, 8] and [p, T] / [p] / [p, 8] and [p]"""
+        m12, p, t = _mesh_poses(other, poses, name)
+        if np.ndim(rmax) != 0:
+            raise ValueError("%s: rmax must be one scalar" % name)
+        if skip is None:
+            s = -1
+        else:
+            s = int(skip)
+            if s != skip or isinstance(skip, bool) or not 0 <= s < len(self.hierarchies):   # (refused here: no call is made)
+                raise PsmError("%s: skip must be None or an instance index 0 .. %d" % (name, len(self.hierarchies) - 1))
+        self._fresh(name)
+        shape = {"closest": (p, t, 8), "bool": (p,), "clearance": (p, 8)}[out]
+        fn = getattr(lib(), name)
+
+        def call(d_out, d_inst):
+            tail = () if d_inst is None else (C.c_void_p(d_inst),)
+            self.ctx.check(fn(self._w, other._h, _p(m12), C.c_size_t(p), C.c_int32(s), C.c_float(rmax), C.c_void_p(d_out), *tail), name)
+
+        if as_torch:
+            import torch
+            dev = torch.device("cuda", self.ctx.device)
+            res = torch.empty(shape, dtype=torch.uint8 if out == "bool" else torch.float32, device=dev)
+            inst = None if out == "bool" else torch.empty(shape[:-1], dtype=torch.int32, device=dev)
+            _torch_ordered(self.ctx, dev, lambda: call(res.data_ptr(), None if inst is None else inst.data_ptr()))
+            if out == "bool":
+                return res.view(torch.bool)
+            return QueryTriHits(res, inst) if out == "closest" else QueryMeshHits(res, True, inst)
+        ctx = self.ctx
+        n = int(np.prod(shape))
+        ho = ctx.buf_alloc(max(n if out == "bool" else 4 * n, 16))
+        hi = None if out == "bool" else ctx.buf_alloc(max(n // 2, 16))
+        try:
+            call(ctx.buf_ptr(ho)[0], None if hi is None else ctx.buf_ptr(hi)[0])
+            if out == "bool":
+                return ctx.buf_download(ho, np.uint8, p).view(np.bool_) if p else np.zeros(0, np.bool_)
+            rec = (ctx.buf_download(ho, np.float32, n) if n else np.zeros(0, np.float32)).reshape(shape)
+            ins = (ctx.buf_download(hi, np.int32, n // 8) if n else np.zeros(0, np.int32)).reshape(shape[:-1])
+            return QueryTriHits(rec, ins) if out == "closest" else QueryMeshHits(rec, True, ins)
+        finally:
+            ctx.buf_free(ho)
+            if hi is not None:
+                ctx.buf_free(hi)
 
     def _call(self, name, d_in, n, extra, d_out, d_geom):
         name = name.replace("psm_bvh_", "psm_world_")

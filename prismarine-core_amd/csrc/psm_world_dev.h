@@ -1,5 +1,5 @@
 // psm_world_dev.h -- the device pieces the kernel files of a world share (world.hip, world_box.hip, world_sweep.hip,
-// world_tri.hip, world_tri_dist.hip, world_mesh.hip): the table row, the node of the tree over the instances, the kernel arguments, the padding and the slacks,
+// world_tri.hip, world_tri_dist.hip, world_mesh.hip, world_mesh_dist.hip): the table row, the node of the tree over the instances, the kernel arguments, the padding and the slacks,
 // the two-level walk, the loads of a row, the best record of a world (WorldBest) and a ray in a world (WorldRay). Moved here
 // from world.hip as they were; every kernel of world.hip compiles to the same instructions as with the pieces in its own file
 // (tools/kernel_diff.py; the digests of tests/test_world_query_cpu.py and tests/test_world_kbest_cpu.py).
@@ -81,6 +81,21 @@ constexpr uint64_t WORLD_MESH_ANSWERS_MAX = (uint64_t)1 << 32;
 // world_mesh.hip: the launch of a world's mesh kernel (mode: 0 overlaps, 1 count, 2 triangles) for world.hip's host path
 // (world_mesh_query()); a.w.samples is the triangles query's k; magic is set there from a.L (mesh_magic, psm_mesh_dev.h)
 int world_mesh_launch(psm_ctx* c, int mode, uint32_t grid, WorldMeshArgs a);
+
+// WorldMeshArgs keeps its layout; what a mesh clearance query over a world (world_mesh_dist.hip) adds travels
+// beside it. m.w: the world, spill and outputs (closest: hits = psm_tri_hit [p][T], geom [p][T]; within: occluded, the flag per
+// pose; pick: hits = psm_mesh_hit [p], geom [p]), n = p x L (pick: p); m.flags: WORLD_MESH_FLAG_SKIP for the within kernel
+struct WorldMeshDistArgs {
+    WorldMeshArgs m;
+    unsigned long long* keys;   // [p]: the poses' shared words (clearance, pick; psm_mesh_dist_key.h)
+    float rmax;                 // one per call
+};
+enum { WMD_CLOSEST = 0, WMD_WITHIN = 1, WMD_CLEAR = 2, WMD_PICK = 3, WMD_FILL = 4 };
+
+// world_mesh_dist.hip: the launch of a world's mesh clearance kernel for world.hip's host path (world_mesh_dist_query()); magic is
+// set there from a.m.L. mode WMD_CLEAR: bound is PSM_MESH_BOUND's letter ('0' .. '3'; mesh_dist.hip has the meanings). mode
+// WMD_FILL: the miss record in a.m.w.n cells of hits (the word after s, t: -1 where the records are psm_mesh_hit, `pick`) and -1 in geom
+int world_mesh_dist_launch(psm_ctx* c, int mode, char bound, bool pick, uint32_t grid, WorldMeshDistArgs a);
 
 namespace {
 

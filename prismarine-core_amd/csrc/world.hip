@@ -982,6 +982,114 @@ int world_mesh_query(psm_world* w, psm_bvh* o, const float* poses, size_t p, int
     return world_mesh_launch(c, mode, grid, m);
 }
 
+const char* const WORLD_MESH_DIST_NAME[] = {"psm_world_mesh_closest_dev", "psm_world_mesh_within_dev", "psm_world_mesh_clearance_dev"};
+
+// A mesh clearance query of a world (world_mesh_dist.hip): world_mesh_query()'s checks in its order and with its
+// texts under the new names, and the alignment of the records; all on the host, before any launch, the outputs untouched. Then
+// the poses go to the device as world_mesh_query() sends them (one copy, one synchronisation), every word of the clearance
+// query is set to "none" in stream order, and the kernels run -- unless the world is empty or the other hierarchy has no leaf:
+// then the miss records are written without a walk. mode: WMD_CLOSEST, WMD_WITHIN, WMD_CLEAR
+int world_mesh_dist_query(psm_world* w, psm_bvh* o, const float* poses, size_t p, int32_t skip, int mode, float rmax, void* d_out,
+                          int32_t* d_inst) {
+    if (!w) return PSM_ERR_INVALID;
+    if (p == 0) return PSM_OK;
+    psm_ctx* c = w->ctx;
+    const char* name = WORLD_MESH_DIST_NAME[mode];
+    char msg[192];
+    const bool records = mode != WMD_WITHIN;
+    if (!o || !poses || !d_out || (records && !d_inst)) {
+        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (records && ((uintptr_t)d_out & 15u) != 0) {
+        snprintf(msg, sizeof msg, "%s: hits not 16-byte aligned", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (records && ((uintptr_t)d_inst & 3u) != 0) {
+        snprintf(msg, sizeof msg, "%s: inst not 4-byte aligned", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (!o->built) return set_err(c, PSM_ERR_STATE, "mesh query before build");
+    if (o->ctx != c) {
+        snprintf(msg, sizeof msg, "%s: the world and the other hierarchy are of different contexts", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    const int stale = first_stale(w);
+    if (stale >= 0) return refuse_stale(w, name, stale);
+    for (size_t q = 0; q < p; q++)
+        if (const char* why = pose_fault(poses + 12 * q)) {
+            snprintf(msg, sizeof msg, "%s: pose %zu %s", name, q, why);
+            return set_err(c, PSM_ERR_INVALID, msg);
+        }
+    if (skip < -1 || (skip >= 0 && (uint32_t)skip >= w->count)) {
+        snprintf(msg, sizeof msg, "%s: skip %d of a world of %u (-1: no instance is left out)", name, (int)skip, w->count);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    const uint32_t T = o->tri_count;
+    if ((uint64_t)p * T >= WORLD_MESH_ANSWERS_MAX) {
+        snprintf(msg, sizeof msg, "%s: %zu poses of %u triangles are more than 2^32 answers", name, p, T);
+        return set_err(c, PSM_ERR_CAPACITY, msg);
+    }
+    (void)hipSetDevice(c->device);
+    uint32_t L = 0;
+    void *d_poses = nullptr, *d_keys = nullptr;
+    WorldMeshDistArgs a = {};
+    uint32_t grid = 0;
+    int rc = PSM_OK;
+    if (w->count != 0) {   // (an empty world: no query kernel, nothing to upload; the miss records alone)
+        rc = poses_for(c, p * 12 * sizeof(float), &d_poses);
+        if (rc != PSM_OK) return rc;
+        if (mode == WMD_CLEAR) {
+            rc = mesh_keys_for(c, p * sizeof(uint64_t), &d_keys);
+            if (rc != PSM_OK) return rc;
+        }
+        PSM_HIP(c, hipMemcpyAsync(d_poses, poses, p * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        PSM_HIP(c, hipMemcpyAsync(&L, o->d_small + SM_COUNT, sizeof L, hipMemcpyDeviceToHost, c->stream));
+        PSM_HIP(c, hipStreamSynchronize(c->stream));
+        if (L > T) return set_err(c, PSM_ERR_STATE, "mesh query: the other hierarchy's leaf count exceeds its triangle count");
+        // (the context's stack area is allocated here, on its first query: the last thing that can fail before the outputs change)
+        rc = batch_args(c, nullptr, p * (size_t)L, d_out, 0, a.m.w, grid);
+        if (rc != PSM_OK) return rc;
+    }
+    const bool walk = w->count != 0 && L != 0;
+    if (mode == WMD_WITHIN) PSM_HIP(c, hipMemsetAsync(d_out, 0, p, c->stream));
+    else if (!walk || (mode == WMD_CLOSEST && L < T)) {   // the miss records: no walk, or a dropped triangle's cells
+        WorldMeshDistArgs f = {};
+        f.m.w.n = mode == WMD_CLOSEST ? p * (size_t)T : p;
+        f.m.w.hits = (float4*)d_out;
+        f.m.w.geom = d_inst;
+        rc = world_mesh_dist_launch(c, WMD_FILL, 0, mode == WMD_CLEAR, 0, f);
+        if (rc != PSM_OK) return rc;
+    }
+    if (!walk) return PSM_OK;
+    a.m.w.geom = d_inst;
+    a.m.w.root = w->count == 1 ? ~0 : 0;
+    a.m.w.rows = w->d_rows;
+    a.m.w.nodes = w->d_nodes;
+    a.m.tri48 = o->d_tri48; a.m.leaf_tri = o->d_leaftri; a.m.poses = (const float4*)d_poses;
+    a.m.L = L; a.m.T = T; a.m.skip = skip;
+    a.keys = (unsigned long long*)d_keys;
+    a.rmax = rmax;
+    if (mode == WMD_CLOSEST) return world_mesh_dist_launch(c, WMD_CLOSEST, 0, false, grid, a);
+    if (mode == WMD_WITHIN) {
+        // the skip of lanes whose pose is already flagged, under the mesh queries' rule and knob (world_mesh_query() above)
+        const char* knob = getenv("PSM_MESH_SKIP");
+        const bool strided = (p * (size_t)L + QUERY_BLOCK - 1) / QUERY_BLOCK > QUERY_GRID_CAP;
+        a.m.flags = (knob ? knob[0] != '0' : strided) ? WORLD_MESH_FLAG_SKIP : 0u;
+        return world_mesh_dist_launch(c, WMD_WITHIN, 0, false, grid, a);
+    }
+    // every word: "none"; the clearance kernel (PSM_MESH_BOUND = 0 .. 3: the study knob of mesh_dist.hip, the same answer under
+    // each); then one lane per pose walks the winner again and writes the record (a word left at "none": the miss)
+    PSM_HIP(c, hipMemsetAsync(d_keys, 0xff, p * sizeof(uint64_t), c->stream));
+    const char* knob = getenv("PSM_MESH_BOUND");
+    rc = world_mesh_dist_launch(c, WMD_CLEAR, knob ? knob[0] : '1', false, grid, a);
+    if (rc != PSM_OK) return rc;
+    WorldMeshDistArgs pick = a;
+    rc = batch_args(c, nullptr, p, d_out, 0, pick.m.w, grid);
+    if (rc != PSM_OK) return rc;
+    return world_mesh_dist_launch(c, WMD_PICK, 0, true, grid, pick);
+}
+
 template <class T>
 int world_alloc(psm_ctx* c, T** p, size_t n) {
     PSM_HIP(c, hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
@@ -1166,4 +1274,15 @@ int psm_world_mesh_count_dev(psm_world* w, psm_bvh* other, const float* poses, s
 int psm_world_mesh_triangles_dev(psm_world* w, psm_bvh* other, const float* poses, size_t p, int32_t skip, uint32_t k, int32_t* d_tri,
                                  int32_t* d_inst, uint32_t* d_count) {
     return psm::world_mesh_query(w, other, poses, p, skip, 2, k, d_tri, d_inst, d_count);
+}
+int psm_world_mesh_closest_dev(psm_world* w, psm_bvh* other, const float* poses, size_t p, int32_t skip, float rmax, psm_tri_hit* d_hits,
+                               int32_t* d_inst) {
+    return psm::world_mesh_dist_query(w, other, poses, p, skip, psm::WMD_CLOSEST, rmax, d_hits, d_inst);
+}
+int psm_world_mesh_within_dev(psm_world* w, psm_bvh* other, const float* poses, size_t p, int32_t skip, float r, uint8_t* d_flag) {
+    return psm::world_mesh_dist_query(w, other, poses, p, skip, psm::WMD_WITHIN, r, d_flag, nullptr);
+}
+int psm_world_mesh_clearance_dev(psm_world* w, psm_bvh* other, const float* poses, size_t p, int32_t skip, float rmax, psm_mesh_hit* d_hits,
+                                 int32_t* d_inst) {
+    return psm::world_mesh_dist_query(w, other, poses, p, skip, psm::WMD_CLEAR, rmax, d_hits, d_inst);
 }

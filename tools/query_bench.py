@@ -98,6 +98,14 @@ REPS, the whole call): meshClearance with the shared bound off and on (PSM_MESH_
 (2: the word read in begin() alone and published at finish() alone; 3: re-read before every leaf, published at finish() alone),
 meshClearance against meshClosest plus a torch min over the device buffer (what a caller had), meshWithin at 1 % of the diagonal
 against meshOverlaps (context: it answers less) and with its skip forced on and off (PSM_MESH_SKIP = 1 / 0). No ratio is fixed in advance.
+`query_bench.py world-mesh-clearance`: mesh clearance over an instance world (psm_world_mesh_clearance_dev) on the world-clearance
+mode's worlds -- 1, 64 and 1 024 turned grid poses (WMCLEAR_INSTANCES) of the Sponza-class scene and of the torus (WMCLEAR_SCENES) --,
+the other mesh the 2 304-triangle torus at a quarter of a body's extent, at 1 and 1 024 poses (WMCLEAR_POSES) anywhere in the
+world's box, at rmax = +inf and at 1 % of a body's diagonal. clearanceToMesh (the whole numpy call) alternated A B A B (host-timed
+medians of REPS; one timed call where a side's warm-up call takes more than WMCLEAR_SLOW seconds) with (1) what a caller could do
+before: the torus posed on the host, closestToTriangle over the p x T triangles, the minimum per pose on the host, and with (2)
+the same call under PSM_MESH_BOUND=0. Both ratios and whether the two paths agree in (dist, tri, other, instance) at every pose.
+Each case's figures are also appended to WMCLEAR_LOG as they come. No ratio is fixed in advance.
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -1577,6 +1585,113 @@ def worldclearance():
     print(json.dumps(out))
 
 
+def worldmeshclearance():
+    out = {"mode": "world-mesh-clearance", "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+    counts = [int(x) for x in os.environ.get("WMCLEAR_INSTANCES", "1,64,1024").split(",")]
+    pose_counts = [int(x) for x in os.environ.get("WMCLEAR_POSES", "1,1024").split(",")]
+    slow = float(os.environ.get("WMCLEAR_SLOW", "1.5"))
+    log = os.environ.get("WMCLEAR_LOG")
+    tor = torus(48, 24, 0.7, 0.25).reshape(-1, 3, 3)
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        r = fn()
+        return (time.perf_counter() - t0) * 1e3, r
+
+    def abab_n(fa, fb):
+        """medians (ms) of the two whole calls, alternated A B A B after a warm-up call of each -- the warm-up call alone where it
+        took more than `slow` seconds on either side -- their last results and the timed calls per side"""
+        (wa, ra), (wb, rb) = timed(fa), timed(fb)
+        if max(wa, wb) > slow * 1e3:
+            return round(wa, 3), round(wb, 3), ra, rb, 1
+        ta, tb = [], []
+        for _ in range(REPS):
+            a, ra = timed(fa)
+            b, rb = timed(fb)
+            ta.append(a)
+            tb.append(b)
+        return round(float(np.median(ta)), 3), round(float(np.median(tb)), 3), ra, rb, REPS
+
+    for scene_name in os.environ.get("WMCLEAR_SCENES", "torus,sponza").split(","):
+        tris = (scenes.sponza_like()["tris"] if scene_name == "sponza" else tor).reshape(-1, 3, 3).astype(np.float32)
+        ctx = psm.Context(0)
+
+        def hier(t):
+            th = psm.TriangleHierarchy(ctx)
+            th.allocate(t.shape[0])
+            th.loadTriangles(np.ascontiguousarray(t.reshape(-1, 9), np.float32))
+            th.build()
+            return th
+        th = hier(tris)
+        out[scene_name + "_tris"] = int(th.info().leaf_count)
+        v = tris.reshape(-1, 3).astype(np.float64)
+        centre, radius = 0.5 * (v.min(0) + v.max(0)), 0.5 * float(np.linalg.norm(v.max(0) - v.min(0)))
+        otris = (tor.astype(np.float64) * (0.25 * 2.0 * radius / 1.9)).astype(np.float32)
+        other = hier(otris)
+        t = otris.shape[0]
+        rng = np.random.RandomState(29)
+        for insts_n in counts:
+            side = int(np.ceil(np.sqrt(insts_n)))       # world-clearance's grid: a body's diameter apart, each turned about a random axis
+            ip = np.zeros((insts_n, 3, 4))
+            for j in range(insts_n):
+                q_, r_ = np.linalg.qr(rng.normal(size=(3, 3)))
+                rot = q_ * np.sign(np.diag(r_))
+                ip[j, :, :3] = rot
+                ip[j, :, 3] = np.array([2.0 * radius * (j % side), 2.0 * radius * (j // side), 0.0]) - rot @ centre
+            wd = psm.InstanceWorld(ctx, [(th, m) for m in ip.astype(np.float32)])
+            lo = np.array([-radius, -radius, -radius])
+            hi = np.array([2.0 * radius * (side - 1) + radius, 2.0 * radius * ((insts_n - 1) // side) + radius, radius])
+            for p in pose_counts:
+                poses = np.zeros((p, 3, 4))
+                for j in range(p):
+                    q_, r_ = np.linalg.qr(rng.normal(size=(3, 3)))
+                    poses[j, :, :3] = q_ * np.sign(np.diag(r_))
+                    poses[j, :, 3] = rng.uniform(lo, hi)
+                poses = poses.astype(np.float32)
+                for rname, rmax in (("inf", np.inf), ("small", 0.01 * 2.0 * radius)):
+                    key = "%s_inst%d_p%d_rmax_%s_" % (scene_name, insts_n, p, rname)
+                    print("world-mesh-clearance: " + key[:-1], file=sys.stderr, flush=True)
+
+                    def clearance(bound=None):
+                        def run():
+                            if bound is not None:
+                                os.environ["PSM_MESH_BOUND"] = bound
+                            try:
+                                return wd.clearanceToMesh(other, poses, rmax)
+                            finally:
+                                if bound is not None:
+                                    del os.environ["PSM_MESH_BOUND"]
+                        return run
+
+                    def before():
+                        """the parent's path: pose on the host, closestToTriangle over p x T triangles, the minimum on the host"""
+                        got = wd.closestToTriangle(posed(otris, poses).reshape(-1, 3, 3), rmax)
+                        dist = got.dist.reshape(p, t)
+                        best = np.argmin(dist, axis=1)          # (the first of equal minima: the lowest t)
+                        r = np.arange(p)
+                        return dist[r, best], got.tri.reshape(p, t)[r, best], np.where(np.isfinite(dist[r, best]), best, -1), got.geom.reshape(p, t)[r, best]
+                    row = {}
+                    a, b, got, (dist, tri, best, inst), n1 = abab_n(clearance(), before)
+                    row["clearance_ms"], row["before_ms"], row["before_over_clearance"], row["timed_calls"] = a, b, round(b / a, 2), n1
+                    a, b, _, off, n2 = abab_n(clearance(), clearance("0"))
+                    row["clearance_again_ms"], row["bound_off_ms"], row["bound_off_over_clearance"], row["timed_calls_bound"] = a, b, round(b / a, 2), n2
+                    row["agree"] = bool(np.array_equal(got.dist, dist) and np.array_equal(got.tri, tri) and np.array_equal(got.other, best)
+                                        and np.array_equal(got.geom, inst) and np.array_equal(off.buffer.view(np.uint32), got.buffer.view(np.uint32))
+                                        and np.array_equal(off.geom, got.geom))
+                    row["found_fraction"] = round(float((got.tri >= 0).mean()), 4)
+                    row["at_distance_0_fraction"] = round(float((got.dist == 0).mean()), 4)
+                    for k_, x in row.items():
+                        out[key + k_] = x
+                    if log:
+                        with open(log, "a") as fh:
+                            fh.write(json.dumps({key[:-1]: row}) + "\n")
+            wd.close()
+        other.close()
+        th.close()
+        ctx.close()
+    print(json.dumps(out))
+
+
 def worldmeshes():
     lib = psm.lib()
     ctx = psm.Context(0)
@@ -1819,4 +1934,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "world-clearance": worldclearance, "worldmeshes": worldmeshes}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "world-clearance": worldclearance, "world-mesh-clearance": worldmeshclearance, "worldmeshes": worldmeshes}.get(" ".join(sys.argv[1:]), main)()
