@@ -68,6 +68,15 @@ namespace NSM {
         int boxOverlaps(const psm_box_query * d_boxes, size_t n, uint8_t * d_hit);
         int boxCount(const psm_box_query * d_boxes, size_t n, uint32_t * d_count);
         int boxTriangles(const psm_box_query * d_boxes, size_t n, uint32_t k, int32_t * d_tris, uint32_t * d_count);
+        // not in the reference: the voxels of a regular grid that a triangle overlaps, as one 64-bit word per 4 x 4 x 4 brick (bit
+        // (z & 3) * 16 + (y & 3) * 4 + (x & 3) of brick (bz * nby + by) * nbx + bx), the same with the inside of a closed mesh
+        // filled by the vote of `samples` (1, 3 or 5) rays from each voxel's centre, and the number of triangles per voxel, dense
+        // [nz][ny][nx]; each voxel answered as boxOverlaps / boxCount answer its box (psm_hip.h "voxel grids"; psm_grid_surface_dev
+        // / psm_grid_solid_dev / psm_grid_counts_dev). The result is read back into the vector (the call waits for it; a refused
+        // call leaves the vector empty); returns the psm_status
+        int voxelize(const psm_grid & grid, std::vector<uint64_t> & bricks);
+        int voxelizeSolid(const psm_grid & grid, uint32_t samples, std::vector<uint64_t> & bricks);
+        int voxelCounts(const psm_grid & grid, std::vector<uint32_t> & counts);
         // not in the reference: whether / how many / which triangles meet each of n query triangles (closed: touching counts; a
         // separating-axis test in float32, psm_hip.h "triangle queries"); triTriangles: 1 <= k <= PSM_QUERY_K_MAX, d_ids [n][k] =
         // the lowest ids that count, ascending, then -1, d_count [n] = the slots that hold one (psm_bvh_tri_overlaps_dev /

@@ -87,6 +87,37 @@ namespace NSM {
         check(rc, "TriangleHierarchy::boxCount");
         return rc;
     }
+    // one grid call into a device buffer of `count` words of T, read back into `out` (emptied first; left empty on a refusal)
+    template<class T, class Call>
+    inline int gridReadBack(size_t count, std::vector<T> & out, const char * what, Call call) {
+        out.clear();
+        if (count == 0) { check(PSM_ERR_INVALID, what); return PSM_ERR_INVALID; }   // (an invalid grid: no bricks)
+        GLuint h = allocateBuffer<T>(count);
+        void * d_out = nullptr;
+        size_t bytes = 0;
+        int rc = psm_buf_ptr(context(), h, &d_out, &bytes);
+        if (rc == PSM_OK) rc = call((T *)d_out);
+        check(rc, what);
+        if (rc == PSM_OK) {
+            out.resize(count);
+            getBufferSubData(h, 0, strided<T>(count), out.data());
+        }
+        deleteBuffer(h);
+        return rc;
+    }
+    inline int TriangleHierarchy::voxelize(const psm_grid & grid, std::vector<uint64_t> & bricks) {
+        return gridReadBack<uint64_t>((size_t)psm_grid_brick_count(&grid), bricks, "TriangleHierarchy::voxelize",
+                                      [&](uint64_t * d) { return psm_grid_surface_dev(bvh, &grid, d); });
+    }
+    inline int TriangleHierarchy::voxelizeSolid(const psm_grid & grid, uint32_t samples, std::vector<uint64_t> & bricks) {
+        return gridReadBack<uint64_t>((size_t)psm_grid_brick_count(&grid), bricks, "TriangleHierarchy::voxelizeSolid",
+                                      [&](uint64_t * d) { return psm_grid_solid_dev(bvh, &grid, samples, d); });
+    }
+    inline int TriangleHierarchy::voxelCounts(const psm_grid & grid, std::vector<uint32_t> & counts) {
+        const size_t cells = psm_grid_brick_count(&grid) ? (size_t)grid.dims[0] * grid.dims[1] * grid.dims[2] : 0;
+        return gridReadBack<uint32_t>(cells, counts, "TriangleHierarchy::voxelCounts",
+                                      [&](uint32_t * d) { return psm_grid_counts_dev(bvh, &grid, d); });
+    }
     inline int TriangleHierarchy::boxTriangles(const psm_box_query * d_boxes, size_t n, uint32_t k, int32_t * d_tris, uint32_t * d_count) {
         const int rc = psm_bvh_box_triangles_dev(bvh, d_boxes, n, k, d_tris, d_count);
         check(rc, "TriangleHierarchy::boxTriangles");

@@ -1166,6 +1166,50 @@ int psm_world_mesh_within_dev(psm_world* world, psm_bvh* other, const float* pos
 int psm_world_mesh_clearance_dev(psm_world* world, psm_bvh* other, const float* poses, size_t p, int32_t skip, float rmax,
                                  psm_mesh_hit* d_hits /*[p]*/, int32_t* d_inst /*[p]*/);
 
+/* voxel grids over a built hierarchy (new; no reference counterpart): which voxels of a regular axis-aligned
+ * grid a triangle overlaps (surface), how many triangles overlap each voxel (counts), and the surface with its inside filled
+ * (solid) -- one call per grid, no box records: the grid is nine numbers. The answers are DEFINED by the box and inside
+ * queries above, voxel by voxel and bit for bit; grid.hip gets them with one wave per 4 x 4 x 4 brick of voxels instead of one
+ * lane per box. Semantics:
+ *   - voxel (ix, iy, iz), 0 <= i_k < dims[k], is the closed box with, per axis k, lo_k = origin_k + (float)i_k * cell_k and
+ *     hi_k = origin_k + (float)(i_k + 1) * cell_k: one float32 multiplication, then one float32 addition, nothing fused. The hi
+ *     of voxel i is therefore the lo of voxel i + 1 bit for bit, and a triangle lying in that plane counts in both (the box
+ *     test is closed). Its centre is c_k = origin_k + ((float)i_k + 0.5f) * cell_k
+ *   - a grid is valid iff origin is finite, cell is finite and > 0, every dims[k] is in 1 .. PSM_GRID_DIM_MAX, the last voxel's
+ *     hi, origin_k + (float)dims[k] * cell_k, is finite on every axis, and the brick count is below 2^31
+ *   - bricks: nb_k = ceil(dims[k] / 4); brick (bx, by, bz) has index (bz * nb_y + by) * nb_x + bx and is one 64-bit word; bit
+ *     j = (z & 3) * 16 + (y & 3) * 4 + (x & 3) of it is voxel (x, y, z) = (4 bx + (x & 3), 4 by + (y & 3), 4 bz + (z & 3)).
+ *     Bits of voxels outside dims are 0. d_bricks holds psm_grid_brick_count(grid) = nb_x nb_y nb_z words
+ *   - surface: a voxel's bit is 1 iff psm_bvh_box_overlaps_dev answers 1 for the voxel's box
+ *   - counts: d_counts[(iz * ny + iy) * nx + ix] = what psm_bvh_box_count_dev answers for the voxel's box; dense, nx ny nz
+ *     entries, no padding voxels
+ *   - solid: a voxel's bit is its surface bit | what psm_bvh_inside_dev(centre, samples) answers, samples 1, 3 or 5 as there:
+ *     for a closed mesh the filled model, for an open one merely deterministic, as inside is
+ *   - nothing depends on the order of the walk or on timing: a flag, a sum
+ *   - refusals, all on the host before any launch and with the output untouched: NULL bvh (PSM_ERR_INVALID, no message: there
+ *     is no context to hold one); NULL grid or output; an invalid grid; d_bricks not 8-byte, d_counts not 4-byte aligned;
+ *     samples not 1, 3 or 5 (PSM_ERR_INVALID); before the first build (PSM_ERR_STATE, "grid query before build"); a hierarchy
+ *     deeper than the query stack (PSM_ERR_CAPACITY)
+ *   - the grid is host memory, read during the call: its numbers travel as kernel arguments. The calls are stream-ordered on
+ *     the hierarchy's context. surface and counts allocate nothing and can be captured into a graph. solid allocates a
+ *     context-owned scratch at its first use and grows it for a larger grid (the centres and flags of at most 65 536 bricks: 68
+ *     MiB, freed with the context), and its inside launches use the context's stack area, which the context's first query
+ *     allocates: capture it only after a plain call with a grid at least as large
+ *   - 0 leaves: all zero; 1 leaf: that leaf is tested; after psm_bvh_refit the refitted boxes are used
+ *   - not covered: grids over a world, a flat scene or an instanced list; a signed-distance grid; a sparse output (a list of
+ *     the non-empty bricks); a coarse level that culls empty regions before the brick walk; conservative or 6-separating thin
+ *     voxelisation; oriented grids */
+#define PSM_GRID_DIM_MAX (1u << 20)
+typedef struct {
+    float origin[3];   /* corner of voxel (0, 0, 0) */
+    float cell[3];     /* voxel size per axis, > 0 */
+    uint32_t dims[3];  /* nx, ny, nz, each >= 1 */
+} psm_grid;            /* host memory, read during the call */
+int psm_grid_surface_dev(psm_bvh* bvh, const psm_grid* grid, uint64_t* d_bricks);
+int psm_grid_counts_dev(psm_bvh* bvh, const psm_grid* grid, uint32_t* d_counts);
+int psm_grid_solid_dev(psm_bvh* bvh, const psm_grid* grid, uint32_t samples, uint64_t* d_bricks);
+uint64_t psm_grid_brick_count(const psm_grid* grid);   /* 0 for an invalid grid (NULL too); host only */
+
 /* ---------------------------------------------------------------------------------------------
  * several frames in flight (new; DESIGN.md "lanes")
  * `frames` x GltfViewer::process() (Viewer.cpp:296-312) with up to `lanes` of them in flight: lane s =

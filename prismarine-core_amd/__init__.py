@@ -47,6 +47,7 @@ EXPORTS = [
     "psm_world_tri_closest_dev", "psm_world_tri_within_dev",
     "psm_world_mesh_overlaps_dev", "psm_world_mesh_count_dev", "psm_world_mesh_triangles_dev",
     "psm_world_mesh_closest_dev", "psm_world_mesh_within_dev", "psm_world_mesh_clearance_dev",
+    "psm_grid_surface_dev", "psm_grid_counts_dev", "psm_grid_solid_dev", "psm_grid_brick_count",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -95,6 +96,11 @@ class PsmError(RuntimeError):
 class BvhInfo(C.Structure):
     _fields_ = [("triangle_count", C.c_uint32), ("leaf_count", C.c_uint32), ("root", C.c_int32),
                 ("transform", C.c_float * 16), ("bounds_min", C.c_float * 4), ("bounds_max", C.c_float * 4)]
+
+
+class Grid(C.Structure):
+    """psm_grid: origin, cell and dims of a voxel grid (host memory, read during the call)"""
+    _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float * 3), ("dims", C.c_uint32 * 3)]
 
 
 class Instance(C.Structure):
@@ -146,6 +152,7 @@ def lib():
         _lib.psm_ctx_stream.restype = C.c_void_p
         _lib.psm_world_create.restype = C.c_void_p
         _lib.psm_world_count.restype = C.c_uint32
+        _lib.psm_grid_brick_count.restype = C.c_uint64
         for name in EXPORTS:
             getattr(_lib, name)  # AttributeError if an export is missing
     return _lib
@@ -476,6 +483,53 @@ class TriangleHierarchy:
         boxes = np.zeros((a.shape[0], 8), np.float32)
         boxes[:, 0:3], boxes[:, 4:7] = a, b
         return self._launch_np(boxes, out, name, *extra)
+
+    def voxelize(self, origin, cell, dims, solid=False, samples=3, as_torch=False):
+        """The voxels of a regular grid that a triangle overlaps (psm_grid_surface_dev; not in the reference), or with solid=True
+        those and the voxels whose centre inside() takes as inside with `samples` (1, 3 or 5) rays (psm_grid_solid_dev): the filled
+        model of a closed mesh. origin: the corner of voxel (0, 0, 0); cell: the voxel size, a scalar or one per axis; dims: (nx,
+        ny, nz). Voxel (ix, iy, iz) is the closed box voxel_boxes() states, and its bit is bit for bit what boxOverlaps() answers
+        for that box: one call, no box records, 8 bytes of answer per 64 voxels. Returns VoxelGrid: bricks [nbz, nby, nbx] of 4 x 4
+        x 4 voxels, a uint64 word each (with as_torch=True an int64 tensor of the same bits on the context's device, the launch
+        ordered against torch's current stream by events, no host synchronisation); dense() and occupied() read them. An invalid
+        grid raises ValueError before any call. QueryScene, InstancedScene and InstanceWorld have no grids."""
+        g = _grid(origin, cell, dims)
+        if solid:
+            name, extra = "psm_grid_solid_dev", (C.c_uint32(_samples(samples, "psm_grid_solid_dev")),)
+        else:
+            name, extra = "psm_grid_surface_dev", ()
+        nb = tuple((int(d) + 3) // 4 for d in g.dims)
+        bricks = self._grid_call(g, name, extra, (nb[2], nb[1], nb[0]), np.uint64, as_torch)
+        return VoxelGrid(bricks, tuple(g.dims), tuple(g.origin), tuple(g.cell))
+
+    def voxelCounts(self, origin, cell, dims, as_torch=False):
+        """How many triangles overlap each voxel of a regular grid (psm_grid_counts_dev; not in the reference): uint32 [nz, ny, nx]
+        (an int32 tensor with as_torch=True, as boxCount()'s), each entry what boxCount() answers for the voxel's box. Arguments
+        and placement as voxelize()."""
+        g = _grid(origin, cell, dims)
+        return self._grid_call(g, "psm_grid_counts_dev", (), (g.dims[2], g.dims[1], g.dims[0]), np.uint32, as_torch)
+
+    def _grid_call(self, g, name, extra, shape, dtype, as_torch):
+        """one grid call: the output [shape] of uint64 words or uint32 counts, on the device for torch, else staged and read back"""
+        fn = getattr(lib(), name)
+        cells = int(np.prod(shape, dtype=np.int64))
+
+        def call(d_out):
+            self.ctx.check(fn(self._h, C.byref(g), *extra, C.c_void_p(d_out)), name)
+
+        if as_torch:
+            import torch
+            dev = torch.device("cuda", self.ctx.device)
+            res = torch.empty(shape, dtype=torch.int64 if dtype == np.uint64 else torch.int32, device=dev)
+            _torch_ordered(self.ctx, dev, lambda: call(res.data_ptr()))
+            return res
+        ctx = self.ctx
+        ho = ctx.buf_alloc(max(cells * np.dtype(dtype).itemsize, 16))
+        try:
+            call(ctx.buf_ptr(ho)[0])
+            return ctx.buf_download(ho, dtype, cells).reshape(shape)
+        finally:
+            ctx.buf_free(ho)
 
     def triOverlaps(self, tris):
         """Whether some triangle of the hierarchy meets each query triangle (psm_bvh_tri_overlaps_dev; not in the reference): tris
@@ -822,6 +876,93 @@ def _k(k, name):
     if v != k or not 0 <= v < 1 << 32:
         raise ValueError("%s: k must be 1 .. %d" % (name, QUERY_K_MAX))
     return v
+
+
+GRID_DIM_MAX = 1 << 20   # psm_hip.h PSM_GRID_DIM_MAX
+
+
+def _grid(origin, cell, dims):
+    """a psm_grid from origin [3], cell (a scalar or [3]) and dims [3], refused here by the rules of psm_hip.h "voxel grids" (no
+    call is made for an invalid grid: ValueError)"""
+    o = np.asarray(origin, np.float64).reshape(-1)
+    c = np.asarray(cell, np.float64).reshape(-1)
+    d = np.asarray(dims).reshape(-1)
+    if c.size == 1:
+        c = np.repeat(c, 3)
+    if o.size != 3 or c.size != 3 or d.size != 3:
+        raise ValueError("voxel grid: origin and dims take 3 numbers, cell 1 or 3")
+    with np.errstate(over="ignore"):
+        o, c = o.astype(np.float32), c.astype(np.float32)
+    if not np.isfinite(o).all():
+        raise ValueError("voxel grid: origin is not finite")
+    if not (np.isfinite(c) & (c > 0)).all():
+        raise ValueError("voxel grid: cell must be finite and > 0")
+    if any(int(x) != x or not 1 <= int(x) <= GRID_DIM_MAX for x in d.tolist()):
+        raise ValueError("voxel grid: dims must be whole numbers in 1 .. 2^20")
+    d = d.astype(np.int64)
+    with np.errstate(over="ignore"):
+        top = o + d.astype(np.float32) * c   # (the last voxel's hi: one float32 product, then one float32 sum)
+    if not np.isfinite(top).all():
+        raise ValueError("voxel grid: the last voxel's hi is not finite")
+    nb = (d + 3) // 4
+    if int(nb[0]) * int(nb[1]) * int(nb[2]) >= 1 << 31:
+        raise ValueError("voxel grid: 2^31 bricks or more")
+    g = Grid()
+    g.origin[:], g.cell[:], g.dims[:] = o.tolist(), c.tolist(), [int(x) for x in d]
+    return g
+
+
+def voxel_boxes(origin, cell, dims):
+    """The boxes of a grid's voxels, (lo, hi) float32 [nz * ny * nx, 3] with voxel (ix, iy, iz) in row (iz * ny + iy) * nx + ix:
+    per axis k, lo_k = origin_k + float32(i_k) * cell_k and hi_k = origin_k + float32(i_k + 1) * cell_k, each one float32
+    product and then one float32 sum (psm_hip.h "voxel grids"). hi of voxel i is lo of voxel i + 1 bit for bit. This is the
+    public statement of the voxel box: voxelize() and voxelCounts() answer boxOverlaps() and boxCount() of these boxes."""
+    g = _grid(origin, cell, dims)
+    o, c = np.array(g.origin, np.float32), np.array(g.cell, np.float32)
+    planes = [(o[k] + np.arange(g.dims[k] + 1, dtype=np.float32) * c[k]).astype(np.float32) for k in range(3)]
+    iz, iy, ix = np.meshgrid(np.arange(g.dims[2]), np.arange(g.dims[1]), np.arange(g.dims[0]), indexing="ij")
+    ix, iy, iz = ix.reshape(-1), iy.reshape(-1), iz.reshape(-1)
+    lo = np.stack([planes[0][ix], planes[1][iy], planes[2][iz]], axis=1)
+    hi = np.stack([planes[0][ix + 1], planes[1][iy + 1], planes[2][iz + 1]], axis=1)
+    return lo, hi
+
+
+def voxel_centres(origin, cell, dims):
+    """The centres of a grid's voxels, float32 [nz * ny * nx, 3] in voxel_boxes()'s order: c_k = origin_k + (float32(i_k) + 0.5) *
+    cell_k in float32: the points voxelize(solid=True) asks inside() about."""
+    g = _grid(origin, cell, dims)
+    o, c = np.array(g.origin, np.float32), np.array(g.cell, np.float32)
+    mids = [(o[k] + (np.arange(g.dims[k], dtype=np.float32) + np.float32(0.5)) * c[k]).astype(np.float32) for k in range(3)]
+    iz, iy, ix = np.meshgrid(np.arange(g.dims[2]), np.arange(g.dims[1]), np.arange(g.dims[0]), indexing="ij")
+    return np.stack([mids[0][ix.reshape(-1)], mids[1][iy.reshape(-1)], mids[2][iz.reshape(-1)]], axis=1)
+
+
+class VoxelGrid:
+    """What TriangleHierarchy.voxelize returns. bricks: [nbz, nby, nbx], nb = ceil(dims / 4), one 64-bit word per 4 x 4 x 4 brick
+    (a uint64 array; for torch an int64 tensor holding the same bits): bit (z & 3) * 16 + (y & 3) * 4 + (x & 3) of brick (x // 4,
+    y // 4, z // 4) is voxel (x, y, z), and the bits of voxels outside dims are 0. dims = (nx, ny, nz), origin and cell as given
+    (float32 values)."""
+
+    def __init__(self, bricks, dims, origin, cell):
+        self.bricks, self.dims, self.origin, self.cell = bricks, dims, origin, cell
+
+    def dense(self):
+        """bool [nz, ny, nx] (a numpy array, or a torch bool tensor on the bricks' device)"""
+        nx, ny, nz = self.dims
+        nbz, nby, nbx = self.bricks.shape
+        if isinstance(self.bricks, np.ndarray):
+            bits = (self.bricks[..., None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)
+            cube = bits.astype(np.bool_).reshape(nbz, nby, nbx, 4, 4, 4).transpose(0, 3, 1, 4, 2, 5)
+            return np.ascontiguousarray(cube.reshape(4 * nbz, 4 * nby, 4 * nbx)[:nz, :ny, :nx])
+        import torch
+        bits = (self.bricks[..., None] >> torch.arange(64, dtype=torch.int64, device=self.bricks.device)) & 1   # (bit 63: the sign's copies are masked off)
+        cube = bits.to(torch.bool).reshape(nbz, nby, nbx, 4, 4, 4).permute(0, 3, 1, 4, 2, 5)
+        return cube.reshape(4 * nbz, 4 * nby, 4 * nbx)[:nz, :ny, :nx].contiguous()
+
+    def occupied(self):
+        """the number of voxels set: the sum of the words' popcounts"""
+        words = self.bricks if isinstance(self.bricks, np.ndarray) else self.bricks.cpu().numpy().view(np.uint64)
+        return int(np.unpackbits(np.ascontiguousarray(words).view(np.uint8)).sum(dtype=np.int64))
 
 
 class QueryHitLists:

@@ -179,6 +179,7 @@ int psm_ctx_destroy(psm_ctx* c) {
     dev_free(c->d_counters);
     psm::query_release(c);   // query.hip: the ray queries' stack area
     psm::mesh_release(c);    // mesh.hip: the mesh queries' pose area
+    psm::grid_release(c);    // grid.hip: the solid grids' scratch
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return PSM_OK;

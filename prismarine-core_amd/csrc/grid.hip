@@ -1,0 +1,339 @@
+// grid.hip -- voxel grids over a built hierarchy (new; no reference counterpart; include/psm_hip.h "voxel grids", DESIGN.md
+// 4.27): which voxels of a regular grid a triangle overlaps (surface), how many triangles each voxel holds (counts), and the
+// surface with the inside filled (solid). Every voxel is answered bit for bit as box.hip answers the voxel's box.
+//
+// The walk is not query_walk's one query per lane: a 4 x 4 x 4 brick of voxels is one wave64, lane j = (z & 3) * 16 + (y & 3) * 4
+// + (x & 3), and the wave walks the tree ONCE for its 64 voxels. The node link is wave-uniform (readfirstlane: the record's two
+// 16-byte loads and a leaf's triangle are fetched once per wave, as scalars), each lane judges the two child boxes with its own
+// voxel's grown interval (BoxBody::keep's compares), and a child is entered iff some lane that still wants an answer keeps it
+// (__ballot). The wave has one stack of QSTACK_MAX links in LDS: no spill area. The boxes are never stored: a lane makes its
+// voxel's box from the grid's nine numbers, which travel as kernel arguments. A brick's surface answer leaves as one 64-bit
+// ballot word, written by one lane with an ordinary store.
+#include <cmath>
+#include <cstdio>
+#include <mutex>
+#include <unordered_map>
+
+#include "psm_common.h"
+#include "psm_internal.h"
+#include "psm_query_host.h"
+#include "psm_query_dev.h"
+#include "psm_box_dev.h"   // box_tri, box_row
+
+namespace psm {
+
+namespace {
+
+enum { GRID_SURFACE = 0, GRID_COUNTS = 1 };
+
+// (the walk's tree and its output are kernel parameters of their own, __restrict__: only then can the compiler tell that no
+// store of the kernel changes a record or a triangle, and fetch them with scalar loads)
+struct GridArgs {
+    const uint32_t* sm;           // transform, leaf count, root
+    const int32_t* sorted_tri;    // [0]: the lone leaf's triangle when the leaf count is 1
+    float ox, oy, oz, cx, cy, cz; // psm_grid: origin, cell
+    uint32_t nx, ny, nz;          // ... dims
+    uint32_t nbx, nby;            // bricks along x and y
+    uint32_t first, bricks;       // the bricks [first, first + bricks) are this launch's
+    uint64_t* words;              // solid's fill: a word per brick of the whole grid
+    float4* points;              // solid: the slab's centres, psm_point_query records in lane order
+    const uint8_t* flags;         // solid: the slab's inside flags
+};
+
+// the voxel of lane `lane` in brick b, and whether it lies inside dims
+struct Voxel {
+    uint32_t ix, iy, iz;
+    bool inside;
+};
+PSM_D Voxel voxel_of(const GridArgs& g, uint32_t b, int lane) {
+    const uint32_t bx = b % g.nbx, t = b / g.nbx, by = t % g.nby, bz = t / g.nby;
+    Voxel v;
+    v.ix = 4u * bx + ((uint32_t)lane & 3u);
+    v.iy = 4u * by + (((uint32_t)lane >> 2) & 3u);
+    v.iz = 4u * bz + ((uint32_t)lane >> 4);
+    v.inside = v.ix < g.nx && v.iy < g.ny && v.iz < g.nz;
+    return v;
+}
+
+// the grown image interval of a lane's voxel per normalised axis, and BoxBody::keep (box.hip) compare for compare: a child box
+// [mn, mx] is kept iff it meets the interval on all three axes (negations: a NaN keeps the box)
+struct Interval {
+    float glx, gly, glz, ghx, ghy, ghz;
+};
+PSM_D bool keep(const Interval& I, float mnx, float mny, float mnz, float mxx, float mxy, float mxz) {
+    bool out = mxx < I.glx;
+    out |= mnx > I.ghx;
+    out |= mxy < I.gly;
+    out |= mny > I.ghy;
+    out |= mxz < I.glz;
+    out |= mnz > I.ghz;
+    return !out;
+}
+
+// One wave per brick, grid-stride over the bricks. MODE: GRID_SURFACE -- a lane that has its bit stops voting, and the walk
+// ends when no lane wants anything --, GRID_COUNTS -- every live lane wants every leaf its interval keeps.
+// node32: the build's traversal records (bvh_emit); tri48: v0, e1, e2 per triangle; out: a uint64_t word per brick of the whole
+// grid (surface) or the dense uint32_t [nz][ny][nx] (counts)
+template <int MODE, class Out>
+PSM_D void grid_walk(const GridArgs& g, const uint4* __restrict__ node32, const float4* __restrict__ tri48, Out* __restrict__ out) {
+    __shared__ int stack[QSTACK_MAX];   // the wave's: every lane writes and reads the same entry
+    const int lane = (int)threadIdx.x;
+    __builtin_assume(lane >= 0 && lane < QUERY_BLOCK);
+    const int root = (int)g.sm[SM_ROOT];
+    const uint32_t count = g.sm[SM_COUNT];
+    const int lone = (count == 1u) ? g.sorted_tri[0] : -1;   // one leaf: no tree, the leaf's triangle is the only candidate
+    float M[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) M[k] = u2f(g.sm[SM_M + k]);
+    for (uint32_t b = blockIdx.x; b < g.bricks; b += gridDim.x) {
+        const Voxel v = voxel_of(g, g.first + b, lane);
+        v3 lo = mk3(0.f, 0.f, 0.f), hi = mk3(-1.f, -1.f, -1.f);   // a dead lane: lo > hi (BoxBody::begin)
+        if (v.inside) {
+            // one multiplication, then one addition (the build contracts nothing): neighbours share their face plane bit for bit
+            lo = mk3(g.ox + (float)v.ix * g.cx, g.oy + (float)v.iy * g.cy, g.oz + (float)v.iz * g.cz);
+            hi = mk3(g.ox + (float)(v.ix + 1u) * g.cx, g.oy + (float)(v.iy + 1u) * g.cy, g.oz + (float)(v.iz + 1u) * g.cz);
+        }
+        const bool valid = v.inside && finite3(lo) && finite3(hi) && lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z;
+        Interval I;   // exactly as BoxBody::begin
+        box_row(M, 0, lo, hi, I.glx, I.ghx);
+        box_row(M, 1, lo, hi, I.gly, I.ghy);
+        box_row(M, 2, lo, hi, I.glz, I.ghz);
+        uint32_t cnt = 0u;   // per brick: the grid-stride loop comes here again
+        bool wants = valid;
+        int t0 = lone, t1 = -1;   // the leaves to test, wave-uniform
+        int cur = root, sp = 0;
+        bool walking = root >= 0;
+        for (;;) {
+            // the accepted leaves, one test after the other: the triangle is loaded once for the wave
+            while (t0 >= 0) {
+                const float4* tp = tri48 + (size_t)3 * (size_t)__builtin_amdgcn_readfirstlane(t0);
+                const float4 A = tp[0], B = tp[1], C = tp[2];
+                if (wants && box_tri(mk3(A.x, A.y, A.z), mk3(B.x, B.y, B.z), mk3(C.x, C.y, C.z), lo, hi)) cnt++;
+                t0 = t1;
+                t1 = -1;
+            }
+            if (MODE == GRID_SURFACE) wants = valid && cnt == 0u;
+            if (!walking || __ballot(wants) == 0ull) break;
+            cur = __builtin_amdgcn_readfirstlane(cur);
+            const uint4* np = (const uint4*)((const char*)node32 + ((size_t)(uint32_t)cur << 5));
+            const uint4 n0 = np[0], n1 = np[1];
+            const int lkx = (int)n1.z, lky = (int)n1.w;
+            // each lane judges both children against its own interval (the record's fp16 corners as BoxBody::children reads them)
+            const bool keepL = keep(I, half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z));
+            const bool keepR = keep(I, half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y));
+            const bool okL = __ballot(keepL && wants) != 0ull, okR = __ballot(keepR && wants) != 0ull;
+            const bool leafL = okL && lkx < 0, leafR = okR && lky < 0;
+            t0 = leafL ? ~lkx : (leafR ? ~lky : -1);
+            t1 = (leafL && leafR) ? ~lky : -1;
+            const bool intL = okL && !leafL, intR = okR && !leafR;
+            if (intL && intR) {
+                // (sp < QSTACK_MAX always: one entry per internal ancestor of the current node, as a lane's own stack; the host
+                // refuses hierarchies whose bound exceeds it. The test keeps every store and every pop inside the array)
+                if (sp < QSTACK_MAX) {
+                    stack[sp] = lky;
+                    sp++;
+                }
+            }
+            cur = intL ? lkx : lky;
+            if (!(intL || intR)) {
+                if (sp == 0) walking = false;   // (the node's leaves are still tested)
+                else {
+                    sp--;
+                    cur = stack[sp];
+                }
+            }
+        }
+        if (MODE == GRID_SURFACE) {
+            const unsigned long long word = __ballot(cnt != 0u);
+            if (lane == 0) out[g.first + b] = (Out)word;
+        } else if (valid) {
+            out[((size_t)v.iz * g.ny + v.iy) * g.nx + v.ix] = (Out)cnt;
+        }
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void grid_surface(GridArgs g, const uint4* __restrict__ node32, const float4* __restrict__ tri48,
+                                                               uint64_t* __restrict__ words) {
+    grid_walk<GRID_SURFACE>(g, node32, tri48, words);
+}
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void grid_counts(GridArgs g, const uint4* __restrict__ node32, const float4* __restrict__ tri48,
+                                                              uint32_t* __restrict__ counts) {
+    grid_walk<GRID_COUNTS>(g, node32, tri48, counts);
+}
+
+// solid, before the inside launch: the centres of the slab's voxels as psm_point_query records in lane order (rmax is not read).
+// A voxel outside dims gets a centre too (its flag is dropped by grid_fill)
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void grid_centres(GridArgs g) {
+    const int lane = (int)threadIdx.x;
+    for (uint32_t b = blockIdx.x; b < g.bricks; b += gridDim.x) {
+        const Voxel v = voxel_of(g, g.first + b, lane);
+        g.points[(size_t)b * QUERY_BLOCK + lane] =
+            make_float4(g.ox + ((float)v.ix + 0.5f) * g.cx, g.oy + ((float)v.iy + 0.5f) * g.cy, g.oz + ((float)v.iz + 0.5f) * g.cz, 0.f);
+    }
+}
+
+// solid, after it: the ballot of the slab's flags ORed into the words the surface launch wrote
+__global__ __launch_bounds__(QUERY_BLOCK, 8) void grid_fill(GridArgs g) {
+    const int lane = (int)threadIdx.x;
+    for (uint32_t b = blockIdx.x; b < g.bricks; b += gridDim.x) {
+        const Voxel v = voxel_of(g, g.first + b, lane);
+        const unsigned long long word = __ballot(v.inside && g.flags[(size_t)b * QUERY_BLOCK + lane] != 0);
+        if (lane == 0) g.words[g.first + b] |= word;
+    }
+}
+
+namespace {
+
+// A grid as the host reads it: the brick counts, or why it is refused (psm_hip.h "voxel grids": the rules in their order)
+struct GridShape {
+    uint32_t nb[3];
+    uint64_t bricks;
+};
+const char* grid_fault(const psm_grid* g, GridShape& s) {
+    s = GridShape();
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(g->origin[k])) return "origin is not finite";
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(g->cell[k]) || !(g->cell[k] > 0.f)) return "cell must be finite and > 0";
+    for (int k = 0; k < 3; k++)
+        if (g->dims[k] < 1u || g->dims[k] > PSM_GRID_DIM_MAX) return "dims must be 1 .. 2^20";
+    for (int k = 0; k < 3; k++) {
+        const float top = (float)g->dims[k] * g->cell[k];   // (the last voxel's hi: one multiplication, one addition)
+        const float hi = g->origin[k] + top;
+        if (!std::isfinite(hi)) return "the last voxel's hi is not finite";
+    }
+    for (int k = 0; k < 3; k++) s.nb[k] = (g->dims[k] + 3u) / 4u;
+    s.bricks = (uint64_t)s.nb[0] * s.nb[1] * s.nb[2];   // (each <= 2^18: no overflow)
+    if (s.bricks >= ((uint64_t)1 << 31)) return "2^31 bricks or more";
+    return nullptr;
+}
+
+// solid's scratch, per context (grown on demand, at most SLAB_BRICKS bricks of points and flags: 68 MiB; every call runs on
+// the context's stream, never two at once)
+constexpr uint32_t SLAB_BRICKS = 1u << 16;
+constexpr size_t SLAB_BRICK_BYTES = (size_t)QUERY_BLOCK * (sizeof(float4) + sizeof(uint8_t));
+struct Scratch {
+    void* ptr = nullptr;
+    uint32_t bricks = 0;
+};
+std::mutex scratch_mu;
+std::unordered_map<const psm_ctx*, Scratch> scratch_area;
+
+int scratch_for(psm_ctx* c, uint32_t bricks, void** out) {
+    std::lock_guard<std::mutex> lk(scratch_mu);
+    Scratch& a = scratch_area[c];
+    if (a.bricks < bricks) {
+        // (a kernel that reads the old area is in stream order before the free)
+        if (a.ptr) PSM_HIP(c, hipStreamSynchronize(c->stream));
+        if (a.ptr) PSM_HIP(c, hipFree(a.ptr));
+        a = Scratch();
+        uint32_t want = 64;
+        while (want < bricks) want *= 2;
+        PSM_HIP(c, hipMalloc(&a.ptr, (size_t)want * SLAB_BRICK_BYTES));
+        a.bricks = want;
+    }
+    *out = a.ptr;
+    return PSM_OK;
+}
+
+const char* const GRID_NAME[] = {"psm_grid_surface_dev", "psm_grid_counts_dev", "psm_grid_solid_dev"};
+enum { CALL_SURFACE = 0, CALL_COUNTS = 1, CALL_SOLID = 2 };
+
+uint32_t grid_for(uint64_t bricks) { return (uint32_t)(bricks < QUERY_GRID_CAP ? bricks : QUERY_GRID_CAP); }
+
+// A grid call: a NULL hierarchy is answered before anything else; then the pointers, the grid, the alignment, samples, the
+// state, the depth -- all on the host, before any launch, the output untouched.
+int grid_query(psm_bvh* b, const psm_grid* grid, int call, uint32_t samples, void* d_out) {
+    if (!b) return PSM_ERR_INVALID;
+    psm_ctx* c = b->ctx;
+    const char* name = GRID_NAME[call];
+    char msg[160];
+    if (!grid || !d_out) {
+        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    GridShape s;
+    if (const char* why = grid_fault(grid, s)) {
+        snprintf(msg, sizeof msg, "%s: invalid grid: %s", name, why);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    const unsigned align = call == CALL_COUNTS ? 4u : 8u;
+    if (((uintptr_t)d_out & (uintptr_t)(align - 1u)) != 0) {
+        snprintf(msg, sizeof msg, "%s: %s not %u-byte aligned", name, call == CALL_COUNTS ? "counts" : "bricks", align);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (call == CALL_SOLID && samples != 1 && samples != 3 && samples != 5) {
+        snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (!b->built) return set_err(c, PSM_ERR_STATE, "grid query before build");
+    if (depth_bound(b) > QSTACK_MAX) return set_err(c, PSM_ERR_CAPACITY, "grid query: hierarchy deeper than the query stack");
+    (void)hipSetDevice(c->device);
+    GridArgs g = {};
+    g.sm = b->d_small; g.sorted_tri = b->d_sorted_tri;
+    g.ox = grid->origin[0]; g.oy = grid->origin[1]; g.oz = grid->origin[2];
+    g.cx = grid->cell[0]; g.cy = grid->cell[1]; g.cz = grid->cell[2];
+    g.nx = grid->dims[0]; g.ny = grid->dims[1]; g.nz = grid->dims[2];
+    g.nbx = s.nb[0]; g.nby = s.nb[1];
+    g.first = 0u; g.bricks = (uint32_t)s.bricks;
+    g.words = (uint64_t*)d_out;
+    void* scratch = nullptr;
+    const uint32_t slab = s.bricks < SLAB_BRICKS ? (uint32_t)s.bricks : SLAB_BRICKS;
+    if (call == CALL_SOLID) {   // (the last thing that can fail before the output changes)
+        const int rc = scratch_for(c, slab, &scratch);
+        if (rc != PSM_OK) return rc;
+    }
+    if (call == CALL_COUNTS) grid_counts<<<grid_for(s.bricks), QUERY_BLOCK, 0, c->stream>>>(g, b->d_node32, b->d_tri48, (uint32_t*)d_out);
+    else grid_surface<<<grid_for(s.bricks), QUERY_BLOCK, 0, c->stream>>>(g, b->d_node32, b->d_tri48, (uint64_t*)d_out);
+    PSM_HIP(c, hipGetLastError());
+    if (call != CALL_SOLID) return PSM_OK;
+    // the inside of the surface, a slab of bricks at a time, all in stream order: the centres, query.hip's inside path over
+    // them, the flags' ballots ORed into the words
+    g.points = (float4*)scratch;
+    g.flags = (const uint8_t*)scratch + (size_t)slab * QUERY_BLOCK * sizeof(float4);
+    for (uint64_t first = 0; first < s.bricks; first += slab) {
+        const uint64_t left = s.bricks - first;
+        g.first = (uint32_t)first;
+        g.bricks = left < slab ? (uint32_t)left : slab;
+        grid_centres<<<grid_for(g.bricks), QUERY_BLOCK, 0, c->stream>>>(g);
+        PSM_HIP(c, hipGetLastError());
+        const int rc = psm_bvh_inside_dev(b, (const psm_point_query*)g.points, (size_t)g.bricks * QUERY_BLOCK, samples, (uint8_t*)g.flags);
+        if (rc != PSM_OK) return rc;
+        grid_fill<<<grid_for(g.bricks), QUERY_BLOCK, 0, c->stream>>>(g);
+        PSM_HIP(c, hipGetLastError());
+    }
+    return PSM_OK;
+}
+
+}  // namespace
+
+// for psm_ctx_destroy: solid's scratch goes with the context
+void grid_release(psm_ctx* c) {
+    std::lock_guard<std::mutex> lk(scratch_mu);
+    auto it = scratch_area.find(c);
+    if (it == scratch_area.end()) return;
+    if (it->second.ptr) (void)hipFree(it->second.ptr);
+    scratch_area.erase(it);
+}
+
+}  // namespace psm
+
+int psm_grid_surface_dev(psm_bvh* bvh, const psm_grid* grid, uint64_t* d_bricks) {
+    return psm::grid_query(bvh, grid, psm::CALL_SURFACE, 0, d_bricks);
+}
+
+int psm_grid_counts_dev(psm_bvh* bvh, const psm_grid* grid, uint32_t* d_counts) {
+    return psm::grid_query(bvh, grid, psm::CALL_COUNTS, 0, d_counts);
+}
+
+int psm_grid_solid_dev(psm_bvh* bvh, const psm_grid* grid, uint32_t samples, uint64_t* d_bricks) {
+    return psm::grid_query(bvh, grid, psm::CALL_SOLID, samples, d_bricks);
+}
+
+uint64_t psm_grid_brick_count(const psm_grid* grid) {
+    psm::GridShape s;
+    if (!grid || psm::grid_fault(grid, s)) return 0;
+    return s.bricks;
+}

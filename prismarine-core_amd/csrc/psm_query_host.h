@@ -9,6 +9,7 @@ namespace psm {
 
 void query_release(psm_ctx* c);               // query.hip, for psm_ctx_destroy: the context's stack area goes with it
 void mesh_release(psm_ctx* c);                // mesh.hip, for psm_ctx_destroy: the device copy of the mesh queries' poses goes with it
+void grid_release(psm_ctx* c);                // grid.hip, for psm_ctx_destroy: the solid grids' scratch goes with it
 // mesh.hip: the device copy of a call's poses, per context (grown on demand; every call runs on the context's stream)
 int poses_for(psm_ctx* c, size_t bytes, void** out);
 // mesh.hip: beside them, the 64-bit words the poses of a mesh clearance call share (mesh_dist.hip), grown and released alike

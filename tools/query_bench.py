@@ -106,6 +106,11 @@ medians of REPS; one timed call where a side's warm-up call takes more than WMCL
 before: the torus posed on the host, closestToTriangle over the p x T triangles, the minimum per pose on the host, and with (2)
 the same call under PSM_MESH_BOUND=0. Both ratios and whether the two paths agree in (dist, tri, other, instance) at every pose.
 Each case's figures are also appended to WMCLEAR_LOG as they come. No ratio is fixed in advance.
+`query_bench.py grids`: the voxel grids (psm_grid_surface_dev / psm_grid_counts_dev / psm_grid_solid_dev) on the Sponza-class scene:
+64^3, 128^3 and 256^3 grids over its bounds (GRID_SIZES), per size the ms of surface, counts and solid (3 rays), the occupied voxels,
+and surface alternated A B A B (host-timed medians of REPS) with the way a caller had to the same bits -- boxOverlaps over
+voxel_boxes of the same grid: the kernel alone over resident records, the package's torch call over resident lo / hi, and the same
+from host arrays (the box upload included) --, with a check that the bits are the same. No ratio is fixed in advance.
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -1869,6 +1874,80 @@ def worldsweeps():
     print(json.dumps(out))
 
 
+def grids():
+    import torch   # (before the library loads its HIP runtime)
+    dev = torch.device("cuda", 0)
+    lib = psm.lib()
+    sc = scenes.sponza_like()
+    ctx = psm.Context(0, stream=torch.cuda.current_stream(dev).cuda_stream)   # torch's packing and the launches: one stream
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(sc["tris"].shape[0])
+    th.loadTriangles(sc["tris"], sc["normals"], sc["mats"])
+    th.build()
+    v = sc["tris"].reshape(-1, 3)
+    lo, hi = v.min(0).astype(np.float64), v.max(0).astype(np.float64)
+    out = {"mode": "grids", "reps": REPS, "lib": os.path.basename(psm.LIB_PATH), "tris": int(th.info().leaf_count)}
+    for g in (int(x) for x in os.environ.get("GRID_SIZES", "64,128,256").split(",")):
+        origin, cell, dims = lo, (hi - lo) / g, (g, g, g)
+        n = g ** 3
+        grid = psm._grid(origin, cell, dims)
+        words = torch.zeros(((g + 3) // 4,) * 3, dtype=torch.int64, device=dev)
+        counts = torch.zeros((g, g, g), dtype=torch.int32, device=dev)
+        p_words, p_counts = C.c_void_p(words.data_ptr()), C.c_void_p(counts.data_ptr())
+
+        def surface():
+            ctx.check(lib.psm_grid_surface_dev(th._h, C.byref(grid), p_words), "psm_grid_surface_dev")
+
+        def count():
+            ctx.check(lib.psm_grid_counts_dev(th._h, C.byref(grid), p_counts), "psm_grid_counts_dev")
+
+        def solid():
+            ctx.check(lib.psm_grid_solid_dev(th._h, C.byref(grid), C.c_uint32(3), p_words), "psm_grid_solid_dev")
+
+        # the parent's way to the same bits: boxOverlaps over the voxels' boxes -- (1) the kernel alone over records that are
+        # resident, (2) the package's torch call over resident lo / hi (it packs the records on the device), (3) the same
+        # from host arrays: the upload of 24 bytes per voxel included
+        blo, bhi = psm.voxel_boxes(origin, cell, dims)
+        tlo, thi = torch.from_numpy(blo).to(dev), torch.from_numpy(bhi).to(dev)
+        records = torch.zeros((n, 8), dtype=torch.float32, device=dev)
+        records[:, 0:3], records[:, 4:7] = tlo, thi
+        flags = torch.zeros((n,), dtype=torch.uint8, device=dev)
+        p_rec, p_flags, size = C.c_void_p(records.data_ptr()), C.c_void_p(flags.data_ptr()), C.c_size_t(n)
+
+        def box_kernel():
+            ctx.check(lib.psm_bvh_box_overlaps_dev(th._h, p_rec, size, p_flags), "psm_bvh_box_overlaps_dev")
+
+        def box_torch():
+            return th.boxOverlaps(tlo, thi)
+
+        def box_upload():
+            return th.boxOverlaps(torch.from_numpy(blo).to(dev), torch.from_numpy(bhi).to(dev))
+
+        key = "g%d_" % g
+        out[key + "voxels"] = n
+        out[key + "surface_ms"], out[key + "box_overlaps_kernel_ms"] = abab(ctx, surface, box_kernel)
+        out[key + "surface_again_ms"], out[key + "box_overlaps_torch_ms"] = abab(ctx, surface, box_torch)
+        out[key + "surface_third_ms"], out[key + "box_overlaps_with_upload_ms"] = abab(ctx, surface, box_upload)
+        box_counts = torch.zeros((n,), dtype=torch.int32, device=dev)
+        p_box_counts = C.c_void_p(box_counts.data_ptr())
+
+        def box_count_kernel():
+            ctx.check(lib.psm_bvh_box_count_dev(th._h, p_rec, size, p_box_counts), "psm_bvh_box_count_dev")
+
+        out[key + "counts_ms"], out[key + "box_count_kernel_ms"] = abab(ctx, count, box_count_kernel)
+        surface()
+        vg = psm.VoxelGrid(words.clone(), dims, tuple(grid.origin), tuple(grid.cell))
+        out[key + "solid_ms"] = round(median_ms(ctx, solid), 4)
+        filled = psm.VoxelGrid(words, dims, tuple(grid.origin), tuple(grid.cell))
+        out[key + "occupied"], out[key + "occupied_solid"] = vg.occupied(), filled.occupied()
+        box_kernel()
+        out[key + "same_bits"] = bool(torch.equal(vg.dense().reshape(-1), flags.view(torch.bool)) and torch.equal(counts.reshape(-1), box_counts))
+        out[key + "surface_over_box_kernel"] = round(out[key + "surface_ms"] / out[key + "box_overlaps_kernel_ms"], 3)
+    th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def main():
     sc = scenes.sponza_like()
     ctx = psm.Context(0)
@@ -1934,4 +2013,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "world-clearance": worldclearance, "world-mesh-clearance": worldmeshclearance, "worldmeshes": worldmeshes}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "world-clearance": worldclearance, "world-mesh-clearance": worldmeshclearance, "worldmeshes": worldmeshes, "grids": grids}.get(" ".join(sys.argv[1:]), main)()
