@@ -512,24 +512,11 @@ class TriangleHierarchy:
     def _grid_call(self, g, name, extra, shape, dtype, as_torch):
         """one grid call: the output [shape] of uint64 words or uint32 counts, on the device for torch, else staged and read back"""
         fn = getattr(lib(), name)
-        cells = int(np.prod(shape, dtype=np.int64))
 
         def call(d_out):
             self.ctx.check(fn(self._h, C.byref(g), *extra, C.c_void_p(d_out)), name)
 
-        if as_torch:
-            import torch
-            dev = torch.device("cuda", self.ctx.device)
-            res = torch.empty(shape, dtype=torch.int64 if dtype == np.uint64 else torch.int32, device=dev)
-            _torch_ordered(self.ctx, dev, lambda: call(res.data_ptr()))
-            return res
-        ctx = self.ctx
-        ho = ctx.buf_alloc(max(cells * np.dtype(dtype).itemsize, 16))
-        try:
-            call(ctx.buf_ptr(ho)[0])
-            return ctx.buf_download(ho, dtype, cells).reshape(shape)
-        finally:
-            ctx.buf_free(ho)
+        return _device_call(self.ctx, call, [(shape, dtype)], as_torch)[0]
 
     def triOverlaps(self, tris):
         """Whether some triangle of the hierarchy meets each query triangle (psm_bvh_tri_overlaps_dev; not in the reference): tris
@@ -638,38 +625,15 @@ class TriangleHierarchy:
         """one mesh query: the poses checked and packed [p, 12] on the host, the outputs [p] / [p, T] / [p, T, k] and [p, T]"""
         m12, p, t = _mesh_poses(other, poses, name)
         extra = () if k is None else (C.c_uint32(k),)
-        cells, kk = p * t, 1 if k is None else k
         fn = getattr(lib(), name)
 
-        def call(d_out, d_count):
-            tail = () if d_count is None else (C.c_void_p(d_count),)
-            self.ctx.check(fn(self._h, other._h, _p(m12), C.c_size_t(p), *extra, C.c_void_p(d_out), *tail), name)
+        def call(*d_outs):
+            self.ctx.check(fn(self._h, other._h, _p(m12), C.c_size_t(p), *extra, *map(C.c_void_p, d_outs)), name)
 
-        if as_torch:
-            import torch
-            dev = torch.device("cuda", self.ctx.device)
-            shape, dtype = {"bool": ((p,), torch.uint8), "count": ((p, t), torch.int32), "tris": ((p, t, kk), torch.int32)}[out]
-            res = torch.empty(shape, dtype=dtype, device=dev)
-            cnt = torch.empty((p, t), dtype=torch.int32, device=dev) if out == "tris" else None
-            _torch_ordered(self.ctx, dev, lambda: call(res.data_ptr(), None if cnt is None else cnt.data_ptr()))
-            return QueryTriLists(res, cnt) if out == "tris" else (res.view(torch.bool) if out == "bool" else res)
-        ctx = self.ctx
-        per = {"bool": p, "count": 4 * cells, "tris": 4 * cells * kk}[out]
-        ho = ctx.buf_alloc(max(per, 16))
-        hc = ctx.buf_alloc(max(4 * cells, 16)) if out == "tris" else None
-        try:
-            call(ctx.buf_ptr(ho)[0], None if hc is None else ctx.buf_ptr(hc)[0])
-            if out == "bool":
-                return ctx.buf_download(ho, np.uint8, p).view(np.bool_) if p else np.zeros(0, np.bool_)
-            if out == "count":
-                return (ctx.buf_download(ho, np.uint32, cells) if cells else np.zeros(0, np.uint32)).reshape(p, t)
-            ids = ctx.buf_download(ho, np.int32, cells * kk) if cells else np.zeros(0, np.int32)
-            cnt = ctx.buf_download(hc, np.uint32, cells) if cells else np.zeros(0, np.uint32)
-            return QueryTriLists(ids.reshape(p, t, kk), cnt.reshape(p, t))
-        finally:
-            ctx.buf_free(ho)
-            if hc is not None:
-                ctx.buf_free(hc)
+        res = _device_call(self.ctx, call, _mesh_outs(out, p, t, k, False), as_torch)
+        if out == "tris":
+            return QueryTriLists(*res)
+        return _bool_view(res[0]) if out == "bool" else res[0]
 
     def meshClosest(self, other, poses, rmax=np.inf, as_torch=False):
         """The nearest triangle of this hierarchy to each triangle of `other` at each pose within rmax, its distance and the two
@@ -699,28 +663,13 @@ class TriangleHierarchy:
         m12, p, t = _mesh_poses(other, poses, name)
         if np.ndim(rmax) != 0:
             raise ValueError("%s: rmax must be one scalar" % name)
-        shape = {"closest": (p, t, 8), "bool": (p,), "clearance": (p, 8)}[out]
         fn = getattr(lib(), name)
 
         def call(d_out):
             self.ctx.check(fn(self._h, other._h, _p(m12), C.c_size_t(p), C.c_float(rmax), C.c_void_p(d_out)), name)
 
-        if as_torch:
-            import torch
-            dev = torch.device("cuda", self.ctx.device)
-            res = torch.empty(shape, dtype=torch.uint8 if out == "bool" else torch.float32, device=dev)
-            _torch_ordered(self.ctx, dev, lambda: call(res.data_ptr()))
-            return res.view(torch.bool) if out == "bool" else QueryMeshHits(res, out == "clearance")
-        ctx = self.ctx
-        n = int(np.prod(shape))
-        ho = ctx.buf_alloc(max(n if out == "bool" else 4 * n, 16))
-        try:
-            call(ctx.buf_ptr(ho)[0])
-            if out == "bool":
-                return ctx.buf_download(ho, np.uint8, p).view(np.bool_) if p else np.zeros(0, np.bool_)
-            return QueryMeshHits((ctx.buf_download(ho, np.float32, n) if n else np.zeros(0, np.float32)).reshape(shape), out == "clearance")
-        finally:
-            ctx.buf_free(ho)
+        res, = _device_call(self.ctx, call, _mesh_dist_outs(out, p, t, False), as_torch)
+        return _bool_view(res) if out == "bool" else QueryMeshHits(res, out == "clearance")
 
     def sweepSphere(self, origins, directions, radius, tmax=np.inf):
         """Where a sphere of `radius` that moves from each origin along its direction first touches a triangle within the distance
@@ -1269,6 +1218,70 @@ def _torch_ordered(ctx, dev, call):
         _hip_check(hip.hipEventDestroy(ev), "hipEventDestroy")
 
 
+_TORCH_OF = {np.uint8: "uint8", np.int32: "int32", np.uint32: "int32", np.uint64: "int64", np.float32: "float32"}   # (torch has no general uint32 / uint64)
+
+
+def _device_call(ctx, call, outs, as_torch):
+    """One native call that writes device outputs, outs a list of (shape, numpy dtype): call(*pointers), one per output in
+    order. as_torch: the outputs are torch tensors on the context's device and the call runs under _torch_ordered; else they are
+    staged in the context's buffers, read back (an empty one is not) and freed. Returns the tensors / arrays in order."""
+    if as_torch:
+        import torch
+        dev = torch.device("cuda", ctx.device)
+        res = [torch.empty(shape, dtype=getattr(torch, _TORCH_OF[dtype]), device=dev) for shape, dtype in outs]
+        _torch_ordered(ctx, dev, lambda: call(*[r.data_ptr() for r in res]))
+        return res
+    bufs = []
+    try:
+        for shape, dtype in outs:
+            bufs.append(ctx.buf_alloc(max(int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize, 16)))
+        call(*[ctx.buf_ptr(h)[0] for h in bufs])
+        res = []
+        for h, (shape, dtype) in zip(bufs, outs):
+            n = int(np.prod(shape, dtype=np.int64))
+            res.append((ctx.buf_download(h, dtype, n) if n else np.zeros(0, dtype)).reshape(shape))
+        return res
+    finally:
+        for h in bufs:
+            ctx.buf_free(h)
+
+
+def _bool_view(flags):
+    """a uint8 array / tensor of 0 / 1 as bools, the same memory"""
+    if isinstance(flags, np.ndarray):
+        return flags.view(np.bool_)
+    import torch
+    return flags.view(torch.bool)
+
+
+def _mesh_outs(out, p, t, k, world):
+    """the output spec of a mesh query: the flags [p], the counts [p, T], or the rows [p, T, k] (a world's twice: the
+    instances) and the counts"""
+    if out == "bool":
+        return [((p,), np.uint8)]
+    if out == "count":
+        return [((p, t), np.uint32)]
+    return [((p, t, k), np.int32)] * (2 if world else 1) + [((p, t), np.uint32)]
+
+
+def _mesh_dist_outs(out, p, t, world):
+    """the output spec of a mesh clearance query: the flags [p], or the records [p, T, 8] / [p, 8] and a world's instances"""
+    if out == "bool":
+        return [((p,), np.uint8)]
+    shape = (p, t, 8) if out == "closest" else (p, 8)
+    return [(shape, np.float32)] + ([(shape[:-1], np.int32)] if world else [])
+
+
+def _mesh_skip(world, skip, name):
+    """a world's skip argument as the library takes it: -1 for None, else an instance index (refused here: no call is made)"""
+    if skip is None:
+        return -1
+    s = int(skip)
+    if s != skip or isinstance(skip, bool) or not 0 <= s < len(world.hierarchies):
+        raise PsmError("%s: skip must be None or an instance index 0 .. %d" % (name, len(world.hierarchies) - 1))
+    return s
+
+
 def _launch_torch(th, packed, kind, name, *extra):
     """One query launch over device records `packed` (made on torch's current stream) on the context's stream: the two streams
     ordered by events when they differ -- no host synchronisation. kind: the result's (_QUERY_OUT): QueryHits, a bool or an int32
@@ -1610,59 +1623,20 @@ class InstanceWorld(QueryScene):
     def _mesh_query(self, other, poses, skip, out, name, k, as_torch):
         """one mesh query of the world (TriangleHierarchy._mesh_query's shape): the poses and skip checked on the host, the
         poses packed [p, 12], the outputs [p] / [p, T] / [p, T, k] twice and [p, T]"""
-        if not isinstance(other, TriangleHierarchy):
-            raise TypeError("%s: other must be a TriangleHierarchy" % name)
-        m = np.asarray(poses)
-        if m.ndim == 2:
-            m = m[None]
-        if m.ndim != 3:
-            raise ValueError("%s: poses must be one matrix or [p, 3, 4] / [p, 4, 4]" % name)
-        p, t = m.shape[0], int(other.triangleCount)
-        m12 = np.ascontiguousarray(np.stack([_pose(x, name) for x in m]).reshape(p, 12) if p else np.zeros((0, 12)), np.float32)
-        if skip is None:
-            s = -1
-        else:
-            s = int(skip)
-            if s != skip or isinstance(skip, bool) or not 0 <= s < len(self.hierarchies):   # (refused here: no call is made)
-                raise PsmError("%s: skip must be None or an instance index 0 .. %d" % (name, len(self.hierarchies) - 1))
+        m12, p, t = _mesh_poses(other, poses, name)
+        s = _mesh_skip(self, skip, name)
         self._fresh(name)
         extra = () if k is None else (C.c_uint32(k),)
-        cells, kk = p * t, 1 if k is None else k
         fn = getattr(lib(), name)
 
-        def call(d_out, d_inst, d_count):
-            tail = () if d_count is None else (C.c_void_p(d_inst), C.c_void_p(d_count))
-            self.ctx.check(fn(self._w, other._h, _p(m12), C.c_size_t(p), C.c_int32(s), *extra, C.c_void_p(d_out), *tail), name)
+        def call(*d_outs):
+            self.ctx.check(fn(self._w, other._h, _p(m12), C.c_size_t(p), C.c_int32(s), *extra, *map(C.c_void_p, d_outs)), name)
 
-        if as_torch:
-            import torch
-            dev = torch.device("cuda", self.ctx.device)
-            shape, dtype = {"bool": ((p,), torch.uint8), "count": ((p, t), torch.int32), "tris": ((p, t, kk), torch.int32)}[out]
-            res = torch.empty(shape, dtype=dtype, device=dev)
-            inst = torch.empty(shape, dtype=dtype, device=dev) if out == "tris" else None
-            cnt = torch.empty((p, t), dtype=torch.int32, device=dev) if out == "tris" else None
-            _torch_ordered(self.ctx, dev, lambda: call(res.data_ptr(), None if inst is None else inst.data_ptr(),
-                                                       None if cnt is None else cnt.data_ptr()))
-            return QueryTriLists(res, cnt, inst) if out == "tris" else (res.view(torch.bool) if out == "bool" else res)
-        ctx = self.ctx
-        per = {"bool": p, "count": 4 * cells, "tris": 4 * cells * kk}[out]
-        ho = ctx.buf_alloc(max(per, 16))
-        hi = ctx.buf_alloc(max(per, 16)) if out == "tris" else None
-        hc = ctx.buf_alloc(max(4 * cells, 16)) if out == "tris" else None
-        try:
-            call(ctx.buf_ptr(ho)[0], None if hi is None else ctx.buf_ptr(hi)[0], None if hc is None else ctx.buf_ptr(hc)[0])
-            if out == "bool":
-                return ctx.buf_download(ho, np.uint8, p).view(np.bool_) if p else np.zeros(0, np.bool_)
-            if out == "count":
-                return (ctx.buf_download(ho, np.uint32, cells) if cells else np.zeros(0, np.uint32)).reshape(p, t)
-            ids = ctx.buf_download(ho, np.int32, cells * kk) if cells else np.zeros(0, np.int32)
-            ins = ctx.buf_download(hi, np.int32, cells * kk) if cells else np.zeros(0, np.int32)
-            cnt = ctx.buf_download(hc, np.uint32, cells) if cells else np.zeros(0, np.uint32)
-            return QueryTriLists(ids.reshape(p, t, kk), cnt.reshape(p, t), ins.reshape(p, t, kk))
-        finally:
-            for h in (ho, hi, hc):
-                if h is not None:
-                    ctx.buf_free(h)
+        res = _device_call(self.ctx, call, _mesh_outs(out, p, t, k, True), as_torch)
+        if out == "tris":
+            ids, inst, cnt = res
+            return QueryTriLists(ids, cnt, inst)
+        return _bool_view(res[0]) if out == "bool" else res[0]
 
     def closestToMesh(self, other, poses, rmax=np.inf, skip=None, as_torch=False):
         """The nearest (instance, triangle) pair of the world to each triangle of `other` at each pose within rmax
@@ -1694,44 +1668,17 @@ class InstanceWorld(QueryScene):
         m12, p, t = _mesh_poses(other, poses, name)
         if np.ndim(rmax) != 0:
             raise ValueError("%s: rmax must be one scalar" % name)
-        if skip is None:
-            s = -1
-        else:
-            s = int(skip)
-            if s != skip or isinstance(skip, bool) or not 0 <= s < len(self.hierarchies):   # (refused here: no call is made)
-                raise PsmError("%s: skip must be None or an instance index 0 .. %d" % (name, len(self.hierarchies) - 1))
+        s = _mesh_skip(self, skip, name)
         self._fresh(name)
-        shape = {"closest": (p, t, 8), "bool": (p,), "clearance": (p, 8)}[out]
         fn = getattr(lib(), name)
 
-        def call(d_out, d_inst):
-            tail = () if d_inst is None else (C.c_void_p(d_inst),)
-            self.ctx.check(fn(self._w, other._h, _p(m12), C.c_size_t(p), C.c_int32(s), C.c_float(rmax), C.c_void_p(d_out), *tail), name)
+        def call(*d_outs):
+            self.ctx.check(fn(self._w, other._h, _p(m12), C.c_size_t(p), C.c_int32(s), C.c_float(rmax), *map(C.c_void_p, d_outs)), name)
 
-        if as_torch:
-            import torch
-            dev = torch.device("cuda", self.ctx.device)
-            res = torch.empty(shape, dtype=torch.uint8 if out == "bool" else torch.float32, device=dev)
-            inst = None if out == "bool" else torch.empty(shape[:-1], dtype=torch.int32, device=dev)
-            _torch_ordered(self.ctx, dev, lambda: call(res.data_ptr(), None if inst is None else inst.data_ptr()))
-            if out == "bool":
-                return res.view(torch.bool)
-            return QueryTriHits(res, inst) if out == "closest" else QueryMeshHits(res, True, inst)
-        ctx = self.ctx
-        n = int(np.prod(shape))
-        ho = ctx.buf_alloc(max(n if out == "bool" else 4 * n, 16))
-        hi = None if out == "bool" else ctx.buf_alloc(max(n // 2, 16))
-        try:
-            call(ctx.buf_ptr(ho)[0], None if hi is None else ctx.buf_ptr(hi)[0])
-            if out == "bool":
-                return ctx.buf_download(ho, np.uint8, p).view(np.bool_) if p else np.zeros(0, np.bool_)
-            rec = (ctx.buf_download(ho, np.float32, n) if n else np.zeros(0, np.float32)).reshape(shape)
-            ins = (ctx.buf_download(hi, np.int32, n // 8) if n else np.zeros(0, np.int32)).reshape(shape[:-1])
-            return QueryTriHits(rec, ins) if out == "closest" else QueryMeshHits(rec, True, ins)
-        finally:
-            ctx.buf_free(ho)
-            if hi is not None:
-                ctx.buf_free(hi)
+        res = _device_call(self.ctx, call, _mesh_dist_outs(out, p, t, True), as_torch)
+        if out == "bool":
+            return _bool_view(res[0])
+        return QueryTriHits(*res) if out == "closest" else QueryMeshHits(res[0], True, res[1])
 
     def _call(self, name, d_in, n, extra, d_out, d_geom):
         name = name.replace("psm_bvh_", "psm_world_")

@@ -10,6 +10,10 @@
 // anywhere. From there the body is tri.hip's TriBody restated: tri_tri, the box family's prune on the query triangle's bounding
 // box, the list of the k lowest ids. Results go to [q][t], t the leaf's load-order triangle id; the host path clears the
 // outputs first, so a triangle the other's build dropped reads 0 / -1.
+//
+// This file also holds the host pieces all twelve posed-mesh entry points share (psm_query_host.h): the
+// refusals they have in common, the contexts' pose and key areas with the one upload, and the two study knobs.
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
@@ -183,16 +187,76 @@ int area_for(psm_ctx* c, PoseArea& a, size_t bytes, void** out) {
 
 }  // namespace
 
-// (psm_query_host.h: the mesh queries over a world, world.hip's world_mesh_query(), upload their poses here too)
-int poses_for(psm_ctx* c, size_t bytes, void** out) {
-    std::lock_guard<std::mutex> lk(pose_mu);
-    return area_for(c, pose_area[c].poses, bytes, out);
+// ---- The host pieces every posed-mesh entry point shares (psm_query_host.h): mesh_query() below, mesh_dist.hip's
+// mesh_dist_query(), world.hip's world_mesh_query() and world_mesh_dist_query() are sequences of these and of what is their own.
+// Each check answers PSM_OK or refuses under the entry point's name, on the host, nothing launched and no output byte changed.
+
+int mesh_refuse(psm_ctx* c, int code, const char* format, ...) {
+    char msg[192];
+    va_list args;
+    va_start(args, format);
+    vsnprintf(msg, sizeof msg, format, args);
+    va_end(args);
+    return set_err(c, code, msg);
 }
 
-// (psm_query_host.h: mesh_dist.hip's key words, one uint64 per pose of a clearance call)
-int mesh_keys_for(psm_ctx* c, size_t bytes, void** out) {
-    std::lock_guard<std::mutex> lk(pose_mu);
-    return area_for(c, pose_area[c].keys, bytes, out);
+int mesh_pointers(psm_ctx* c, const char* name, bool all) {
+    return all ? PSM_OK : mesh_refuse(c, PSM_ERR_INVALID, "%s: NULL pointer", name);
+}
+
+int mesh_aligned(psm_ctx* c, const char* name, const char* what, const void* ptr, unsigned align) {
+    return ((uintptr_t)ptr & (align - 1u)) == 0 ? PSM_OK : mesh_refuse(c, PSM_ERR_INVALID, "%s: %s not %u-byte aligned", name, what, align);
+}
+
+int mesh_poses_rigid(psm_ctx* c, const char* name, const float* poses, size_t p) {
+    for (size_t q = 0; q < p; q++)
+        if (const char* why = pose_fault(poses + 12 * q)) return mesh_refuse(c, PSM_ERR_INVALID, "%s: pose %zu %s", name, q, why);
+    return PSM_OK;
+}
+
+int mesh_answers_fit(psm_ctx* c, const char* name, size_t p, uint32_t T) {
+    if ((uint64_t)p * T < MESH_QUERIES_MAX) return PSM_OK;
+    return mesh_refuse(c, PSM_ERR_CAPACITY, "%s: %zu poses of %u triangles are more than 2^32 answers", name, p, T);
+}
+
+// The upload: the poses go to the device as a world's do (psm_world_set_transforms: a copy on the context's stream and a
+// synchronisation, the caller's memory being pageable and the caller's to change), with the other hierarchy's leaf count coming
+// back in the same wait -- the one synchronisation of a call.
+int mesh_upload(psm_ctx* c, const psm_bvh* o, const float* poses, size_t p, void** d_poses, void** d_keys, uint32_t* L) {
+    {
+        std::lock_guard<std::mutex> lk(pose_mu);
+        PoseAreas& a = pose_area[c];
+        int rc = area_for(c, a.poses, p * 12 * sizeof(float), d_poses);
+        if (rc == PSM_OK && d_keys) rc = area_for(c, a.keys, p * sizeof(uint64_t), d_keys);
+        if (rc != PSM_OK) return rc;
+    }
+    *L = 0;
+    PSM_HIP(c, hipMemcpyAsync(*d_poses, poses, p * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    PSM_HIP(c, hipMemcpyAsync(L, o->d_small + SM_COUNT, sizeof *L, hipMemcpyDeviceToHost, c->stream));
+    PSM_HIP(c, hipStreamSynchronize(c->stream));
+    if (*L > o->tri_count) return set_err(c, PSM_ERR_STATE, "mesh query: the other hierarchy's leaf count exceeds its triangle count");
+    return PSM_OK;
+}
+
+// The flag kernels' skip pays where workgroups start after others have finished: a launch that takes the grid-stride loop. The
+// overlaps kernels read the flag in begin() (measured: 7 to 22 % faster at 1 024 poses; without a second trip every wave starts
+// at once, nothing is skipped and the load alone cost up to 8 % at one pose -- DESIGN.md 4.21); the within kernels read it before
+// every leaf too, a leaf costing far more than the load (measured at 1 024 poses: 6.5 against 27 ms, 64 against 191 ms --
+// DESIGN.md 4.24). PSM_MESH_SKIP = 0 / 1 forces it off / on (a study knob: psm_hip.h).
+bool mesh_skip(size_t queries) {
+    const char* knob = getenv("PSM_MESH_SKIP");
+    return knob ? knob[0] != '0' : (queries + QUERY_BLOCK - 1) / QUERY_BLOCK > QUERY_GRID_CAP;
+}
+
+// PSM_MESH_BOUND = 0 / 1 forces the clearance kernels' shared bound off / on (a study knob: psm_hip.h); 2 and 3 are the
+// alternatives DESIGN.md 4.24 measures: the word read in begin() alone and published at finish() alone; re-read before every
+// leaf but published at finish() alone. The answer is the same under each. On by default at every launch size (measured, the
+// torus of 2 304 triangles against the Sponza-class / the stress scene: 0.71 against 3.3 ms and 1.3 against 17 ms at one pose,
+// 29 against 238 ms and 81 against 961 ms at 1 024; read in begin() alone 3.2 / 17 / 133 / 573 ms, published late 1.3 / 3.7 /
+// 47 / 273 ms).
+char mesh_bound() {
+    const char* knob = getenv("PSM_MESH_BOUND");
+    return knob ? knob[0] : '1';
 }
 
 namespace {
@@ -200,57 +264,30 @@ namespace {
 const char* const MESH_NAME[] = {"psm_bvh_mesh_overlaps_dev", "psm_bvh_mesh_count_dev", "psm_bvh_mesh_triangles_dev"};
 
 // A mesh query: NULL handles and p == 0 are answered before anything else is looked at; then the data, k, the state, the depth,
-// the contexts, the poses -- all on the host, before any launch, the outputs untouched. Then the poses go to the device as a
-// world's do (psm_world_set_transforms: a copy on the context's stream and a synchronisation, the caller's memory being
-// pageable and the caller's to change), with the other hierarchy's leaf count coming back in the same wait.
+// the contexts, the poses, the number of answers -- all on the host, before any launch, the outputs untouched. Then the upload.
 int mesh_query(psm_bvh* b, psm_bvh* o, const float* poses, size_t p, int mode, uint32_t k, void* d_out, uint32_t* d_count) {
     if (!b || !o) return PSM_ERR_INVALID;
     if (p == 0) return PSM_OK;
     psm_ctx* c = b->ctx;
     const char* name = MESH_NAME[mode];
-    char msg[192];
     const bool rows = mode == MESH_TRIS;
-    if (!poses || !d_out || (rows && !d_count)) {
-        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (mode != MESH_ANY && ((uintptr_t)d_out & 3u) != 0) {
-        snprintf(msg, sizeof msg, "%s: %s not 4-byte aligned", name, rows ? "tris" : "counts");
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (rows && ((uintptr_t)d_count & 3u) != 0) {
-        snprintf(msg, sizeof msg, "%s: counts not 4-byte aligned", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (rows && (k == 0 || k > PSM_QUERY_K_MAX)) {
-        snprintf(msg, sizeof msg, "%s: k must be 1 .. %d", name, PSM_QUERY_K_MAX);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
+    int rc = mesh_pointers(c, name, poses && d_out && (!rows || d_count));
+    if (rc == PSM_OK && mode != MESH_ANY) rc = mesh_aligned(c, name, rows ? "tris" : "counts", d_out, 4);
+    if (rc == PSM_OK && rows) rc = mesh_aligned(c, name, "counts", d_count, 4);
+    if (rc != PSM_OK) return rc;
+    if (rows && (k == 0 || k > PSM_QUERY_K_MAX)) return mesh_refuse(c, PSM_ERR_INVALID, "%s: k must be 1 .. %d", name, PSM_QUERY_K_MAX);
     if (!b->built || !o->built) return set_err(c, PSM_ERR_STATE, "mesh query before build");
     if (depth_bound(b) > QSTACK_MAX) return set_err(c, PSM_ERR_CAPACITY, "mesh query: hierarchy deeper than the query stack");
-    if (o->ctx != c) {
-        snprintf(msg, sizeof msg, "%s: the two hierarchies are of different contexts", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    for (size_t q = 0; q < p; q++)
-        if (const char* why = pose_fault(poses + 12 * q)) {
-            snprintf(msg, sizeof msg, "%s: pose %zu %s", name, q, why);
-            return set_err(c, PSM_ERR_INVALID, msg);
-        }
+    if (o->ctx != c) return mesh_refuse(c, PSM_ERR_INVALID, "%s: the two hierarchies are of different contexts", name);
     const uint32_t T = o->tri_count;
-    if ((uint64_t)p * T >= MESH_QUERIES_MAX) {
-        snprintf(msg, sizeof msg, "%s: %zu poses of %u triangles are more than 2^32 answers", name, p, T);
-        return set_err(c, PSM_ERR_CAPACITY, msg);
-    }
+    rc = mesh_poses_rigid(c, name, poses, p);
+    if (rc == PSM_OK) rc = mesh_answers_fit(c, name, p, T);
+    if (rc != PSM_OK) return rc;
     (void)hipSetDevice(c->device);
     void* d_poses = nullptr;
-    int rc = poses_for(c, p * 12 * sizeof(float), &d_poses);
-    if (rc != PSM_OK) return rc;
     uint32_t L = 0;
-    PSM_HIP(c, hipMemcpyAsync(d_poses, poses, p * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    PSM_HIP(c, hipMemcpyAsync(&L, o->d_small + SM_COUNT, sizeof L, hipMemcpyDeviceToHost, c->stream));
-    PSM_HIP(c, hipStreamSynchronize(c->stream));
-    if (L > T) return set_err(c, PSM_ERR_STATE, "mesh query: the other hierarchy's leaf count exceeds its triangle count");
+    rc = mesh_upload(c, o, poses, p, &d_poses, nullptr, &L);
+    if (rc != PSM_OK) return rc;
     // (the context's stack area is allocated here, on its first query: the last thing that can fail before the outputs change)
     MeshArgs m = {};
     uint32_t grid = 0;
@@ -269,12 +306,7 @@ int mesh_query(psm_bvh* b, psm_bvh* o, const float* poses, size_t p, int mode, u
     if (rows) m.q.count = d_count;
     m.tri48 = o->d_tri48; m.leaf_tri = o->d_leaftri; m.poses = (const float4*)d_poses;
     m.magic = mesh_magic(L); m.L = L; m.T = T;
-    // The flag kernel's skip pays where workgroups start after others have finished: a launch that takes the grid-stride loop
-    // (measured: 7 to 22 % faster at 1 024 poses; without a second trip every wave starts at once, nothing is skipped and the
-    // load alone cost up to 8 % at one pose -- DESIGN.md 4.21). PSM_MESH_SKIP = 0 / 1 forces it off / on (a study knob: psm_hip.h).
-    const char* skip = getenv("PSM_MESH_SKIP");
-    const bool strided = (p * (size_t)L + QUERY_BLOCK - 1) / QUERY_BLOCK > QUERY_GRID_CAP;
-    m.flags = (skip ? skip[0] != '0' : strided) ? MESH_FLAG_SKIP : 0u;
+    m.flags = mesh_skip(p * (size_t)L) ? MESH_FLAG_SKIP : 0u;   // (read by the flag kernel alone)
     if (mode == MESH_ANY) bvh_query_mesh_any<<<grid, QUERY_BLOCK, 0, c->stream>>>(m);
     else if (mode == MESH_COUNT) bvh_query_mesh_count<<<grid, QUERY_BLOCK, 0, c->stream>>>(m);
     else bvh_query_mesh_tris<<<grid, QUERY_BLOCK, (size_t)k * QUERY_BLOCK * sizeof(uint32_t), c->stream>>>(m);

@@ -30,14 +30,9 @@
 //   * the weights never travel through the word: a second, tiny launch of p lanes (bvh_query_mesh_pick) reads t* from each word
 //     and walks that one posed triangle as the closest kernel would, with Dmin for rmax (the same record: the winner of the
 //     walk with rmax counts under Dmin too), and writes the psm_mesh_hit. A word that still reads "none" gives the miss record
-#include <cstdio>
-#include <cstdlib>
-#include <mutex>
-#include <unordered_map>
-
 #include "psm_common.h"
 #include "psm_internal.h"
-#include "psm_query_host.h"     // batch_args, depth_bound, pose_fault, poses_for, mesh_keys_for; psm_query_dev.h through it
+#include "psm_query_host.h"     // batch_args, depth_bound, mesh.hip's shared host pieces; psm_query_dev.h through it
 #include "psm_mesh_dev.h"       // mesh_split, mesh_query_tri
 #include "psm_tri_dist_dev.h"   // tri_dist; box_row through psm_tri_dev.h
 #include "psm_mesh_dist_key.h"  // mesh_key
@@ -265,52 +260,30 @@ namespace {
 
 const char* const MESH_DIST_NAME[] = {"psm_bvh_mesh_closest_dev", "psm_bvh_mesh_within_dev", "psm_bvh_mesh_clearance_dev"};
 
-// A mesh clearance query: mesh.hip's mesh_query() under the new names -- NULL handles and p == 0 are answered before anything
-// else is looked at; then the data, the state, the depth, the contexts, the poses, all on the host, before any launch, the
-// outputs untouched. The poses go to the device as a mesh query's do: one copy, one synchronisation, no graph capture.
+// A mesh clearance query, of mesh.hip's shared pieces (psm_query_host.h) in mesh_query()'s order: NULL handles and p == 0 are
+// answered before anything else is looked at; then the data, the state, the depth, the contexts, the poses, the number of
+// answers, all on the host, before any launch, the outputs untouched. Then the upload: one copy, one synchronisation, no graph
+// capture.
 int mesh_dist_query(psm_bvh* b, psm_bvh* o, const float* poses, size_t p, int mode, float rmax, void* d_out) {
     if (!b || !o) return PSM_ERR_INVALID;
     if (p == 0) return PSM_OK;
     psm_ctx* c = b->ctx;
     const char* name = MESH_DIST_NAME[mode];
-    char msg[192];
-    if (!poses || !d_out) {
-        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (mode != MD_WITHIN && ((uintptr_t)d_out & 15u) != 0) {
-        snprintf(msg, sizeof msg, "%s: hits not 16-byte aligned", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
+    int rc = mesh_pointers(c, name, poses && d_out);
+    if (rc == PSM_OK && mode != MD_WITHIN) rc = mesh_aligned(c, name, "hits", d_out, 16);
+    if (rc != PSM_OK) return rc;
     if (!b->built || !o->built) return set_err(c, PSM_ERR_STATE, "mesh query before build");
     if (depth_bound(b) > QSTACK_MAX) return set_err(c, PSM_ERR_CAPACITY, "mesh query: hierarchy deeper than the query stack");
-    if (o->ctx != c) {
-        snprintf(msg, sizeof msg, "%s: the two hierarchies are of different contexts", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    for (size_t q = 0; q < p; q++)
-        if (const char* why = pose_fault(poses + 12 * q)) {
-            snprintf(msg, sizeof msg, "%s: pose %zu %s", name, q, why);
-            return set_err(c, PSM_ERR_INVALID, msg);
-        }
+    if (o->ctx != c) return mesh_refuse(c, PSM_ERR_INVALID, "%s: the two hierarchies are of different contexts", name);
     const uint32_t T = o->tri_count;
-    if ((uint64_t)p * T >= MESH_QUERIES_MAX) {
-        snprintf(msg, sizeof msg, "%s: %zu poses of %u triangles are more than 2^32 answers", name, p, T);
-        return set_err(c, PSM_ERR_CAPACITY, msg);
-    }
+    rc = mesh_poses_rigid(c, name, poses, p);
+    if (rc == PSM_OK) rc = mesh_answers_fit(c, name, p, T);
+    if (rc != PSM_OK) return rc;
     (void)hipSetDevice(c->device);
     void *d_poses = nullptr, *d_keys = nullptr;
-    int rc = poses_for(c, p * 12 * sizeof(float), &d_poses);
-    if (rc != PSM_OK) return rc;
-    if (mode == MD_CLEAR) {
-        rc = mesh_keys_for(c, p * sizeof(uint64_t), &d_keys);
-        if (rc != PSM_OK) return rc;
-    }
     uint32_t L = 0;
-    PSM_HIP(c, hipMemcpyAsync(d_poses, poses, p * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    PSM_HIP(c, hipMemcpyAsync(&L, o->d_small + SM_COUNT, sizeof L, hipMemcpyDeviceToHost, c->stream));
-    PSM_HIP(c, hipStreamSynchronize(c->stream));
-    if (L > T) return set_err(c, PSM_ERR_STATE, "mesh query: the other hierarchy's leaf count exceeds its triangle count");
+    rc = mesh_upload(c, o, poses, p, &d_poses, mode == MD_CLEAR ? &d_keys : nullptr, &L);
+    if (rc != PSM_OK) return rc;
     // (the context's stack area is allocated here, on its first query: the last thing that can fail before the outputs change)
     MeshDistArgs m = {};
     uint32_t grid = 0;
@@ -319,7 +292,6 @@ int mesh_dist_query(psm_bvh* b, psm_bvh* o, const float* poses, size_t p, int mo
     m.q.node32 = b->d_node32; m.q.tri48 = b->d_tri48; m.q.sm = b->d_small; m.q.sorted_tri = b->d_sorted_tri;
     m.tri48 = o->d_tri48; m.leaf_tri = o->d_leaftri; m.poses = (const float4*)d_poses; m.keys = (unsigned long long*)d_keys;
     m.magic = mesh_magic(L); m.L = L; m.T = T; m.rmax = rmax;
-    const bool strided = (p * (size_t)L + QUERY_BLOCK - 1) / QUERY_BLOCK > QUERY_GRID_CAP;
     if (mode == MD_CLOSEST) {
         const size_t cells = p * (size_t)T;
         if (L < T) {   // a dropped triangle's cells read the miss record
@@ -332,22 +304,12 @@ int mesh_dist_query(psm_bvh* b, psm_bvh* o, const float* poses, size_t p, int mo
     } else if (mode == MD_WITHIN) {
         PSM_HIP(c, hipMemsetAsync(d_out, 0, p, c->stream));
         if (L == 0) return PSM_OK;
-        // the skip, under the mesh queries' flag kernel's rule and knob (mesh.hip), here in begin() and before
-        // every leaf: a leaf costs far more than the load (measured at 1 024 poses: 6.5 against 27 ms, 64 against 191 ms)
-        const char* skip = getenv("PSM_MESH_SKIP");
-        m.flags = (skip ? skip[0] != '0' : strided) ? MD_FLAG_SKIP : 0u;
+        m.flags = mesh_skip(p * (size_t)L) ? MD_FLAG_SKIP : 0u;   // (the flag read in begin() and before every leaf)
         bvh_query_mesh_within<<<grid, QUERY_BLOCK, 0, c->stream>>>(m);
     } else {
         PSM_HIP(c, hipMemsetAsync(d_keys, 0xff, p * sizeof(uint64_t), c->stream));   // every word: "none"
         if (L != 0) {
-            // PSM_MESH_BOUND = 0 / 1 forces the shared bound off / on (a study knob: psm_hip.h); 2 and 3 are the alternatives
-            // DESIGN.md 4.24 measures: the word read in begin() alone and published at finish() alone; re-read before every leaf
-            // but published at finish() alone. The answer is the same under each. On by default at every launch size (measured,
-            // the torus of 2 304 triangles against the Sponza-class / the stress scene: 0.71 against 3.3 ms and 1.3 against 17 ms
-            // at one pose, 29 against 238 ms and 81 against 961 ms at 1 024; read in begin() alone 3.2 / 17 / 133 / 573 ms,
-            // published late 1.3 / 3.7 / 47 / 273 ms).
-            const char* knob = getenv("PSM_MESH_BOUND");
-            const char how = knob ? knob[0] : '1';
+            const char how = mesh_bound();   // (the study knob: the same answer under each letter)
             if (how == '0') bvh_query_mesh_clearance<0u><<<grid, QUERY_BLOCK, 0, c->stream>>>(m);
             else if (how == '2') bvh_query_mesh_clearance<MD_FLAG_BOUND><<<grid, QUERY_BLOCK, 0, c->stream>>>(m);
             else if (how == '3') bvh_query_mesh_clearance<MD_FLAG_BOUND | MD_FLAG_REREAD><<<grid, QUERY_BLOCK, 0, c->stream>>>(m);

@@ -15,7 +15,8 @@
 
 namespace psm {
 
-// the most answers (poses x triangles) of one call: the kernels index them with 32 bits (mesh_split is exact up to 2^37)
+// the most answers (poses x triangles) of one call, over a hierarchy or a world: the kernels index them with 32 bits (mesh_split
+// is exact up to 2^37); mesh.hip's mesh_answers_fit() is the one check
 constexpr uint64_t MESH_QUERIES_MAX = (uint64_t)1 << 32;
 
 // The multiplier of mesh_split for L leaves, 1 <= L < 2^27: ceil(2^64 / L), and 0 for L = 1 (2^64 has no 64-bit form).

@@ -10,10 +10,21 @@ namespace psm {
 void query_release(psm_ctx* c);               // query.hip, for psm_ctx_destroy: the context's stack area goes with it
 void mesh_release(psm_ctx* c);                // mesh.hip, for psm_ctx_destroy: the device copy of the mesh queries' poses goes with it
 void grid_release(psm_ctx* c);                // grid.hip, for psm_ctx_destroy: the solid grids' scratch goes with it
-// mesh.hip: the device copy of a call's poses, per context (grown on demand; every call runs on the context's stream)
-int poses_for(psm_ctx* c, size_t bytes, void** out);
-// mesh.hip: beside them, the 64-bit words the poses of a mesh clearance call share (mesh_dist.hip), grown and released alike
-int mesh_keys_for(psm_ctx* c, size_t bytes, void** out);
+// mesh.hip: the host pieces the twelve posed-mesh entry points share (mesh.hip, mesh_dist.hip and world.hip's two host functions;
+// DESIGN.md 4.28). A check answers PSM_OK, or refuses under the entry point's name with the context's error set.
+int mesh_refuse(psm_ctx* c, int code, const char* format, ...) __attribute__((format(printf, 3, 4)));   // the formatted text as the error
+int mesh_pointers(psm_ctx* c, const char* name, bool all);                                               // "<name>: NULL pointer" unless all
+int mesh_aligned(psm_ctx* c, const char* name, const char* what, const void* ptr, unsigned align);      // "<name>: <what> not <align>-byte aligned"
+int mesh_poses_rigid(psm_ctx* c, const char* name, const float* poses, size_t p);                        // the first pose pose_fault() refuses, by index
+int mesh_answers_fit(psm_ctx* c, const char* name, size_t p, uint32_t T);                                // p x T below 2^32, else PSM_ERR_CAPACITY
+// The upload of a call, on the context's stream: the poses into the context's pose area (grown on demand, released by
+// mesh_release), the area of one 64-bit word per pose a clearance call's lanes share (d_keys NULL: none), other's leaf count L
+// back, one synchronisation for all of it; L above other's triangle count is refused
+int mesh_upload(psm_ctx* c, const psm_bvh* o, const float* poses, size_t p, void** d_poses, void** d_keys, uint32_t* L);
+// Whether a flag kernel's lanes skip a pose already flagged: PSM_MESH_SKIP, else whether a launch of `queries` lanes strides
+bool mesh_skip(size_t queries);
+// PSM_MESH_BOUND's letter for the clearance kernels' shared bound, '1' when unset
+char mesh_bound();
 uint64_t bvh_generation(const psm_bvh* b);    // api.hip: bumped by every build of the hierarchy
 
 // (Q_FIRST_HITS, Q_NEAREST: the k-best queries of kbest.hip and of world.hip's worlds: no entry in the kernel tables; Q_BOX_ANY,

@@ -75,8 +75,7 @@ struct WorldMeshArgs {
     int32_t skip;               // the instance that is never entered, -1: none
 };
 constexpr uint32_t WORLD_MESH_FLAG_SKIP = 1u;   // the flag kernel: a lane whose pose's flag already reads 1 does not walk
-// the most answers (poses x triangles) of one call: the kernels index them with 32 bits (psm_mesh_dev.h's MESH_QUERIES_MAX)
-constexpr uint64_t WORLD_MESH_ANSWERS_MAX = (uint64_t)1 << 32;
+// (the most answers, poses x triangles, of one call is psm_mesh_dev.h's MESH_QUERIES_MAX: the kernels index them with 32 bits)
 
 // world_mesh.hip: the launch of a world's mesh kernel (mode: 0 overlaps, 1 count, 2 triangles) for world.hip's host path
 // (world_mesh_query()); a.w.samples is the triangles query's k; magic is set there from a.L (mesh_magic, psm_mesh_dev.h)
@@ -93,7 +92,7 @@ struct WorldMeshDistArgs {
 enum { WMD_CLOSEST = 0, WMD_WITHIN = 1, WMD_CLEAR = 2, WMD_PICK = 3, WMD_FILL = 4 };
 
 // world_mesh_dist.hip: the launch of a world's mesh clearance kernel for world.hip's host path (world_mesh_dist_query()); magic is
-// set there from a.m.L. mode WMD_CLEAR: bound is PSM_MESH_BOUND's letter ('0' .. '3'; mesh_dist.hip has the meanings). mode
+// set there from a.m.L. mode WMD_CLEAR: bound is PSM_MESH_BOUND's letter ('0' .. '3'; mesh.hip's mesh_bound() has the meanings). mode
 // WMD_FILL: the miss record in a.m.w.n cells of hits (the word after s, t: -1 where the records are psm_mesh_hit, `pick`) and -1 in geom
 int world_mesh_dist_launch(psm_ctx* c, int mode, char bound, bool pick, uint32_t grid, WorldMeshDistArgs a);
 

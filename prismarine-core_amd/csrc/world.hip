@@ -29,7 +29,7 @@
 #include "psm_common.h"
 #include "psm_internal.h"
 #include "psm_query_dev.h"    // the constants, the triangle / box / point tests, inst_point / inst_rotate, INSIDE_DIR
-#include "psm_query_host.h"   // QueryKind, check_data / check_instances, batch_args / launch
+#include "psm_query_host.h"   // QueryKind, check_data / check_instances, batch_args / launch; mesh.hip's shared host pieces
 #include "psm_world_dev.h"    // WorldRow / WorldNode / WorldArgs, the WORLD_* constants, world_walk, load_row / load_pose,
                               // WorldBest, WorldRay
 #define PSM_KLIST_FN PSM_D
@@ -890,69 +890,48 @@ int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* 
 
 const char* const WORLD_MESH_NAME[] = {"psm_world_mesh_overlaps_dev", "psm_world_mesh_count_dev", "psm_world_mesh_triangles_dev"};
 
-// A mesh query of a world (world_mesh.hip): mesh.hip's mesh_query() with a world where the queried hierarchy was.
-// The NULL world and p == 0 are answered before anything else is looked at; then the data, k, the other hierarchy's state and
-// context, the stale check (every world query's), the poses, skip, the number of answers -- all on the host, before any launch,
-// the outputs untouched. Then the poses go to the device (mesh.hip's pose area: a copy on the context's stream and one
-// synchronisation, the other hierarchy's leaf count coming back in the same wait), the outputs are cleared in stream order, and
-// one kernel runs unless the world is empty or the other hierarchy has no leaf. mode: 0 overlaps, 1 count, 2 triangles
+// A world's skip argument: an instance index, or -1
+int world_mesh_skip_ok(const psm_world* w, const char* name, int32_t skip) {
+    if (skip >= -1 && (skip < 0 || (uint32_t)skip < w->count)) return PSM_OK;
+    return mesh_refuse(w->ctx, PSM_ERR_INVALID, "%s: skip %d of a world of %u (-1: no instance is left out)", name, (int)skip, w->count);
+}
+
+// A mesh query of a world (world_mesh.hip): mesh.hip's mesh_query() with a world where the queried hierarchy was,
+// of the same shared pieces (psm_query_host.h). The NULL world and p == 0 are answered before anything else is
+// looked at; then the data, k, the other hierarchy's state and context, the stale check (every world query's), the poses, skip,
+// the number of answers -- all on the host, before any launch, the outputs untouched. Then the upload (one synchronisation),
+// the outputs are cleared in stream order, and one kernel runs unless the world is empty or the other hierarchy has no leaf.
+// mode: 0 overlaps, 1 count, 2 triangles
 int world_mesh_query(psm_world* w, psm_bvh* o, const float* poses, size_t p, int32_t skip, int mode, uint32_t k, void* d_out,
                      int32_t* d_inst, uint32_t* d_count) {
     if (!w) return PSM_ERR_INVALID;
     if (p == 0) return PSM_OK;
     psm_ctx* c = w->ctx;
     const char* name = WORLD_MESH_NAME[mode];
-    char msg[192];
     const bool rows = mode == 2;
-    if (!o || !poses || !d_out || (rows && (!d_inst || !d_count))) {
-        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (mode != 0 && ((uintptr_t)d_out & 3u) != 0) {
-        snprintf(msg, sizeof msg, "%s: %s not 4-byte aligned", name, rows ? "tris" : "counts");
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (rows && (((uintptr_t)d_inst & 3u) != 0 || ((uintptr_t)d_count & 3u) != 0)) {
-        snprintf(msg, sizeof msg, "%s: %s not 4-byte aligned", name, ((uintptr_t)d_inst & 3u) != 0 ? "inst" : "counts");
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (rows && (k == 0 || k > PSM_QUERY_K_MAX)) {
-        snprintf(msg, sizeof msg, "%s: k must be 1 .. %d", name, PSM_QUERY_K_MAX);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
+    int rc = mesh_pointers(c, name, o && poses && d_out && (!rows || (d_inst && d_count)));
+    if (rc == PSM_OK && mode != 0) rc = mesh_aligned(c, name, rows ? "tris" : "counts", d_out, 4);
+    if (rc == PSM_OK && rows) rc = mesh_aligned(c, name, "inst", d_inst, 4);
+    if (rc == PSM_OK && rows) rc = mesh_aligned(c, name, "counts", d_count, 4);
+    if (rc != PSM_OK) return rc;
+    if (rows && (k == 0 || k > PSM_QUERY_K_MAX)) return mesh_refuse(c, PSM_ERR_INVALID, "%s: k must be 1 .. %d", name, PSM_QUERY_K_MAX);
     if (!o->built) return set_err(c, PSM_ERR_STATE, "mesh query before build");
-    if (o->ctx != c) {
-        snprintf(msg, sizeof msg, "%s: the world and the other hierarchy are of different contexts", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
+    if (o->ctx != c) return mesh_refuse(c, PSM_ERR_INVALID, "%s: the world and the other hierarchy are of different contexts", name);
     const int stale = first_stale(w);
     if (stale >= 0) return refuse_stale(w, name, stale);
-    for (size_t q = 0; q < p; q++)
-        if (const char* why = pose_fault(poses + 12 * q)) {
-            snprintf(msg, sizeof msg, "%s: pose %zu %s", name, q, why);
-            return set_err(c, PSM_ERR_INVALID, msg);
-        }
-    if (skip < -1 || (skip >= 0 && (uint32_t)skip >= w->count)) {
-        snprintf(msg, sizeof msg, "%s: skip %d of a world of %u (-1: no instance is left out)", name, (int)skip, w->count);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
     const uint32_t T = o->tri_count;
-    if ((uint64_t)p * T >= WORLD_MESH_ANSWERS_MAX) {
-        snprintf(msg, sizeof msg, "%s: %zu poses of %u triangles are more than 2^32 answers", name, p, T);
-        return set_err(c, PSM_ERR_CAPACITY, msg);
-    }
+    rc = mesh_poses_rigid(c, name, poses, p);
+    if (rc == PSM_OK) rc = world_mesh_skip_ok(w, name, skip);
+    if (rc == PSM_OK) rc = mesh_answers_fit(c, name, p, T);
+    if (rc != PSM_OK) return rc;
     (void)hipSetDevice(c->device);
     uint32_t L = 0;
     void* d_poses = nullptr;
     WorldMeshArgs m = {};
     uint32_t grid = 0;
     if (w->count != 0) {   // (an empty world: no query kernel, nothing to upload; the clears alone)
-        int rc = poses_for(c, p * 12 * sizeof(float), &d_poses);
+        rc = mesh_upload(c, o, poses, p, &d_poses, nullptr, &L);
         if (rc != PSM_OK) return rc;
-        PSM_HIP(c, hipMemcpyAsync(d_poses, poses, p * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        PSM_HIP(c, hipMemcpyAsync(&L, o->d_small + SM_COUNT, sizeof L, hipMemcpyDeviceToHost, c->stream));
-        PSM_HIP(c, hipStreamSynchronize(c->stream));
-        if (L > T) return set_err(c, PSM_ERR_STATE, "mesh query: the other hierarchy's leaf count exceeds its triangle count");
         // (the context's stack area is allocated here, on its first query: the last thing that can fail before the outputs change)
         rc = batch_args(c, nullptr, p * (size_t)L, d_out, k, m.w, grid);
         if (rc != PSM_OK) return rc;
@@ -974,79 +953,44 @@ int world_mesh_query(psm_world* w, psm_bvh* o, const float* poses, size_t p, int
     m.w.nodes = w->d_nodes;
     m.tri48 = o->d_tri48; m.leaf_tri = o->d_leaftri; m.poses = (const float4*)d_poses;
     m.L = L; m.T = T; m.skip = skip;
-    // The flag kernel's skip of lanes whose pose is already flagged: mesh.hip's rule (on by itself where the launch takes the
-    // grid-stride loop) and mesh.hip's study knob, PSM_MESH_SKIP = 0 / 1 (psm_hip.h)
-    const char* knob = getenv("PSM_MESH_SKIP");
-    const bool strided = (p * (size_t)L + QUERY_BLOCK - 1) / QUERY_BLOCK > QUERY_GRID_CAP;
-    m.flags = (knob ? knob[0] != '0' : strided) ? WORLD_MESH_FLAG_SKIP : 0u;
+    m.flags = mesh_skip(p * (size_t)L) ? WORLD_MESH_FLAG_SKIP : 0u;   // (read by the flag kernel alone)
     return world_mesh_launch(c, mode, grid, m);
 }
 
 const char* const WORLD_MESH_DIST_NAME[] = {"psm_world_mesh_closest_dev", "psm_world_mesh_within_dev", "psm_world_mesh_clearance_dev"};
 
-// A mesh clearance query of a world (world_mesh_dist.hip): world_mesh_query()'s checks in its order and with its
-// texts under the new names, and the alignment of the records; all on the host, before any launch, the outputs untouched. Then
-// the poses go to the device as world_mesh_query() sends them (one copy, one synchronisation), every word of the clearance
-// query is set to "none" in stream order, and the kernels run -- unless the world is empty or the other hierarchy has no leaf:
-// then the miss records are written without a walk. mode: WMD_CLOSEST, WMD_WITHIN, WMD_CLEAR
+// A mesh clearance query of a world (world_mesh_dist.hip): world_mesh_query()'s sequence with the records'
+// alignment where its k was; all on the host, before any launch, the outputs untouched. Then the upload (one synchronisation),
+// every word of the clearance query is set to "none" in stream order, and the kernels run -- unless the world is empty or the
+// other hierarchy has no leaf: then the miss records are written without a walk. mode: WMD_CLOSEST, WMD_WITHIN, WMD_CLEAR
 int world_mesh_dist_query(psm_world* w, psm_bvh* o, const float* poses, size_t p, int32_t skip, int mode, float rmax, void* d_out,
                           int32_t* d_inst) {
     if (!w) return PSM_ERR_INVALID;
     if (p == 0) return PSM_OK;
     psm_ctx* c = w->ctx;
     const char* name = WORLD_MESH_DIST_NAME[mode];
-    char msg[192];
     const bool records = mode != WMD_WITHIN;
-    if (!o || !poses || !d_out || (records && !d_inst)) {
-        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (records && ((uintptr_t)d_out & 15u) != 0) {
-        snprintf(msg, sizeof msg, "%s: hits not 16-byte aligned", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (records && ((uintptr_t)d_inst & 3u) != 0) {
-        snprintf(msg, sizeof msg, "%s: inst not 4-byte aligned", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
+    int rc = mesh_pointers(c, name, o && poses && d_out && (!records || d_inst));
+    if (rc == PSM_OK && records) rc = mesh_aligned(c, name, "hits", d_out, 16);
+    if (rc == PSM_OK && records) rc = mesh_aligned(c, name, "inst", d_inst, 4);
+    if (rc != PSM_OK) return rc;
     if (!o->built) return set_err(c, PSM_ERR_STATE, "mesh query before build");
-    if (o->ctx != c) {
-        snprintf(msg, sizeof msg, "%s: the world and the other hierarchy are of different contexts", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
+    if (o->ctx != c) return mesh_refuse(c, PSM_ERR_INVALID, "%s: the world and the other hierarchy are of different contexts", name);
     const int stale = first_stale(w);
     if (stale >= 0) return refuse_stale(w, name, stale);
-    for (size_t q = 0; q < p; q++)
-        if (const char* why = pose_fault(poses + 12 * q)) {
-            snprintf(msg, sizeof msg, "%s: pose %zu %s", name, q, why);
-            return set_err(c, PSM_ERR_INVALID, msg);
-        }
-    if (skip < -1 || (skip >= 0 && (uint32_t)skip >= w->count)) {
-        snprintf(msg, sizeof msg, "%s: skip %d of a world of %u (-1: no instance is left out)", name, (int)skip, w->count);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
     const uint32_t T = o->tri_count;
-    if ((uint64_t)p * T >= WORLD_MESH_ANSWERS_MAX) {
-        snprintf(msg, sizeof msg, "%s: %zu poses of %u triangles are more than 2^32 answers", name, p, T);
-        return set_err(c, PSM_ERR_CAPACITY, msg);
-    }
+    rc = mesh_poses_rigid(c, name, poses, p);
+    if (rc == PSM_OK) rc = world_mesh_skip_ok(w, name, skip);
+    if (rc == PSM_OK) rc = mesh_answers_fit(c, name, p, T);
+    if (rc != PSM_OK) return rc;
     (void)hipSetDevice(c->device);
     uint32_t L = 0;
     void *d_poses = nullptr, *d_keys = nullptr;
     WorldMeshDistArgs a = {};
     uint32_t grid = 0;
-    int rc = PSM_OK;
     if (w->count != 0) {   // (an empty world: no query kernel, nothing to upload; the miss records alone)
-        rc = poses_for(c, p * 12 * sizeof(float), &d_poses);
+        rc = mesh_upload(c, o, poses, p, &d_poses, mode == WMD_CLEAR ? &d_keys : nullptr, &L);
         if (rc != PSM_OK) return rc;
-        if (mode == WMD_CLEAR) {
-            rc = mesh_keys_for(c, p * sizeof(uint64_t), &d_keys);
-            if (rc != PSM_OK) return rc;
-        }
-        PSM_HIP(c, hipMemcpyAsync(d_poses, poses, p * 12 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        PSM_HIP(c, hipMemcpyAsync(&L, o->d_small + SM_COUNT, sizeof L, hipMemcpyDeviceToHost, c->stream));
-        PSM_HIP(c, hipStreamSynchronize(c->stream));
-        if (L > T) return set_err(c, PSM_ERR_STATE, "mesh query: the other hierarchy's leaf count exceeds its triangle count");
         // (the context's stack area is allocated here, on its first query: the last thing that can fail before the outputs change)
         rc = batch_args(c, nullptr, p * (size_t)L, d_out, 0, a.m.w, grid);
         if (rc != PSM_OK) return rc;
@@ -1072,17 +1016,13 @@ int world_mesh_dist_query(psm_world* w, psm_bvh* o, const float* poses, size_t p
     a.rmax = rmax;
     if (mode == WMD_CLOSEST) return world_mesh_dist_launch(c, WMD_CLOSEST, 0, false, grid, a);
     if (mode == WMD_WITHIN) {
-        // the skip of lanes whose pose is already flagged, under the mesh queries' rule and knob (world_mesh_query() above)
-        const char* knob = getenv("PSM_MESH_SKIP");
-        const bool strided = (p * (size_t)L + QUERY_BLOCK - 1) / QUERY_BLOCK > QUERY_GRID_CAP;
-        a.m.flags = (knob ? knob[0] != '0' : strided) ? WORLD_MESH_FLAG_SKIP : 0u;
+        a.m.flags = mesh_skip(p * (size_t)L) ? WORLD_MESH_FLAG_SKIP : 0u;
         return world_mesh_dist_launch(c, WMD_WITHIN, 0, false, grid, a);
     }
-    // every word: "none"; the clearance kernel (PSM_MESH_BOUND = 0 .. 3: the study knob of mesh_dist.hip, the same answer under
-    // each); then one lane per pose walks the winner again and writes the record (a word left at "none": the miss)
+    // every word: "none"; the clearance kernel (mesh_bound(): the study knob, the same answer under each letter); then one lane
+    // per pose walks the winner again and writes the record (a word left at "none": the miss)
     PSM_HIP(c, hipMemsetAsync(d_keys, 0xff, p * sizeof(uint64_t), c->stream));
-    const char* knob = getenv("PSM_MESH_BOUND");
-    rc = world_mesh_dist_launch(c, WMD_CLEAR, knob ? knob[0] : '1', false, grid, a);
+    rc = world_mesh_dist_launch(c, WMD_CLEAR, mesh_bound(), false, grid, a);
     if (rc != PSM_OK) return rc;
     WorldMeshDistArgs pick = a;
     rc = batch_args(c, nullptr, p, d_out, 0, pick.m.w, grid);

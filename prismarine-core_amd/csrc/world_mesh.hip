@@ -139,10 +139,9 @@ __global__ __launch_bounds__(QUERY_BLOCK, WORLD_MESH_WAVES) void world_query_mes
     world_walk(m.w, q);
 }
 
-// world.hip's host path (world_mesh_query(): the checks, the stale refusal, the pose upload, the clears, the grid) launches
-// through this. mode: 0 overlaps, 1 count, 2 triangles (a.w.samples = k, 1 .. PSM_QUERY_K_MAX: the list's LDS is the launch's)
-static_assert(WORLD_MESH_ANSWERS_MAX == MESH_QUERIES_MAX, "one bound on the answers of a call");
-
+// world.hip's host path (world_mesh_query(): the stale refusal, the clears, the grid and, shared with the other posed-mesh
+// entry points through mesh.hip, the checks and the upload) launches through this. mode: 0 overlaps, 1 count, 2 triangles
+// (a.w.samples = k, 1 .. PSM_QUERY_K_MAX: the list's LDS is the launch's)
 int world_mesh_launch(psm_ctx* c, int mode, uint32_t grid, WorldMeshArgs a) {
     a.magic = mesh_magic(a.L);
     if (mode == WMESH_ANY) world_query_mesh_any<<<grid, QUERY_BLOCK, 0, c->stream>>>(a);

@@ -254,8 +254,8 @@ __global__ __launch_bounds__(256) void world_mesh_dist_fill(float4* hits, int32_
     }
 }
 
-// world.hip's host path (world_mesh_dist_query(): the checks, the stale refusal, the pose upload, the words, the grid) launches
-// through this (psm_world_dev.h has the modes)
+// world.hip's host path (world_mesh_dist_query(): the stale refusal, the fill, the words' reset, the grid and, shared with the
+// other posed-mesh entry points through mesh.hip, the checks and the upload) launches through this (psm_world_dev.h has the modes)
 int world_mesh_dist_launch(psm_ctx* c, int mode, char bound, bool pick, uint32_t grid, WorldMeshDistArgs a) {
     a.m.magic = mesh_magic(a.m.L);
     if (mode == WMD_FILL) {

@@ -314,7 +314,9 @@ def test_library_exports_world_mesh_clearance(psm):
         assert text in src, text
     assert "asm(" not in src and "asm volatile" not in src                                 # plain HIP atomics throughout
     host = open(os.path.join(csrc, "world.hip")).read()
-    assert 'getenv("PSM_MESH_BOUND")' in host and "hipMemsetAsync(d_keys, 0xff" in host
+    # (the knob is read once for every clearance entry point, beside the other shared host pieces: DESIGN.md 4.28)
+    assert 'getenv("PSM_MESH_BOUND")' in open(os.path.join(csrc, "mesh.hip")).read() and "mesh_bound()" in host
+    assert "hipMemsetAsync(d_keys, 0xff" in host
     for doc in ("README.md", "INTEGRATION.md", "DESIGN.md"):
         assert "clearanceToMesh" in open(os.path.join(ROOT, doc)).read(), doc
 
