@@ -89,5 +89,16 @@ namespace NSM {
         int closestToMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, float rmax, psm_tri_hit * d_hits, int32_t * d_inst);
         int withinOfMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, float r, uint8_t * d_flag);
         int clearanceToMesh(TriangleHierarchy * other, const glm::mat4 * poses, size_t p, int skip, float rmax, psm_mesh_hit * d_hits, int32_t * d_inst);
+        // the voxels of a regular WORLD grid that a posed triangle of some instance overlaps (one 64-bit word per 4 x 4 x 4 brick,
+        // TriangleHierarchy::voxelize's layout), the same with the inside filled by the vote of `samples` (1, 3 or 5) rays of
+        // inside() from each voxel's centre, the number of (instance, triangle) pairs per voxel and the lowest instance that has a
+        // triangle in it (-1: none), both dense [nz][ny][nx]; each voxel answered as overlapsBox / countInBox / trianglesInBox(k =
+        // 1) answer its box (psm_hip.h "voxel grids over a world"; psm_grid_world_surface_dev / psm_grid_world_solid_dev /
+        // psm_grid_world_counts_dev / psm_grid_world_instances_dev). The result is read back into the vector (the call waits for
+        // it; a refused call leaves the vector empty); the flat lists have no grids
+        int voxelize(const psm_grid & grid, std::vector<uint64_t> & bricks);
+        int voxelizeSolid(const psm_grid & grid, uint32_t samples, std::vector<uint64_t> & bricks);
+        int voxelCounts(const psm_grid & grid, std::vector<uint32_t> & counts);
+        int voxelInstances(const psm_grid & grid, std::vector<int32_t> & labels);
     };
 }

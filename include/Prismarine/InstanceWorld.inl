@@ -152,4 +152,23 @@ namespace NSM {
         check(rc, "InstanceWorld::clearanceToMesh");
         return rc;
     }
+    // (gridReadBack: TriangleHierarchy.inl -- one call into a device buffer, read back into the vector)
+    inline int InstanceWorld::voxelize(const psm_grid & grid, std::vector<uint64_t> & bricks) {
+        return gridReadBack<uint64_t>((size_t)psm_grid_brick_count(&grid), bricks, "InstanceWorld::voxelize",
+                                      [&](uint64_t * d) { return psm_grid_world_surface_dev(world, &grid, d); });
+    }
+    inline int InstanceWorld::voxelizeSolid(const psm_grid & grid, uint32_t samples, std::vector<uint64_t> & bricks) {
+        return gridReadBack<uint64_t>((size_t)psm_grid_brick_count(&grid), bricks, "InstanceWorld::voxelizeSolid",
+                                      [&](uint64_t * d) { return psm_grid_world_solid_dev(world, &grid, samples, d); });
+    }
+    inline int InstanceWorld::voxelCounts(const psm_grid & grid, std::vector<uint32_t> & counts) {
+        const size_t cells = psm_grid_brick_count(&grid) ? (size_t)grid.dims[0] * grid.dims[1] * grid.dims[2] : 0;
+        return gridReadBack<uint32_t>(cells, counts, "InstanceWorld::voxelCounts",
+                                      [&](uint32_t * d) { return psm_grid_world_counts_dev(world, &grid, d); });
+    }
+    inline int InstanceWorld::voxelInstances(const psm_grid & grid, std::vector<int32_t> & labels) {
+        const size_t cells = psm_grid_brick_count(&grid) ? (size_t)grid.dims[0] * grid.dims[1] * grid.dims[2] : 0;
+        return gridReadBack<int32_t>(cells, labels, "InstanceWorld::voxelInstances",
+                                     [&](int32_t * d) { return psm_grid_world_instances_dev(world, &grid, d); });
+    }
 }

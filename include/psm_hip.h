@@ -1196,7 +1196,8 @@ int psm_world_mesh_clearance_dev(psm_world* world, psm_bvh* other, const float* 
  *     MiB, freed with the context), and its inside launches use the context's stack area, which the context's first query
  *     allocates: capture it only after a plain call with a grid at least as large
  *   - 0 leaves: all zero; 1 leaf: that leaf is tested; after psm_bvh_refit the refitted boxes are used
- *   - not covered: grids over a world, a flat scene or an instanced list; a signed-distance grid; a sparse output (a list of
+ *   - not covered: grids over a flat scene or an instanced list (a world has its own, "voxel grids over a world" below); a
+ *     signed-distance grid; a sparse output (a list of
  *     the non-empty bricks); a coarse level that culls empty regions before the brick walk; conservative or 6-separating thin
  *     voxelisation; oriented grids */
 #define PSM_GRID_DIM_MAX (1u << 20)
@@ -1209,6 +1210,38 @@ int psm_grid_surface_dev(psm_bvh* bvh, const psm_grid* grid, uint64_t* d_bricks)
 int psm_grid_counts_dev(psm_bvh* bvh, const psm_grid* grid, uint32_t* d_counts);
 int psm_grid_solid_dev(psm_bvh* bvh, const psm_grid* grid, uint32_t samples, uint64_t* d_bricks);
 uint64_t psm_grid_brick_count(const psm_grid* grid);   /* 0 for an invalid grid (NULL too); host only */
+
+/* voxel grids over a world (new; no reference counterpart): the grids above over the posed instances of a
+ * psm_world -- the occupancy map of an assembled scene whose bodies move by a matrix per step --, and which body owns each
+ * voxel. psm_grid, its validity rules, the voxel box, the centre, the brick layout and psm_grid_brick_count are those of "voxel
+ * grids"; the grid is a WORLD grid and is never moved. The answers are DEFINED by the world's box and inside queries, voxel by
+ * voxel and bit for bit; world_grid.hip gets them with one wave per 4 x 4 x 4 brick, which walks the tree over the instances and
+ * the hierarchies it enters once for its 64 voxels. Semantics:
+ *   - surface: a voxel's bit is 1 iff psm_world_box_overlaps_dev answers 1 for the voxel's box; one 64-bit word per brick,
+ *     the bits of voxels outside dims 0, exactly psm_grid_surface_dev's layout
+ *   - counts: d_counts[(iz * ny + iy) * nx + ix] = what psm_world_box_count_dev answers for the voxel's box: the number of
+ *     (instance, triangle) pairs; dense, nx ny nz entries
+ *   - instances (the owner): d_inst[(iz * ny + iy) * nx + ix] = slot 0 of the instance row psm_world_box_triangles_dev(k = 1)
+ *     answers for the voxel's box: the lowest instance index that has a counting triangle, -1 for none; dense int32
+ *   - solid: a voxel's bit is its surface bit | what psm_world_inside_dev(centre, samples) answers, samples 1, 3 or 5
+ *   - nothing depends on the order of the walk or on timing: a flag, a sum, a minimum
+ *   - refusals, all on the host before any launch and with the output untouched, in this order: NULL world (PSM_ERR_INVALID, no
+ *     message: there is no context to hold one); NULL grid or output; an invalid grid ("<name>: invalid grid: <why>"); d_bricks
+ *     not 8-byte, d_counts or d_inst not 4-byte aligned; samples not 1, 3 or 5 (PSM_ERR_INVALID). Then an empty world is answered
+ *     in stream order without a query kernel: zero words, zero counts, -1 labels. Then a world one of whose hierarchies was
+ *     rebuilt after psm_world_set_instances is refused as by every world query (PSM_ERR_STATE). The depth rule is
+ *     psm_world_set_instances': a world that was accepted fits the wave's one stack
+ *   - the grid is host memory, read during the call. The calls are stream-ordered on the world's context. surface, counts and
+ *     instances allocate nothing and can be captured into a graph. solid runs the surface launch and then, per slab of at most
+ *     65 536 bricks, the centres, psm_world_inside_dev and the fill, with the context-owned scratch and the stack area of "voxel
+ *     grids"
+ *   - not covered: grids over a flat scene or an instanced list; the skip of one instance; per-voxel lists of more than one
+ *     instance; a signed-distance grid; a sparse output; a coarse level that culls empty bricks before the walk; oriented grids;
+ *     graph capture of solid */
+int psm_grid_world_surface_dev(psm_world* world, const psm_grid* grid, uint64_t* d_bricks);
+int psm_grid_world_counts_dev(psm_world* world, const psm_grid* grid, uint32_t* d_counts);
+int psm_grid_world_instances_dev(psm_world* world, const psm_grid* grid, int32_t* d_inst);
+int psm_grid_world_solid_dev(psm_world* world, const psm_grid* grid, uint32_t samples, uint64_t* d_bricks);
 
 /* ---------------------------------------------------------------------------------------------
  * several frames in flight (new; DESIGN.md "lanes")

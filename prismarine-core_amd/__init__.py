@@ -48,6 +48,7 @@ EXPORTS = [
     "psm_world_mesh_overlaps_dev", "psm_world_mesh_count_dev", "psm_world_mesh_triangles_dev",
     "psm_world_mesh_closest_dev", "psm_world_mesh_within_dev", "psm_world_mesh_clearance_dev",
     "psm_grid_surface_dev", "psm_grid_counts_dev", "psm_grid_solid_dev", "psm_grid_brick_count",
+    "psm_grid_world_surface_dev", "psm_grid_world_counts_dev", "psm_grid_world_instances_dev", "psm_grid_world_solid_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -492,7 +493,8 @@ class TriangleHierarchy:
         for that box: one call, no box records, 8 bytes of answer per 64 voxels. Returns VoxelGrid: bricks [nbz, nby, nbx] of 4 x 4
         x 4 voxels, a uint64 word each (with as_torch=True an int64 tensor of the same bits on the context's device, the launch
         ordered against torch's current stream by events, no host synchronisation); dense() and occupied() read them. An invalid
-        grid raises ValueError before any call. QueryScene, InstancedScene and InstanceWorld have no grids."""
+        grid raises ValueError before any call. QueryScene and InstancedScene have no grids; InstanceWorld has its own (voxelize /
+        voxelCounts / voxelInstances: the grid in world space)."""
         g = _grid(origin, cell, dims)
         if solid:
             name, extra = "psm_grid_solid_dev", (C.c_uint32(_samples(samples, "psm_grid_solid_dev")),)
@@ -1679,6 +1681,46 @@ class InstanceWorld(QueryScene):
         if out == "bool":
             return _bool_view(res[0])
         return QueryTriHits(*res) if out == "closest" else QueryMeshHits(res[0], True, res[1])
+
+    def voxelize(self, origin, cell, dims, solid=False, samples=3, as_torch=False):
+        """The voxels of a regular WORLD grid that a posed triangle of some instance overlaps (psm_grid_world_surface_dev; not in
+        the reference), or with solid=True those and the voxels whose centre inside() takes as inside with `samples` (1, 3 or 5)
+        rays (psm_grid_world_solid_dev). The grid, its voxel boxes (voxel_boxes()) and the VoxelGrid returned are
+        TriangleHierarchy.voxelize()'s; a voxel's bit is bit for bit what overlapsBox() answers for its box: one call, no box
+        records. An invalid grid raises ValueError before any call. Not covered: the skip of one instance, a signed-distance
+        grid, sparse output, oriented grids, graph capture of solid."""
+        g = _grid(origin, cell, dims)
+        if solid:
+            name, extra = "psm_grid_world_solid_dev", (C.c_uint32(_samples(samples, "psm_grid_world_solid_dev")),)
+        else:
+            name, extra = "psm_grid_world_surface_dev", ()
+        nb = tuple((int(d) + 3) // 4 for d in g.dims)
+        bricks = self._grid_call(g, name, extra, (nb[2], nb[1], nb[0]), np.uint64, as_torch)
+        return VoxelGrid(bricks, tuple(g.dims), tuple(g.origin), tuple(g.cell))
+
+    def voxelCounts(self, origin, cell, dims, as_torch=False):
+        """How many (instance, triangle) pairs overlap each voxel of a regular world grid (psm_grid_world_counts_dev; not in the
+        reference): uint32 [nz, ny, nx] (an int32 tensor with as_torch=True), each entry what countInBox() answers for the voxel's
+        box. Arguments and placement as voxelize()."""
+        g = _grid(origin, cell, dims)
+        return self._grid_call(g, "psm_grid_world_counts_dev", (), (g.dims[2], g.dims[1], g.dims[0]), np.uint32, as_torch)
+
+    def voxelInstances(self, origin, cell, dims, as_torch=False):
+        """Which body owns each voxel of a regular world grid (psm_grid_world_instances_dev; not in the reference): int32 [nz, ny,
+        nx], the lowest instance index that has a triangle overlapping the voxel -- trianglesInBox(lo, hi, 1).geom[:, 0] of the
+        voxel's box --, -1 where voxelCounts() is 0: a labelled occupancy map. Arguments and placement as voxelize()."""
+        g = _grid(origin, cell, dims)
+        return self._grid_call(g, "psm_grid_world_instances_dev", (), (g.dims[2], g.dims[1], g.dims[0]), np.int32, as_torch)
+
+    def _grid_call(self, g, name, extra, shape, dtype, as_torch):
+        """one grid call of the world (TriangleHierarchy._grid_call's shape)"""
+        self._fresh(name)
+        fn = getattr(lib(), name)
+
+        def call(d_out):
+            self.ctx.check(fn(self._w, C.byref(g), *extra, C.c_void_p(d_out)), name)
+
+        return _device_call(self.ctx, call, [(shape, dtype)], as_torch)[0]
 
     def _call(self, name, d_in, n, extra, d_out, d_geom):
         name = name.replace("psm_bvh_", "psm_world_")

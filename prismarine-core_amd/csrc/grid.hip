@@ -184,13 +184,8 @@ __global__ __launch_bounds__(QUERY_BLOCK, 8) void grid_fill(GridArgs g) {
     }
 }
 
-namespace {
-
-// A grid as the host reads it: the brick counts, or why it is refused (psm_hip.h "voxel grids": the rules in their order)
-struct GridShape {
-    uint32_t nb[3];
-    uint64_t bricks;
-};
+// A grid as the host reads it: the brick counts, or why it is refused (psm_hip.h "voxel grids": the rules in their order;
+// GridShape: psm_query_host.h -- the grids over a world, world.hip, read a grid by the same rules)
 const char* grid_fault(const psm_grid* g, GridShape& s) {
     s = GridShape();
     for (int k = 0; k < 3; k++)
@@ -210,9 +205,11 @@ const char* grid_fault(const psm_grid* g, GridShape& s) {
     return nullptr;
 }
 
+namespace {
+
 // solid's scratch, per context (grown on demand, at most SLAB_BRICKS bricks of points and flags: 68 MiB; every call runs on
 // the context's stream, never two at once)
-constexpr uint32_t SLAB_BRICKS = 1u << 16;
+constexpr uint32_t SLAB_BRICKS = GRID_SLAB_BRICKS;
 constexpr size_t SLAB_BRICK_BYTES = (size_t)QUERY_BLOCK * (sizeof(float4) + sizeof(uint8_t));
 struct Scratch {
     void* ptr = nullptr;
@@ -220,6 +217,21 @@ struct Scratch {
 };
 std::mutex scratch_mu;
 std::unordered_map<const psm_ctx*, Scratch> scratch_area;
+
+uint32_t grid_for(uint64_t bricks) { return (uint32_t)(bricks < QUERY_GRID_CAP ? bricks : QUERY_GRID_CAP); }
+
+// the grid's nine numbers and its bricks as the kernels take them
+GridArgs grid_args(const psm_grid* grid, const GridShape& s) {
+    GridArgs g = {};
+    g.ox = grid->origin[0]; g.oy = grid->origin[1]; g.oz = grid->origin[2];
+    g.cx = grid->cell[0]; g.cy = grid->cell[1]; g.cz = grid->cell[2];
+    g.nx = grid->dims[0]; g.ny = grid->dims[1]; g.nz = grid->dims[2];
+    g.nbx = s.nb[0]; g.nby = s.nb[1];
+    g.first = 0u; g.bricks = (uint32_t)s.bricks;
+    return g;
+}
+
+}  // namespace
 
 int scratch_for(psm_ctx* c, uint32_t bricks, void** out) {
     std::lock_guard<std::mutex> lk(scratch_mu);
@@ -238,10 +250,28 @@ int scratch_for(psm_ctx* c, uint32_t bricks, void** out) {
     return PSM_OK;
 }
 
+int grid_centres_launch(psm_ctx* c, const psm_grid* grid, const GridShape& s, uint32_t first, uint32_t bricks, void* points) {
+    GridArgs g = grid_args(grid, s);
+    g.first = first; g.bricks = bricks;
+    g.points = (float4*)points;
+    grid_centres<<<grid_for(bricks), QUERY_BLOCK, 0, c->stream>>>(g);
+    PSM_HIP(c, hipGetLastError());
+    return PSM_OK;
+}
+
+int grid_fill_launch(psm_ctx* c, const psm_grid* grid, const GridShape& s, uint32_t first, uint32_t bricks, const uint8_t* flags, uint64_t* words) {
+    GridArgs g = grid_args(grid, s);
+    g.first = first; g.bricks = bricks;
+    g.flags = flags; g.words = words;
+    grid_fill<<<grid_for(bricks), QUERY_BLOCK, 0, c->stream>>>(g);
+    PSM_HIP(c, hipGetLastError());
+    return PSM_OK;
+}
+
+namespace {
+
 const char* const GRID_NAME[] = {"psm_grid_surface_dev", "psm_grid_counts_dev", "psm_grid_solid_dev"};
 enum { CALL_SURFACE = 0, CALL_COUNTS = 1, CALL_SOLID = 2 };
-
-uint32_t grid_for(uint64_t bricks) { return (uint32_t)(bricks < QUERY_GRID_CAP ? bricks : QUERY_GRID_CAP); }
 
 // A grid call: a NULL hierarchy is answered before anything else; then the pointers, the grid, the alignment, samples, the
 // state, the depth -- all on the host, before any launch, the output untouched.
@@ -271,14 +301,8 @@ int grid_query(psm_bvh* b, const psm_grid* grid, int call, uint32_t samples, voi
     if (!b->built) return set_err(c, PSM_ERR_STATE, "grid query before build");
     if (depth_bound(b) > QSTACK_MAX) return set_err(c, PSM_ERR_CAPACITY, "grid query: hierarchy deeper than the query stack");
     (void)hipSetDevice(c->device);
-    GridArgs g = {};
+    GridArgs g = grid_args(grid, s);
     g.sm = b->d_small; g.sorted_tri = b->d_sorted_tri;
-    g.ox = grid->origin[0]; g.oy = grid->origin[1]; g.oz = grid->origin[2];
-    g.cx = grid->cell[0]; g.cy = grid->cell[1]; g.cz = grid->cell[2];
-    g.nx = grid->dims[0]; g.ny = grid->dims[1]; g.nz = grid->dims[2];
-    g.nbx = s.nb[0]; g.nby = s.nb[1];
-    g.first = 0u; g.bricks = (uint32_t)s.bricks;
-    g.words = (uint64_t*)d_out;
     void* scratch = nullptr;
     const uint32_t slab = s.bricks < SLAB_BRICKS ? (uint32_t)s.bricks : SLAB_BRICKS;
     if (call == CALL_SOLID) {   // (the last thing that can fail before the output changes)
@@ -291,18 +315,16 @@ int grid_query(psm_bvh* b, const psm_grid* grid, int call, uint32_t samples, voi
     if (call != CALL_SOLID) return PSM_OK;
     // the inside of the surface, a slab of bricks at a time, all in stream order: the centres, query.hip's inside path over
     // them, the flags' ballots ORed into the words
-    g.points = (float4*)scratch;
-    g.flags = (const uint8_t*)scratch + (size_t)slab * QUERY_BLOCK * sizeof(float4);
+    uint8_t* flags = grid_slab_flags(scratch, slab);
     for (uint64_t first = 0; first < s.bricks; first += slab) {
         const uint64_t left = s.bricks - first;
-        g.first = (uint32_t)first;
-        g.bricks = left < slab ? (uint32_t)left : slab;
-        grid_centres<<<grid_for(g.bricks), QUERY_BLOCK, 0, c->stream>>>(g);
-        PSM_HIP(c, hipGetLastError());
-        const int rc = psm_bvh_inside_dev(b, (const psm_point_query*)g.points, (size_t)g.bricks * QUERY_BLOCK, samples, (uint8_t*)g.flags);
+        const uint32_t bricks = left < slab ? (uint32_t)left : slab;
+        int rc = grid_centres_launch(c, grid, s, (uint32_t)first, bricks, scratch);
         if (rc != PSM_OK) return rc;
-        grid_fill<<<grid_for(g.bricks), QUERY_BLOCK, 0, c->stream>>>(g);
-        PSM_HIP(c, hipGetLastError());
+        rc = psm_bvh_inside_dev(b, (const psm_point_query*)scratch, (size_t)bricks * QUERY_BLOCK, samples, flags);
+        if (rc != PSM_OK) return rc;
+        rc = grid_fill_launch(c, grid, s, (uint32_t)first, bricks, flags, (uint64_t*)d_out);
+        if (rc != PSM_OK) return rc;
     }
     return PSM_OK;
 }

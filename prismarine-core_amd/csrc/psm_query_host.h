@@ -27,6 +27,24 @@ bool mesh_skip(size_t queries);
 char mesh_bound();
 uint64_t bvh_generation(const psm_bvh* b);    // api.hip: bumped by every build of the hierarchy
 
+// grid.hip: the host pieces the grids over a hierarchy and over a world share (grid.hip, world.hip's world_grid_query();
+// DESIGN.md 4.27, 4.29). A grid as the host reads it: the bricks per axis and in all
+struct GridShape {
+    uint32_t nb[3];
+    uint64_t bricks;
+};
+// Why a grid is refused, or NULL with s filled in (psm_hip.h "voxel grids": the rules in their order)
+const char* grid_fault(const psm_grid* g, GridShape& s);
+// solid's scratch of the context for slabs of at most `bricks` bricks (<= GRID_SLAB_BRICKS), grown on demand and released by
+// grid_release: bricks x 64 centres (psm_point_query records in lane order), then at grid_slab_flags() the bricks x 64 flags
+constexpr uint32_t GRID_SLAB_BRICKS = 1u << 16;
+int scratch_for(psm_ctx* c, uint32_t bricks, void** out);
+inline uint8_t* grid_slab_flags(void* scratch, uint32_t slab) { return (uint8_t*)scratch + (size_t)slab * 64 * 16; }
+// solid's two launches around the inside query of a slab, the bricks [first, first + bricks) of the grid, on the context's
+// stream: the centres into points; the ballots of flags ORed into words (a word per brick of the whole grid)
+int grid_centres_launch(psm_ctx* c, const psm_grid* g, const GridShape& s, uint32_t first, uint32_t bricks, void* points);
+int grid_fill_launch(psm_ctx* c, const psm_grid* g, const GridShape& s, uint32_t first, uint32_t bricks, const uint8_t* flags, uint64_t* words);
+
 // (Q_FIRST_HITS, Q_NEAREST: the k-best queries of kbest.hip and of world.hip's worlds: no entry in the kernel tables; Q_BOX_ANY,
 // Q_BOX_COUNT, Q_BOX_TRIS: the box queries of box.hip and world_box.hip: no entry there either; Q_SWEEP, Q_SWEEP_ANY: the sphere
 // sweeps of sweep.hip and world_sweep.hip: no entry there either; Q_TRI_ANY, Q_TRI_COUNT, Q_TRI_TRIS: the triangle queries of tri.hip and world_tri.hip: no entry

@@ -87,13 +87,17 @@ struct WorldBoxPrune {
         float M[16];
 #pragma unroll
         for (int k = 0; k < 16; k++) M[k] = u2f(r.sm[SM_M + k]);
-        const v3 T = mk3(r.m[3], r.m[7], r.m[11]);
+        intervals(M, r.m);
+        return r;
+    }
+    // ... from the hierarchy's fit transform M and the instance's pose m (world_grid.hip comes here with a row its wave loaded)
+    PSM_D void intervals(const float* M, const float* m) {
+        const v3 T = mk3(m[3], m[7], m[11]);
         const v3 sl = lo - T, sh = hi - T;
         const float reach = smaxf(absmax3(sl), absmax3(sh)) + WORLD_BOX_QREL * qmax;
-        axis(M, r.m, 0, sl, sh, reach, glx, ghx);
-        axis(M, r.m, 1, sl, sh, reach, gly, ghy);
-        axis(M, r.m, 2, sl, sh, reach, glz, ghz);
-        return r;
+        axis(M, m, 0, sl, sh, reach, glx, ghx);
+        axis(M, m, 1, sl, sh, reach, gly, ghy);
+        axis(M, m, 2, sl, sh, reach, glz, ghz);
     }
     // a child box [mn, mx] is kept iff it meets the grown interval on all three axes (negations: a NaN keeps the box)
     PSM_D bool keep(float mnx, float mny, float mnz, float mxx, float mxy, float mxz) const {

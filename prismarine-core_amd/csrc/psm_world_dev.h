@@ -1,5 +1,5 @@
 // psm_world_dev.h -- the device pieces the kernel files of a world share (world.hip, world_box.hip, world_sweep.hip,
-// world_tri.hip, world_tri_dist.hip, world_mesh.hip, world_mesh_dist.hip): the table row, the node of the tree over the instances, the kernel arguments, the padding and the slacks,
+// world_tri.hip, world_tri_dist.hip, world_mesh.hip, world_mesh_dist.hip, world_grid.hip): the table row, the node of the tree over the instances, the kernel arguments, the padding and the slacks,
 // the two-level walk, the loads of a row, the best record of a world (WorldBest) and a ray in a world (WorldRay). Moved here
 // from world.hip as they were; every kernel of world.hip compiles to the same instructions as with the pieces in its own file
 // (tools/kernel_diff.py; the digests of tests/test_world_query_cpu.py and tests/test_world_kbest_cpu.py).
@@ -96,9 +96,24 @@ enum { WMD_CLOSEST = 0, WMD_WITHIN = 1, WMD_CLEAR = 2, WMD_PICK = 3, WMD_FILL = 
 // WMD_FILL: the miss record in a.m.w.n cells of hits (the word after s, t: -1 where the records are psm_mesh_hit, `pick`) and -1 in geom
 int world_mesh_dist_launch(psm_ctx* c, int mode, char bound, bool pick, uint32_t grid, WorldMeshDistArgs a);
 
+// A voxel grid over a world (world_grid.hip): the grid's nine numbers, its bricks, the world's root. The table
+// and the tree travel beside it as kernel parameters of their own
+struct WorldGridArgs {
+    float ox, oy, oz, cx, cy, cz;   // psm_grid: origin, cell
+    uint32_t nx, ny, nz;            // ... dims
+    uint32_t nbx, nby;              // bricks along x and y
+    uint32_t bricks;                // all of them: one launch
+    int root;                       // as WorldArgs
+};
+enum { WGRID_SURFACE = 0, WGRID_COUNTS = 1, WGRID_INSTANCES = 2 };
+
+// world_grid.hip: the launch of a world's grid kernel for world.hip's host path (world_grid_query()). out: a uint64_t word per
+// brick (WGRID_SURFACE), the dense uint32_t [nz][ny][nx] counts (WGRID_COUNTS) or int32_t labels (WGRID_INSTANCES)
+int world_grid_launch(psm_ctx* c, int mode, uint32_t grid, const WorldGridArgs& g, const WorldRow* rows, const WorldNode* nodes, void* out);
+
 namespace {
 
-constexpr int WORLD_TOP = 0x40000000;   // tag of a top-level node link (hierarchy node links stay below 2^28)
+constexpr int WORLD_TOP = 0x40000000;  // tag of a top-level node link (hierarchy node links stay below 2^28)
 
 // The padding and the slacks (DESIGN.md 4.11 has the derivation). The box test works on the world query and the forward image
 // of the object box, T + R box; the candidate test on the query moved by inst_point / inst_rotate, R^T (x - T). They differ by

@@ -1030,6 +1030,81 @@ int world_mesh_dist_query(psm_world* w, psm_bvh* o, const float* poses, size_t p
     return world_mesh_dist_launch(c, WMD_PICK, 0, true, grid, pick);
 }
 
+const char* const WORLD_GRID_NAME[] = {"psm_grid_world_surface_dev", "psm_grid_world_counts_dev", "psm_grid_world_instances_dev",
+                                       "psm_grid_world_solid_dev"};
+enum { WGRID_SOLID = 3 };   // (beside psm_world_dev.h's WGRID_SURFACE, WGRID_COUNTS, WGRID_INSTANCES: the surface launch, then the fill)
+
+// A grid over a world (world_grid.hip): grid.hip's grid_query() with a world where the hierarchy was, of the same
+// shared pieces (psm_query_host.h). The NULL world is answered before anything else is looked at; then the pointers, the grid,
+// the alignment, samples -- all on the host, before any launch, the output untouched. An empty world is answered in stream order
+// without a query kernel; then the stale refusal (every world query's). The depth rule is psm_world_set_instances': the wave's one
+// stack holds depth + deepest + 1 links. Solid: the surface launch, then grid.hip's scheme slab by slab with
+// psm_world_inside_dev where the hierarchy's inside query was
+int world_grid_query(psm_world* w, const psm_grid* grid, int call, uint32_t samples, void* d_out) {
+    if (!w) return PSM_ERR_INVALID;
+    psm_ctx* c = w->ctx;
+    const char* name = WORLD_GRID_NAME[call];
+    char msg[160];
+    if (!grid || !d_out) {
+        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    GridShape s;
+    if (const char* why = grid_fault(grid, s)) {
+        snprintf(msg, sizeof msg, "%s: invalid grid: %s", name, why);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    const bool words = call == WGRID_SURFACE || call == WGRID_SOLID;
+    const unsigned align = words ? 8u : 4u;
+    if (((uintptr_t)d_out & (uintptr_t)(align - 1u)) != 0) {
+        snprintf(msg, sizeof msg, "%s: %s not %u-byte aligned", name, words ? "bricks" : (call == WGRID_COUNTS ? "counts" : "inst"), align);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (call == WGRID_SOLID && samples != 1 && samples != 3 && samples != 5) {
+        snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    (void)hipSetDevice(c->device);
+    if (w->count == 0) {   // an empty world: no voxel is set, no query kernel runs
+        const size_t voxels = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];   // (a valid grid: below 2^37)
+        if (words) PSM_HIP(c, hipMemsetAsync(d_out, 0, (size_t)s.bricks * sizeof(uint64_t), c->stream));
+        else PSM_HIP(c, hipMemsetAsync(d_out, call == WGRID_COUNTS ? 0 : 0xFF, voxels * sizeof(uint32_t), c->stream));
+        return PSM_OK;
+    }
+    const int stale = first_stale(w);
+    if (stale >= 0) return refuse_stale(w, name, stale);
+    WorldGridArgs g = {};
+    g.ox = grid->origin[0]; g.oy = grid->origin[1]; g.oz = grid->origin[2];
+    g.cx = grid->cell[0]; g.cy = grid->cell[1]; g.cz = grid->cell[2];
+    g.nx = grid->dims[0]; g.ny = grid->dims[1]; g.nz = grid->dims[2];
+    g.nbx = s.nb[0]; g.nby = s.nb[1];
+    g.bricks = (uint32_t)s.bricks;
+    g.root = w->count == 1 ? ~0 : 0;
+    void* scratch = nullptr;
+    const uint32_t slab = s.bricks < GRID_SLAB_BRICKS ? (uint32_t)s.bricks : GRID_SLAB_BRICKS;
+    if (call == WGRID_SOLID) {   // (the last thing that can fail before the output changes)
+        const int rc = scratch_for(c, slab, &scratch);
+        if (rc != PSM_OK) return rc;
+    }
+    const uint32_t blocks = (uint32_t)(s.bricks < QUERY_GRID_CAP ? s.bricks : QUERY_GRID_CAP);
+    int rc = world_grid_launch(c, call == WGRID_SOLID ? (int)WGRID_SURFACE : call, blocks, g, w->d_rows, w->d_nodes, d_out);
+    if (rc != PSM_OK || call != WGRID_SOLID) return rc;
+    // the inside of the surface, a slab of bricks at a time, all in stream order: the centres, the world's inside query over
+    // them, the flags' ballots ORed into the words
+    uint8_t* flags = grid_slab_flags(scratch, slab);
+    for (uint64_t first = 0; first < s.bricks; first += slab) {
+        const uint64_t left = s.bricks - first;
+        const uint32_t bricks = left < slab ? (uint32_t)left : slab;
+        rc = grid_centres_launch(c, grid, s, (uint32_t)first, bricks, scratch);
+        if (rc != PSM_OK) return rc;
+        rc = psm_world_inside_dev(w, (const psm_point_query*)scratch, (size_t)bricks * QUERY_BLOCK, samples, flags);
+        if (rc != PSM_OK) return rc;
+        rc = grid_fill_launch(c, grid, s, (uint32_t)first, bricks, flags, (uint64_t*)d_out);
+        if (rc != PSM_OK) return rc;
+    }
+    return PSM_OK;
+}
+
 template <class T>
 int world_alloc(psm_ctx* c, T** p, size_t n) {
     PSM_HIP(c, hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
@@ -1225,4 +1300,16 @@ int psm_world_mesh_within_dev(psm_world* w, psm_bvh* other, const float* poses, 
 int psm_world_mesh_clearance_dev(psm_world* w, psm_bvh* other, const float* poses, size_t p, int32_t skip, float rmax, psm_mesh_hit* d_hits,
                                  int32_t* d_inst) {
     return psm::world_mesh_dist_query(w, other, poses, p, skip, psm::WMD_CLEAR, rmax, d_hits, d_inst);
+}
+int psm_grid_world_surface_dev(psm_world* w, const psm_grid* grid, uint64_t* d_bricks) {
+    return psm::world_grid_query(w, grid, psm::WGRID_SURFACE, 0, d_bricks);
+}
+int psm_grid_world_counts_dev(psm_world* w, const psm_grid* grid, uint32_t* d_counts) {
+    return psm::world_grid_query(w, grid, psm::WGRID_COUNTS, 0, d_counts);
+}
+int psm_grid_world_instances_dev(psm_world* w, const psm_grid* grid, int32_t* d_inst) {
+    return psm::world_grid_query(w, grid, psm::WGRID_INSTANCES, 0, d_inst);
+}
+int psm_grid_world_solid_dev(psm_world* w, const psm_grid* grid, uint32_t samples, uint64_t* d_bricks) {
+    return psm::world_grid_query(w, grid, psm::WGRID_SOLID, samples, d_bricks);
 }

@@ -106,6 +106,13 @@ medians of REPS; one timed call where a side's warm-up call takes more than WMCL
 before: the torus posed on the host, closestToTriangle over the p x T triangles, the minimum per pose on the host, and with (2)
 the same call under PSM_MESH_BOUND=0. Both ratios and whether the two paths agree in (dist, tri, other, instance) at every pose.
 Each case's figures are also appended to WMCLEAR_LOG as they come. No ratio is fixed in advance.
+`query_bench.py worldgrids`: the voxel grids over a world (psm_grid_world_surface_dev / _counts_dev / _instances_dev / _solid_dev) on
+the worldboxes mode's world, the torus at 256 and 4 096 turned grid poses (WORLD_GRID_POSES): 64^3, 128^3 and 256^3 grids over the
+world's bounds (GRID_SIZES), per size surface, counts and instances alternated A B A B (host-timed medians of REPS) with overlapsBox /
+countInBox / trianglesInBox(k = 1) over voxel_boxes() of the same grid, twice: launch against launch with the box records resident,
+and the package's whole call from host memory (the records' packing and upload and the answers' read-back included). Also solid at
+3 rays, the occupied voxels, and whether all three answers were the box queries' (same_answers).
+
 `query_bench.py grids`: the voxel grids (psm_grid_surface_dev / psm_grid_counts_dev / psm_grid_solid_dev) on the Sponza-class scene:
 64^3, 128^3 and 256^3 grids over its bounds (GRID_SIZES), per size the ms of surface, counts and solid (3 rays), the occupied voxels,
 and surface alternated A B A B (host-timed medians of REPS) with the way a caller had to the same bits -- boxOverlaps over
@@ -1948,6 +1955,99 @@ def grids():
     print(json.dumps(out))
 
 
+def worldgrids():
+    """the voxel grids over a world against the world's box queries over voxel_boxes() of the same grid"""
+    lib = psm.lib()
+    ctx = psm.Context(0)
+    tor = torus(48, 24, 0.7, 0.25)
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(tor.shape[0])
+    th.loadTriangles(tor)
+    th.build()
+    rng = np.random.RandomState(1)
+    out = {"mode": "worldgrids", "torus_triangles": int(tor.shape[0]), "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+    for poses_n in (int(x) for x in os.environ.get("WORLD_GRID_POSES", "256,4096").split(",")):
+        side = int(np.ceil(np.sqrt(poses_n)))      # the worldboxes mode's world: a grid of poses, each turned about a random axis
+        poses = np.zeros((poses_n, 3, 4), np.float32)
+        k_ = np.arange(poses_n)
+        for j in range(poses_n):
+            q, r = np.linalg.qr(rng.normal(size=(3, 3)))
+            poses[j, :, :3] = q * np.sign(np.diag(r))
+        poses[:, 0, 3], poses[:, 1, 3] = 2.5 * (k_ % side), 2.5 * (k_ // side)
+        lo = np.array([-1.25, -1.25, -1.25])
+        hi = np.array([2.5 * (side - 1) + 1.25, 2.5 * ((poses_n - 1) // side) + 1.25, 1.25])
+        wd = psm.InstanceWorld(ctx, [(th, m) for m in poses])
+        w = wd._w
+        for g in (int(x) for x in os.environ.get("GRID_SIZES", "64,128,256").split(",")):
+            origin, cell, dims = lo, (hi - lo) / g, (g, g, g)
+            n = g ** 3
+            grid = psm._grid(origin, cell, dims)
+            bricks = ((g + 3) // 4) ** 3
+            blo, bhi = psm.voxel_boxes(origin, cell, dims)
+            rec = np.zeros((n, 8), np.float32)
+            rec[:, 0:3], rec[:, 4:7] = blo, bhi
+            hs = [ctx.buf_alloc(x) for x in (32 * n, n, 4 * n, 4 * n, 4 * n, 8 * bricks, 4 * n, 4 * n)]
+            p_rec, p_flag, p_count, p_row, p_rinst, p_words, p_cells, p_labels = (C.c_void_p(ctx.buf_ptr(h)[0]) for h in hs)
+            ctx.buf_upload(hs[0], rec)
+            del rec
+            size = C.c_size_t(n)
+
+            def surface():
+                ctx.check(lib.psm_grid_world_surface_dev(w, C.byref(grid), p_words), "psm_grid_world_surface_dev")
+
+            def counts():
+                ctx.check(lib.psm_grid_world_counts_dev(w, C.byref(grid), p_cells), "psm_grid_world_counts_dev")
+
+            def owners():
+                ctx.check(lib.psm_grid_world_instances_dev(w, C.byref(grid), p_labels), "psm_grid_world_instances_dev")
+
+            def solid():
+                ctx.check(lib.psm_grid_world_solid_dev(w, C.byref(grid), C.c_uint32(3), p_words), "psm_grid_world_solid_dev")
+
+            def box_overlaps():
+                ctx.check(lib.psm_world_box_overlaps_dev(w, p_rec, size, p_flag), "psm_world_box_overlaps_dev")
+
+            def box_count():
+                ctx.check(lib.psm_world_box_count_dev(w, p_rec, size, p_count), "psm_world_box_count_dev")
+
+            def box_first():
+                ctx.check(lib.psm_world_box_triangles_dev(w, p_rec, size, C.c_uint32(1), p_row, p_rinst, p_count), "psm_world_box_triangles_dev")
+
+            key = "poses%d_g%d_" % (poses_n, g)
+            out[key + "voxels"] = n
+            # (1) the records resident: launch against launch. (2) the whole call from host memory: the grid's nine numbers and
+            # the read-back of its answer against voxel_boxes()' records packed, uploaded, queried and read back
+            out[key + "surface_ms"], out[key + "overlaps_resident_ms"] = abab(ctx, surface, box_overlaps)
+            out[key + "counts_ms"], out[key + "count_resident_ms"] = abab(ctx, counts, box_count)
+            out[key + "instances_ms"], out[key + "triangles_k1_resident_ms"] = abab(ctx, owners, box_first)
+            out[key + "surface_call_ms"], out[key + "overlaps_with_upload_ms"] = abab(ctx, lambda: wd.voxelize(origin, cell, dims), lambda: wd.overlapsBox(blo, bhi))
+            out[key + "counts_call_ms"], out[key + "count_with_upload_ms"] = abab(ctx, lambda: wd.voxelCounts(origin, cell, dims), lambda: wd.countInBox(blo, bhi))
+            out[key + "instances_call_ms"], out[key + "triangles_k1_with_upload_ms"] = abab(ctx, lambda: wd.voxelInstances(origin, cell, dims),
+                                                                                          lambda: wd.trianglesInBox(blo, bhi, 1))
+            surface()
+            ctx.sync()
+            words = ctx.buf_download(hs[5], np.uint64, bricks).reshape(((g + 3) // 4,) * 3)
+            vg = psm.VoxelGrid(words, dims, tuple(grid.origin), tuple(grid.cell))
+            out[key + "solid_ms"] = round(median_ms(ctx, solid), 4)
+            filled = psm.VoxelGrid(ctx.buf_download(hs[5], np.uint64, bricks).reshape(((g + 3) // 4,) * 3), dims, tuple(grid.origin), tuple(grid.cell))
+            out[key + "occupied"], out[key + "occupied_solid"] = vg.occupied(), filled.occupied()
+            box_overlaps(); box_count(); counts()
+            ctx.sync()
+            flags, cells = ctx.buf_download(hs[1], np.uint8, n), ctx.buf_download(hs[6], np.uint32, n)
+            same = np.array_equal(vg.dense().reshape(-1), flags.view(np.bool_)) and np.array_equal(cells, ctx.buf_download(hs[2], np.uint32, n))
+            box_first(); owners()
+            ctx.sync()
+            same = same and np.array_equal(ctx.buf_download(hs[7], np.int32, n), ctx.buf_download(hs[4], np.int32, n))
+            out[key + "same_answers"] = bool(same)
+            out[key + "mean_count"] = round(float(cells.mean()), 3)
+            for h in hs:
+                ctx.buf_free(h)
+        wd.close()
+    th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def main():
     sc = scenes.sponza_like()
     ctx = psm.Context(0)
@@ -2013,4 +2113,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "world-clearance": worldclearance, "world-mesh-clearance": worldmeshclearance, "worldmeshes": worldmeshes, "grids": grids}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "world-clearance": worldclearance, "world-mesh-clearance": worldmeshclearance, "worldmeshes": worldmeshes, "grids": grids, "worldgrids": worldgrids}.get(" ".join(sys.argv[1:]), main)()
