@@ -17,6 +17,7 @@ import box_query_model as BQ
 import instance_query_model as NQ
 import world_box_query_model as WB
 from util import ROOT, csrc_asm, kernel_asm, kernel_meta
+from world_pose_cases import touching_boxes as _touching_boxes
 
 F = np.float32
 D = np.float64
@@ -198,28 +199,6 @@ def _edge_pose(rng, t):
     e = np.abs(r.T @ r - np.eye(3)).max()
     assert 0.8e-5 < e <= 1e-5, e
     return p
-
-
-def _touching_boxes(rng, inst, scale, per):
-    """`per` world boxes per triangle of an instance that touch the posed triangle (float64) or miss it by a few ulps: a
-    corner, an edge or a face of the box through a vertex, a point of an edge or an interior point, moved by -8 .. 8 ulps"""
-    tris, cand, pose, _ = inst
-    v0, e1, e2 = (x.astype(D) for x in WB.posed_leaves(np.asarray(tris, F)[np.sort(cand)], pose))
-    t = np.repeat(np.stack([v0, v0 + e1, v0 + e2], axis=1), per, axis=0)
-    n = t.shape[0]
-    w = rng.uniform(0, 1, (n, 3))
-    kind = rng.randint(0, 3, n)
-    w[kind == 0] = np.eye(3)[rng.randint(0, 3, (kind == 0).sum())]
-    w[kind == 1, rng.randint(0, 3, (kind == 1).sum())] = 0
-    w /= w.sum(axis=1, keepdims=True)
-    q = (t * w[:, :, None]).sum(axis=1)
-    away = -np.sign(t.mean(axis=1) - q)
-    away[away == 0] = 1
-    ext = 10.0 ** rng.uniform(-3, 0.5, (n, 3)) * scale
-    back = np.where(rng.uniform(size=(n, 3)) < 0.3, rng.uniform(0, 1, (n, 3)) * ext, 0)
-    nudge = rng.randint(-8, 9, (n, 1)) * np.spacing(np.abs(q).astype(F)).astype(D)
-    a, b = q + away * (nudge - back), q + away * (nudge + ext)
-    return np.minimum(a, b).astype(F), np.maximum(a, b).astype(F)
 
 
 def test_prune_margin_covers_every_candidate_that_counts():

@@ -348,3 +348,17 @@ def move_discrepancy(pose, x):
     x32 = NQ.move(pose, np.asarray(x, F).reshape(1, 3))[0].astype(np.float64)
     back = np.linalg.solve(m[:, :3].T, x32) + m[:, 3]   # R^-T x' + T: the world point whose exact move is x'
     return float(np.abs(back - np.asarray(x, F).astype(np.float64)).max()), float(np.abs(x32).max())
+
+
+def forward_discrepancy(pose, x_obj):
+    """observed, the other way round and with no inverse in what is measured: the distance (float64, the largest coordinate)
+    between the forward image R x' + T of an object point -- what world_inst_boxes bounds -- and the float32 world point x whose
+    float32 move gives x'. x is the float nearest to the exact preimage T + R^-T x_obj, and x' is the move's own result for it
+    (x_obj up to the float32 grid), so the move's rounding and R against R^-T are both in the figure and the grid is not.
+    Returns (observed, the largest |coordinate| of x', x)."""
+    m = np.asarray(pose, F).reshape(3, 4).astype(np.float64)
+    xo = np.asarray(x_obj, np.float64).reshape(3)
+    x = (np.linalg.solve(m[:, :3].T, xo) + m[:, 3]).astype(F)
+    seen = NQ.move(pose, x.reshape(1, 3))[0].astype(np.float64)
+    fwd = m[:, :3] @ seen + m[:, 3]
+    return float(np.abs(fwd - x.astype(np.float64)).max()), float(np.abs(seen).max()), x
