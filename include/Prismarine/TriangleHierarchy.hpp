@@ -77,6 +77,13 @@ namespace NSM {
         int voxelize(const psm_grid & grid, std::vector<uint64_t> & bricks);
         int voxelizeSolid(const psm_grid & grid, uint32_t samples, std::vector<uint64_t> & bricks);
         int voxelCounts(const psm_grid & grid, std::vector<uint32_t> & counts);
+        // not in the reference: the distance from every voxel centre of a regular grid to the nearest triangle within rmax (>= 0
+        // or +inf; +inf in the field where there is none), dense [nz][ny][nx], and with tri the nearest triangle's id (-1 where
+        // there is none); signed: with the sign of the vote of `samples` (1, 3 or 5) rays from the centre. Each voxel answered as
+        // closestPoint / signedDistance answer its centre (psm_hip.h "voxel grids: distance fields"; psm_grid_distance_dev /
+        // psm_grid_signed_distance_dev). Read back into the vectors as voxelize does; returns the psm_status
+        int distanceField(const psm_grid & grid, float rmax, std::vector<float> & dist, std::vector<int32_t> * tri = nullptr);
+        int signedDistanceField(const psm_grid & grid, float rmax, uint32_t samples, std::vector<float> & dist, std::vector<int32_t> * tri = nullptr);
         // not in the reference: whether / how many / which triangles meet each of n query triangles (closed: touching counts; a
         // separating-axis test in float32, psm_hip.h "triangle queries"); triTriangles: 1 <= k <= PSM_QUERY_K_MAX, d_ids [n][k] =
         // the lowest ids that count, ascending, then -1, d_count [n] = the slots that hold one (psm_bvh_tri_overlaps_dev /

@@ -1197,7 +1197,7 @@ int psm_world_mesh_clearance_dev(psm_world* world, psm_bvh* other, const float* 
  *     allocates: capture it only after a plain call with a grid at least as large
  *   - 0 leaves: all zero; 1 leaf: that leaf is tested; after psm_bvh_refit the refitted boxes are used
  *   - not covered: grids over a flat scene or an instanced list (a world has its own, "voxel grids over a world" below); a
- *     signed-distance grid; a sparse output (a list of
+ *     sparse output (a list of
  *     the non-empty bricks); a coarse level that culls empty regions before the brick walk; conservative or 6-separating thin
  *     voxelisation; oriented grids */
 #define PSM_GRID_DIM_MAX (1u << 20)
@@ -1210,6 +1210,36 @@ int psm_grid_surface_dev(psm_bvh* bvh, const psm_grid* grid, uint64_t* d_bricks)
 int psm_grid_counts_dev(psm_bvh* bvh, const psm_grid* grid, uint32_t* d_counts);
 int psm_grid_solid_dev(psm_bvh* bvh, const psm_grid* grid, uint32_t samples, uint64_t* d_bricks);
 uint64_t psm_grid_brick_count(const psm_grid* grid);   /* 0 for an invalid grid (NULL too); host only */
+
+/* voxel grids: distance fields (new; no reference counterpart): the distance from every voxel centre of a
+ * psm_grid to the nearest triangle within rmax, and that triangle's id -- one call per grid, no point records. The answers are
+ * DEFINED by the point queries above, voxel by voxel and bit for bit; grid_dist.hip gets them with one wave per 4 x 4 x 4 brick,
+ * which walks the tree once for its 64 centres. psm_grid, its validity rules and the centre are those of "voxel grids".
+ * Semantics:
+ *   - d_dist[(iz * ny + iy) * nx + ix] (float32) is bit for bit the t psm_bvh_closest_point_dev writes for {centre, rmax}: +inf
+ *     when no triangle lies within rmax. d_tri (int32, same index) is that record's tri, the load-order id; on a bit-equal
+ *     squared distance the lowest id wins; -1 on a miss. Both dense, nx ny nz entries, no padding voxels. d_tri may be NULL: the
+ *     ids are then not stored
+ *   - signed: d_dist is bit for bit the t of psm_bvh_signed_distance_dev for {centre, rmax} with `samples` rays: the sign bit
+ *     is set iff the voxel has a record and psm_bvh_inside_dev(centre, samples) holds (-0 can occur); a voxel with no record
+ *     stays +inf, sign bit clear, and casts no rays. d_tri is unchanged by the sign
+ *   - u, v and the closest point itself are not written: psm_bvh_closest_point_dev answers them for the voxels that need them
+ *   - rmax must be >= 0 or +inf (-0 is 0); NaN or a negative rmax is refused, it does not become a grid of misses
+ *   - nothing depends on the order of the walk or on timing: a minimum with the lowest id on ties
+ *   - refusals, all on the host before any launch and with the outputs untouched, in this order: NULL bvh (PSM_ERR_INVALID, no
+ *     message); NULL grid or d_dist; an invalid grid; d_dist or d_tri not 4-byte aligned; rmax ("rmax must be >= 0"); samples
+ *     not 1, 3 or 5 (signed only; all PSM_ERR_INVALID); before the first build (PSM_ERR_STATE, "grid query before build"); a
+ *     hierarchy deeper than the query stack (PSM_ERR_CAPACITY)
+ *   - stream-ordered on the hierarchy's context. psm_grid_distance_dev allocates nothing and can be captured into a graph.
+ *     psm_grid_signed_distance_dev works a slab of at most 32 768 bricks at a time (the centres, the records, the sign kernel
+ *     of psm_bvh_signed_distance_dev over both, the records into the dense arrays) in solid's context-owned scratch, which it
+ *     allocates at its first use and grows for a larger grid (solid's 68 MiB at most, freed with the context); its sign launches use
+ *     the context's stack area, which the context's first query allocates
+ *   - 0 leaves: all +inf / -1; 1 leaf: that leaf is tested; after psm_bvh_refit the refitted boxes are used
+ *   - not covered: distance grids over a world, a flat scene or an instanced list; u, v and the closest point per voxel; a
+ *     per-voxel rmax; a sparse output; sweeping-based (approximate) distance transforms; graph capture of the signed call */
+int psm_grid_distance_dev(psm_bvh* bvh, const psm_grid* grid, float rmax, float* d_dist /*[nz][ny][nx]*/, int32_t* d_tri /*[nz][ny][nx] or NULL*/);
+int psm_grid_signed_distance_dev(psm_bvh* bvh, const psm_grid* grid, float rmax, uint32_t samples, float* d_dist, int32_t* d_tri);
 
 /* voxel grids over a world (new; no reference counterpart): the grids above over the posed instances of a
  * psm_world -- the occupancy map of an assembled scene whose bodies move by a matrix per step --, and which body owns each

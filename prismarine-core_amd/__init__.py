@@ -48,6 +48,7 @@ EXPORTS = [
     "psm_world_mesh_overlaps_dev", "psm_world_mesh_count_dev", "psm_world_mesh_triangles_dev",
     "psm_world_mesh_closest_dev", "psm_world_mesh_within_dev", "psm_world_mesh_clearance_dev",
     "psm_grid_surface_dev", "psm_grid_counts_dev", "psm_grid_solid_dev", "psm_grid_brick_count",
+    "psm_grid_distance_dev", "psm_grid_signed_distance_dev",
     "psm_grid_world_surface_dev", "psm_grid_world_counts_dev", "psm_grid_world_instances_dev", "psm_grid_world_solid_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
@@ -511,6 +512,38 @@ class TriangleHierarchy:
         g = _grid(origin, cell, dims)
         return self._grid_call(g, "psm_grid_counts_dev", (), (g.dims[2], g.dims[1], g.dims[0]), np.uint32, as_torch)
 
+    def distanceField(self, origin, cell, dims, rmax=np.inf, signed=False, samples=3, nearest=True, as_torch=False):
+        """The distance from every voxel centre of a regular grid to the nearest triangle (psm_grid_distance_dev; not in the
+        reference), or with signed=True that distance with the sign of inside(centre, samples) (psm_grid_signed_distance_dev):
+        a distance field for planners, collision margins, offset surfaces and narrow-band level sets in one call, with no point
+        records to make, upload or read back. origin, cell, dims: the grid, as voxelize() takes it; the centres are
+        voxel_centres()'s. rmax: the narrow band, >= 0 or inf; a voxel with no triangle within rmax holds +inf (and tri -1), and
+        in a signed field casts no rays and keeps its sign bit clear. Every voxel is bit for bit what closestPoint() /
+        signedDistance() answer for its centre with the same rmax and samples (t and tri; -0.0 can occur in a signed field); on
+        a bit-equal squared distance the lowest triangle id wins. Returns DistanceGrid: dist float32 [nz, ny, nx] and tri int32
+        [nz, ny, nx] (None with nearest=False: the ids are not stored); with as_torch=True torch tensors on the context's
+        device, the launch ordered against torch's current stream by events, no host synchronisation. An invalid grid and a NaN
+        or negative rmax raise ValueError before any call; samples other than 1, 3 or 5 are the library's to refuse. Not
+        covered: distance fields over a QueryScene, an InstancedScene or an InstanceWorld; u, v and the closest point per voxel
+        (closestPoint() answers them for the voxels that need them); a per-voxel rmax; a sparse output; sweeping-based
+        (approximate) distance transforms; graph capture of the signed call."""
+        g = _grid(origin, cell, dims)
+        r = float(rmax)
+        if not r >= 0.0:   # (NaN too)
+            raise ValueError("distance field: rmax must be >= 0")
+        if signed:
+            name, extra = "psm_grid_signed_distance_dev", (C.c_float(r), C.c_uint32(_samples(samples, "psm_grid_signed_distance_dev")))
+        else:
+            name, extra = "psm_grid_distance_dev", (C.c_float(r),)
+        fn = getattr(lib(), name)
+        shape = (g.dims[2], g.dims[1], g.dims[0])
+
+        def call(d_dist, d_tri=None):
+            self.ctx.check(fn(self._h, C.byref(g), *extra, C.c_void_p(d_dist), C.c_void_p(d_tri)), name)
+
+        outs = _device_call(self.ctx, call, [(shape, np.float32)] + ([(shape, np.int32)] if nearest else []), as_torch)
+        return DistanceGrid(outs[0], outs[1] if nearest else None, tuple(g.dims), tuple(g.origin), tuple(g.cell))
+
     def _grid_call(self, g, name, extra, shape, dtype, as_torch):
         """one grid call: the output [shape] of uint64 words or uint32 counts, on the device for torch, else staged and read back"""
         fn = getattr(lib(), name)
@@ -914,6 +947,16 @@ class VoxelGrid:
         """the number of voxels set: the sum of the words' popcounts"""
         words = self.bricks if isinstance(self.bricks, np.ndarray) else self.bricks.cpu().numpy().view(np.uint64)
         return int(np.unpackbits(np.ascontiguousarray(words).view(np.uint8)).sum(dtype=np.int64))
+
+
+class DistanceGrid:
+    """What TriangleHierarchy.distanceField returns. dist: float32 [nz, ny, nx], the (signed) distance at each voxel centre, +inf
+    where no triangle lies within rmax; tri: int32 [nz, ny, nx], the nearest triangle's id, -1 where dist is +inf, or None when
+    the ids were not asked for (numpy arrays, or torch tensors on the context's device). dims = (nx, ny, nz), origin and cell as
+    given (float32 values)."""
+
+    def __init__(self, dist, tri, dims, origin, cell):
+        self.dist, self.tri, self.dims, self.origin, self.cell = dist, tri, dims, origin, cell
 
 
 class QueryHitLists:

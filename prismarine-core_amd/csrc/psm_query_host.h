@@ -44,6 +44,9 @@ inline uint8_t* grid_slab_flags(void* scratch, uint32_t slab) { return (uint8_t*
 // stream: the centres into points; the ballots of flags ORed into words (a word per brick of the whole grid)
 int grid_centres_launch(psm_ctx* c, const psm_grid* g, const GridShape& s, uint32_t first, uint32_t bricks, void* points);
 int grid_fill_launch(psm_ctx* c, const psm_grid* g, const GridShape& s, uint32_t first, uint32_t bricks, const uint8_t* flags, uint64_t* words);
+// query.hip, for the signed distance grids (grid_dist.hip): the sign kernel of psm_bvh_signed_distance_dev alone over n points
+// and their closest-point records, on the context's stream; the caller has checked the hierarchy and samples
+int sign_launch(psm_bvh* b, const void* d_points, size_t n, uint32_t samples, void* d_hits);
 
 // (Q_FIRST_HITS, Q_NEAREST: the k-best queries of kbest.hip and of world.hip's worlds: no entry in the kernel tables; Q_BOX_ANY,
 // Q_BOX_COUNT, Q_BOX_TRIS: the box queries of box.hip and world_box.hip: no entry there either; Q_SWEEP, Q_SWEEP_ANY: the sphere

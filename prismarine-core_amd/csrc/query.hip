@@ -1073,6 +1073,19 @@ int check_instances(psm_ctx* c, const psm_instance* list, uint32_t count, const 
     return check_entries<InstEntry>(c, list, count, name);
 }
 
+// psm_grid_signed_distance_dev (grid_dist.hip): the second kernel of psm_bvh_signed_distance_dev alone, over n points and the
+// closest-point records a grid walk wrote for them. The caller has made every check (the hierarchy is built, samples is 1, 3 or 5)
+int sign_launch(psm_bvh* b, const void* d_points, size_t n, uint32_t samples, void* d_hits) {
+    QueryArgs qa = {};
+    uint32_t grid = 0;
+    const int rc = batch_args(b->ctx, d_points, n, d_hits, samples, qa, grid);
+    if (rc != PSM_OK) return rc;
+    qa.node32 = b->d_node32; qa.tri48 = b->d_tri48; qa.sm = b->d_small; qa.sorted_tri = b->d_sorted_tri;
+    bvh_query_sign<<<grid, QUERY_BLOCK, 0, b->ctx->stream>>>(qa);
+    PSM_HIP(b->ctx, hipGetLastError());
+    return PSM_OK;
+}
+
 }  // namespace psm
 
 int psm_bvh_intersect_dev(psm_bvh* bvh, const psm_query_ray* d_rays, size_t n, psm_hit* d_hits) {

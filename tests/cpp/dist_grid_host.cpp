@@ -1,0 +1,60 @@
+#include "Prismarine/Prismarine.hpp"
+#include "Prismarine/Implementations.hpp"   // as the reference: one translation unit of the application includes the bodies
+// The distance fields of the header layer (not in the reference) on a GPU: dist_grid_host <in> <out>.
+// <in>: int32 n; n x 9 float32 triangle positions; psm_grid (3 float32 origin, 3 float32 cell, 3 uint32 dims); float32 rmax;
+// uint32 samples.
+// <out>: uint64 V; V float32 dist, V int32 tri (unsigned); V float32 dist without ids; V float32 dist, V int32 tri (signed).
+// tests/test_gpu_dist_grid.py holds them to Python's.
+#include <cstdio>
+#include <vector>
+
+static_assert(sizeof(psm_grid) == 36, "psm_grid: nine 4-byte numbers");
+
+int main(int argc, char ** argv) {
+    if (argc != 3) return 2;
+    FILE * in = std::fopen(argv[1], "rb");
+    if (!in) return 3;
+    int32_t n = 0;
+    psm_grid grid;
+    float rmax = 0.0f;
+    uint32_t samples = 0;
+    if (std::fread(&n, sizeof n, 1, in) != 1 || n <= 0) return 4;
+    std::vector<float> pos((size_t)n * 9);
+    if (std::fread(pos.data(), sizeof(float), pos.size(), in) != pos.size()) return 4;
+    if (std::fread(&grid, sizeof grid, 1, in) != 1 || std::fread(&rmax, sizeof rmax, 1, in) != 1 ||
+        std::fread(&samples, sizeof samples, 1, in) != 1) return 4;
+    std::fclose(in);
+
+    psm::TriangleHierarchy th;
+    th.allocate((size_t)n);
+    th.loadTriangles(pos.data(), nullptr, nullptr, (size_t)n);
+    th.build();
+    std::vector<float> dist, alone, sdist, none;
+    std::vector<int32_t> tri, stri, ids;
+    if (th.distanceField(grid, rmax, dist, &tri) != PSM_OK || th.distanceField(grid, rmax, alone) != PSM_OK ||
+        th.signedDistanceField(grid, rmax, samples, sdist, &stri) != PSM_OK) return 5;
+    const size_t cells = (size_t)grid.dims[0] * grid.dims[1] * grid.dims[2];
+    if (dist.size() != cells || tri.size() != cells || alone.size() != cells || sdist.size() != cells || stri.size() != cells) return 6;
+    // a refusal leaves the vectors empty and says why
+    psm_grid bad = grid;
+    bad.cell[1] = 0.0f;
+    none.assign(3, 7.0f);
+    ids.assign(3, 7);
+    if (th.distanceField(bad, rmax, none, &ids) != PSM_ERR_INVALID || !none.empty() || !ids.empty()) return 7;
+    none.assign(3, 7.0f);
+    if (th.distanceField(grid, -1.0f, none) != PSM_ERR_INVALID || !none.empty()) return 7;
+    none.assign(3, 7.0f);
+    if (th.signedDistanceField(grid, rmax, 2u, none) != PSM_ERR_INVALID || !none.empty()) return 7;
+
+    FILE * out = std::fopen(argv[2], "wb");
+    if (!out) return 3;
+    const uint64_t V = cells;
+    std::fwrite(&V, sizeof V, 1, out);
+    std::fwrite(dist.data(), sizeof(float), cells, out);
+    std::fwrite(tri.data(), sizeof(int32_t), cells, out);
+    std::fwrite(alone.data(), sizeof(float), cells, out);
+    std::fwrite(sdist.data(), sizeof(float), cells, out);
+    std::fwrite(stri.data(), sizeof(int32_t), cells, out);
+    std::fclose(out);
+    return 0;
+}

@@ -118,6 +118,12 @@ and the package's whole call from host memory (the records' packing and upload a
 and surface alternated A B A B (host-timed medians of REPS) with the way a caller had to the same bits -- boxOverlaps over
 voxel_boxes of the same grid: the kernel alone over resident records, the package's torch call over resident lo / hi, and the same
 from host arrays (the box upload included) --, with a check that the bits are the same. No ratio is fixed in advance.
+`query_bench.py distgrids`: the distance-field grids (psm_grid_distance_dev / psm_grid_signed_distance_dev) on the Sponza-class
+scene: 64^3, 128^3 and 256^3 grids over its bounds (GRID_SIZES), rmax = +inf and a band of two cell diagonals, unsigned and signed
+with 3 rays; per case the field alternated A B A B (host-timed medians of REPS) with the way a caller had to the same bits --
+closestPoint / signedDistance over voxel_centres of the same grid: the entry point alone over resident records, the package's
+torch call over resident centres, and the same from host arrays (the upload included) --, the fraction of voxels with a triangle
+within rmax, and a check that dist and tri are the same bits (same_bits). No ratio is fixed in advance.
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -1955,6 +1961,81 @@ def grids():
     print(json.dumps(out))
 
 
+def distgrids():
+    """the distance-field grids against the point queries over voxel_centres() of the same grid"""
+    import torch   # (before the library loads its HIP runtime)
+    dev = torch.device("cuda", 0)
+    lib = psm.lib()
+    sc = scenes.sponza_like()
+    ctx = psm.Context(0, stream=torch.cuda.current_stream(dev).cuda_stream)   # torch's packing and the launches: one stream
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(sc["tris"].shape[0])
+    th.loadTriangles(sc["tris"], sc["normals"], sc["mats"])
+    th.build()
+    v = sc["tris"].reshape(-1, 3)
+    lo, hi = v.min(0).astype(np.float64), v.max(0).astype(np.float64)
+    out = {"mode": "distgrids", "reps": REPS, "lib": os.path.basename(psm.LIB_PATH), "tris": int(th.info().leaf_count)}
+    for g in (int(x) for x in os.environ.get("GRID_SIZES", "64,128,256").split(",")):
+        origin, cell, dims = lo, (hi - lo) / g, (g, g, g)
+        n = g ** 3
+        grid = psm._grid(origin, cell, dims)
+        dist = torch.zeros((g, g, g), dtype=torch.float32, device=dev)
+        tri = torch.zeros((g, g, g), dtype=torch.int32, device=dev)
+        p_dist, p_tri = C.c_void_p(dist.data_ptr()), C.c_void_p(tri.data_ptr())
+        centres = psm.voxel_centres(origin, cell, dims)
+        tcentres = torch.from_numpy(centres).to(dev)
+        records = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+        records[:, 0:3] = tcentres
+        hits = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+        p_rec, p_hits, size = C.c_void_p(records.data_ptr()), C.c_void_p(hits.data_ptr()), C.c_size_t(n)
+        out["g%d_voxels" % g] = n
+        band = 2.0 * float(np.linalg.norm(np.array(grid.cell, np.float64)))
+        for rname, rmax in (("inf", float("inf")), ("band", band)):
+            records[:, 3] = rmax
+            r32 = C.c_float(rmax)
+            for sname, samples in (("dist", None), ("signed", 3)):
+
+                def field():
+                    if samples is None:
+                        ctx.check(lib.psm_grid_distance_dev(th._h, C.byref(grid), r32, p_dist, p_tri), "psm_grid_distance_dev")
+                    else:
+                        ctx.check(lib.psm_grid_signed_distance_dev(th._h, C.byref(grid), r32, C.c_uint32(samples), p_dist, p_tri),
+                                  "psm_grid_signed_distance_dev")
+
+                # the parent's way to the same bits: the point query over the voxels' centres -- (1) the entry point alone over
+                # records that are resident, (2) the package's torch call over resident centres (it packs the records on the
+                # device), (3) the same from host arrays: the upload of 12 bytes per voxel included
+                def point_kernel():
+                    if samples is None:
+                        ctx.check(lib.psm_bvh_closest_point_dev(th._h, p_rec, size, p_hits), "psm_bvh_closest_point_dev")
+                    else:
+                        ctx.check(lib.psm_bvh_signed_distance_dev(th._h, p_rec, size, C.c_uint32(samples), p_hits), "psm_bvh_signed_distance_dev")
+
+                def point_torch(c=None):
+                    c = tcentres if c is None else c
+                    return th.closestPoint(c, rmax) if samples is None else th.signedDistance(c, rmax, samples)
+
+                def point_upload():
+                    return point_torch(torch.from_numpy(centres).to(dev))
+
+                key = "g%d_%s_%s_" % (g, rname, sname)
+                out[key + "field_ms"], out[key + "point_kernel_ms"] = abab(ctx, field, point_kernel)
+                out[key + "field_again_ms"], out[key + "point_torch_ms"] = abab(ctx, field, point_torch)
+                out[key + "field_third_ms"], out[key + "point_with_upload_ms"] = abab(ctx, field, point_upload)
+                field()
+                point_kernel()
+                ctx.sync()
+                out[key + "hit_fraction"] = round(float((tri >= 0).float().mean()), 4)
+                out[key + "same_bits"] = bool(torch.equal(dist.reshape(-1).view(torch.int32), hits[:, 2].contiguous().view(torch.int32))
+                                              and torch.equal(tri.reshape(-1), hits[:, 3].contiguous().view(torch.int32)))
+                out[key + "field_over_point_kernel"] = round(out[key + "field_ms"] / out[key + "point_kernel_ms"], 3)
+                out[key + "field_over_point_with_upload"] = round(out[key + "field_third_ms"] / out[key + "point_with_upload_ms"], 3)
+        del dist, tri, tcentres, records, hits
+    th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def worldgrids():
     """the voxel grids over a world against the world's box queries over voxel_boxes() of the same grid"""
     lib = psm.lib()
@@ -2113,4 +2194,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "world-clearance": worldclearance, "world-mesh-clearance": worldmeshclearance, "worldmeshes": worldmeshes, "grids": grids, "worldgrids": worldgrids}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "world-clearance": worldclearance, "world-mesh-clearance": worldmeshclearance, "worldmeshes": worldmeshes, "grids": grids, "distgrids": distgrids, "worldgrids": worldgrids}.get(" ".join(sys.argv[1:]), main)()
