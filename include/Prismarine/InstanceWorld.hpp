@@ -100,5 +100,15 @@ namespace NSM {
         int voxelizeSolid(const psm_grid & grid, uint32_t samples, std::vector<uint64_t> & bricks);
         int voxelCounts(const psm_grid & grid, std::vector<uint32_t> & counts);
         int voxelInstances(const psm_grid & grid, std::vector<int32_t> & labels);
+        // the distance from every voxel centre of a regular WORLD grid to the nearest posed triangle of any instance within rmax
+        // (+inf: none), that triangle's id and its instance (-1: none; on a bit-equal squared distance the lowest (instance,
+        // triangle)), and the same with the sign of inside(centre, samples); dense [nz][ny][nx], each voxel as
+        // closestPoint / signedDistance answer its centre (psm_hip.h "voxel grids over a world: distance fields";
+        // psm_grid_world_distance_dev / psm_grid_world_signed_distance_dev). tri, inst: NULL when not wanted. Read back as
+        // TriangleHierarchy::distanceField's; a refused call leaves the vectors empty
+        int distanceField(const psm_grid & grid, float rmax, std::vector<float> & dist, std::vector<int32_t> * tri = nullptr,
+                          std::vector<int32_t> * inst = nullptr);
+        int signedDistanceField(const psm_grid & grid, float rmax, uint32_t samples, std::vector<float> & dist, std::vector<int32_t> * tri = nullptr,
+                                std::vector<int32_t> * inst = nullptr);
     };
 }

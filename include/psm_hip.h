@@ -1236,8 +1236,9 @@ uint64_t psm_grid_brick_count(const psm_grid* grid);   /* 0 for an invalid grid 
  *     allocates at its first use and grows for a larger grid (solid's 68 MiB at most, freed with the context); its sign launches use
  *     the context's stack area, which the context's first query allocates
  *   - 0 leaves: all +inf / -1; 1 leaf: that leaf is tested; after psm_bvh_refit the refitted boxes are used
- *   - not covered: distance grids over a world, a flat scene or an instanced list; u, v and the closest point per voxel; a
- *     per-voxel rmax; a sparse output; sweeping-based (approximate) distance transforms; graph capture of the signed call */
+ *   - not covered: distance grids over a flat scene or an instanced list (a world has its own, "voxel grids over a world:
+ *     distance fields" below); u, v and the closest point per voxel; a per-voxel rmax; a sparse output; sweeping-based
+ *     (approximate) distance transforms; graph capture of the signed call */
 int psm_grid_distance_dev(psm_bvh* bvh, const psm_grid* grid, float rmax, float* d_dist /*[nz][ny][nx]*/, int32_t* d_tri /*[nz][ny][nx] or NULL*/);
 int psm_grid_signed_distance_dev(psm_bvh* bvh, const psm_grid* grid, float rmax, uint32_t samples, float* d_dist, int32_t* d_tri);
 
@@ -1266,12 +1267,50 @@ int psm_grid_signed_distance_dev(psm_bvh* bvh, const psm_grid* grid, float rmax,
  *     65 536 bricks, the centres, psm_world_inside_dev and the fill, with the context-owned scratch and the stack area of "voxel
  *     grids"
  *   - not covered: grids over a flat scene or an instanced list; the skip of one instance; per-voxel lists of more than one
- *     instance; a signed-distance grid; a sparse output; a coarse level that culls empty bricks before the walk; oriented grids;
- *     graph capture of solid */
+ *     instance; a sparse output; a coarse level that culls empty bricks before the walk; oriented grids;
+ *     graph capture of solid (the signed-distance grid of a world is the next section's) */
 int psm_grid_world_surface_dev(psm_world* world, const psm_grid* grid, uint64_t* d_bricks);
 int psm_grid_world_counts_dev(psm_world* world, const psm_grid* grid, uint32_t* d_counts);
 int psm_grid_world_instances_dev(psm_world* world, const psm_grid* grid, int32_t* d_inst);
 int psm_grid_world_solid_dev(psm_world* world, const psm_grid* grid, uint32_t samples, uint64_t* d_bricks);
+
+/* voxel grids over a world: distance fields (new; no reference counterpart): the distance from every voxel
+ * centre of a psm_grid to the nearest posed triangle of any instance of a psm_world within rmax, that triangle's id and its
+ * instance -- a planner's clearance map, or with the sign a narrow-band signed-distance grid, over bodies that each move by a
+ * matrix per step; one call per grid, no point records. psm_grid, its validity rules and the centre are those of "voxel
+ * grids"; the grid is a WORLD grid and is never moved. The answers are DEFINED by the world's point queries, voxel by voxel and
+ * bit for bit; world_grid_dist.hip gets them with one wave per 4 x 4 x 4 brick, which walks the tree over the instances and the
+ * hierarchies it enters once for its 64 centres. Semantics:
+ *   - d_dist[(iz * ny + iy) * nx + ix] (float32) is bit for bit the t psm_world_closest_point_dev writes for {centre, rmax}:
+ *     +inf when no triangle lies within rmax. d_tri (int32, same index) is that record's tri, d_inst (int32, same index) its
+ *     instance; -1 in both on a miss. On a bit-equal squared distance the lexicographically lowest (instance, triangle) wins.
+ *     All dense, nx ny nz entries, no padding voxels. d_tri and d_inst may each be NULL: they are then not stored
+ *   - signed: d_dist is bit for bit the t of psm_world_signed_distance_dev for {centre, rmax} with `samples` rays: the sign bit
+ *     is set iff the voxel has a record and psm_world_inside_dev(centre, samples) holds -- the parity summed over all
+ *     instances (-0 can occur); a voxel with no record stays +inf, sign bit clear, and casts no rays. d_tri and d_inst are
+ *     unchanged by the sign
+ *   - u, v and the closest point itself are not written: psm_world_closest_point_dev answers them for the voxels that need them
+ *   - rmax must be >= 0 or +inf (-0 is 0); NaN or a negative rmax is refused, it does not become a grid of misses
+ *   - nothing depends on the order of the walk or on timing: a minimum with the lowest (instance, triangle) on ties
+ *   - refusals, all on the host before any launch and with the outputs untouched, in this order: NULL world (PSM_ERR_INVALID, no
+ *     message: there is no context to hold one); NULL grid or d_dist; an invalid grid ("<name>: invalid grid: <why>"); d_dist,
+ *     d_tri or d_inst not 4-byte aligned; rmax ("rmax must be >= 0"); samples not 1, 3 or 5 (signed only; all PSM_ERR_INVALID).
+ *     Then an empty world is answered in stream order by fills alone, without a query kernel: +inf, -1, -1. Then a world one of
+ *     whose hierarchies was rebuilt after psm_world_set_instances is refused as by every world query (PSM_ERR_STATE). The depth
+ *     rule is psm_world_set_instances': a world that was accepted fits the wave's one stack
+ *   - the grid is host memory, read during the call. Stream-ordered on the world's context. psm_grid_world_distance_dev
+ *     allocates nothing and can be captured into a graph. psm_grid_world_signed_distance_dev works a slab of at most 32 768
+ *     bricks at a time (the centres, the walk's records, the sign kernel of psm_world_signed_distance_dev over both, the
+ *     records into the dense arrays; the instances are written by the walk) in the context-owned scratch of "voxel grids",
+ *     32 bytes a voxel, and its sign launches use the context's stack area
+ *   - instances of 0-leaf hierarchies hold nothing; a 1-leaf hierarchy's leaf is tested; after psm_bvh_refit and
+ *     psm_world_set_transforms over the whole range the refitted boxes are used
+ *   - not covered: distance grids over a flat scene or an instanced list; the skip of one instance; a per-voxel rmax; a sparse
+ *     output; graph capture of the signed call */
+int psm_grid_world_distance_dev(psm_world* world, const psm_grid* grid, float rmax, float* d_dist /*[nz][ny][nx]*/,
+                                int32_t* d_tri /*same, or NULL*/, int32_t* d_inst /*same, or NULL*/);
+int psm_grid_world_signed_distance_dev(psm_world* world, const psm_grid* grid, float rmax, uint32_t samples, float* d_dist,
+                                       int32_t* d_tri, int32_t* d_inst);
 
 /* ---------------------------------------------------------------------------------------------
  * several frames in flight (new; DESIGN.md "lanes")

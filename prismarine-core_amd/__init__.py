@@ -50,6 +50,7 @@ EXPORTS = [
     "psm_grid_surface_dev", "psm_grid_counts_dev", "psm_grid_solid_dev", "psm_grid_brick_count",
     "psm_grid_distance_dev", "psm_grid_signed_distance_dev",
     "psm_grid_world_surface_dev", "psm_grid_world_counts_dev", "psm_grid_world_instances_dev", "psm_grid_world_solid_dev",
+    "psm_grid_world_distance_dev", "psm_grid_world_signed_distance_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
     "psm_rt_set_lights", "psm_rt_set_sky", "psm_rt_set_skybox", "psm_rt_set_texture", "psm_rt_set_materials", "psm_rt_camera", "psm_rt_set_camera_mode", "psm_rt_ray_count",
     "psm_rt_traverse", "psm_rt_set_traverse_mode", "psm_rt_set_traverse_phases", "psm_rt_set_traverse_adaptive", "psm_rt_set_traverse_solo", "psm_rt_reset_hits", "psm_rt_shade", "psm_rt_sample", "psm_rt_sample_from", "psm_lanes_render", "psm_lanes_run_sharded", "psm_rt_clear_sampler", "psm_rt_snap",
@@ -524,7 +525,8 @@ class TriangleHierarchy:
         [nz, ny, nx] (None with nearest=False: the ids are not stored); with as_torch=True torch tensors on the context's
         device, the launch ordered against torch's current stream by events, no host synchronisation. An invalid grid and a NaN
         or negative rmax raise ValueError before any call; samples other than 1, 3 or 5 are the library's to refuse. Not
-        covered: distance fields over a QueryScene, an InstancedScene or an InstanceWorld; u, v and the closest point per voxel
+        covered: distance fields over a QueryScene or an InstancedScene (an InstanceWorld has its own distanceField); u, v and
+        the closest point per voxel
         (closestPoint() answers them for the voxels that need them); a per-voxel rmax; a sparse output; sweeping-based
         (approximate) distance transforms; graph capture of the signed call."""
         g = _grid(origin, cell, dims)
@@ -950,13 +952,15 @@ class VoxelGrid:
 
 
 class DistanceGrid:
-    """What TriangleHierarchy.distanceField returns. dist: float32 [nz, ny, nx], the (signed) distance at each voxel centre, +inf
-    where no triangle lies within rmax; tri: int32 [nz, ny, nx], the nearest triangle's id, -1 where dist is +inf, or None when
-    the ids were not asked for (numpy arrays, or torch tensors on the context's device). dims = (nx, ny, nz), origin and cell as
-    given (float32 values)."""
+    """What TriangleHierarchy.distanceField and InstanceWorld.distanceField return. dist: float32 [nz, ny, nx], the (signed)
+    distance at each voxel centre, +inf where no triangle lies within rmax; tri: int32 [nz, ny, nx], the nearest triangle's id, -1
+    where dist is +inf, or None when the ids were not asked for (numpy arrays, or torch tensors on the context's device). dims =
+    (nx, ny, nz), origin and cell as given (float32 values). inst: for an InstanceWorld's field the int32 [nz, ny, nx] instance
+    of each voxel's nearest triangle (tri is that instance's id), -1 where dist is +inf, None with tri; None for a single
+    hierarchy's field."""
 
-    def __init__(self, dist, tri, dims, origin, cell):
-        self.dist, self.tri, self.dims, self.origin, self.cell = dist, tri, dims, origin, cell
+    def __init__(self, dist, tri, dims, origin, cell, inst=None):
+        self.dist, self.tri, self.dims, self.origin, self.cell, self.inst = dist, tri, dims, origin, cell, inst
 
 
 class QueryHitLists:
@@ -1479,7 +1483,8 @@ class InstanceWorld(QueryScene):
     countOnTriangle() and trianglesOnTriangle() on world-space triangles, and the mesh queries overlapsMesh(), countOnMesh()
     and trianglesOnMesh() of another hierarchy at world poses, and the clearance queries closestToTriangle() and
     withinOfTriangle() on world-space triangles, and mesh clearance closestToMesh(), withinOfMesh() and clearanceToMesh() of
-    another hierarchy at world poses, which the flat lists (QueryScene, InstancedScene) have not."""
+    another hierarchy at world poses, and the grids voxelize(), voxelCounts(), voxelInstances() and distanceField() over a
+    world-space grid, which the flat lists (QueryScene, InstancedScene) have not."""
 
     def __init__(self, ctx, entries, capacity=None):
         self.ctx = ctx
@@ -1730,8 +1735,8 @@ class InstanceWorld(QueryScene):
         the reference), or with solid=True those and the voxels whose centre inside() takes as inside with `samples` (1, 3 or 5)
         rays (psm_grid_world_solid_dev). The grid, its voxel boxes (voxel_boxes()) and the VoxelGrid returned are
         TriangleHierarchy.voxelize()'s; a voxel's bit is bit for bit what overlapsBox() answers for its box: one call, no box
-        records. An invalid grid raises ValueError before any call. Not covered: the skip of one instance, a signed-distance
-        grid, sparse output, oriented grids, graph capture of solid."""
+        records. An invalid grid raises ValueError before any call. Not covered: the skip of one instance, sparse output,
+        oriented grids, graph capture of solid (the signed-distance grid of a world is distanceField())."""
         g = _grid(origin, cell, dims)
         if solid:
             name, extra = "psm_grid_world_solid_dev", (C.c_uint32(_samples(samples, "psm_grid_world_solid_dev")),)
@@ -1754,6 +1759,36 @@ class InstanceWorld(QueryScene):
         voxel's box --, -1 where voxelCounts() is 0: a labelled occupancy map. Arguments and placement as voxelize()."""
         g = _grid(origin, cell, dims)
         return self._grid_call(g, "psm_grid_world_instances_dev", (), (g.dims[2], g.dims[1], g.dims[0]), np.int32, as_torch)
+
+    def distanceField(self, origin, cell, dims, rmax=np.inf, signed=False, samples=3, nearest=True, as_torch=False):
+        """The distance from every voxel centre of a regular WORLD grid to the nearest posed triangle of any instance
+        (psm_grid_world_distance_dev; not in the reference), or with signed=True that distance with the sign of inside(centre,
+        samples) over all instances (psm_grid_world_signed_distance_dev): a planner's clearance map or a narrow-band level set
+        over bodies that each move by a matrix per step, in one call. Arguments, the centres (voxel_centres()) and rmax are
+        TriangleHierarchy.distanceField()'s. Every voxel is bit for bit what closestPoint() / signedDistance() of the world
+        answer for its centre with the same rmax and samples (t, tri and the instance; -0.0 can occur in a signed field); on a
+        bit-equal squared distance the lexicographically lowest (instance, triangle) wins. Returns DistanceGrid with dist float32,
+        tri and inst int32, each [nz, ny, nx] (tri and inst None with nearest=False); a miss holds +inf, -1, -1; with
+        as_torch=True torch tensors on the context's device, ordered against torch's current stream by events. An invalid grid
+        and a NaN or negative rmax raise ValueError before any call. Not covered: the skip of one instance, a per-voxel rmax,
+        sparse output, graph capture of the signed call."""
+        g = _grid(origin, cell, dims)
+        r = float(rmax)
+        if not r >= 0.0:   # (NaN too)
+            raise ValueError("distance field: rmax must be >= 0")
+        if signed:
+            name, extra = "psm_grid_world_signed_distance_dev", (C.c_float(r), C.c_uint32(_samples(samples, "psm_grid_world_signed_distance_dev")))
+        else:
+            name, extra = "psm_grid_world_distance_dev", (C.c_float(r),)
+        self._fresh(name)
+        fn = getattr(lib(), name)
+        shape = (g.dims[2], g.dims[1], g.dims[0])
+
+        def call(d_dist, d_tri=None, d_inst=None):
+            self.ctx.check(fn(self._w, C.byref(g), *extra, C.c_void_p(d_dist), C.c_void_p(d_tri), C.c_void_p(d_inst)), name)
+
+        outs = _device_call(self.ctx, call, [(shape, np.float32)] + ([(shape, np.int32)] * 2 if nearest else []), as_torch)
+        return DistanceGrid(outs[0], outs[1] if nearest else None, tuple(g.dims), tuple(g.origin), tuple(g.cell), outs[2] if nearest else None)
 
     def _grid_call(self, g, name, extra, shape, dtype, as_torch):
         """one grid call of the world (TriangleHierarchy._grid_call's shape)"""

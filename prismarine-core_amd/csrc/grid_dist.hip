@@ -145,6 +145,17 @@ __global__ __launch_bounds__(QUERY_BLOCK, 8) void grid_dist_scatter(GridArgs g, 
     }
 }
 
+// world.hip's signed distance grids over a world (world_grid_dist_query()) scatter their slabs through this: the
+// one copy of the kernel. The bricks [first, first + bricks) of the grid, the records in lane order, tri may be NULL
+int grid_dist_scatter_launch(psm_ctx* c, const psm_grid* grid, const GridShape& s, uint32_t first, uint32_t bricks, const void* hits,
+                             float* d_dist, int32_t* d_tri) {
+    GridArgs g = grid_args(grid, s);
+    g.first = first; g.bricks = bricks;
+    grid_dist_scatter<<<grid_for(bricks), QUERY_BLOCK, 0, c->stream>>>(g, (const float4*)hits, d_dist, d_tri);
+    PSM_HIP(c, hipGetLastError());
+    return PSM_OK;
+}
+
 namespace {
 
 // A distance grid call: grid_query's order of refusals (grid.hip) with rmax between the alignment and samples -- all on the

@@ -27,8 +27,8 @@ bool mesh_skip(size_t queries);
 char mesh_bound();
 uint64_t bvh_generation(const psm_bvh* b);    // api.hip: bumped by every build of the hierarchy
 
-// grid.hip: the host pieces the grids over a hierarchy and over a world share (grid.hip, world.hip's world_grid_query();
-// DESIGN.md 4.27, 4.29). A grid as the host reads it: the bricks per axis and in all
+// grid.hip: the host pieces the grids over a hierarchy and over a world share (grid.hip, world.hip's world_grid_query() and
+// world_grid_dist_query()). A grid as the host reads it: the bricks per axis and in all
 struct GridShape {
     uint32_t nb[3];
     uint64_t bricks;
@@ -47,6 +47,10 @@ int grid_fill_launch(psm_ctx* c, const psm_grid* g, const GridShape& s, uint32_t
 // query.hip, for the signed distance grids (grid_dist.hip): the sign kernel of psm_bvh_signed_distance_dev alone over n points
 // and their closest-point records, on the context's stream; the caller has checked the hierarchy and samples
 int sign_launch(psm_bvh* b, const void* d_points, size_t n, uint32_t samples, void* d_hits);
+// grid_dist.hip, for the signed distance grids over a world (world.hip's world_grid_dist_query()): a slab's records (lane order,
+// after the sign kernel) into the dense dist / tri of the whole grid, on the context's stream; d_tri may be NULL
+int grid_dist_scatter_launch(psm_ctx* c, const psm_grid* g, const GridShape& s, uint32_t first, uint32_t bricks, const void* hits,
+                             float* d_dist, int32_t* d_tri);
 
 // (Q_FIRST_HITS, Q_NEAREST: the k-best queries of kbest.hip and of world.hip's worlds: no entry in the kernel tables; Q_BOX_ANY,
 // Q_BOX_COUNT, Q_BOX_TRIS: the box queries of box.hip and world_box.hip: no entry there either; Q_SWEEP, Q_SWEEP_ANY: the sphere

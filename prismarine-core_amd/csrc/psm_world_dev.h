@@ -1,5 +1,5 @@
 // psm_world_dev.h -- the device pieces the kernel files of a world share (world.hip, world_box.hip, world_sweep.hip,
-// world_tri.hip, world_tri_dist.hip, world_mesh.hip, world_mesh_dist.hip, world_grid.hip): the table row, the node of the tree over the instances, the kernel arguments, the padding and the slacks,
+// world_tri.hip, world_tri_dist.hip, world_mesh.hip, world_mesh_dist.hip, world_grid.hip, world_grid_dist.hip): the table row, the node of the tree over the instances, the kernel arguments, the padding and the slacks,
 // the two-level walk, the loads of a row, the best record of a world (WorldBest) and a ray in a world (WorldRay). Moved here
 // from world.hip as they were; every kernel of world.hip compiles to the same instructions as with the pieces in its own file
 // (tools/kernel_diff.py; the digests of tests/test_world_query_cpu.py and tests/test_world_kbest_cpu.py).
@@ -110,6 +110,21 @@ enum { WGRID_SURFACE = 0, WGRID_COUNTS = 1, WGRID_INSTANCES = 2 };
 // world_grid.hip: the launch of a world's grid kernel for world.hip's host path (world_grid_query()). out: a uint64_t word per
 // brick (WGRID_SURFACE), the dense uint32_t [nz][ny][nx] counts (WGRID_COUNTS) or int32_t labels (WGRID_INSTANCES)
 int world_grid_launch(psm_ctx* c, int mode, uint32_t grid, const WorldGridArgs& g, const WorldRow* rows, const WorldNode* nodes, void* out);
+
+// A distance-field grid over a world (world_grid_dist.hip): WorldGridArgs, whose `bricks` is then the launch's own,
+// the first brick of the launch (signed works a slab at a time) and the call's one rmax
+struct WorldGridDistArgs {
+    WorldGridArgs g;
+    uint32_t first;                 // the bricks [first, first + g.bricks) of the grid are this launch's
+    float rmax;
+};
+
+// world_grid_dist.hip: the launch of a world's distance-field kernel for world.hip's host path (world_grid_dist_query()).
+// hits == NULL: the dense float32 dist and int32 tri / inst [nz][ny][nx] of the whole grid (tri and inst may each be NULL);
+// else a psm_hit per lane of the launch's bricks in lane order into hits (u = v = 0, a miss for a dead lane) for the world's sign
+// kernel, and the instance straight into the dense inst (may be NULL); dist and tri are then not read
+int world_grid_dist_launch(psm_ctx* c, uint32_t grid, const WorldGridDistArgs& a, const WorldRow* rows, const WorldNode* nodes, float* dist,
+                           int32_t* tri, int32_t* inst, void* hits);
 
 namespace {
 

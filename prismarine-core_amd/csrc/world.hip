@@ -1105,6 +1105,108 @@ int world_grid_query(psm_world* w, const psm_grid* grid, int call, uint32_t samp
     return PSM_OK;
 }
 
+// psm_world_signed_distance_dev's second kernel alone, over n points and the closest-point records a grid walk wrote for them:
+// the twin of query.hip's sign_launch. The caller has made every check (the world is not empty and not stale, samples is 1, 3 or 5)
+int world_sign_launch(psm_world* w, const void* d_points, size_t n, uint32_t samples, void* d_hits) {
+    WorldArgs a = {};
+    uint32_t grid = 0;
+    const int rc = batch_args(w->ctx, d_points, n, d_hits, samples, a, grid);
+    if (rc != PSM_OK) return rc;
+    a.root = w->count == 1 ? ~0 : 0;
+    a.rows = w->d_rows;
+    a.nodes = w->d_nodes;
+    world_query_sign<<<grid, QUERY_BLOCK, 0, w->ctx->stream>>>(a);
+    PSM_HIP(w->ctx, hipGetLastError());
+    return PSM_OK;
+}
+
+// A distance-field grid over a world (world_grid_dist.hip): grid_dist.hip's dist_query() with a world where the
+// hierarchy was. The NULL world is answered before anything else is looked at; then the pointers, the grid, the alignment, rmax,
+// samples -- all on the host, before any launch, the outputs untouched. An empty world is answered in stream order by fills
+// alone; then the stale refusal (every world query's). The depth rule is psm_world_set_instances'. Signed: grid_dist.hip's scheme
+// slab by slab -- the centres, the walk's records beside them, the world's sign kernel over both, the records into the dense
+// arrays --, the instances written by the walk itself
+int world_grid_dist_query(psm_world* w, const psm_grid* grid, float rmax, bool sign, uint32_t samples, float* d_dist, int32_t* d_tri,
+                          int32_t* d_inst) {
+    if (!w) return PSM_ERR_INVALID;
+    psm_ctx* c = w->ctx;
+    const char* name = sign ? "psm_grid_world_signed_distance_dev" : "psm_grid_world_distance_dev";
+    char msg[160];
+    if (!grid || !d_dist) {
+        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    GridShape s;
+    if (const char* why = grid_fault(grid, s)) {
+        snprintf(msg, sizeof msg, "%s: invalid grid: %s", name, why);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if ((((uintptr_t)d_dist | (uintptr_t)d_tri | (uintptr_t)d_inst) & (uintptr_t)3u) != 0) {
+        snprintf(msg, sizeof msg, "%s: dist, tri or inst not 4-byte aligned", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (!(rmax >= 0.f)) {   // (NaN too; -0 is 0, +inf is no limit)
+        snprintf(msg, sizeof msg, "%s: rmax must be >= 0", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    if (sign && samples != 1 && samples != 3 && samples != 5) {
+        snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", name);
+        return set_err(c, PSM_ERR_INVALID, msg);
+    }
+    (void)hipSetDevice(c->device);
+    if (w->count == 0) {   // an empty world: every voxel misses, no query kernel runs
+        const size_t voxels = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];   // (a valid grid: below 2^37)
+        PSM_HIP(c, hipMemsetD32Async((hipDeviceptr_t)d_dist, 0x7F800000, voxels, c->stream));   // +inf
+        if (d_tri) PSM_HIP(c, hipMemsetAsync(d_tri, 0xFF, voxels * sizeof(int32_t), c->stream));
+        if (d_inst) PSM_HIP(c, hipMemsetAsync(d_inst, 0xFF, voxels * sizeof(int32_t), c->stream));
+        return PSM_OK;
+    }
+    const int stale = first_stale(w);
+    if (stale >= 0) return refuse_stale(w, name, stale);
+    WorldGridDistArgs a = {};
+    a.g.ox = grid->origin[0]; a.g.oy = grid->origin[1]; a.g.oz = grid->origin[2];
+    a.g.cx = grid->cell[0]; a.g.cy = grid->cell[1]; a.g.cz = grid->cell[2];
+    a.g.nx = grid->dims[0]; a.g.ny = grid->dims[1]; a.g.nz = grid->dims[2];
+    a.g.nbx = s.nb[0]; a.g.nby = s.nb[1];
+    a.g.bricks = (uint32_t)s.bricks;
+    a.g.root = w->count == 1 ? ~0 : 0;
+    a.first = 0u;
+    a.rmax = rmax;
+    if (!sign) {
+        const uint32_t blocks = (uint32_t)(s.bricks < QUERY_GRID_CAP ? s.bricks : QUERY_GRID_CAP);
+        return world_grid_dist_launch(c, blocks, a, w->d_rows, w->d_nodes, d_dist, d_tri, d_inst, nullptr);
+    }
+    // signed, a slab of bricks at a time, all in stream order. A voxel takes 32 bytes of scratch where solid's takes 17: a slab of
+    // n bricks asks for the area of 2 n of solid's, and a slab is half of solid's at most
+    const uint32_t cap = GRID_SLAB_BRICKS / 2u;
+    const uint32_t slab = s.bricks < cap ? (uint32_t)s.bricks : cap;
+    void* scratch = nullptr;
+    int rc = scratch_for(c, 2u * slab, &scratch);
+    if (rc != PSM_OK) return rc;
+    {   // (the context's stack area, which the sign launches use: with the scratch the last things that can fail before the outputs change)
+        void* spill = nullptr;
+        rc = spill_for(c, &spill);
+        if (rc != PSM_OK) return rc;
+    }
+    float4* points = (float4*)scratch;
+    float4* hits = points + (size_t)slab * QUERY_BLOCK;
+    for (uint64_t first = 0; first < s.bricks; first += slab) {
+        const uint64_t left = s.bricks - first;
+        const uint32_t bricks = left < slab ? (uint32_t)left : slab;
+        rc = grid_centres_launch(c, grid, s, (uint32_t)first, bricks, points);
+        if (rc != PSM_OK) return rc;
+        a.first = (uint32_t)first; a.g.bricks = bricks;
+        const uint32_t blocks = bricks < QUERY_GRID_CAP ? bricks : QUERY_GRID_CAP;
+        rc = world_grid_dist_launch(c, blocks, a, w->d_rows, w->d_nodes, nullptr, nullptr, d_inst, hits);
+        if (rc != PSM_OK) return rc;
+        rc = world_sign_launch(w, points, (size_t)bricks * QUERY_BLOCK, samples, hits);
+        if (rc != PSM_OK) return rc;
+        rc = grid_dist_scatter_launch(c, grid, s, (uint32_t)first, bricks, hits, d_dist, d_tri);
+        if (rc != PSM_OK) return rc;
+    }
+    return PSM_OK;
+}
+
 template <class T>
 int world_alloc(psm_ctx* c, T** p, size_t n) {
     PSM_HIP(c, hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
@@ -1312,4 +1414,11 @@ int psm_grid_world_instances_dev(psm_world* w, const psm_grid* grid, int32_t* d_
 }
 int psm_grid_world_solid_dev(psm_world* w, const psm_grid* grid, uint32_t samples, uint64_t* d_bricks) {
     return psm::world_grid_query(w, grid, psm::WGRID_SOLID, samples, d_bricks);
+}
+int psm_grid_world_distance_dev(psm_world* w, const psm_grid* grid, float rmax, float* d_dist, int32_t* d_tri, int32_t* d_inst) {
+    return psm::world_grid_dist_query(w, grid, rmax, false, 0, d_dist, d_tri, d_inst);
+}
+int psm_grid_world_signed_distance_dev(psm_world* w, const psm_grid* grid, float rmax, uint32_t samples, float* d_dist, int32_t* d_tri,
+                                       int32_t* d_inst) {
+    return psm::world_grid_dist_query(w, grid, rmax, true, samples, d_dist, d_tri, d_inst);
 }

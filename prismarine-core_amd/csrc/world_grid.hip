@@ -20,22 +20,11 @@
 #include "psm_world_dev.h"       // WorldRow, WorldNode, WorldGridArgs, WORLD_TOP, WORLD_QSLACK
 #include "psm_box_dev.h"         // box_tri
 #include "psm_world_box_dev.h"   // fwd_point, fwd_vec, WorldBoxPrune
+#include "psm_world_uni_dev.h"   // uni, uni_ptr, PSM_CONST, words4, floats3
 
 namespace psm {
 
 namespace {
-
-// a value every lane holds alike, as the scalar the compiler may not know it to be
-PSM_D uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-// The pointers a row holds are integers a lane loaded: the compiler knows neither that the kernel's stores leave what they point
-// to alone nor which address space they mean, and fetches through them with flat vector loads. They point to records, triangles
-// and hierarchy constants that no store of these kernels touches: read as constant memory, they come through scalar loads, as
-// grid.hip's do
-#define PSM_CONST __attribute__((address_space(4)))
-PSM_D const PSM_CONST uint32_t* uni_ptr(uint32_t lo, uint32_t hi) { return (const PSM_CONST uint32_t*)(((uint64_t)uni(hi) << 32) | uni(lo)); }
-// (word by word: the vector types copy from generic memory alone; the compiler makes one s_load_dwordx4 / x8 of the words)
-PSM_D uint4 words4(const PSM_CONST uint32_t* p) { return make_uint4(p[0], p[1], p[2], p[3]); }
-PSM_D v3 floats3(const PSM_CONST uint32_t* p) { return mk3(u2f(p[0]), u2f(p[1]), u2f(p[2])); }
 
 // One wave per brick, grid-stride over the bricks. MODE: WGRID_SURFACE -- a lane that has its bit stops voting, and the walk
 // ends when no lane wants anything --, WGRID_COUNTS -- every live lane wants every pair its tests keep --, WGRID_INSTANCES -- a

@@ -124,6 +124,14 @@ with 3 rays; per case the field alternated A B A B (host-timed medians of REPS) 
 closestPoint / signedDistance over voxel_centres of the same grid: the entry point alone over resident records, the package's
 torch call over resident centres, and the same from host arrays (the upload included) --, the fraction of voxels with a triangle
 within rmax, and a check that dist and tri are the same bits (same_bits). No ratio is fixed in advance.
+`query_bench.py worlddistgrids`: the distance-field grids over a world (psm_grid_world_distance_dev /
+psm_grid_world_signed_distance_dev) on the worldgrids mode's worlds, the torus at 256 and 4 096 turned grid poses
+(WORLD_GRID_POSES): 64^3, 128^3 and 256^3 grids over the world's bounds (GRID_SIZES), rmax = +inf and a band of two cell diagonals,
+unsigned and signed with 3 rays; per case the field alternated A B A B (host-timed medians of REPS, each call ending in a
+synchronise) with the ways a caller had to the same bits -- the world's closestPoint / signedDistance over voxel_centres of the
+same grid: the entry point alone over resident records, the package's torch call over resident centres, and the same from the
+host array (the upload included) --, the fraction of voxels with a triangle within rmax, and a check that dist, tri and inst are
+the same bits (same_bits). Each case's figures are also appended to WORLD_DIST_LOG as they come. No ratio is fixed in advance.
 A kernel trace of its own: rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/query_bench.py [points | signed | scene | instances]"""
 import ctypes as C
 import importlib
@@ -2129,6 +2137,103 @@ def worldgrids():
     print(json.dumps(out))
 
 
+def worlddistgrids():
+    """the distance-field grids over a world against the world's point queries over voxel_centres() of the same grid"""
+    import torch   # (before the library loads its HIP runtime)
+    dev = torch.device("cuda", 0)
+    lib = psm.lib()
+    log = os.environ.get("WORLD_DIST_LOG")
+    ctx = psm.Context(0, stream=torch.cuda.current_stream(dev).cuda_stream)   # torch's packing and the launches: one stream
+    tor = torus(48, 24, 0.7, 0.25)
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(tor.shape[0])
+    th.loadTriangles(tor)
+    th.build()
+    rng = np.random.RandomState(1)
+    out = {"mode": "worlddistgrids", "torus_triangles": int(tor.shape[0]), "reps": REPS, "lib": os.path.basename(psm.LIB_PATH)}
+    for poses_n in (int(x) for x in os.environ.get("WORLD_GRID_POSES", "256,4096").split(",")):
+        side = int(np.ceil(np.sqrt(poses_n)))      # the worldgrids mode's world: a grid of poses, each turned about a random axis
+        poses = np.zeros((poses_n, 3, 4), np.float32)
+        k_ = np.arange(poses_n)
+        for j in range(poses_n):
+            q, r = np.linalg.qr(rng.normal(size=(3, 3)))
+            poses[j, :, :3] = q * np.sign(np.diag(r))
+        poses[:, 0, 3], poses[:, 1, 3] = 2.5 * (k_ % side), 2.5 * (k_ // side)
+        lo = np.array([-1.25, -1.25, -1.25])
+        hi = np.array([2.5 * (side - 1) + 1.25, 2.5 * ((poses_n - 1) // side) + 1.25, 1.25])
+        wd = psm.InstanceWorld(ctx, [(th, m) for m in poses])
+        w = wd._w
+        for g in (int(x) for x in os.environ.get("GRID_SIZES", "64,128,256").split(",")):
+            origin, cell, dims = lo, (hi - lo) / g, (g, g, g)
+            n = g ** 3
+            grid = psm._grid(origin, cell, dims)
+            dist = torch.zeros((g, g, g), dtype=torch.float32, device=dev)
+            tri = torch.zeros((g, g, g), dtype=torch.int32, device=dev)
+            inst = torch.zeros((g, g, g), dtype=torch.int32, device=dev)
+            p_dist, p_tri, p_inst = (C.c_void_p(x.data_ptr()) for x in (dist, tri, inst))
+            centres = psm.voxel_centres(origin, cell, dims)
+            tcentres = torch.from_numpy(centres).to(dev)
+            records = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+            records[:, 0:3] = tcentres
+            hits = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+            geom = torch.zeros((n,), dtype=torch.int32, device=dev)
+            p_rec, p_hits, p_geom, size = C.c_void_p(records.data_ptr()), C.c_void_p(hits.data_ptr()), C.c_void_p(geom.data_ptr()), C.c_size_t(n)
+            out["poses%d_g%d_voxels" % (poses_n, g)] = n
+            band = 2.0 * float(np.linalg.norm(np.array(grid.cell, np.float64)))
+            for rname, rmax in (("inf", float("inf")), ("band", band)):
+                records[:, 3] = rmax
+                r32 = C.c_float(rmax)
+                for sname, samples in (("dist", None), ("signed", 3)):
+
+                    def field():
+                        if samples is None:
+                            ctx.check(lib.psm_grid_world_distance_dev(w, C.byref(grid), r32, p_dist, p_tri, p_inst), "psm_grid_world_distance_dev")
+                        else:
+                            ctx.check(lib.psm_grid_world_signed_distance_dev(w, C.byref(grid), r32, C.c_uint32(samples), p_dist, p_tri, p_inst),
+                                      "psm_grid_world_signed_distance_dev")
+
+                    # the parent's ways to the same bits: the world's point query over the voxels' centres -- (1) the entry point
+                    # alone over records that are resident, (2) the package's torch call over resident centres (it packs the
+                    # records on the device), (3) the same from the host array: the upload of 12 bytes per voxel included
+                    def point_kernel():
+                        if samples is None:
+                            ctx.check(lib.psm_world_closest_point_dev(w, p_rec, size, p_hits, p_geom), "psm_world_closest_point_dev")
+                        else:
+                            ctx.check(lib.psm_world_signed_distance_dev(w, p_rec, size, C.c_uint32(samples), p_hits, p_geom), "psm_world_signed_distance_dev")
+
+                    def point_torch(c=None):
+                        c = tcentres if c is None else c
+                        return wd.closestPoint(c, rmax) if samples is None else wd.signedDistance(c, rmax, samples)
+
+                    def point_upload():
+                        return point_torch(torch.from_numpy(centres).to(dev))
+
+                    key = "poses%d_g%d_%s_%s_" % (poses_n, g, rname, sname)
+                    case = {}
+                    case[key + "field_ms"], case[key + "point_kernel_ms"] = abab(ctx, field, point_kernel)
+                    case[key + "field_again_ms"], case[key + "point_torch_ms"] = abab(ctx, field, point_torch)
+                    case[key + "field_third_ms"], case[key + "point_with_upload_ms"] = abab(ctx, field, point_upload)
+                    field()
+                    point_kernel()
+                    ctx.sync()
+                    case[key + "hit_fraction"] = round(float((tri >= 0).float().mean()), 4)
+                    case[key + "same_bits"] = bool(torch.equal(dist.reshape(-1).view(torch.int32), hits[:, 2].contiguous().view(torch.int32))
+                                                   and torch.equal(tri.reshape(-1), hits[:, 3].contiguous().view(torch.int32))
+                                                   and torch.equal(inst.reshape(-1), geom))
+                    case[key + "field_over_point_kernel"] = round(case[key + "field_ms"] / case[key + "point_kernel_ms"], 3)
+                    case[key + "field_over_point_torch"] = round(case[key + "field_again_ms"] / case[key + "point_torch_ms"], 3)
+                    case[key + "field_over_point_with_upload"] = round(case[key + "field_third_ms"] / case[key + "point_with_upload_ms"], 3)
+                    out.update(case)
+                    if log:
+                        with open(log, "a") as f:
+                            f.write(json.dumps(case) + "\n")
+            del dist, tri, inst, tcentres, records, hits, geom
+        wd.close()
+    th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def main():
     sc = scenes.sponza_like()
     ctx = psm.Context(0)
@@ -2194,4 +2299,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "world-clearance": worldclearance, "world-mesh-clearance": worldmeshclearance, "worldmeshes": worldmeshes, "grids": grids, "distgrids": distgrids, "worldgrids": worldgrids}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "world-clearance": worldclearance, "world-mesh-clearance": worldmeshclearance, "worldmeshes": worldmeshes, "grids": grids, "distgrids": distgrids, "worldgrids": worldgrids, "worlddistgrids": worlddistgrids}.get(" ".join(sys.argv[1:]), main)()
