@@ -171,40 +171,15 @@ namespace NSM {
         return gridReadBack<int32_t>(cells, labels, "InstanceWorld::voxelInstances",
                                      [&](int32_t * d) { return psm_grid_world_instances_dev(world, &grid, d); });
     }
-    // the distance fields: dist and, when asked for, tri and inst behind it in one device buffer of 4-byte entries, read back and
-    // split (TriangleHierarchy.inl's distanceReadBack with a third part)
-    template <class Call>
-    inline int worldDistanceReadBack(const psm_grid & grid, std::vector<float> & dist, std::vector<int32_t> * tri, std::vector<int32_t> * inst,
-                                     const char * what, Call call) {
-        const size_t cells = psm_grid_brick_count(&grid) ? (size_t)grid.dims[0] * grid.dims[1] * grid.dims[2] : 0;
-        if (tri) tri->clear();
-        if (inst) inst->clear();
-        const size_t tri_at = cells, inst_at = cells * (tri ? 2 : 1);
-        std::vector<float> all;
-        const int rc = gridReadBack<float>(cells * (1 + (tri ? 1 : 0) + (inst ? 1 : 0)), all, what, [&](float * d) {
-            return call(d, tri ? (int32_t *)(d + tri_at) : nullptr, inst ? (int32_t *)(d + inst_at) : nullptr);
-        });
-        dist.clear();
-        if (rc != PSM_OK) return rc;
-        dist.assign(all.begin(), all.begin() + cells);
-        if (tri) {
-            tri->resize(cells);
-            std::memcpy(tri->data(), all.data() + tri_at, cells * sizeof(int32_t));
-        }
-        if (inst) {
-            inst->resize(cells);
-            std::memcpy(inst->data(), all.data() + inst_at, cells * sizeof(int32_t));
-        }
-        return rc;
-    }
+    // (distanceReadBack: TriangleHierarchy.inl -- dist, tri and inst in one device buffer, read back and split)
     inline int InstanceWorld::distanceField(const psm_grid & grid, float rmax, std::vector<float> & dist, std::vector<int32_t> * tri,
                                             std::vector<int32_t> * inst) {
-        return worldDistanceReadBack(grid, dist, tri, inst, "InstanceWorld::distanceField",
-                                     [&](float * d, int32_t * t, int32_t * i) { return psm_grid_world_distance_dev(world, &grid, rmax, d, t, i); });
+        return distanceReadBack(grid, dist, tri, inst, "InstanceWorld::distanceField",
+                                [&](float * d, int32_t * t, int32_t * i) { return psm_grid_world_distance_dev(world, &grid, rmax, d, t, i); });
     }
     inline int InstanceWorld::signedDistanceField(const psm_grid & grid, float rmax, uint32_t samples, std::vector<float> & dist,
                                                   std::vector<int32_t> * tri, std::vector<int32_t> * inst) {
-        return worldDistanceReadBack(grid, dist, tri, inst, "InstanceWorld::signedDistanceField", [&](float * d, int32_t * t, int32_t * i) {
+        return distanceReadBack(grid, dist, tri, inst, "InstanceWorld::signedDistanceField", [&](float * d, int32_t * t, int32_t * i) {
             return psm_grid_world_signed_distance_dev(world, &grid, rmax, samples, d, t, i);
         });
     }

@@ -118,31 +118,40 @@ namespace NSM {
         return gridReadBack<uint32_t>(cells, counts, "TriangleHierarchy::voxelCounts",
                                       [&](uint32_t * d) { return psm_grid_counts_dev(bvh, &grid, d); });
     }
-    // the distance fields: dist and, when asked for, tri behind it in one device buffer of 4-byte entries, read back and split
+    // the distance fields of a hierarchy and of a world (InstanceWorld.inl): dist and, when asked for, tri and inst behind it in one
+    // device buffer of 4-byte entries, read back and split (a hierarchy's call has no inst: NULL)
     template <class Call>
-    inline int distanceReadBack(const psm_grid & grid, std::vector<float> & dist, std::vector<int32_t> * tri, const char * what, Call call) {
+    inline int distanceReadBack(const psm_grid & grid, std::vector<float> & dist, std::vector<int32_t> * tri, std::vector<int32_t> * inst,
+                                const char * what, Call call) {
         const size_t cells = psm_grid_brick_count(&grid) ? (size_t)grid.dims[0] * grid.dims[1] * grid.dims[2] : 0;
         if (tri) tri->clear();
-        std::vector<float> both;
-        const int rc = gridReadBack<float>(cells * (tri ? 2 : 1), both, what,
-                                           [&](float * d) { return call(d, tri ? (int32_t *)(d + cells) : nullptr); });
+        if (inst) inst->clear();
+        const size_t tri_at = cells, inst_at = cells * (tri ? 2 : 1);
+        std::vector<float> all;
+        const int rc = gridReadBack<float>(cells * (1 + (tri ? 1 : 0) + (inst ? 1 : 0)), all, what, [&](float * d) {
+            return call(d, tri ? (int32_t *)(d + tri_at) : nullptr, inst ? (int32_t *)(d + inst_at) : nullptr);
+        });
         dist.clear();
         if (rc != PSM_OK) return rc;
-        dist.assign(both.begin(), both.begin() + cells);
+        dist.assign(all.begin(), all.begin() + cells);
         if (tri) {
             tri->resize(cells);
-            std::memcpy(tri->data(), both.data() + cells, cells * sizeof(int32_t));
+            std::memcpy(tri->data(), all.data() + tri_at, cells * sizeof(int32_t));
+        }
+        if (inst) {
+            inst->resize(cells);
+            std::memcpy(inst->data(), all.data() + inst_at, cells * sizeof(int32_t));
         }
         return rc;
     }
     inline int TriangleHierarchy::distanceField(const psm_grid & grid, float rmax, std::vector<float> & dist, std::vector<int32_t> * tri) {
-        return distanceReadBack(grid, dist, tri, "TriangleHierarchy::distanceField",
-                                [&](float * d, int32_t * t) { return psm_grid_distance_dev(bvh, &grid, rmax, d, t); });
+        return distanceReadBack(grid, dist, tri, nullptr, "TriangleHierarchy::distanceField",
+                                [&](float * d, int32_t * t, int32_t *) { return psm_grid_distance_dev(bvh, &grid, rmax, d, t); });
     }
     inline int TriangleHierarchy::signedDistanceField(const psm_grid & grid, float rmax, uint32_t samples, std::vector<float> & dist,
                                                       std::vector<int32_t> * tri) {
-        return distanceReadBack(grid, dist, tri, "TriangleHierarchy::signedDistanceField",
-                                [&](float * d, int32_t * t) { return psm_grid_signed_distance_dev(bvh, &grid, rmax, samples, d, t); });
+        return distanceReadBack(grid, dist, tri, nullptr, "TriangleHierarchy::signedDistanceField",
+                                [&](float * d, int32_t * t, int32_t *) { return psm_grid_signed_distance_dev(bvh, &grid, rmax, samples, d, t); });
     }
     inline int TriangleHierarchy::boxTriangles(const psm_box_query * d_boxes, size_t n, uint32_t k, int32_t * d_tris, uint32_t * d_count) {
         const int rc = psm_bvh_box_triangles_dev(bvh, d_boxes, n, k, d_tris, d_count);

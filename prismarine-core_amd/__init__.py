@@ -498,20 +498,15 @@ class TriangleHierarchy:
         grid raises ValueError before any call. QueryScene and InstancedScene have no grids; InstanceWorld has its own (voxelize /
         voxelCounts / voxelInstances: the grid in world space)."""
         g = _grid(origin, cell, dims)
-        if solid:
-            name, extra = "psm_grid_solid_dev", (C.c_uint32(_samples(samples, "psm_grid_solid_dev")),)
-        else:
-            name, extra = "psm_grid_surface_dev", ()
-        nb = tuple((int(d) + 3) // 4 for d in g.dims)
-        bricks = self._grid_call(g, name, extra, (nb[2], nb[1], nb[0]), np.uint64, as_torch)
-        return VoxelGrid(bricks, tuple(g.dims), tuple(g.origin), tuple(g.cell))
+        return _voxel_call(self.ctx, self._h, "psm_grid_", "solid" if solid else "surface", g, np.uint64, as_torch,
+                           samples if solid else None)
 
     def voxelCounts(self, origin, cell, dims, as_torch=False):
         """How many triangles overlap each voxel of a regular grid (psm_grid_counts_dev; not in the reference): uint32 [nz, ny, nx]
         (an int32 tensor with as_torch=True, as boxCount()'s), each entry what boxCount() answers for the voxel's box. Arguments
         and placement as voxelize()."""
         g = _grid(origin, cell, dims)
-        return self._grid_call(g, "psm_grid_counts_dev", (), (g.dims[2], g.dims[1], g.dims[0]), np.uint32, as_torch)
+        return _voxel_call(self.ctx, self._h, "psm_grid_", "counts", g, np.uint32, as_torch)
 
     def distanceField(self, origin, cell, dims, rmax=np.inf, signed=False, samples=3, nearest=True, as_torch=False):
         """The distance from every voxel centre of a regular grid to the nearest triangle (psm_grid_distance_dev; not in the
@@ -529,31 +524,8 @@ class TriangleHierarchy:
         the closest point per voxel
         (closestPoint() answers them for the voxels that need them); a per-voxel rmax; a sparse output; sweeping-based
         (approximate) distance transforms; graph capture of the signed call."""
-        g = _grid(origin, cell, dims)
-        r = float(rmax)
-        if not r >= 0.0:   # (NaN too)
-            raise ValueError("distance field: rmax must be >= 0")
-        if signed:
-            name, extra = "psm_grid_signed_distance_dev", (C.c_float(r), C.c_uint32(_samples(samples, "psm_grid_signed_distance_dev")))
-        else:
-            name, extra = "psm_grid_distance_dev", (C.c_float(r),)
-        fn = getattr(lib(), name)
-        shape = (g.dims[2], g.dims[1], g.dims[0])
-
-        def call(d_dist, d_tri=None):
-            self.ctx.check(fn(self._h, C.byref(g), *extra, C.c_void_p(d_dist), C.c_void_p(d_tri)), name)
-
-        outs = _device_call(self.ctx, call, [(shape, np.float32)] + ([(shape, np.int32)] if nearest else []), as_torch)
-        return DistanceGrid(outs[0], outs[1] if nearest else None, tuple(g.dims), tuple(g.origin), tuple(g.cell))
-
-    def _grid_call(self, g, name, extra, shape, dtype, as_torch):
-        """one grid call: the output [shape] of uint64 words or uint32 counts, on the device for torch, else staged and read back"""
-        fn = getattr(lib(), name)
-
-        def call(d_out):
-            self.ctx.check(fn(self._h, C.byref(g), *extra, C.c_void_p(d_out)), name)
-
-        return _device_call(self.ctx, call, [(shape, dtype)], as_torch)[0]
+        g, r = _grid(origin, cell, dims), _rmax(rmax)
+        return _distance_call(self.ctx, self._h, "psm_grid_", g, r, signed, samples, nearest, as_torch)
 
     def triOverlaps(self, tris):
         """Whether some triangle of the hierarchy meets each query triangle (psm_bvh_tri_overlaps_dev; not in the reference): tris
@@ -865,6 +837,14 @@ def _k(k, name):
 
 
 GRID_DIM_MAX = 1 << 20   # psm_hip.h PSM_GRID_DIM_MAX
+
+
+def _rmax(rmax):
+    """a distance field's narrow band as a float; NaN or a negative one raises ValueError"""
+    r = float(rmax)
+    if not r >= 0.0:   # (NaN too)
+        raise ValueError("distance field: rmax must be >= 0")
+    return r
 
 
 def _grid(origin, cell, dims):
@@ -1293,6 +1273,45 @@ def _device_call(ctx, call, outs, as_torch):
     finally:
         for h in bufs:
             ctx.buf_free(h)
+
+
+def _voxel_call(ctx, handle, prefix, what, g, dtype, as_torch, samples=None, fresh=None):
+    """One voxel grid call of a hierarchy ("psm_grid_") or a world ("psm_grid_world_"), what: surface, solid (with samples),
+    counts or instances. g: the Grid (_grid()'s: an invalid one has raised ValueError before); fresh(name): the owner's check
+    before the library sees the handle. uint64: the bricks as a VoxelGrid; else the dense [nz, ny, nx] array / tensor."""
+    name = prefix + what + "_dev"
+    extra = () if samples is None else (C.c_uint32(_samples(samples, name)),)
+    if fresh:
+        fresh(name)
+    fn = getattr(lib(), name)
+    words = dtype is np.uint64
+    shape = tuple((int(d) + 3) // 4 if words else int(d) for d in reversed(g.dims))
+
+    def call(d_out):
+        ctx.check(fn(handle, C.byref(g), *extra, C.c_void_p(d_out)), name)
+
+    out = _device_call(ctx, call, [(shape, dtype)], as_torch)[0]
+    return VoxelGrid(out, tuple(g.dims), tuple(g.origin), tuple(g.cell)) if words else out
+
+
+def _distance_call(ctx, handle, prefix, g, r, signed, samples, nearest, as_torch, inst=False, fresh=None):
+    """One distance-field call of a hierarchy or a world (prefix, g and fresh as _voxel_call's; r: _rmax()'s): dist, with nearest
+    tri and, where the call has an instance output, inst behind it; an output not asked for is passed as NULL. Returns DistanceGrid."""
+    name = prefix + ("signed_distance_dev" if signed else "distance_dev")
+    extra = (C.c_float(r), C.c_uint32(_samples(samples, name))) if signed else (C.c_float(r),)
+    if fresh:
+        fresh(name)
+    fn = getattr(lib(), name)
+    shape = (g.dims[2], g.dims[1], g.dims[0])
+    ids = 2 if inst else 1   # (the outputs behind dist)
+
+    def call(*ptrs):
+        ptrs += (None,) * (1 + ids - len(ptrs))
+        ctx.check(fn(handle, C.byref(g), *extra, *[C.c_void_p(p) for p in ptrs]), name)
+
+    outs = _device_call(ctx, call, [(shape, np.float32)] + ([(shape, np.int32)] * ids if nearest else []), as_torch)
+    outs += [None] * (3 - len(outs))
+    return DistanceGrid(outs[0], outs[1], tuple(g.dims), tuple(g.origin), tuple(g.cell), outs[2])
 
 
 def _bool_view(flags):
@@ -1738,27 +1757,22 @@ class InstanceWorld(QueryScene):
         records. An invalid grid raises ValueError before any call. Not covered: the skip of one instance, sparse output,
         oriented grids, graph capture of solid (the signed-distance grid of a world is distanceField())."""
         g = _grid(origin, cell, dims)
-        if solid:
-            name, extra = "psm_grid_world_solid_dev", (C.c_uint32(_samples(samples, "psm_grid_world_solid_dev")),)
-        else:
-            name, extra = "psm_grid_world_surface_dev", ()
-        nb = tuple((int(d) + 3) // 4 for d in g.dims)
-        bricks = self._grid_call(g, name, extra, (nb[2], nb[1], nb[0]), np.uint64, as_torch)
-        return VoxelGrid(bricks, tuple(g.dims), tuple(g.origin), tuple(g.cell))
+        return _voxel_call(self.ctx, self._w, "psm_grid_world_", "solid" if solid else "surface", g, np.uint64, as_torch,
+                           samples if solid else None, self._fresh)
 
     def voxelCounts(self, origin, cell, dims, as_torch=False):
         """How many (instance, triangle) pairs overlap each voxel of a regular world grid (psm_grid_world_counts_dev; not in the
         reference): uint32 [nz, ny, nx] (an int32 tensor with as_torch=True), each entry what countInBox() answers for the voxel's
         box. Arguments and placement as voxelize()."""
         g = _grid(origin, cell, dims)
-        return self._grid_call(g, "psm_grid_world_counts_dev", (), (g.dims[2], g.dims[1], g.dims[0]), np.uint32, as_torch)
+        return _voxel_call(self.ctx, self._w, "psm_grid_world_", "counts", g, np.uint32, as_torch, fresh=self._fresh)
 
     def voxelInstances(self, origin, cell, dims, as_torch=False):
         """Which body owns each voxel of a regular world grid (psm_grid_world_instances_dev; not in the reference): int32 [nz, ny,
         nx], the lowest instance index that has a triangle overlapping the voxel -- trianglesInBox(lo, hi, 1).geom[:, 0] of the
         voxel's box --, -1 where voxelCounts() is 0: a labelled occupancy map. Arguments and placement as voxelize()."""
         g = _grid(origin, cell, dims)
-        return self._grid_call(g, "psm_grid_world_instances_dev", (), (g.dims[2], g.dims[1], g.dims[0]), np.int32, as_torch)
+        return _voxel_call(self.ctx, self._w, "psm_grid_world_", "instances", g, np.int32, as_torch, fresh=self._fresh)
 
     def distanceField(self, origin, cell, dims, rmax=np.inf, signed=False, samples=3, nearest=True, as_torch=False):
         """The distance from every voxel centre of a regular WORLD grid to the nearest posed triangle of any instance
@@ -1772,33 +1786,9 @@ class InstanceWorld(QueryScene):
         as_torch=True torch tensors on the context's device, ordered against torch's current stream by events. An invalid grid
         and a NaN or negative rmax raise ValueError before any call. Not covered: the skip of one instance, a per-voxel rmax,
         sparse output, graph capture of the signed call."""
-        g = _grid(origin, cell, dims)
-        r = float(rmax)
-        if not r >= 0.0:   # (NaN too)
-            raise ValueError("distance field: rmax must be >= 0")
-        if signed:
-            name, extra = "psm_grid_world_signed_distance_dev", (C.c_float(r), C.c_uint32(_samples(samples, "psm_grid_world_signed_distance_dev")))
-        else:
-            name, extra = "psm_grid_world_distance_dev", (C.c_float(r),)
-        self._fresh(name)
-        fn = getattr(lib(), name)
-        shape = (g.dims[2], g.dims[1], g.dims[0])
-
-        def call(d_dist, d_tri=None, d_inst=None):
-            self.ctx.check(fn(self._w, C.byref(g), *extra, C.c_void_p(d_dist), C.c_void_p(d_tri), C.c_void_p(d_inst)), name)
-
-        outs = _device_call(self.ctx, call, [(shape, np.float32)] + ([(shape, np.int32)] * 2 if nearest else []), as_torch)
-        return DistanceGrid(outs[0], outs[1] if nearest else None, tuple(g.dims), tuple(g.origin), tuple(g.cell), outs[2] if nearest else None)
-
-    def _grid_call(self, g, name, extra, shape, dtype, as_torch):
-        """one grid call of the world (TriangleHierarchy._grid_call's shape)"""
-        self._fresh(name)
-        fn = getattr(lib(), name)
-
-        def call(d_out):
-            self.ctx.check(fn(self._w, C.byref(g), *extra, C.c_void_p(d_out)), name)
-
-        return _device_call(self.ctx, call, [(shape, dtype)], as_torch)[0]
+        g, r = _grid(origin, cell, dims), _rmax(rmax)
+        return _distance_call(self.ctx, self._w, "psm_grid_world_", g, r, signed, samples, nearest, as_torch,
+                              inst=True, fresh=self._fresh)
 
     def _call(self, name, d_in, n, extra, d_out, d_geom):
         name = name.replace("psm_bvh_", "psm_world_")

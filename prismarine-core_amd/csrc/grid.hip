@@ -9,8 +9,11 @@
 // (__ballot). The wave has one stack of QSTACK_MAX links in LDS: no spill area. The boxes are never stored: a lane makes its
 // voxel's box from the grid's nine numbers, which travel as kernel arguments. A brick's surface answer leaves as one 64-bit
 // ballot word, written by one lane with an ordinary store.
+//
+// The file also defines the host pieces all eleven grid entry points share (psm_query_host.h): how a grid is read
+// (grid_fault), the front of a call (grid_front), a hierarchy's state (grid_built), the context's scratch and the slabs of solid
+// and signed (slabs_for, walked by grid_slabs), and the launches around a slab's inside query or sign kernel.
 #include <cmath>
-#include <cstdio>
 #include <mutex>
 #include <unordered_map>
 
@@ -179,11 +182,34 @@ const char* grid_fault(const psm_grid* g, GridShape& s) {
     return nullptr;
 }
 
+// ---- The host pieces the eleven grid entry points share (psm_query_host.h): grid_query() below, grid_dist.hip's
+// dist_query(), world.hip's world_grid_query() and world_grid_dist_query() are sequences of these and of what is their own.
+
+// The front of every grid call, under the entry point's name, on the host, nothing launched and no output byte changed: NULL grid
+// or output, the grid's rules (s filled in), the outputs' alignment, rmax and samples where the call has them (else NULL)
+int grid_front(psm_ctx* c, const char* name, const psm_grid* grid, const void* out, GridShape& s, const char* what, const void* aligned,
+               unsigned align, const float* rmax, const uint32_t* samples) {
+    int rc = mesh_pointers(c, name, grid && out);
+    if (rc != PSM_OK) return rc;
+    if (const char* why = grid_fault(grid, s)) return mesh_refuse(c, PSM_ERR_INVALID, "%s: invalid grid: %s", name, why);
+    rc = mesh_aligned(c, name, what, aligned, align);
+    if (rc != PSM_OK) return rc;
+    if (rmax && !(*rmax >= 0.f)) return mesh_refuse(c, PSM_ERR_INVALID, "%s: rmax must be >= 0", name);   // (NaN too; -0 is 0, +inf is no limit)
+    if (samples && *samples != 1 && *samples != 3 && *samples != 5) return mesh_refuse(c, PSM_ERR_INVALID, "%s: samples must be 1, 3 or 5", name);
+    return PSM_OK;
+}
+
+// A hierarchy's state as a grid call needs it: built, and no deeper than the wave's one stack
+int grid_built(const psm_bvh* b) {
+    if (!b->built) return set_err(b->ctx, PSM_ERR_STATE, "grid query before build");
+    if (depth_bound(b) > QSTACK_MAX) return set_err(b->ctx, PSM_ERR_CAPACITY, "grid query: hierarchy deeper than the query stack");
+    return PSM_OK;
+}
+
 namespace {
 
-// solid's scratch, per context (grown on demand, at most SLAB_BRICKS bricks of points and flags: 68 MiB; every call runs on
-// the context's stream, never two at once)
-constexpr uint32_t SLAB_BRICKS = GRID_SLAB_BRICKS;
+// the scratch of solid and signed, per context (grown on demand, at most GRID_SLAB_BRICKS bricks of points and flags: 68 MiB; every
+// call runs on the context's stream, never two at once)
 constexpr size_t SLAB_BRICK_BYTES = (size_t)QUERY_BLOCK * (sizeof(float4) + sizeof(uint8_t));
 struct Scratch {
     void* ptr = nullptr;
@@ -191,8 +217,6 @@ struct Scratch {
 };
 std::mutex scratch_mu;
 std::unordered_map<const psm_ctx*, Scratch> scratch_area;
-
-}  // namespace
 
 int scratch_for(psm_ctx* c, uint32_t bricks, void** out) {
     std::lock_guard<std::mutex> lk(scratch_mu);
@@ -209,6 +233,22 @@ int scratch_for(psm_ctx* c, uint32_t bricks, void** out) {
     }
     *out = a.ptr;
     return PSM_OK;
+}
+
+}  // namespace
+
+// The slabs of a solid or a signed call over `bricks` bricks and the context's scratch for one of them: the slab's centres first,
+// then solid's flags or signed's hits. A voxel of signed takes 32 bytes where solid's takes 17: a slab of n bricks asks for the
+// area of 2 n of solid's, and a slab is half of solid's at most
+int slabs_for(psm_ctx* c, uint64_t bricks, bool sign, GridSlabs& a) {
+    const uint32_t cap = sign ? GRID_SLAB_BRICKS / 2u : GRID_SLAB_BRICKS;
+    a.slab = bricks < cap ? (uint32_t)bricks : cap;
+    void* area = nullptr;
+    const int rc = scratch_for(c, sign ? 2u * a.slab : a.slab, &area);
+    a.points = (float4*)area;
+    a.hits = a.points + (size_t)a.slab * QUERY_BLOCK;
+    a.flags = (uint8_t*)a.hits;
+    return rc;
 }
 
 int grid_centres_launch(psm_ctx* c, const psm_grid* grid, const GridShape& s, uint32_t first, uint32_t bricks, void* points) {
@@ -234,40 +274,23 @@ namespace {
 const char* const GRID_NAME[] = {"psm_grid_surface_dev", "psm_grid_counts_dev", "psm_grid_solid_dev"};
 enum { CALL_SURFACE = 0, CALL_COUNTS = 1, CALL_SOLID = 2 };
 
-// A grid call: a NULL hierarchy is answered before anything else; then the pointers, the grid, the alignment, samples, the
-// state, the depth -- all on the host, before any launch, the output untouched.
+// A grid call: a NULL hierarchy is answered before anything else; then the front every grid call shares (grid_front), the state
+// and the depth (grid_built) -- all on the host, before any launch, the output untouched --, the walk over the whole grid, and for
+// solid the inside of the surface slab by slab
 int grid_query(psm_bvh* b, const psm_grid* grid, int call, uint32_t samples, void* d_out) {
     if (!b) return PSM_ERR_INVALID;
     psm_ctx* c = b->ctx;
-    const char* name = GRID_NAME[call];
-    char msg[160];
-    if (!grid || !d_out) {
-        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
     GridShape s;
-    if (const char* why = grid_fault(grid, s)) {
-        snprintf(msg, sizeof msg, "%s: invalid grid: %s", name, why);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    const unsigned align = call == CALL_COUNTS ? 4u : 8u;
-    if (((uintptr_t)d_out & (uintptr_t)(align - 1u)) != 0) {
-        snprintf(msg, sizeof msg, "%s: %s not %u-byte aligned", name, call == CALL_COUNTS ? "counts" : "bricks", align);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (call == CALL_SOLID && samples != 1 && samples != 3 && samples != 5) {
-        snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (!b->built) return set_err(c, PSM_ERR_STATE, "grid query before build");
-    if (depth_bound(b) > QSTACK_MAX) return set_err(c, PSM_ERR_CAPACITY, "grid query: hierarchy deeper than the query stack");
+    int rc = grid_front(c, GRID_NAME[call], grid, d_out, s, call == CALL_COUNTS ? "counts" : "bricks", d_out, call == CALL_COUNTS ? 4u : 8u,
+                        nullptr, call == CALL_SOLID ? &samples : nullptr);
+    if (rc == PSM_OK) rc = grid_built(b);
+    if (rc != PSM_OK) return rc;
     (void)hipSetDevice(c->device);
     GridArgs g = grid_args(grid, s);
     g.sm = b->d_small; g.sorted_tri = b->d_sorted_tri;
-    void* scratch = nullptr;
-    const uint32_t slab = s.bricks < SLAB_BRICKS ? (uint32_t)s.bricks : SLAB_BRICKS;
+    GridSlabs a;
     if (call == CALL_SOLID) {   // (the last thing that can fail before the output changes)
-        const int rc = scratch_for(c, slab, &scratch);
+        rc = slabs_for(c, s.bricks, false, a);
         if (rc != PSM_OK) return rc;
     }
     if (call == CALL_COUNTS) grid_counts<<<grid_for(s.bricks), QUERY_BLOCK, 0, c->stream>>>(g, b->d_node32, b->d_tri48, (uint32_t*)d_out);
@@ -276,18 +299,12 @@ int grid_query(psm_bvh* b, const psm_grid* grid, int call, uint32_t samples, voi
     if (call != CALL_SOLID) return PSM_OK;
     // the inside of the surface, a slab of bricks at a time, all in stream order: the centres, query.hip's inside path over
     // them, the flags' ballots ORed into the words
-    uint8_t* flags = grid_slab_flags(scratch, slab);
-    for (uint64_t first = 0; first < s.bricks; first += slab) {
-        const uint64_t left = s.bricks - first;
-        const uint32_t bricks = left < slab ? (uint32_t)left : slab;
-        int rc = grid_centres_launch(c, grid, s, (uint32_t)first, bricks, scratch);
-        if (rc != PSM_OK) return rc;
-        rc = psm_bvh_inside_dev(b, (const psm_point_query*)scratch, (size_t)bricks * QUERY_BLOCK, samples, flags);
-        if (rc != PSM_OK) return rc;
-        rc = grid_fill_launch(c, grid, s, (uint32_t)first, bricks, flags, (uint64_t*)d_out);
-        if (rc != PSM_OK) return rc;
-    }
-    return PSM_OK;
+    return grid_slabs(s.bricks, a.slab, [&](uint32_t first, uint32_t bricks) {
+        int rc = grid_centres_launch(c, grid, s, first, bricks, a.points);
+        if (rc == PSM_OK) rc = psm_bvh_inside_dev(b, (const psm_point_query*)a.points, (size_t)bricks * QUERY_BLOCK, samples, a.flags);
+        if (rc == PSM_OK) rc = grid_fill_launch(c, grid, s, first, bricks, a.flags, (uint64_t*)d_out);
+        return rc;
+    });
 }
 
 }  // namespace

@@ -11,8 +11,8 @@
 // answer does not depend on which boxes the wave enters beyond a lane's own, nor on the order: a box a lane would have dropped
 // holds no triangle that passes that lane's comparison (LB^2 > best: psm_query_dev.h), and the comparison takes the smaller d2
 // and on a bit-equal d2 the lower id, whatever came first. The wave has one stack of QSTACK_MAX links in LDS: no spill area.
+// The host function is a sequence of the pieces every grid call shares (grid.hip, psm_query_host.h).
 #include <cmath>
-#include <cstdio>
 
 #include "psm_common.h"
 #include "psm_internal.h"
@@ -158,36 +158,16 @@ int grid_dist_scatter_launch(psm_ctx* c, const psm_grid* grid, const GridShape& 
 
 namespace {
 
-// A distance grid call: grid_query's order of refusals (grid.hip) with rmax between the alignment and samples -- all on the
-// host, before any launch, the outputs untouched.
+// A distance grid call: grid_query's sequence (grid.hip) with rmax between the alignment and samples -- the shared front and the
+// hierarchy's state, all on the host, before any launch, the outputs untouched.
 int dist_query(psm_bvh* b, const psm_grid* grid, float rmax, bool sign, uint32_t samples, float* d_dist, int32_t* d_tri) {
     if (!b) return PSM_ERR_INVALID;
     psm_ctx* c = b->ctx;
-    const char* name = sign ? "psm_grid_signed_distance_dev" : "psm_grid_distance_dev";
-    char msg[160];
-    if (!grid || !d_dist) {
-        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
     GridShape s;
-    if (const char* why = grid_fault(grid, s)) {
-        snprintf(msg, sizeof msg, "%s: invalid grid: %s", name, why);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if ((((uintptr_t)d_dist | (uintptr_t)d_tri) & (uintptr_t)3u) != 0) {
-        snprintf(msg, sizeof msg, "%s: dist or tri not 4-byte aligned", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (!(rmax >= 0.f)) {   // (NaN too; -0 is 0, +inf is no limit)
-        snprintf(msg, sizeof msg, "%s: rmax must be >= 0", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (sign && samples != 1 && samples != 3 && samples != 5) {
-        snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (!b->built) return set_err(c, PSM_ERR_STATE, "grid query before build");
-    if (depth_bound(b) > QSTACK_MAX) return set_err(c, PSM_ERR_CAPACITY, "grid query: hierarchy deeper than the query stack");
+    int rc = grid_front(c, sign ? "psm_grid_signed_distance_dev" : "psm_grid_distance_dev", grid, d_dist, s, "dist or tri",
+                        (const void*)((uintptr_t)d_dist | (uintptr_t)d_tri), 4, &rmax, sign ? &samples : nullptr);
+    if (rc == PSM_OK) rc = grid_built(b);
+    if (rc != PSM_OK) return rc;
     (void)hipSetDevice(c->device);
     GridArgs g = grid_args(grid, s);
     g.sm = b->d_small; g.sorted_tri = b->d_sorted_tri;
@@ -197,29 +177,20 @@ int dist_query(psm_bvh* b, const psm_grid* grid, float rmax, bool sign, uint32_t
         return PSM_OK;
     }
     // signed, a slab of bricks at a time, all in stream order: the centres, the walk's records beside them, query.hip's sign
-    // kernel over both, the records into the dense arrays. A voxel takes 32 bytes of scratch where solid's takes 17: a slab of
-    // n bricks asks for the area of 2 n of solid's, and a slab is half of solid's at most
-    const uint32_t cap = GRID_SLAB_BRICKS / 2u;
-    const uint32_t slab = s.bricks < cap ? (uint32_t)s.bricks : cap;
-    void* scratch = nullptr;
-    int rc = scratch_for(c, 2u * slab, &scratch);   // (the last thing that can fail before the outputs change)
+    // kernel over both, the records into the dense arrays
+    GridSlabs a;
+    rc = slabs_for(c, s.bricks, true, a);   // (the last thing that can fail before the outputs change)
     if (rc != PSM_OK) return rc;
-    float4* points = (float4*)scratch;
-    float4* hits = points + (size_t)slab * QUERY_BLOCK;
-    for (uint64_t first = 0; first < s.bricks; first += slab) {
-        const uint64_t left = s.bricks - first;
-        const uint32_t bricks = left < slab ? (uint32_t)left : slab;
-        rc = grid_centres_launch(c, grid, s, (uint32_t)first, bricks, points);
+    return grid_slabs(s.bricks, a.slab, [&](uint32_t first, uint32_t bricks) {
+        int rc = grid_centres_launch(c, grid, s, first, bricks, a.points);
         if (rc != PSM_OK) return rc;
-        g.first = (uint32_t)first; g.bricks = bricks;
-        grid_dist_records<<<grid_for(bricks), QUERY_BLOCK, 0, c->stream>>>(g, rmax, b->d_node32, b->d_tri48, hits);
+        g.first = first; g.bricks = bricks;
+        grid_dist_records<<<grid_for(bricks), QUERY_BLOCK, 0, c->stream>>>(g, rmax, b->d_node32, b->d_tri48, a.hits);
         PSM_HIP(c, hipGetLastError());
-        rc = sign_launch(b, points, (size_t)bricks * QUERY_BLOCK, samples, hits);
+        rc = sign_launch(b, a.points, (size_t)bricks * QUERY_BLOCK, samples, a.hits);
         if (rc != PSM_OK) return rc;
-        grid_dist_scatter<<<grid_for(bricks), QUERY_BLOCK, 0, c->stream>>>(g, hits, d_dist, d_tri);
-        PSM_HIP(c, hipGetLastError());
-    }
-    return PSM_OK;
+        return grid_dist_scatter_launch(c, grid, s, first, bricks, a.hits, d_dist, d_tri);
+    });
 }
 
 }  // namespace

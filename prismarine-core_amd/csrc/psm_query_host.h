@@ -1,6 +1,7 @@
 // psm_query_host.h -- the host path every query entry point shares (query.hip, world.hip): the kinds, what
 // their messages call things, the data and list checks, the context's stack area, the launch. The functions are defined once,
-// in query.hip. api.hip takes the declarations alone (PSM_QUERY_HOST_DECLARATIONS_ONLY): it holds no kernels, and the
+// in query.hip; the pieces the posed-mesh calls share in mesh.hip (4.28), those of the grid calls in grid.hip (4.32), which also
+// refuse through mesh_refuse / mesh_pointers / mesh_aligned. api.hip takes the declarations alone (PSM_QUERY_HOST_DECLARATIONS_ONLY): it holds no kernels, and the
 // templates below need the walk's constants of psm_query_dev.h.
 #pragma once
 #include "psm_internal.h"
@@ -27,21 +28,45 @@ bool mesh_skip(size_t queries);
 char mesh_bound();
 uint64_t bvh_generation(const psm_bvh* b);    // api.hip: bumped by every build of the hierarchy
 
-// grid.hip: the host pieces the grids over a hierarchy and over a world share (grid.hip, world.hip's world_grid_query() and
-// world_grid_dist_query()). A grid as the host reads it: the bricks per axis and in all
+// grid.hip: the host pieces the eleven grid entry points share (grid.hip's grid_query(), grid_dist.hip's dist_query(), world.hip's
+// world_grid_query() and world_grid_dist_query()). A grid as the host reads it: the bricks per axis and in all
 struct GridShape {
     uint32_t nb[3];
     uint64_t bricks;
 };
 // Why a grid is refused, or NULL with s filled in (psm_hip.h "voxel grids": the rules in their order)
 const char* grid_fault(const psm_grid* g, GridShape& s);
-// solid's scratch of the context for slabs of at most `bricks` bricks (<= GRID_SLAB_BRICKS), grown on demand and released by
-// grid_release: bricks x 64 centres (psm_point_query records in lane order), then at grid_slab_flags() the bricks x 64 flags
+// The front of every grid call, PSM_OK or the refusal under the entry point's name with the context's error set: "<name>: NULL
+// pointer" for a NULL grid or out, "<name>: invalid grid: <grid_fault()>" (else s is filled in), "<name>: <what> not <align>-byte
+// aligned" by the bits of `aligned` (the outputs' addresses ORed), then rmax ("must be >= 0") and samples ("must be 1, 3 or 5"),
+// each NULL where the call has none
+int grid_front(psm_ctx* c, const char* name, const psm_grid* grid, const void* out, GridShape& s, const char* what, const void* aligned,
+               unsigned align, const float* rmax, const uint32_t* samples);
+// A hierarchy's state for a grid call: PSM_ERR_STATE before its first build, PSM_ERR_CAPACITY when deeper than the wave's stack
+int grid_built(const psm_bvh* b);
+// The slabs solid and signed work in, and the context's scratch for one slab (grown on demand, released by grid_release): the
+// slab's 64 centres a brick in lane order (psm_point_query records), then solid's flags or, at the same place, signed's hits.
+// Solid's slab is at most GRID_SLAB_BRICKS bricks, signed's half of that with twice the bytes a brick
 constexpr uint32_t GRID_SLAB_BRICKS = 1u << 16;
-int scratch_for(psm_ctx* c, uint32_t bricks, void** out);
-inline uint8_t* grid_slab_flags(void* scratch, uint32_t slab) { return (uint8_t*)scratch + (size_t)slab * 64 * 16; }
-// solid's two launches around the inside query of a slab, the bricks [first, first + bricks) of the grid, on the context's
-// stream: the centres into points; the ballots of flags ORed into words (a word per brick of the whole grid)
+struct GridSlabs {
+    uint32_t slab = 0;
+    float4* points = nullptr;
+    float4* hits = nullptr;
+    uint8_t* flags = nullptr;
+};
+int slabs_for(psm_ctx* c, uint64_t bricks, bool sign, GridSlabs& a);
+// body(first, bricks) for each slab of at most `slab` bricks in order, until one does not answer PSM_OK
+template <class Body>
+int grid_slabs(uint64_t bricks, uint32_t slab, Body body) {
+    for (uint64_t first = 0; first < bricks; first += slab) {
+        const uint64_t left = bricks - first;
+        const int rc = body((uint32_t)first, left < slab ? (uint32_t)left : slab);
+        if (rc != PSM_OK) return rc;
+    }
+    return PSM_OK;
+}
+// the launches around the inside query or the sign kernel of a slab, the bricks [first, first + bricks) of the grid, on the
+// context's stream: the centres into points; the ballots of flags ORed into words (a word per brick of the whole grid)
 int grid_centres_launch(psm_ctx* c, const psm_grid* g, const GridShape& s, uint32_t first, uint32_t bricks, void* points);
 int grid_fill_launch(psm_ctx* c, const psm_grid* g, const GridShape& s, uint32_t first, uint32_t bricks, const uint8_t* flags, uint64_t* words);
 // query.hip, for the signed distance grids (grid_dist.hip): the sign kernel of psm_bvh_signed_distance_dev alone over n points

@@ -10,6 +10,9 @@
 // launch of psm_query_host.h. This file holds what is a world's own: rows, tree, walk, stale check, depth rule.
 // The k-best queries of a world (a ray's first k hits, a point's k nearest triangles over all instances) are
 // here too: two more bodies for the same walk, with the sorted list of psm_world_klist.h in the place of the one best record.
+// So are the host functions of every other query family over a world (psm_world is private to this file); those of the posed
+// meshes and of the grids are sequences of the pieces mesh.hip and grid.hip define once, and all of them
+// take how a walk starts from world_start().
 //
 // The walk is one loop over one stack ([depth][lane] in LDS, the rest in the context's spill area). A stack entry is a link:
 //   link < 0               instance ~link of the world: the lane enters it (loads its row, moves the query, sets up)
@@ -29,7 +32,7 @@
 #include "psm_common.h"
 #include "psm_internal.h"
 #include "psm_query_dev.h"    // the constants, the triangle / box / point tests, inst_point / inst_rotate, INSIDE_DIR
-#include "psm_query_host.h"   // QueryKind, check_data / check_instances, batch_args / launch; mesh.hip's shared host pieces
+#include "psm_query_host.h"   // QueryKind, check_data / check_instances, batch_args / launch; mesh.hip's and grid.hip's shared host pieces
 #include "psm_world_dev.h"    // WorldRow / WorldNode / WorldArgs, the WORLD_* constants, world_walk, load_row / load_pose,
                               // WorldBest, WorldRay
 #define PSM_KLIST_FN PSM_D
@@ -813,6 +816,27 @@ int world_upload_and_build(psm_world* w, const char* name) {
     return check_depth(w, name);
 }
 
+// How a walk of the world starts, the rest zero: the tree's root or the one instance of a world of one, the table, the tree
+WorldArgs world_start(const psm_world* w) {
+    WorldArgs a = {};
+    a.root = w->count == 1 ? ~0 : 0;
+    a.rows = w->d_rows;
+    a.nodes = w->d_nodes;
+    return a;
+}
+
+// the grid's nine numbers, its bricks and the world's root as the kernels take them (the twin of psm_grid_dev.h's grid_args)
+WorldGridArgs world_grid_args(const psm_grid* grid, const GridShape& s, const psm_world* w) {
+    WorldGridArgs g = {};
+    g.ox = grid->origin[0]; g.oy = grid->origin[1]; g.oz = grid->origin[2];
+    g.cx = grid->cell[0]; g.cy = grid->cell[1]; g.cz = grid->cell[2];
+    g.nx = grid->dims[0]; g.ny = grid->dims[1]; g.nz = grid->dims[2];
+    g.nbx = s.nb[0]; g.nby = s.nb[1];
+    g.bricks = (uint32_t)s.bricks;
+    g.root = world_start(w).root;
+    return g;
+}
+
 // A query of a world: the data (check_data, as every query's), the empty world's answer, the stale check, the launch. The
 // k-best kinds come through here too: samples is their k, d_out and d_inst their [n][k] rows, d_count their counts (which go
 // through check_data's index slot as "counts", as in query.hip's query(); d_inst is then checked here). And the box kinds
@@ -859,14 +883,11 @@ int world_query(psm_world* w, QueryKind kind, const void* d_in, size_t n, void* 
     }
     const int stale = first_stale(w);
     if (stale >= 0) return refuse_stale(w, name, stale);
-    WorldArgs a = {};
+    WorldArgs a = world_start(w);
     uint32_t grid = 0;
     rc = batch_args(c, d_in, n, d_out, samples, a, grid);
     if (rc != PSM_OK) return rc;
     a.geom = d_inst;
-    a.root = w->count == 1 ? ~0 : 0;
-    a.rows = w->d_rows;
-    a.nodes = w->d_nodes;
     if (box) {   // (world_box.hip; the triangles query's list: k x 64 x 8 B of dynamic LDS, the launch's)
         if (kind == Q_BOX_TRIS) a.count = d_count;
         return world_box_launch(c, (int)kind - (int)Q_BOX_ANY, grid, a);
@@ -928,6 +949,7 @@ int world_mesh_query(psm_world* w, psm_bvh* o, const float* poses, size_t p, int
     uint32_t L = 0;
     void* d_poses = nullptr;
     WorldMeshArgs m = {};
+    m.w = world_start(w);
     uint32_t grid = 0;
     if (w->count != 0) {   // (an empty world: no query kernel, nothing to upload; the clears alone)
         rc = mesh_upload(c, o, poses, p, &d_poses, nullptr, &L);
@@ -948,9 +970,6 @@ int world_mesh_query(psm_world* w, psm_bvh* o, const float* poses, size_t p, int
     if (w->count == 0 || L == 0) return PSM_OK;
     m.w.geom = d_inst;
     if (rows) m.w.count = d_count;
-    m.w.root = w->count == 1 ? ~0 : 0;
-    m.w.rows = w->d_rows;
-    m.w.nodes = w->d_nodes;
     m.tri48 = o->d_tri48; m.leaf_tri = o->d_leaftri; m.poses = (const float4*)d_poses;
     m.L = L; m.T = T; m.skip = skip;
     m.flags = mesh_skip(p * (size_t)L) ? WORLD_MESH_FLAG_SKIP : 0u;   // (read by the flag kernel alone)
@@ -987,6 +1006,7 @@ int world_mesh_dist_query(psm_world* w, psm_bvh* o, const float* poses, size_t p
     uint32_t L = 0;
     void *d_poses = nullptr, *d_keys = nullptr;
     WorldMeshDistArgs a = {};
+    a.m.w = world_start(w);
     uint32_t grid = 0;
     if (w->count != 0) {   // (an empty world: no query kernel, nothing to upload; the miss records alone)
         rc = mesh_upload(c, o, poses, p, &d_poses, mode == WMD_CLEAR ? &d_keys : nullptr, &L);
@@ -1007,9 +1027,6 @@ int world_mesh_dist_query(psm_world* w, psm_bvh* o, const float* poses, size_t p
     }
     if (!walk) return PSM_OK;
     a.m.w.geom = d_inst;
-    a.m.w.root = w->count == 1 ? ~0 : 0;
-    a.m.w.rows = w->d_rows;
-    a.m.w.nodes = w->d_nodes;
     a.m.tri48 = o->d_tri48; a.m.leaf_tri = o->d_leaftri; a.m.poses = (const float4*)d_poses;
     a.m.L = L; a.m.T = T; a.m.skip = skip;
     a.keys = (unsigned long long*)d_keys;
@@ -1035,35 +1052,21 @@ const char* const WORLD_GRID_NAME[] = {"psm_grid_world_surface_dev", "psm_grid_w
 enum { WGRID_SOLID = 3 };   // (beside psm_world_dev.h's WGRID_SURFACE, WGRID_COUNTS, WGRID_INSTANCES: the surface launch, then the fill)
 
 // A grid over a world (world_grid.hip): grid.hip's grid_query() with a world where the hierarchy was, of the same
-// shared pieces (psm_query_host.h). The NULL world is answered before anything else is looked at; then the pointers, the grid,
-// the alignment, samples -- all on the host, before any launch, the output untouched. An empty world is answered in stream order
-// without a query kernel; then the stale refusal (every world query's). The depth rule is psm_world_set_instances': the wave's one
-// stack holds depth + deepest + 1 links. Solid: the surface launch, then grid.hip's scheme slab by slab with
-// psm_world_inside_dev where the hierarchy's inside query was
+// shared pieces (psm_query_host.h). The NULL world is answered before anything else is looked at; then the front
+// every grid call shares (grid_front: the pointers, the grid, the alignment, samples) -- all on the host, before any launch, the
+// output untouched. An empty world is answered in stream order without a query kernel, BEFORE the stale refusal (every world
+// query's; the mesh queries above have the two the other way round). The depth rule is psm_world_set_instances': the wave's one
+// stack holds depth + deepest + 1 links. Solid: the surface launch, then the shared slab loop with psm_world_inside_dev where the
+// hierarchy's inside query was
 int world_grid_query(psm_world* w, const psm_grid* grid, int call, uint32_t samples, void* d_out) {
     if (!w) return PSM_ERR_INVALID;
     psm_ctx* c = w->ctx;
     const char* name = WORLD_GRID_NAME[call];
-    char msg[160];
-    if (!grid || !d_out) {
-        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    GridShape s;
-    if (const char* why = grid_fault(grid, s)) {
-        snprintf(msg, sizeof msg, "%s: invalid grid: %s", name, why);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
     const bool words = call == WGRID_SURFACE || call == WGRID_SOLID;
-    const unsigned align = words ? 8u : 4u;
-    if (((uintptr_t)d_out & (uintptr_t)(align - 1u)) != 0) {
-        snprintf(msg, sizeof msg, "%s: %s not %u-byte aligned", name, words ? "bricks" : (call == WGRID_COUNTS ? "counts" : "inst"), align);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (call == WGRID_SOLID && samples != 1 && samples != 3 && samples != 5) {
-        snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
+    GridShape s;
+    int rc = grid_front(c, name, grid, d_out, s, words ? "bricks" : (call == WGRID_COUNTS ? "counts" : "inst"), d_out, words ? 8u : 4u,
+                        nullptr, call == WGRID_SOLID ? &samples : nullptr);
+    if (rc != PSM_OK) return rc;
     (void)hipSetDevice(c->device);
     if (w->count == 0) {   // an empty world: no voxel is set, no query kernel runs
         const size_t voxels = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];   // (a valid grid: below 2^37)
@@ -1073,86 +1076,52 @@ int world_grid_query(psm_world* w, const psm_grid* grid, int call, uint32_t samp
     }
     const int stale = first_stale(w);
     if (stale >= 0) return refuse_stale(w, name, stale);
-    WorldGridArgs g = {};
-    g.ox = grid->origin[0]; g.oy = grid->origin[1]; g.oz = grid->origin[2];
-    g.cx = grid->cell[0]; g.cy = grid->cell[1]; g.cz = grid->cell[2];
-    g.nx = grid->dims[0]; g.ny = grid->dims[1]; g.nz = grid->dims[2];
-    g.nbx = s.nb[0]; g.nby = s.nb[1];
-    g.bricks = (uint32_t)s.bricks;
-    g.root = w->count == 1 ? ~0 : 0;
-    void* scratch = nullptr;
-    const uint32_t slab = s.bricks < GRID_SLAB_BRICKS ? (uint32_t)s.bricks : GRID_SLAB_BRICKS;
+    const WorldGridArgs g = world_grid_args(grid, s, w);
+    GridSlabs a;
     if (call == WGRID_SOLID) {   // (the last thing that can fail before the output changes)
-        const int rc = scratch_for(c, slab, &scratch);
+        rc = slabs_for(c, s.bricks, false, a);
         if (rc != PSM_OK) return rc;
     }
     const uint32_t blocks = (uint32_t)(s.bricks < QUERY_GRID_CAP ? s.bricks : QUERY_GRID_CAP);
-    int rc = world_grid_launch(c, call == WGRID_SOLID ? (int)WGRID_SURFACE : call, blocks, g, w->d_rows, w->d_nodes, d_out);
+    rc = world_grid_launch(c, call == WGRID_SOLID ? (int)WGRID_SURFACE : call, blocks, g, w->d_rows, w->d_nodes, d_out);
     if (rc != PSM_OK || call != WGRID_SOLID) return rc;
     // the inside of the surface, a slab of bricks at a time, all in stream order: the centres, the world's inside query over
     // them, the flags' ballots ORed into the words
-    uint8_t* flags = grid_slab_flags(scratch, slab);
-    for (uint64_t first = 0; first < s.bricks; first += slab) {
-        const uint64_t left = s.bricks - first;
-        const uint32_t bricks = left < slab ? (uint32_t)left : slab;
-        rc = grid_centres_launch(c, grid, s, (uint32_t)first, bricks, scratch);
-        if (rc != PSM_OK) return rc;
-        rc = psm_world_inside_dev(w, (const psm_point_query*)scratch, (size_t)bricks * QUERY_BLOCK, samples, flags);
-        if (rc != PSM_OK) return rc;
-        rc = grid_fill_launch(c, grid, s, (uint32_t)first, bricks, flags, (uint64_t*)d_out);
-        if (rc != PSM_OK) return rc;
-    }
-    return PSM_OK;
+    return grid_slabs(s.bricks, a.slab, [&](uint32_t first, uint32_t bricks) {
+        int rc = grid_centres_launch(c, grid, s, first, bricks, a.points);
+        if (rc == PSM_OK) rc = psm_world_inside_dev(w, (const psm_point_query*)a.points, (size_t)bricks * QUERY_BLOCK, samples, a.flags);
+        if (rc == PSM_OK) rc = grid_fill_launch(c, grid, s, first, bricks, a.flags, (uint64_t*)d_out);
+        return rc;
+    });
 }
 
 // psm_world_signed_distance_dev's second kernel alone, over n points and the closest-point records a grid walk wrote for them:
 // the twin of query.hip's sign_launch. The caller has made every check (the world is not empty and not stale, samples is 1, 3 or 5)
 int world_sign_launch(psm_world* w, const void* d_points, size_t n, uint32_t samples, void* d_hits) {
-    WorldArgs a = {};
+    WorldArgs a = world_start(w);
     uint32_t grid = 0;
     const int rc = batch_args(w->ctx, d_points, n, d_hits, samples, a, grid);
     if (rc != PSM_OK) return rc;
-    a.root = w->count == 1 ? ~0 : 0;
-    a.rows = w->d_rows;
-    a.nodes = w->d_nodes;
     world_query_sign<<<grid, QUERY_BLOCK, 0, w->ctx->stream>>>(a);
     PSM_HIP(w->ctx, hipGetLastError());
     return PSM_OK;
 }
 
 // A distance-field grid over a world (world_grid_dist.hip): grid_dist.hip's dist_query() with a world where the
-// hierarchy was. The NULL world is answered before anything else is looked at; then the pointers, the grid, the alignment, rmax,
-// samples -- all on the host, before any launch, the outputs untouched. An empty world is answered in stream order by fills
-// alone; then the stale refusal (every world query's). The depth rule is psm_world_set_instances'. Signed: grid_dist.hip's scheme
-// slab by slab -- the centres, the walk's records beside them, the world's sign kernel over both, the records into the dense
-// arrays --, the instances written by the walk itself
+// hierarchy was, of the same shared pieces. The NULL world is answered before anything else is looked at; then grid_front (the
+// pointers, the grid, the alignment, rmax, samples) -- all on the host, before any launch, the outputs untouched. An empty world is
+// answered in stream order by fills alone; then the stale refusal (every world query's). The depth rule is
+// psm_world_set_instances'. Signed: the shared slab loop over slabs_for()'s scratch -- the centres, the walk's records beside them,
+// the world's sign kernel over both, the records into the dense arrays --, the instances written by the walk itself
 int world_grid_dist_query(psm_world* w, const psm_grid* grid, float rmax, bool sign, uint32_t samples, float* d_dist, int32_t* d_tri,
                           int32_t* d_inst) {
     if (!w) return PSM_ERR_INVALID;
     psm_ctx* c = w->ctx;
     const char* name = sign ? "psm_grid_world_signed_distance_dev" : "psm_grid_world_distance_dev";
-    char msg[160];
-    if (!grid || !d_dist) {
-        snprintf(msg, sizeof msg, "%s: NULL pointer", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
     GridShape s;
-    if (const char* why = grid_fault(grid, s)) {
-        snprintf(msg, sizeof msg, "%s: invalid grid: %s", name, why);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if ((((uintptr_t)d_dist | (uintptr_t)d_tri | (uintptr_t)d_inst) & (uintptr_t)3u) != 0) {
-        snprintf(msg, sizeof msg, "%s: dist, tri or inst not 4-byte aligned", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (!(rmax >= 0.f)) {   // (NaN too; -0 is 0, +inf is no limit)
-        snprintf(msg, sizeof msg, "%s: rmax must be >= 0", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
-    if (sign && samples != 1 && samples != 3 && samples != 5) {
-        snprintf(msg, sizeof msg, "%s: samples must be 1, 3 or 5", name);
-        return set_err(c, PSM_ERR_INVALID, msg);
-    }
+    int rc = grid_front(c, name, grid, d_dist, s, "dist, tri or inst", (const void*)((uintptr_t)d_dist | (uintptr_t)d_tri | (uintptr_t)d_inst),
+                        4, &rmax, sign ? &samples : nullptr);
+    if (rc != PSM_OK) return rc;
     (void)hipSetDevice(c->device);
     if (w->count == 0) {   // an empty world: every voxel misses, no query kernel runs
         const size_t voxels = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];   // (a valid grid: below 2^37)
@@ -1163,48 +1132,27 @@ int world_grid_dist_query(psm_world* w, const psm_grid* grid, float rmax, bool s
     }
     const int stale = first_stale(w);
     if (stale >= 0) return refuse_stale(w, name, stale);
-    WorldGridDistArgs a = {};
-    a.g.ox = grid->origin[0]; a.g.oy = grid->origin[1]; a.g.oz = grid->origin[2];
-    a.g.cx = grid->cell[0]; a.g.cy = grid->cell[1]; a.g.cz = grid->cell[2];
-    a.g.nx = grid->dims[0]; a.g.ny = grid->dims[1]; a.g.nz = grid->dims[2];
-    a.g.nbx = s.nb[0]; a.g.nby = s.nb[1];
-    a.g.bricks = (uint32_t)s.bricks;
-    a.g.root = w->count == 1 ? ~0 : 0;
-    a.first = 0u;
-    a.rmax = rmax;
+    WorldGridDistArgs a = {world_grid_args(grid, s, w), 0u, rmax};
     if (!sign) {
         const uint32_t blocks = (uint32_t)(s.bricks < QUERY_GRID_CAP ? s.bricks : QUERY_GRID_CAP);
         return world_grid_dist_launch(c, blocks, a, w->d_rows, w->d_nodes, d_dist, d_tri, d_inst, nullptr);
     }
-    // signed, a slab of bricks at a time, all in stream order. A voxel takes 32 bytes of scratch where solid's takes 17: a slab of
-    // n bricks asks for the area of 2 n of solid's, and a slab is half of solid's at most
-    const uint32_t cap = GRID_SLAB_BRICKS / 2u;
-    const uint32_t slab = s.bricks < cap ? (uint32_t)s.bricks : cap;
-    void* scratch = nullptr;
-    int rc = scratch_for(c, 2u * slab, &scratch);
+    // signed, a slab of bricks at a time, all in stream order. The scratch and the context's stack area, which the sign launches
+    // use, are the last things that can fail before the outputs change
+    GridSlabs sl;
+    void* spill = nullptr;
+    rc = slabs_for(c, s.bricks, true, sl);
+    if (rc == PSM_OK) rc = spill_for(c, &spill);
     if (rc != PSM_OK) return rc;
-    {   // (the context's stack area, which the sign launches use: with the scratch the last things that can fail before the outputs change)
-        void* spill = nullptr;
-        rc = spill_for(c, &spill);
-        if (rc != PSM_OK) return rc;
-    }
-    float4* points = (float4*)scratch;
-    float4* hits = points + (size_t)slab * QUERY_BLOCK;
-    for (uint64_t first = 0; first < s.bricks; first += slab) {
-        const uint64_t left = s.bricks - first;
-        const uint32_t bricks = left < slab ? (uint32_t)left : slab;
-        rc = grid_centres_launch(c, grid, s, (uint32_t)first, bricks, points);
-        if (rc != PSM_OK) return rc;
-        a.first = (uint32_t)first; a.g.bricks = bricks;
+    return grid_slabs(s.bricks, sl.slab, [&](uint32_t first, uint32_t bricks) {
+        int rc = grid_centres_launch(c, grid, s, first, bricks, sl.points);
+        a.first = first; a.g.bricks = bricks;
         const uint32_t blocks = bricks < QUERY_GRID_CAP ? bricks : QUERY_GRID_CAP;
-        rc = world_grid_dist_launch(c, blocks, a, w->d_rows, w->d_nodes, nullptr, nullptr, d_inst, hits);
-        if (rc != PSM_OK) return rc;
-        rc = world_sign_launch(w, points, (size_t)bricks * QUERY_BLOCK, samples, hits);
-        if (rc != PSM_OK) return rc;
-        rc = grid_dist_scatter_launch(c, grid, s, (uint32_t)first, bricks, hits, d_dist, d_tri);
-        if (rc != PSM_OK) return rc;
-    }
-    return PSM_OK;
+        if (rc == PSM_OK) rc = world_grid_dist_launch(c, blocks, a, w->d_rows, w->d_nodes, nullptr, nullptr, d_inst, sl.hits);
+        if (rc == PSM_OK) rc = world_sign_launch(w, sl.points, (size_t)bricks * QUERY_BLOCK, samples, sl.hits);
+        if (rc == PSM_OK) rc = grid_dist_scatter_launch(c, grid, s, first, bricks, sl.hits, d_dist, d_tri);
+        return rc;
+    });
 }
 
 template <class T>
