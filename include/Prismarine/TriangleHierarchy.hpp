@@ -84,6 +84,16 @@ namespace NSM {
         // psm_grid_signed_distance_dev). Read back into the vectors as voxelize does; returns the psm_status
         int distanceField(const psm_grid & grid, float rmax, std::vector<float> & dist, std::vector<int32_t> * tri = nullptr);
         int signedDistanceField(const psm_grid & grid, float rmax, uint32_t samples, std::vector<float> & dist, std::vector<int32_t> * tri = nullptr);
+        // not in the reference: the same for the non-empty 4 x 4 x 4 bricks alone (psm_hip.h "voxel grids: sparse"): ids = the
+        // ascending brick indices (bz * nby + by) * nbx + bx whose surface word is non-zero (sparseVoxelize) or that hold a voxel
+        // centre within rmax of a triangle (the two distance forms), words [n] = voxelize's words of those bricks, dist / tri
+        // [n][64] = distanceField's / signedDistanceField's answers of their voxels in lane order (z & 3) * 16 + (y & 3) * 4 +
+        // (x & 3), +inf / -1 for a voxel outside dims. Each lists (the count is read back: one wait), fills and reads back into
+        // the vectors (a refused call leaves them empty); returns the psm_status
+        int sparseVoxelize(const psm_grid & grid, std::vector<uint32_t> & ids, std::vector<uint64_t> & words);
+        int sparseDistanceField(const psm_grid & grid, float rmax, std::vector<uint32_t> & ids, std::vector<float> & dist, std::vector<int32_t> * tri = nullptr);
+        int sparseSignedDistanceField(const psm_grid & grid, float rmax, uint32_t samples, std::vector<uint32_t> & ids, std::vector<float> & dist,
+                                      std::vector<int32_t> * tri = nullptr);
         // not in the reference: whether / how many / which triangles meet each of n query triangles (closed: touching counts; a
         // separating-axis test in float32, psm_hip.h "triangle queries"); triTriangles: 1 <= k <= PSM_QUERY_K_MAX, d_ids [n][k] =
         // the lowest ids that count, ascending, then -1, d_count [n] = the slots that hold one (psm_bvh_tri_overlaps_dev /

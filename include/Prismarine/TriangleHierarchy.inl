@@ -153,6 +153,69 @@ namespace NSM {
         return distanceReadBack(grid, dist, tri, nullptr, "TriangleHierarchy::signedDistanceField",
                                 [&](float * d, int32_t * t, int32_t *) { return psm_grid_signed_distance_dev(bvh, &grid, rmax, samples, d, t); });
     }
+    // the sparse grids: the count is read back first (the one wait before the fill), then the list and `per` 4-byte entries of
+    // answer a brick go into one device buffer -- the ids, the count, the answers from an even entry on -- read back and split
+    template <class List, class Fill>
+    inline int sparseReadBack(size_t per, std::vector<uint32_t> & ids, std::vector<uint32_t> & answers, const char * what, List list, Fill fill) {
+        ids.clear();
+        answers.clear();
+        std::vector<uint32_t> all;
+        int rc = gridReadBack<uint32_t>(4, all, what, [&](uint32_t * d) { return list(0u, (uint32_t *)nullptr, d); });
+        if (rc != PSM_OK || all[0] == 0u) return rc;
+        const uint32_t n = all[0];
+        const size_t at = ((size_t)n + 2) & ~(size_t)1;
+        rc = gridReadBack<uint32_t>(at + per * n, all, what, [&](uint32_t * d) {
+            const int listed = list(n, d, d + n);
+            return listed == PSM_OK ? fill(d, n, d + at) : listed;
+        });
+        if (rc != PSM_OK) return rc;
+        ids.assign(all.begin(), all.begin() + n);
+        answers.assign(all.begin() + at, all.end());
+        return rc;
+    }
+    inline int sparseDistanceSplit(int rc, const std::vector<uint32_t> & answers, size_t n, std::vector<float> & dist, std::vector<int32_t> * tri) {
+        dist.clear();
+        if (tri) tri->clear();
+        if (rc != PSM_OK) return rc;
+        dist.resize(64 * n);
+        std::memcpy(dist.data(), answers.data(), 64 * n * sizeof(float));
+        if (tri) {
+            tri->resize(64 * n);
+            std::memcpy(tri->data(), answers.data() + 64 * n, 64 * n * sizeof(int32_t));
+        }
+        return rc;
+    }
+    inline int TriangleHierarchy::sparseVoxelize(const psm_grid & grid, std::vector<uint32_t> & ids, std::vector<uint64_t> & words) {
+        std::vector<uint32_t> answers;
+        words.clear();
+        const int rc = sparseReadBack(2, ids, answers, "TriangleHierarchy::sparseVoxelize",
+                                      [&](uint32_t capacity, uint32_t * d_ids, uint32_t * d_count) { return psm_grid_sparse_surface_bricks_dev(bvh, &grid, capacity, d_ids, d_count); },
+                                      [&](const uint32_t * d_ids, uint32_t n, uint32_t * d) { return psm_grid_sparse_surface_dev(bvh, &grid, d_ids, n, (uint64_t *)d); });
+        if (rc != PSM_OK) return rc;
+        words.resize(ids.size());
+        std::memcpy(words.data(), answers.data(), ids.size() * sizeof(uint64_t));
+        return rc;
+    }
+    inline int TriangleHierarchy::sparseDistanceField(const psm_grid & grid, float rmax, std::vector<uint32_t> & ids, std::vector<float> & dist,
+                                                      std::vector<int32_t> * tri) {
+        std::vector<uint32_t> answers;
+        const int rc = sparseReadBack(tri ? 128 : 64, ids, answers, "TriangleHierarchy::sparseDistanceField",
+                                      [&](uint32_t capacity, uint32_t * d_ids, uint32_t * d_count) { return psm_grid_sparse_distance_bricks_dev(bvh, &grid, rmax, capacity, d_ids, d_count); },
+                                      [&](const uint32_t * d_ids, uint32_t n, uint32_t * d) {
+                                          return psm_grid_sparse_distance_dev(bvh, &grid, rmax, d_ids, n, (float *)d, tri ? (int32_t *)(d + (size_t)64 * n) : nullptr);
+                                      });
+        return sparseDistanceSplit(rc, answers, ids.size(), dist, tri);
+    }
+    inline int TriangleHierarchy::sparseSignedDistanceField(const psm_grid & grid, float rmax, uint32_t samples, std::vector<uint32_t> & ids,
+                                                            std::vector<float> & dist, std::vector<int32_t> * tri) {
+        std::vector<uint32_t> answers;
+        const int rc = sparseReadBack(tri ? 128 : 64, ids, answers, "TriangleHierarchy::sparseSignedDistanceField",
+                                      [&](uint32_t capacity, uint32_t * d_ids, uint32_t * d_count) { return psm_grid_sparse_distance_bricks_dev(bvh, &grid, rmax, capacity, d_ids, d_count); },
+                                      [&](const uint32_t * d_ids, uint32_t n, uint32_t * d) {
+                                          return psm_grid_sparse_signed_distance_dev(bvh, &grid, rmax, samples, d_ids, n, (float *)d, tri ? (int32_t *)(d + (size_t)64 * n) : nullptr);
+                                      });
+        return sparseDistanceSplit(rc, answers, ids.size(), dist, tri);
+    }
     inline int TriangleHierarchy::boxTriangles(const psm_box_query * d_boxes, size_t n, uint32_t k, int32_t * d_tris, uint32_t * d_count) {
         const int rc = psm_bvh_box_triangles_dev(bvh, d_boxes, n, k, d_tris, d_count);
         check(rc, "TriangleHierarchy::boxTriangles");

@@ -1196,10 +1196,9 @@ int psm_world_mesh_clearance_dev(psm_world* world, psm_bvh* other, const float* 
  *     MiB, freed with the context), and its inside launches use the context's stack area, which the context's first query
  *     allocates: capture it only after a plain call with a grid at least as large
  *   - 0 leaves: all zero; 1 leaf: that leaf is tested; after psm_bvh_refit the refitted boxes are used
- *   - not covered: grids over a flat scene or an instanced list (a world has its own, "voxel grids over a world" below); a
- *     sparse output (a list of
- *     the non-empty bricks); a coarse level that culls empty regions before the brick walk; conservative or 6-separating thin
- *     voxelisation; oriented grids */
+ *   - not covered: grids over a flat scene or an instanced list (a world has its own, "voxel grids over a world" below);
+ *     conservative or 6-separating thin voxelisation; oriented grids. (The list of the non-empty bricks and the coarse level
+ *     that culls empty regions before the brick walk are "voxel grids: sparse" below) */
 #define PSM_GRID_DIM_MAX (1u << 20)
 typedef struct {
     float origin[3];   /* corner of voxel (0, 0, 0) */
@@ -1237,10 +1236,58 @@ uint64_t psm_grid_brick_count(const psm_grid* grid);   /* 0 for an invalid grid 
  *     the context's stack area, which the context's first query allocates
  *   - 0 leaves: all +inf / -1; 1 leaf: that leaf is tested; after psm_bvh_refit the refitted boxes are used
  *   - not covered: distance grids over a flat scene or an instanced list (a world has its own, "voxel grids over a world:
- *     distance fields" below); u, v and the closest point per voxel; a per-voxel rmax; a sparse output; sweeping-based
- *     (approximate) distance transforms; graph capture of the signed call */
+ *     distance fields" below); u, v and the closest point per voxel; a per-voxel rmax; sweeping-based
+ *     (approximate) distance transforms; graph capture of the signed call. (The band's bricks alone: "voxel grids: sparse") */
 int psm_grid_distance_dev(psm_bvh* bvh, const psm_grid* grid, float rmax, float* d_dist /*[nz][ny][nx]*/, int32_t* d_tri /*[nz][ny][nx] or NULL*/);
 int psm_grid_signed_distance_dev(psm_bvh* bvh, const psm_grid* grid, float rmax, uint32_t samples, float* d_dist, int32_t* d_tri);
+
+/* voxel grids: sparse (new; no reference counterpart): which 4 x 4 x 4 bricks of a psm_grid hold anything at
+ * all, as an ascending list, and the surface words or the (signed) distances of the bricks of a list -- a narrow band costs
+ * its own bricks, not the grid's. Everything is DEFINED by the dense calls above, bit for bit; psm_grid, its validity rules,
+ * the brick index (bz * nby + by) * nbx + bx and the bit / lane order j = (z & 3) * 16 + (y & 3) * 4 + (x & 3) are those of
+ * "voxel grids".
+ * Listing (the two *_bricks_dev calls):
+ *   - the surface call lists brick b iff word b of psm_grid_surface_dev is non-zero; the distance call lists b iff some voxel
+ *     of b has a record in psm_grid_distance_dev(rmax), tri >= 0 (closed: a centre at exactly rmax counts)
+ *   - *d_count is the number of such bricks in the whole grid, also when it exceeds capacity; d_ids gets the first
+ *     min(count, capacity) of them in ascending index, the slots past that are untouched. capacity 0 with d_ids NULL counts only
+ *   - the list is the same under every schedule: the compaction is an ordered scan (a count per 1 024 bricks, one workgroup's
+ *     scan, a scatter by rank), not an atomic append
+ *   - rmax as the dense rules have it; with +inf every brick of a mesh with a leaf is listed. 0 leaves: count 0
+ *   - how: a coarse pass, one lane per brick, drops the bricks the tree proves empty (the brick's whole box, or its centre
+ *     with rmax widened by the farthest centre's offset and a slack: conservative); the rest are walked as the
+ *     dense kernels walk them, one wave a brick, left at the first hit. PSM_SPARSE_COARSE = 0 (the environment, read at each
+ *     call; a study knob, no part of the contract) and rmax = +inf skip the coarse pass; the list is the same
+ * Filling (the other three):
+ *   - slot i answers brick d_ids[i]: d_words[i] is the dense surface word; d_dist[i * 64 + j] and d_tri[i * 64 + j] are the
+ *     dense dist and tri of the voxel at lane j. A lane outside dims holds +inf / -1: the sparse arrays have these padding
+ *     lanes, 64 a brick always, where the dense arrays have none. d_tri may be NULL
+ *   - an id at or above the grid's brick count is an empty brick: word 0, all +inf / -1; nothing is read or written out of
+ *     range. Duplicates are allowed, any order, any list: last step's band dilated, say. n == 0 is PSM_OK, nothing launched
+ *   - signed: psm_bvh_signed_distance_dev's sign kernel over the listed bricks' records, in slabs of at most 32 768 bricks of
+ *     the list in the scratch of "voxel grids"; a lane with no record casts no ray
+ * Refusals, all on the host before any launch and with the outputs untouched: those of the dense calls in their order and
+ * texts, the output they name being d_count, d_words or d_dist and the alignment that of every pointer passed (4 bytes, the
+ * words 8); then, after the hierarchy's state, a NULL d_ids with capacity > 0 or n > 0 (PSM_ERR_INVALID, "NULL pointer") and a
+ * grid of more than PSM_GRID_SPARSE_BRICKS_MAX bricks (PSM_ERR_CAPACITY; 2^27: a 2048^3 grid).
+ * Scratch: the listing calls keep a byte per brick, 4 bytes per 1 024 bricks, the candidates' count and -- with the coarse
+ * pass -- 4 bytes per brick of candidate ids in a context-owned area: at most 5 bricks + 4 ceil(bricks / 1024) + 768 bytes,
+ * 671 613 696 at the cap, 10.5 MB for a 512^3 grid; grown on demand, freed with the context. The listing calls and the two
+ * unsigned filling calls make no host synchronisation -- the candidates' count stays on the device, and the waves stride
+ * over it under PSM_QUERY_GRID_CAP -- and the unsigned filling calls allocate nothing: those two can always be captured into a
+ * graph, the listing calls after a plain call with a grid of at least as many bricks (and the same coarse setting). The
+ * signed filling call is not capturable, as the dense signed call.
+ * Not covered: sparse grids over a world; sparse counts or solid; bricks other than 4^3; a tree of bricks; dilating or
+ * eroding a list. */
+#define PSM_GRID_SPARSE_BRICKS_MAX (1u << 27)
+int psm_grid_sparse_surface_bricks_dev(psm_bvh* bvh, const psm_grid* grid, uint32_t capacity, uint32_t* d_ids /*[capacity] or NULL when capacity == 0*/,
+                                       uint32_t* d_count);
+int psm_grid_sparse_distance_bricks_dev(psm_bvh* bvh, const psm_grid* grid, float rmax, uint32_t capacity, uint32_t* d_ids, uint32_t* d_count);
+int psm_grid_sparse_surface_dev(psm_bvh* bvh, const psm_grid* grid, const uint32_t* d_ids, uint32_t n, uint64_t* d_words /*[n]*/);
+int psm_grid_sparse_distance_dev(psm_bvh* bvh, const psm_grid* grid, float rmax, const uint32_t* d_ids, uint32_t n, float* d_dist /*[n][64]*/,
+                                 int32_t* d_tri /*[n][64] or NULL*/);
+int psm_grid_sparse_signed_distance_dev(psm_bvh* bvh, const psm_grid* grid, float rmax, uint32_t samples, const uint32_t* d_ids, uint32_t n,
+                                        float* d_dist, int32_t* d_tri);
 
 /* voxel grids over a world (new; no reference counterpart): the grids above over the posed instances of a
  * psm_world -- the occupancy map of an assembled scene whose bodies move by a matrix per step --, and which body owns each

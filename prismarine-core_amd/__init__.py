@@ -49,6 +49,8 @@ EXPORTS = [
     "psm_world_mesh_closest_dev", "psm_world_mesh_within_dev", "psm_world_mesh_clearance_dev",
     "psm_grid_surface_dev", "psm_grid_counts_dev", "psm_grid_solid_dev", "psm_grid_brick_count",
     "psm_grid_distance_dev", "psm_grid_signed_distance_dev",
+    "psm_grid_sparse_surface_bricks_dev", "psm_grid_sparse_distance_bricks_dev", "psm_grid_sparse_surface_dev",
+    "psm_grid_sparse_distance_dev", "psm_grid_sparse_signed_distance_dev",
     "psm_grid_world_surface_dev", "psm_grid_world_counts_dev", "psm_grid_world_instances_dev", "psm_grid_world_solid_dev",
     "psm_grid_world_distance_dev", "psm_grid_world_signed_distance_dev",
     "psm_rt_create", "psm_rt_destroy", "psm_rt_resize_buffers", "psm_rt_resize", "psm_rt_set_tile", "psm_rt_set_tile_interleaved", "psm_rt_set_tile_weighted",
@@ -527,6 +529,28 @@ class TriangleHierarchy:
         g, r = _grid(origin, cell, dims), _rmax(rmax)
         return _distance_call(self.ctx, self._h, "psm_grid_", g, r, signed, samples, nearest, as_torch)
 
+    def sparseVoxelize(self, origin, cell, dims, bricks=None, as_torch=False):
+        """voxelize()'s surface for the non-empty bricks alone (psm_grid_sparse_surface_bricks_dev / psm_grid_sparse_surface_dev;
+        not in the reference): the ascending indices of the 4 x 4 x 4 bricks whose word is non-zero, and those words, bit for bit
+        voxelize()'s. bricks=None: the call lists with capacity 0 and reads the count -- its one synchronisation --, lists into
+        an array of exactly that size and fills it. bricks given (a numpy or torch array of uint32 brick indices (bz * nby +
+        by) * nbx + bx; torch: int32 or uint32 holding those bits): only the fill, slot i answering bricks[i]; any order,
+        duplicates allowed, an index at or above the brick count is an empty brick. Returns SparseVoxelGrid. Grid arguments and
+        as_torch as voxelize(). Not covered: solid or counts in sparse form; an InstanceWorld's grids."""
+        g = _grid(origin, cell, dims)
+        return _sparse_call(self.ctx, self._h, g, None, False, None, False, bricks, as_torch)
+
+    def sparseDistanceField(self, origin, cell, dims, rmax, signed=False, samples=3, nearest=True, bricks=None, as_torch=False):
+        """distanceField()'s narrow band for the bricks it reaches alone (psm_grid_sparse_distance_bricks_dev /
+        psm_grid_sparse_distance_dev / psm_grid_sparse_signed_distance_dev; not in the reference): the ascending indices of the
+        4 x 4 x 4 bricks with a voxel centre within rmax of a triangle, and the (signed) distances and nearest triangles of
+        their 64 voxels each, bit for bit distanceField()'s with the same rmax and samples; a voxel outside dims holds +inf /
+        -1. Memory and time follow the band, not the grid. bricks: as sparseVoxelize() (None: list, one synchronisation, then
+        fill; given: fill that list). Returns SparseDistanceGrid; tri is None with nearest=False. Not covered: an
+        InstanceWorld's fields; dilating a list."""
+        g, r = _grid(origin, cell, dims), _rmax(rmax)
+        return _sparse_call(self.ctx, self._h, g, r, signed, samples, nearest, bricks, as_torch)
+
     def triOverlaps(self, tris):
         """Whether some triangle of the hierarchy meets each query triangle (psm_bvh_tri_overlaps_dev; not in the reference): tris
         [n, 3, 3] or [n, 9], the vertices a, b, c of each. Closed (touching counts); a segment or a point is a valid query
@@ -943,6 +967,79 @@ class DistanceGrid:
         self.dist, self.tri, self.dims, self.origin, self.cell, self.inst = dist, tri, dims, origin, cell, inst
 
 
+def _brick_shape(dims):
+    """(nbz, nby, nbx) of a grid of dims = (nx, ny, nz)"""
+    return tuple((int(d) + 3) // 4 for d in reversed(dims))
+
+
+def _brick_scatter(ids, rows, shape, fill):
+    """rows [n, ...] of the bricks ids into an array / tensor [nbz * nby * nbx, ...] of `fill`; an id at or above the brick
+    count names no brick and is left out"""
+    total = shape[0] * shape[1] * shape[2]
+    if isinstance(rows, np.ndarray):
+        at = np.asarray(ids).astype(np.int64)
+        out = np.full((total,) + rows.shape[1:], fill, rows.dtype)
+        out[at[at < total]] = rows[at < total]
+        return out
+    import torch
+    at = ids.to(torch.int64) & 0xFFFFFFFF   # (an int32 tensor holds the uint32 bits)
+    out = torch.full((total,) + tuple(rows.shape[1:]), fill, dtype=rows.dtype, device=rows.device)
+    out[at[at < total]] = rows[at < total]
+    return out
+
+
+class _SparseGrid:
+    def coords(self):
+        """(bx, by, bz) of each listed brick, int64 [n, 3] (numpy, or a tensor on the ids' device)"""
+        nbz, nby, nbx = _brick_shape(self.dims)
+        if isinstance(self.ids, np.ndarray):
+            b = self.ids.astype(np.int64)
+            return np.stack([b % nbx, (b // nbx) % nby, b // (nbx * nby)], axis=1)
+        import torch
+        b = self.ids.to(torch.int64) & 0xFFFFFFFF
+        return torch.stack([b % nbx, torch.div(b, nbx, rounding_mode="floor") % nby, torch.div(b, nbx * nby, rounding_mode="floor")], dim=1)
+
+    def __len__(self):
+        return int(self.ids.shape[0])
+
+
+class SparseVoxelGrid(_SparseGrid):
+    """What TriangleHierarchy.sparseVoxelize returns. ids: uint32 [n], the brick indices (bz * nby + by) * nbx + bx, ascending
+    when the call listed them; words: uint64 [n], VoxelGrid's word of brick ids[i] (torch: int32 / int64 tensors holding the same
+    bits). dims = (nx, ny, nz), origin and cell as given (float32 values). coords(): (bx, by, bz) per brick; dense(): the
+    VoxelGrid with these words and 0 elsewhere."""
+
+    def __init__(self, ids, words, dims, origin, cell):
+        self.ids, self.words, self.dims, self.origin, self.cell = ids, words, dims, origin, cell
+
+    def dense(self):
+        shape = _brick_shape(self.dims)
+        return VoxelGrid(_brick_scatter(self.ids, self.words, shape, 0).reshape(shape), self.dims, self.origin, self.cell)
+
+
+class SparseDistanceGrid(_SparseGrid):
+    """What TriangleHierarchy.sparseDistanceField returns. ids: uint32 [n] as SparseVoxelGrid's; dist: float32 [n, 4, 4, 4], axes
+    (z, y, x) within the brick, the (signed) distance at each voxel centre of brick ids[i], +inf where no triangle lies within
+    rmax and for a voxel outside dims; tri: int32 [n, 4, 4, 4], the nearest triangle, -1 where dist is +inf, or None when the ids
+    were not asked for. coords(): (bx, by, bz) per brick; dense(): the DistanceGrid [nz, ny, nx] with these bricks and +inf / -1
+    elsewhere."""
+
+    def __init__(self, ids, dist, tri, dims, origin, cell):
+        self.ids, self.dist, self.tri, self.dims, self.origin, self.cell = ids, dist, tri, dims, origin, cell
+
+    def dense(self):
+        nx, ny, nz = self.dims
+        shape = _brick_shape(self.dims)
+
+        def cube(rows, fill):
+            c = _brick_scatter(self.ids, rows, shape, fill).reshape(shape + (4, 4, 4))
+            c = c.transpose(0, 3, 1, 4, 2, 5) if isinstance(c, np.ndarray) else c.permute(0, 3, 1, 4, 2, 5)
+            c = c.reshape(4 * shape[0], 4 * shape[1], 4 * shape[2])[:nz, :ny, :nx]
+            return np.ascontiguousarray(c) if isinstance(c, np.ndarray) else c.contiguous()
+
+        return DistanceGrid(cube(self.dist, np.inf), None if self.tri is None else cube(self.tri, -1), self.dims, self.origin, self.cell)
+
+
 class QueryHitLists:
     """The rows of TriangleHierarchy.firstHits / .nearest and InstanceWorld.firstHits / .nearest: `buffer` [n, k, 4] float32 (numpy
     array or torch tensor) holds psm_hit records (u, v, t, tri); u, v, t and tri (int32) [n, k] are views of it. count [n]: the
@@ -1312,6 +1409,76 @@ def _distance_call(ctx, handle, prefix, g, r, signed, samples, nearest, as_torch
     outs = _device_call(ctx, call, [(shape, np.float32)] + ([(shape, np.int32)] * ids if nearest else []), as_torch)
     outs += [None] * (3 - len(outs))
     return DistanceGrid(outs[0], outs[1], tuple(g.dims), tuple(g.origin), tuple(g.cell), outs[2])
+
+
+def _sparse_call(ctx, handle, g, r, signed, samples, nearest, bricks, as_torch):
+    """One sparse grid call of a hierarchy: r None -- the surface (SparseVoxelGrid) --, else the distance field with band r
+    (_rmax()'s), signed with samples, tri stored iff nearest (SparseDistanceGrid). bricks None: the count (the one
+    synchronisation), then the list into an exact-size array and the fill, in one _device_call; bricks given: the fill alone."""
+    surface = r is None
+    lister = "psm_grid_sparse_surface_bricks_dev" if surface else "psm_grid_sparse_distance_bricks_dev"
+    filler = "psm_grid_sparse_surface_dev" if surface else ("psm_grid_sparse_signed_distance_dev" if signed else "psm_grid_sparse_distance_dev")
+    band = () if surface else (C.c_float(r),)
+    extra = band + ((C.c_uint32(_samples(samples, filler)),) if signed and not surface else ())
+    list_fn, fill_fn = getattr(lib(), lister), getattr(lib(), filler)
+    dims, origin, cell = tuple(g.dims), tuple(g.origin), tuple(g.cell)
+
+    def result(ids, outs):
+        n = ids.shape[0]
+        if surface:
+            return SparseVoxelGrid(ids, outs[0], dims, origin, cell)
+        return SparseDistanceGrid(ids, outs[0].reshape(n, 4, 4, 4), outs[1].reshape(n, 4, 4, 4) if nearest else None, dims, origin, cell)
+
+    def fills(n):
+        return [((n,), np.uint64)] if surface else [((n, 64), np.float32)] + ([((n, 64), np.int32)] if nearest else [])
+
+    def fill(p_ids, n, ptrs):
+        if n:   # (an empty list asks nothing, and an empty array may have no address)
+            ptrs = tuple(ptrs) + (None,) * ((1 if surface else 2) - len(ptrs))
+            ctx.check(fill_fn(handle, C.byref(g), *extra, C.c_void_p(p_ids), C.c_uint32(n), *[C.c_void_p(p) for p in ptrs]), filler)
+
+    if bricks is None:
+        def count(p_count):
+            ctx.check(list_fn(handle, C.byref(g), *band, C.c_uint32(0), None, C.c_void_p(p_count)), lister)
+
+        n = int(_device_call(ctx, count, [((1,), np.uint32)], False)[0][0])
+
+        def call(p_ids, p_count, *ptrs):
+            ctx.check(list_fn(handle, C.byref(g), *band, C.c_uint32(n), C.c_void_p(p_ids) if n else None, C.c_void_p(p_count)), lister)
+            fill(p_ids, n, ptrs)
+
+        outs = _device_call(ctx, call, [((n,), np.uint32), ((1,), np.uint32)] + fills(n), as_torch)
+        return result(outs[0], outs[2:])
+    if type(bricks).__module__.split(".")[0] == "torch":
+        import torch
+        if bricks.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+            raise ValueError("sparse grid: bricks must hold uint32 brick indices")
+        ids = bricks.reshape(-1).contiguous() if as_torch else bricks.detach().cpu().numpy().view(np.uint32).reshape(-1)
+    else:
+        ids = np.ascontiguousarray(bricks)
+        if ids.dtype != np.uint32:
+            if ids.size and (not np.issubdtype(ids.dtype, np.integer) or ids.min() < 0 or ids.max() >= 1 << 32):
+                raise ValueError("sparse grid: bricks must hold uint32 brick indices")
+            ids = ids.astype(np.uint32)
+        ids = ids.reshape(-1)
+    n = int(ids.shape[0])
+    if n >= 1 << 32:
+        raise ValueError("sparse grid: 2^32 bricks or more")
+    if as_torch:
+        import torch
+        dev = torch.device("cuda", ctx.device)
+        if isinstance(ids, np.ndarray):
+            ids = torch.from_numpy(ids.view(np.int32)).to(dev)
+        elif ids.device != dev:
+            raise ValueError("sparse grid: bricks must be a tensor on the context's device")
+        return result(ids, _device_call(ctx, lambda *ptrs: fill(ids.data_ptr(), n, ptrs), fills(n), True))
+    h = ctx.buf_alloc(max(4 * n, 16))
+    try:
+        if n:
+            ctx.buf_upload(h, ids)
+        return result(ids, _device_call(ctx, lambda *ptrs: fill(ctx.buf_ptr(h)[0], n, ptrs), fills(n), False))
+    finally:
+        ctx.buf_free(h)
 
 
 def _bool_view(flags):

@@ -23,121 +23,19 @@
 #include "psm_query_dev.h"
 #include "psm_box_dev.h"   // box_tri, box_row
 #include "psm_grid_dev.h"
+#include "psm_grid_walk.h"   // grid_walk: shared with the list-driven kernels of grid_sparse.hip
 
 namespace psm {
 
-namespace {
-
-enum { GRID_SURFACE = 0, GRID_COUNTS = 1 };
-
-// (GridArgs, voxel_of, grid_for, grid_args: psm_grid_dev.h, shared with grid_dist.hip)
-
-// the grown image interval of a lane's voxel per normalised axis, and BoxBody::keep (box.hip) compare for compare: a child box
-// [mn, mx] is kept iff it meets the interval on all three axes (negations: a NaN keeps the box)
-struct Interval {
-    float glx, gly, glz, ghx, ghy, ghz;
-};
-PSM_D bool keep(const Interval& I, float mnx, float mny, float mnz, float mxx, float mxy, float mxz) {
-    bool out = mxx < I.glx;
-    out |= mnx > I.ghx;
-    out |= mxy < I.gly;
-    out |= mny > I.ghy;
-    out |= mxz < I.glz;
-    out |= mnz > I.ghz;
-    return !out;
-}
-
-// One wave per brick, grid-stride over the bricks. MODE: GRID_SURFACE -- a lane that has its bit stops voting, and the walk
-// ends when no lane wants anything --, GRID_COUNTS -- every live lane wants every leaf its interval keeps.
-// node32: the build's traversal records (bvh_emit); tri48: v0, e1, e2 per triangle; out: a uint64_t word per brick of the whole
-// grid (surface) or the dense uint32_t [nz][ny][nx] (counts)
-template <int MODE, class Out>
-PSM_D void grid_walk(const GridArgs& g, const uint4* __restrict__ node32, const float4* __restrict__ tri48, Out* __restrict__ out) {
-    __shared__ int stack[QSTACK_MAX];   // the wave's: every lane writes and reads the same entry
-    const int lane = (int)threadIdx.x;
-    __builtin_assume(lane >= 0 && lane < QUERY_BLOCK);
-    const int root = (int)g.sm[SM_ROOT];
-    const uint32_t count = g.sm[SM_COUNT];
-    const int lone = (count == 1u) ? g.sorted_tri[0] : -1;   // one leaf: no tree, the leaf's triangle is the only candidate
-    float M[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) M[k] = u2f(g.sm[SM_M + k]);
-    for (uint32_t b = blockIdx.x; b < g.bricks; b += gridDim.x) {
-        const Voxel v = voxel_of(g, g.first + b, lane);
-        v3 lo = mk3(0.f, 0.f, 0.f), hi = mk3(-1.f, -1.f, -1.f);   // a dead lane: lo > hi (BoxBody::begin)
-        if (v.inside) {
-            // one multiplication, then one addition (the build contracts nothing): neighbours share their face plane bit for bit
-            lo = mk3(g.ox + (float)v.ix * g.cx, g.oy + (float)v.iy * g.cy, g.oz + (float)v.iz * g.cz);
-            hi = mk3(g.ox + (float)(v.ix + 1u) * g.cx, g.oy + (float)(v.iy + 1u) * g.cy, g.oz + (float)(v.iz + 1u) * g.cz);
-        }
-        const bool valid = v.inside && finite3(lo) && finite3(hi) && lo.x <= hi.x && lo.y <= hi.y && lo.z <= hi.z;
-        Interval I;   // exactly as BoxBody::begin
-        box_row(M, 0, lo, hi, I.glx, I.ghx);
-        box_row(M, 1, lo, hi, I.gly, I.ghy);
-        box_row(M, 2, lo, hi, I.glz, I.ghz);
-        uint32_t cnt = 0u;   // per brick: the grid-stride loop comes here again
-        bool wants = valid;
-        int t0 = lone, t1 = -1;   // the leaves to test, wave-uniform
-        int cur = root, sp = 0;
-        bool walking = root >= 0;
-        for (;;) {
-            // the accepted leaves, one test after the other: the triangle is loaded once for the wave
-            while (t0 >= 0) {
-                const float4* tp = tri48 + (size_t)3 * (size_t)__builtin_amdgcn_readfirstlane(t0);
-                const float4 A = tp[0], B = tp[1], C = tp[2];
-                if (wants && box_tri(mk3(A.x, A.y, A.z), mk3(B.x, B.y, B.z), mk3(C.x, C.y, C.z), lo, hi)) cnt++;
-                t0 = t1;
-                t1 = -1;
-            }
-            if (MODE == GRID_SURFACE) wants = valid && cnt == 0u;
-            if (!walking || __ballot(wants) == 0ull) break;
-            cur = __builtin_amdgcn_readfirstlane(cur);
-            const uint4* np = (const uint4*)((const char*)node32 + ((size_t)(uint32_t)cur << 5));
-            const uint4 n0 = np[0], n1 = np[1];
-            const int lkx = (int)n1.z, lky = (int)n1.w;
-            // each lane judges both children against its own interval (the record's fp16 corners as BoxBody::children reads them)
-            const bool keepL = keep(I, half_lo(n0.x), half_hi(n0.x), half_lo(n0.y), half_hi(n0.y), half_lo(n0.z), half_hi(n0.z));
-            const bool keepR = keep(I, half_lo(n0.w), half_hi(n0.w), half_lo(n1.x), half_hi(n1.x), half_lo(n1.y), half_hi(n1.y));
-            const bool okL = __ballot(keepL && wants) != 0ull, okR = __ballot(keepR && wants) != 0ull;
-            const bool leafL = okL && lkx < 0, leafR = okR && lky < 0;
-            t0 = leafL ? ~lkx : (leafR ? ~lky : -1);
-            t1 = (leafL && leafR) ? ~lky : -1;
-            const bool intL = okL && !leafL, intR = okR && !leafR;
-            if (intL && intR) {
-                // (sp < QSTACK_MAX always: one entry per internal ancestor of the current node, as a lane's own stack; the host
-                // refuses hierarchies whose bound exceeds it. The test keeps every store and every pop inside the array)
-                if (sp < QSTACK_MAX) {
-                    stack[sp] = lky;
-                    sp++;
-                }
-            }
-            cur = intL ? lkx : lky;
-            if (!(intL || intR)) {
-                if (sp == 0) walking = false;   // (the node's leaves are still tested)
-                else {
-                    sp--;
-                    cur = stack[sp];
-                }
-            }
-        }
-        if (MODE == GRID_SURFACE) {
-            const unsigned long long word = __ballot(cnt != 0u);
-            if (lane == 0) out[g.first + b] = (Out)word;
-        } else if (valid) {
-            out[((size_t)v.iz * g.ny + v.iy) * g.nx + v.ix] = (Out)cnt;
-        }
-    }
-}
-
-}  // namespace
+// (GridArgs, voxel_of, grid_for, grid_args: psm_grid_dev.h; Interval, keep and the walk itself: psm_grid_walk.h)
 
 __global__ __launch_bounds__(QUERY_BLOCK, 8) void grid_surface(GridArgs g, const uint4* __restrict__ node32, const float4* __restrict__ tri48,
                                                                uint64_t* __restrict__ words) {
-    grid_walk<GRID_SURFACE>(g, node32, tri48, words);
+    grid_walk<GRID_SURFACE>(g, DenseBricks(), node32, tri48, words);
 }
 __global__ __launch_bounds__(QUERY_BLOCK, 8) void grid_counts(GridArgs g, const uint4* __restrict__ node32, const float4* __restrict__ tri48,
                                                               uint32_t* __restrict__ counts) {
-    grid_walk<GRID_COUNTS>(g, node32, tri48, counts);
+    grid_walk<GRID_COUNTS>(g, DenseBricks(), node32, tri48, counts);
 }
 
 // solid, before the inside launch: the centres of the slab's voxels as psm_point_query records in lane order (rmax is not read).
@@ -311,6 +209,7 @@ int grid_query(psm_bvh* b, const psm_grid* grid, int call, uint32_t samples, voi
 
 // for psm_ctx_destroy: solid's scratch goes with the context
 void grid_release(psm_ctx* c) {
+    sparse_release(c);   // (grid_sparse.hip: the sparse grids' flags and candidate ids)
     std::lock_guard<std::mutex> lk(scratch_mu);
     auto it = scratch_area.find(c);
     if (it == scratch_area.end()) return;

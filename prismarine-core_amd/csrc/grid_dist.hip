@@ -19,116 +19,18 @@
 #include "psm_query_host.h"
 #include "psm_query_dev.h"
 #include "psm_grid_dev.h"
+#include "psm_grid_walk.h"   // dist_walk: shared with the list-driven kernels of grid_sparse.hip
 
 namespace psm {
-
-namespace {
-
-// One wave per brick, grid-stride over the bricks. RECORDS = false: the dense dist / tri [nz][ny][nx] of the whole grid (tri
-// may be NULL); RECORDS = true: a psm_hit per lane of the launch's bricks in lane order (u = v = 0), a miss for a lane outside
-// dims, for the sign kernel of query.hip.
-// Visiting order: where both children are internal and kept, the wave goes first to the one that most of the lanes that keep a
-// child find nearer (their own kL <= kR): one ballot and two scalar bit counts per node on top of the two ballots that decide
-// the entry, where the minimum key over the lanes would take a cross-lane reduction per child. The 64 centres lie within one brick, so the vote is rarely close.
-template <bool RECORDS>
-PSM_D void dist_walk(const GridArgs& g, float rmax, const uint4* __restrict__ node32, const float4* __restrict__ tri48,
-                     float* __restrict__ dist, int32_t* __restrict__ tri, float4* __restrict__ hits) {
-    __shared__ int stack[QSTACK_MAX];   // the wave's: every lane writes and reads the same entry
-    const int lane = (int)threadIdx.x;
-    __builtin_assume(lane >= 0 && lane < QUERY_BLOCK);
-    const int root = (int)g.sm[SM_ROOT];
-    const uint32_t count = g.sm[SM_COUNT];
-    const int lone = (count == 1u) ? g.sorted_tri[0] : -1;   // one leaf: no tree, the leaf's triangle is the only candidate
-    float M[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) M[k] = u2f(g.sm[SM_M + k]);
-    const PointBound B = point_bound(M);
-    for (uint32_t b = blockIdx.x; b < g.bricks; b += gridDim.x) {
-        const Voxel v = voxel_of(g, g.first + b, lane);
-        // the centre as grid_centres writes it (grid.hip): one operation per rounding
-        const v3 p = mk3(g.ox + ((float)v.ix + 0.5f) * g.cx, g.oy + ((float)v.iy + 0.5f) * g.cy, g.oz + ((float)v.iz + 0.5f) * g.cz);
-        const bool live = v.inside && finite3(p);   // (PointBody::begin's valid; rmax was checked on the host)
-        PointImage P;
-        P.set(M, p);
-        // per brick: the grid-stride loop comes here again
-        float best = (rmax * rmax) * 1.00000095367431640625f + 0x1p-126f;   // fl(rmax^2) (1 + 2^-20) + 2^-126 (PointBody::begin)
-        int btri = -1;
-        bool found = false;
-        int t0 = lone, t1 = -1;   // the leaves to test, wave-uniform
-        int cur = root, sp = 0;
-        bool walking = root >= 0;
-        for (;;) {
-            // the accepted leaves, one test after the other: the triangle is loaded once for the wave
-            while (t0 >= 0) {
-                const int id = __builtin_amdgcn_readfirstlane(t0);
-                const float4* tp = tri48 + (size_t)3 * (size_t)id;
-                const float4 A = tp[0], Bv = tp[1], C = tp[2];
-                float u, w;
-                const float d2 = closest_on_tri(mk3(A.x, A.y, A.z), mk3(Bv.x, Bv.y, Bv.z), mk3(C.x, C.y, C.z), p, u, w);
-                // (PointBody::leaf, compare for compare)
-                if (live && sqrtf(d2) <= rmax && (d2 < best || (d2 == best && (uint32_t)id < (uint32_t)btri))) {
-                    found = true;
-                    best = d2;
-                    btri = id;
-                }
-                t0 = t1;
-                t1 = -1;
-            }
-            if (!walking) break;
-            cur = __builtin_amdgcn_readfirstlane(cur);
-            const uint4* np = (const uint4*)((const char*)node32 + ((size_t)(uint32_t)cur << 5));
-            const uint4 n0 = np[0], n1 = np[1];
-            const int lkx = (int)n1.z, lky = (int)n1.w;
-            bool keepL, keepR;
-            float kL, kR;
-            P.children(B, n0, n1, best, keepL, keepR, kL, kR);
-            const unsigned long long mL = __ballot(keepL && live), mR = __ballot(keepR && live);
-            const bool okL = mL != 0ull, okR = mR != 0ull;
-            const bool leafL = okL && lkx < 0, leafR = okR && lky < 0;
-            t0 = leafL ? ~lkx : (leafR ? ~lky : -1);
-            t1 = (leafL && leafR) ? ~lky : -1;
-            const bool intL = okL && !leafL, intR = okR && !leafR;
-            // nearer child first, by the majority of the lanes that keep one
-            const unsigned long long nearL = __ballot(live && (keepL || keepR) && kL <= kR);
-            const bool leftFirst = intL && (!intR || 2 * __popcll(nearL) >= __popcll(mL | mR));
-            const int first = leftFirst ? lkx : lky, second = leftFirst ? lky : lkx;
-            if (intL && intR) {
-                // (sp < QSTACK_MAX always: one entry per internal ancestor of the current node, as a lane's own stack; the host
-                // refuses hierarchies whose bound exceeds it. The test keeps every store and every pop inside the array)
-                if (sp < QSTACK_MAX) {
-                    stack[sp] = second;
-                    sp++;
-                }
-            }
-            cur = first;
-            if (!(intL || intR)) {
-                if (sp == 0) walking = false;   // (the node's leaves are still tested)
-                else {
-                    sp--;
-                    cur = stack[sp];
-                }
-            }
-        }
-        const float t = found ? sqrtf(best) : __builtin_inff();
-        if (RECORDS) hits[(size_t)b * QUERY_BLOCK + lane] = make_float4(0.f, 0.f, t, __int_as_float(btri));
-        else if (v.inside) {
-            const size_t i = ((size_t)v.iz * g.ny + v.iy) * g.nx + v.ix;
-            dist[i] = t;
-            if (tri) tri[i] = btri;
-        }
-    }
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(QUERY_BLOCK, 4) void grid_dist_dense(GridArgs g, float rmax, const uint4* __restrict__ node32,
                                                                   const float4* __restrict__ tri48, float* __restrict__ dist,
                                                                   int32_t* __restrict__ tri) {
-    dist_walk<false>(g, rmax, node32, tri48, dist, tri, nullptr);
+    dist_walk<DIST_DENSE>(g, DenseBricks(), rmax, node32, tri48, dist, tri, nullptr, nullptr);
 }
 __global__ __launch_bounds__(QUERY_BLOCK, 4) void grid_dist_records(GridArgs g, float rmax, const uint4* __restrict__ node32,
                                                                     const float4* __restrict__ tri48, float4* __restrict__ hits) {
-    dist_walk<true>(g, rmax, node32, tri48, nullptr, nullptr, hits);
+    dist_walk<DIST_RECORDS>(g, DenseBricks(), rmax, node32, tri48, nullptr, nullptr, hits, nullptr);
 }
 
 // signed, after the sign kernel: the slab's records (lane order) into the dense dist / tri of the whole grid

@@ -11,6 +11,7 @@ namespace psm {
 void query_release(psm_ctx* c);               // query.hip, for psm_ctx_destroy: the context's stack area goes with it
 void mesh_release(psm_ctx* c);                // mesh.hip, for psm_ctx_destroy: the device copy of the mesh queries' poses goes with it
 void grid_release(psm_ctx* c);                // grid.hip, for psm_ctx_destroy: the solid grids' scratch goes with it
+void sparse_release(psm_ctx* c);              // grid_sparse.hip, for grid_release: the sparse grids' scratch goes with it
 // mesh.hip: the host pieces the twelve posed-mesh entry points share (mesh.hip, mesh_dist.hip and world.hip's two host functions;
 // DESIGN.md 4.28). A check answers PSM_OK, or refuses under the entry point's name with the context's error set.
 int mesh_refuse(psm_ctx* c, int code, const char* format, ...) __attribute__((format(printf, 3, 4)));   // the formatted text as the error

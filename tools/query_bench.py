@@ -124,6 +124,13 @@ with 3 rays; per case the field alternated A B A B (host-timed medians of REPS) 
 closestPoint / signedDistance over voxel_centres of the same grid: the entry point alone over resident records, the package's
 torch call over resident centres, and the same from host arrays (the upload included) --, the fraction of voxels with a triangle
 within rmax, and a check that dist and tri are the same bits (same_bits). No ratio is fixed in advance.
+`query_bench.py sparsegrids`: the sparse grids (psm_grid_sparse_*_dev) on the Sponza-class scene: 128^3, 256^3, 512^3 and, sparse
+only, 1024^3 grids over its bounds (SPARSE_SIZES; the dense side up to SPARSE_DENSE_MAX), the distance field with a band of two cell
+diagonals and with rmax = +inf, and the surface. Per case the bricks listed and their fraction, the bytes of both outputs, the
+listing with the coarse pass on and off (PSM_SPARSE_COARSE, alternated A B A B, host-timed medians of REPS, and whether both lists
+agree), the fill, and list + fill alternated with the dense call of the same tree, after a check that the sparse answer scattered
+back is the dense one bit for bit (same_bits); the dense call is also alternated with itself (the spread). Each case's figures are
+also appended to SPARSE_LOG as they come. No ratio is fixed in advance.
 `query_bench.py worlddistgrids`: the distance-field grids over a world (psm_grid_world_distance_dev /
 psm_grid_world_signed_distance_dev) on the worldgrids mode's worlds, the torus at 256 and 4 096 turned grid poses
 (WORLD_GRID_POSES): 64^3, 128^3 and 256^3 grids over the world's bounds (GRID_SIZES), rmax = +inf and a band of two cell diagonals,
@@ -2044,6 +2051,145 @@ def distgrids():
     print(json.dumps(out))
 
 
+def sparsegrids():
+    """the sparse grids (list + fill) against the dense calls of the same tree, with the listing's coarse pass on and off"""
+    import torch   # (before the library loads its HIP runtime)
+    dev = torch.device("cuda", 0)
+    lib = psm.lib()
+    sc = scenes.sponza_like()
+    ctx = psm.Context(0, stream=torch.cuda.current_stream(dev).cuda_stream)   # torch's compares and the launches: one stream
+    th = psm.TriangleHierarchy(ctx)
+    th.allocate(sc["tris"].shape[0])
+    th.loadTriangles(sc["tris"], sc["normals"], sc["mats"])
+    th.build()
+    v = sc["tris"].reshape(-1, 3)
+    lo, hi = v.min(0).astype(np.float64), v.max(0).astype(np.float64)
+    dense_max = int(os.environ.get("SPARSE_DENSE_MAX", "512"))
+    log = os.environ.get("SPARSE_LOG")
+    out = {"mode": "sparsegrids", "reps": REPS, "lib": os.path.basename(psm.LIB_PATH), "tris": int(th.info().leaf_count)}
+
+    def coarse(on):
+        os.environ["PSM_SPARSE_COARSE"] = "1" if on else "0"   # (read at each call)
+
+    def note(key, values):
+        for k, x in values.items():
+            out[key + k] = x
+        if log:
+            with open(log, "a") as f:
+                f.write(json.dumps({key + k: x for k, x in values.items()}) + "\n")
+
+    for g in (int(x) for x in os.environ.get("SPARSE_SIZES", "128,256,512,1024").split(",")):
+        origin, cell, dims = lo, (hi - lo) / g, (g, g, g)
+        grid = psm._grid(origin, cell, dims)
+        bricks = int(lib.psm_grid_brick_count(C.byref(grid)))
+        count = torch.zeros(4, dtype=torch.int32, device=dev)
+        p_count = C.c_void_p(count.data_ptr())
+        band = 2.0 * float(np.linalg.norm(np.array(grid.cell, np.float64)))
+        cases = [("band", band, False), ("inf", float("inf"), False), ("surface", None, True)]
+        for rname, rmax, surface in cases:
+            key = "g%d_%s_" % (g, rname)
+            if rname == "inf" and g > dense_max:
+                note(key, {"skipped": "every brick listed: the sparse output is the dense one plus the ids, %d bytes" % (bricks * 516)})
+                continue
+            r32 = C.c_float(rmax if rmax is not None else 0.0)
+
+            def lister(capacity, p_ids):
+                if surface:
+                    ctx.check(lib.psm_grid_sparse_surface_bricks_dev(th._h, C.byref(grid), C.c_uint32(capacity), p_ids, p_count), "psm_grid_sparse_surface_bricks_dev")
+                else:
+                    ctx.check(lib.psm_grid_sparse_distance_bricks_dev(th._h, C.byref(grid), r32, C.c_uint32(capacity), p_ids, p_count),
+                              "psm_grid_sparse_distance_bricks_dev")
+
+            coarse(True)
+            lister(0, None)
+            ctx.sync()
+            n = int(count.cpu()[0])
+            ids = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+            p_ids = C.c_void_p(ids.data_ptr())
+            if surface:
+                words = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+                p_a, p_b = C.c_void_p(words.data_ptr()), None
+            else:
+                sdist = torch.zeros((max(n, 1), 64), dtype=torch.float32, device=dev)
+                stri = torch.zeros((max(n, 1), 64), dtype=torch.int32, device=dev)
+                p_a, p_b = C.c_void_p(sdist.data_ptr()), C.c_void_p(stri.data_ptr())
+
+            def list_on():
+                coarse(True)
+                lister(n, p_ids)
+
+            def list_off():
+                coarse(False)
+                lister(n, p_ids)
+
+            def fill():
+                if surface:
+                    ctx.check(lib.psm_grid_sparse_surface_dev(th._h, C.byref(grid), p_ids, C.c_uint32(n), p_a), "psm_grid_sparse_surface_dev")
+                else:
+                    ctx.check(lib.psm_grid_sparse_distance_dev(th._h, C.byref(grid), r32, p_ids, C.c_uint32(n), p_a, p_b), "psm_grid_sparse_distance_dev")
+
+            def both():   # the library's default: the coarse pass on unless rmax = +inf
+                list_on()
+                fill()
+
+            figures = {"bricks": bricks, "listed": n, "listed_fraction": round(n / bricks, 5),
+                       "sparse_bytes": n * (12 if surface else 516), "dense_bytes": bricks * 8 if surface else 8 * g ** 3}
+            list_off()
+            ids_off = ids.clone()
+            list_on()
+            figures["same_list_coarse_on_off"] = bool(torch.equal(ids, ids_off))
+            figures["list_coarse_ms"], figures["list_plain_ms"] = abab(ctx, list_on, list_off)
+            figures["list_coarse_again_ms"], figures["fill_ms"] = abab(ctx, list_on, fill)
+            if g <= dense_max:
+                if surface:
+                    dwords = torch.zeros(bricks, dtype=torch.int64, device=dev)
+                    p_dense = C.c_void_p(dwords.data_ptr())
+
+                    def dense():
+                        ctx.check(lib.psm_grid_surface_dev(th._h, C.byref(grid), p_dense), "psm_grid_surface_dev")
+                else:
+                    ddist = torch.zeros((g, g, g), dtype=torch.float32, device=dev)
+                    dtri = torch.zeros((g, g, g), dtype=torch.int32, device=dev)
+                    p_dense, p_dtri = C.c_void_p(ddist.data_ptr()), C.c_void_p(dtri.data_ptr())
+
+                    def dense():
+                        ctx.check(lib.psm_grid_distance_dev(th._h, C.byref(grid), r32, p_dense, p_dtri), "psm_grid_distance_dev")
+
+                # the same bits as the dense call, before any timing of the pair
+                both()
+                dense()
+                ctx.sync()
+                shape = (tuple(grid.dims), tuple(grid.origin), tuple(grid.cell))
+                if surface:
+                    back = psm.SparseVoxelGrid(ids[:n], words[:n], *shape).dense().bricks.reshape(-1)
+                    same = bool(torch.equal(back, dwords)) and n == int((dwords != 0).sum())
+                else:
+                    back = psm.SparseDistanceGrid(ids[:n], sdist[:n].reshape(n, 4, 4, 4), stri[:n].reshape(n, 4, 4, 4), *shape).dense()
+                    same = bool(torch.equal(back.dist.view(torch.int32), ddist.view(torch.int32)) and torch.equal(back.tri, dtri))
+                    del back
+                figures["same_bits"] = same
+                figures["sparse_ms"], figures["dense_ms"] = abab(ctx, both, dense)
+                figures["dense_again_ms"], figures["dense_third_ms"] = abab(ctx, dense, dense)   # the spread of one side against itself
+                figures["sparse_over_dense"] = round(figures["sparse_ms"] / figures["dense_ms"], 3)
+                if surface:
+                    del dwords
+                else:
+                    del ddist, dtri
+            else:
+                figures["sparse_ms"] = round(median_ms(ctx, both), 4)
+            note(key, figures)
+            del ids
+            if surface:
+                del words
+            else:
+                del sdist, stri
+            torch.cuda.empty_cache()
+    os.environ.pop("PSM_SPARSE_COARSE", None)
+    th.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def worldgrids():
     """the voxel grids over a world against the world's box queries over voxel_boxes() of the same grid"""
     lib = psm.lib()
@@ -2299,4 +2445,4 @@ def main():
 
 
 if __name__ == "__main__":
-    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "world-clearance": worldclearance, "world-mesh-clearance": worldmeshclearance, "worldmeshes": worldmeshes, "grids": grids, "distgrids": distgrids, "worldgrids": worldgrids, "worlddistgrids": worlddistgrids}.get(" ".join(sys.argv[1:]), main)()
+    {"points": points, "signed": signed, "scene": scene, "instances": instances, "world": world, "kbest": kbest, "worldkbest": worldkbest, "boxes": boxes, "worldboxes": worldboxes, "sweeps": sweeps, "worldsweeps": worldsweeps, "triangles": triangles, "clearance": clearance, "meshes": meshes, "meshclearance": meshclearance, "worldtriangles": worldtriangles, "world-clearance": worldclearance, "world-mesh-clearance": worldmeshclearance, "worldmeshes": worldmeshes, "grids": grids, "distgrids": distgrids, "sparsegrids": sparsegrids, "worldgrids": worldgrids, "worlddistgrids": worlddistgrids}.get(" ".join(sys.argv[1:]), main)()
